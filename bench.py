@@ -6,9 +6,14 @@ NestedPathAbundanceEstimator::estimateBatch() (`-i haplotype-transcripts`, refer
 x 200k paths in ~5k clusters" workload (BASELINE.json configs[2]).  `value` is SURVEY.md section 8(d)'s metric: read pairs
 per second of wall clock with the H2D of every batch's sparse rows and the D2H of its results inside the clock (steady
 state of a double-buffered pipeline: batch n + 1 is uploaded under the kernels of batch n; the first batch is resident
-when the clock starts).  The same K steps on a batch that stays resident are reported next to it (`value_resident`).
+when the clock starts).  With --full the same K steps on a batch that stays resident are reported next to it (`value_resident`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s3|c2] [--model ...] [--scale F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s3|c2] [--model ...] [--scale F] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the K steps (ms_per_step is one of
+them), writes the estimates of the last step with --dump-outputs and prints the line.  --full adds every other leg of the line
+(the resident and one-batch-in-flight steps, the instrumented pass behind the per-family device times, the single data set, the
+predicted host bound, the dense-EM, configs[4] and drop-in lines, the CPU baseline).
 
 One process per GPU: started under torch.distributed.run (WORLD_SIZE in the environment) this process is one
 rank; started plainly with --gpus N > 1 it launches the N ranks itself (torch.distributed.run, rendezvous on
@@ -90,7 +95,49 @@ def parse_args():
                          "call combiner while their batch is on the GPU, so a team far larger than the cores is what keeps batches in flight)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the cpu_baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the line can hold: besides the headline's timed steps, the resident and one-batch legs, the instrumented "
+                         "pass, the single data set, the host bound, the dense-EM / configs[4] / drop-in lines and the CPU baseline.  Without it "
+                         "a run sets up, warms up, times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, at most "
+                         "64 MB in all: a fixed, seeded sample of a longer array)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20261016
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as float64 in directory/<name>.npy, DUMP_BUDGET_BYTES at most in all (files included).  The
+    budget is shared out from the shortest array up: an array that fits its share is written whole, a longer one as a fixed,
+    seeded sample of its elements (sorted positions, the same for the same lengths), so that two builds compare element for
+    element."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64).ravel() for name, a in arrays.items()}
+    left = DUMP_BUDGET_BYTES - 4096 * len(arrays)  # (.npy headers, with room)
+    for i, name in enumerate(sorted(arrays, key=lambda n: (arrays[n].nbytes, n))):
+        a = arrays[name]
+        keep = min(len(a), max(0, left // (len(arrays) - i)) // a.itemsize)
+        if keep < len(a):
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
+def estimate_arrays(est):
+    """The estimates of a batch (PathClusterEstimates per cluster) as flat arrays, cluster after cluster."""
+    import numpy as np
+    sets = [s for e in est for s in e.path_group_sets]
+    return dict(
+        abundances=np.concatenate([e.abundances for e in est]) if est else np.zeros(0),
+        posteriors=np.concatenate([e.posteriors for e in est]) if est else np.zeros(0),
+        noise_count=[e.noise_count for e in est], total_count=[e.total_count for e in est],
+        em_iters=[i for e in est for i in e.em_iters],
+        group_sets_per_cluster=[len(e.path_group_sets) for e in est], abundances_per_cluster=[len(e.abundances) for e in est],
+        group_set_sizes=[len(s) for s in sets], group_set_members=[p for s in sets for p in s])
 
 
 # Test seams (tests/test_distributed_cpu.py drives the launcher and the rank protocol without a GPU): the collective
@@ -302,59 +349,65 @@ def run_s3(args, rank, local_rank, world, dist, torch):
         batch, my_clusters = rdist.shard_batch(full, rank, world)
         global_clusters = full.num_clusters
 
-    eng = eng_mod.Engine(local_rank)
-    t_up = time.perf_counter()
-    prepared = eng.prepare(batch)  # upload: inputs are resident in HBM before the timed region
-    upload_ms = (time.perf_counter() - t_up) * 1e3
-    # engine start-up (second host lane and its device context, scratch pools): one pass outside the measurement,
-    # so that the W warmup steps are warmup and not initialisation
-    eng.run_raw(args.model, params, prepared)
-    for _ in range(args.warmup):
-        eng.run_raw(args.model, params, prepared)
+    # The headline is the batch pipeline (measure_pipeline) wherever there is one.  A plain run (no --full) times it alone: no
+    # resident engine, no other leg, no pass after it but the gather of a multi-rank run.
+    headline_only = (not args.full and args.in_flight == 1 and DEVICE == "cuda" and hasattr(eng_mod, "Pipeline")
+                     and (not os.environ.get("RPVG_BENCH_NO_PIPELINE") or bool(os.environ.get("RPVG_BENCH_NO_SINGLE"))))
+    eng = prepared = None
     others = []  # --in-flight 2: a second engine with its own resident copy of the batch
-    for _ in range(args.in_flight - 1):
-        other = eng_mod.Engine(local_rank)
-        other_prepared = other.prepare(batch)
-        for _ in range(args.warmup + 1):
-            other.run_raw(args.model, params, other_prepared)
-        other.reset_stats()
-        others.append((other, other_prepared))
-    eng.reset_stats()
+    if not headline_only:
+        eng = eng_mod.Engine(local_rank)
+        t_up = time.perf_counter()
+        prepared = eng.prepare(batch)  # upload: inputs are resident in HBM before the timed region
+        upload_ms = (time.perf_counter() - t_up) * 1e3
+        # engine start-up (second host lane and its device context, scratch pools): one pass outside the measurement,
+        # so that the W warmup steps are warmup and not initialisation
+        eng.run_raw(args.model, params, prepared)
+        for _ in range(args.warmup):
+            eng.run_raw(args.model, params, prepared)
+        for _ in range(args.in_flight - 1):
+            other = eng_mod.Engine(local_rank)
+            other_prepared = other.prepare(batch)
+            for _ in range(args.warmup + 1):
+                other.run_raw(args.model, params, other_prepared)
+            other.reset_stats()
+            others.append((other, other_prepared))
+        eng.reset_stats()
 
-    barrier_sync(dist, torch)
-    t0 = time.perf_counter()
-    step_ms = []
-    if not others:
-        for _ in range(args.steps):
-            step_ms.append(eng.run_raw(args.model, params, prepared) * 1e3)
-    else:
-        import threading
-        lanes = [(eng, prepared)] + others
-        share = [args.steps // len(lanes) + (1 if k < args.steps % len(lanes) else 0) for k in range(len(lanes))]
-        errors = []
+        barrier_sync(dist, torch)
+        t0 = time.perf_counter()
+        step_ms = []
+        if not others:
+            for _ in range(args.steps):
+                step_ms.append(eng.run_raw(args.model, params, prepared) * 1e3)
+        else:
+            import threading
+            lanes = [(eng, prepared)] + others
+            share = [args.steps // len(lanes) + (1 if k < args.steps % len(lanes) else 0) for k in range(len(lanes))]
+            errors = []
 
-        def drive(k):
-            try:
-                for _ in range(share[k]):
-                    lanes[k][0].run_raw(args.model, params, lanes[k][1])  # ctypes releases the GIL during the call
-            except Exception as exc:  # noqa: BLE001
-                errors.append(exc)
+            def drive(k):
+                try:
+                    for _ in range(share[k]):
+                        lanes[k][0].run_raw(args.model, params, lanes[k][1])  # ctypes releases the GIL during the call
+                except Exception as exc:  # noqa: BLE001
+                    errors.append(exc)
 
-        threads = [threading.Thread(target=drive, args=(k,)) for k in range(len(lanes))]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        if errors:
-            raise errors[0]
-    barrier_sync(dist, torch)
-    elapsed = time.perf_counter() - t0
-    elapsed = max_over_ranks(elapsed, dist, torch)
-    stats = eng.stats()
-    for other, _ in others:
-        merge_stats(stats, other.stats())
-    if os.environ.get("RPVG_BENCH_STEP_TIMES"):  # spread of the single steps (the JSON line reports the mean)
-        print("step ms:", " ".join(f"{t:.1f}" for t in step_ms), file=sys.stderr)
+            threads = [threading.Thread(target=drive, args=(k,)) for k in range(len(lanes))]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
+            if errors:
+                raise errors[0]
+        barrier_sync(dist, torch)
+        elapsed = time.perf_counter() - t0
+        elapsed = max_over_ranks(elapsed, dist, torch)
+        stats = eng.stats()
+        for other, _ in others:
+            merge_stats(stats, other.stats())
+        if os.environ.get("RPVG_BENCH_STEP_TIMES"):  # spread of the single steps (the JSON line reports the mean)
+            print("step ms:", " ".join(f"{t:.1f}" for t in step_ms), file=sys.stderr)
 
     reads_all = sum_over_ranks(float(batch.total_reads), dist, torch)
 
@@ -363,7 +416,11 @@ def run_s3(args, rank, local_rank, world, dist, torch):
     # batch n + 1 is validated, copied and expanded under the kernels of batch n.  The kernel statistics of the line are
     # those of this loop.
     h2d = None
-    if not others and DEVICE == "cuda" and hasattr(prepared, "reupload"):
+    if headline_only:
+        h2d = measure_pipeline(args, eng_mod, batch, params, local_rank, dist, torch, instrumented_pass=False)
+        stats = h2d.pop("stats")
+        h2d.pop("instrumented_pass")
+    elif not others and DEVICE == "cuda" and hasattr(prepared, "reupload"):
         quick = bool(os.environ.get("RPVG_BENCH_NO_SINGLE")) and hasattr(eng_mod, "Pipeline")  # (the pipeline only: profiling runs, the s5 line inside the default run)
         single = None if quick else measure_with_uploads(args, eng, eng_mod, prepared, batch, params, local_rank, dist, torch)
         single_stats = single.pop("stats") if single else {}
@@ -400,9 +457,14 @@ def run_s3(args, rank, local_rank, world, dist, torch):
             h2d, stats = single, single_stats
 
     # after the timed region: gather the per-path abundances of every rank over RCCL (what a multi-GPU
-    # driver does before writing rpvg.txt); also fetch one decoded result for a sanity check
-    est, _ = eng.run(args.model, params, prepared)
+    # driver does before writing rpvg.txt); also fetch one decoded result for a sanity check (a plain run: the
+    # estimates of the pipeline's last batch)
     pipeline_est = h2d.pop("sample_estimates", None) if h2d is not None else None
+    if headline_only:
+        est, pipeline_est = pipeline_est, None
+    else:
+        est, _ = eng.run(args.model, params, prepared)
+    last_step_est = pipeline_est if pipeline_est is not None else est
     single_dataset = h2d.get("single_dataset") if h2d is not None else None
     if single_dataset and "estimates" in single_dataset:  # the parts' estimates are the whole batch's, bit for bit
         parts_est = single_dataset.pop("estimates")
@@ -440,8 +502,10 @@ def run_s3(args, rank, local_rank, world, dist, torch):
 
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, estimate_arrays(last_step_est))
 
-    ms_resident = elapsed / args.steps * 1e3
+    ms_resident = None if headline_only else elapsed / args.steps * 1e3
     ms_per_step = h2d["ms_per_step_with_h2d"] if h2d is not None else ms_resident
     value = reads_all / (ms_per_step / 1e3)
     # the dominant EM kernel: the variant with the most device time (its own HIP events on its own stream)
@@ -501,12 +565,15 @@ def run_s3(args, rank, local_rank, world, dist, torch):
                     clusters_per_gpu=K, rows_per_gpu=batch.num_rows, entries_per_gpu=int(len(batch.path_idx)),
                     parallelism=f"clusters sharded, {world} rank(s), final abundance gather over RCCL",
                     batches_in_flight=(h2d or {}).get("pipeline", {}).get("workers", args.in_flight)),
-        roofline=roofline, kernels=kernels, em_kernels=em_kernel_lines, mass_conserved=bool(mass_ok),
-        upload_ms=upload_ms, ms_per_step_resident=ms_resident, value_resident=reads_all / (ms_resident / 1e3),
+        roofline=roofline, em_kernels=em_kernel_lines, mass_conserved=bool(mass_ok),
+        **({} if headline_only else dict(kernels=kernels, upload_ms=upload_ms, ms_per_step_resident=ms_resident,
+                                         value_resident=reads_all / (ms_resident / 1e3))),
         engine_module=ENGINE_MODULE, host_threads_per_lane=host_threads_per_lane(),
         value_note="value = read pairs / steady-state step with the H2D of every batch's rows and the D2H of its results inside the "
-                   "clock (SURVEY.md section 8d); value_resident = the same K steps on a batch that stays in HBM")
-    if stats.get("busy_ms") is not None:
+                   "clock (SURVEY.md section 8d)" + ("" if headline_only else "; value_resident = the same K steps on a batch that stays in HBM"))
+    if headline_only and s5:
+        line.pop("roofline")  # (configs[4] runs no EM: its roofline is that of the conditionals, from the instrumented pass of --full)
+    if stats.get("busy_ms") is not None and not headline_only:
         # union of the timed spans of both host lanes' contexts over the wall time of the headline loop: an upper bound of
         # the share of the step during which the GPU had work of this engine (a span runs from the first command of a stage
         # to its last on the stage's stream); the rocprofv3 kernel trace under profiles/ gives the exact figure
@@ -528,6 +595,8 @@ def run_s3(args, rank, local_rank, world, dist, torch):
         line["gathered_abundance_mass"] = gathered
     if tpm_denominator is not None:
         line["tpm_denominator"] = tpm_denominator
+    if headline_only:
+        return line
     # The log-likelihood kernels (diploid search, Gibbs conditionals) are FP64-issue bound, not HBM bound: the search reads
     # its matrices once and works from LDS.  One evaluation = one row of one column set: an add and a multiply on the
     # running-product path (2 flop, the figure used here), a ~22-instruction logarithm on the rest.
@@ -595,7 +664,7 @@ def run_s3(args, rank, local_rank, world, dist, torch):
         eng.close()
     except Exception:  # noqa: BLE001  (a stand-in engine without these)
         pass
-    if args.scale >= 1.0 and not s5 and DEVICE == "cuda":
+    if args.full and args.scale >= 1.0 and not s5 and DEVICE == "cuda":
         try:
             line["roofline_dense_em"] = dense_em_roofline(local_rank)
         except Exception as exc:  # the record is optional; the default workload's line stands on its own
@@ -616,7 +685,7 @@ def run_s3(args, rank, local_rank, world, dist, torch):
                 line["drop_in_team_256"] = drop_in_line(args, local_rank, team=256)
             except Exception as exc:  # noqa: BLE001
                 line["drop_in_team_256"] = dict(error=str(exc))
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_s3(batch, args.model, params, args.cpu_seconds)
         cpu_value = line["cpu_baseline"].get("value") if isinstance(line["cpu_baseline"], dict) else None
         if cpu_value:
@@ -634,7 +703,7 @@ def drop_in_line(args, local_rank, steps=5, team=64):
     --workload a1 bench as a child process (its own engine, its own memory)."""
     import subprocess
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "a1", "--team", str(team), "--steps", str(steps), "--warmup", "2",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
         raise RuntimeError(out.stderr[-400:])
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -642,7 +711,7 @@ def drop_in_line(args, local_rank, steps=5, team=64):
                 team_threads=team, estimates_equal_estimate_batch=d["estimates_equal_estimate_batch"], workload=d["config"]["workload"],
                 note="a step = all 5 000 clusters of the configs[2] data set through estimate(), one call per cluster, every caller blocked until its "
                      "cluster is done; callers flatten their clusters into page-locked segments that the GPU reads in place, the calls in flight are "
-                     "joined into batches (PathEstimator::CallCombiner); python bench.py --workload a1 prints the full line")
+                     "joined into batches (PathEstimator::CallCombiner); python bench.py --workload a1 --full prints the full line")
 
 
 def measure_with_uploads(args, eng, eng_mod, prepared, batch, params, local_rank, dist, torch):
@@ -863,11 +932,11 @@ PAGE_LOCK_MIN_BYTES = 1 << 16  # (smaller arrays — the list of the rows whose 
 NARROW_UPLOADS = not os.environ.get("RPVG_BENCH_WIDE_UPLOADS")  # (A/B: the 32-bit path indices, source ids and read counts of round 5)
 
 
-def measure_pipeline(args, eng_mod, batch, params, local_rank, dist, torch):
+def measure_pipeline(args, eng_mod, batch, params, local_rank, dist, torch, instrumented_pass=True):
     """K batches through BatchPipeline: submit() K times, wait().  The host arrays are page-locked; every batch is validated,
     copied and expanded on the device inside the clock (and its haplotype columns formed), several batches are in flight, the
     estimates of every batch land in host containers (PathClusterEstimates).  The pipeline is empty when the clock starts and
-    when it stops: ramp-up and drain are inside."""
+    when it stops: ramp-up and drain are inside.  instrumented_pass: the second pass below (--full)."""
     import resource
     from rpvg_amd import hip
     arrays = copied_arrays(batch)
@@ -909,7 +978,7 @@ def measure_pipeline(args, eng_mod, batch, params, local_rank, dist, torch):
     # commands between dependent kernels, and with every kernel family timed a batch takes 0.3-0.6 ms longer).  The per-family
     # device times, the busy union and the copies' device time of the line come from a second, shorter pass with all of them on.
     instrumented = stats
-    if stats.get("busy_ms", 0.0) == 0.0 and not os.environ.get("RPVG_HIP_SPANS"):
+    if instrumented_pass and stats.get("busy_ms", 0.0) == 0.0 and not os.environ.get("RPVG_HIP_SPANS"):
         os.environ["RPVG_HIP_SPANS"] = "2"
         try:
             for a in arrays:
@@ -997,7 +1066,7 @@ def run_a1(args, rank, local_rank, world, dist, torch):
     t0 = time.perf_counter()
     prepared = eng.prepare(batch, per_cluster=True)  # the rows as vector<ReadPathProbabilities> per cluster, on the host
     prepare_s = time.perf_counter() - t0
-    steps, warmup = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warmup = max(1, args.steps), max(1, args.warmup)
     for _ in range(warmup):
         eng.run_team(args.model, params, prepared, args.team, decode=False)
     barrier_sync(dist, torch)
@@ -1005,13 +1074,18 @@ def run_a1(args, rank, local_rank, world, dist, torch):
     step_s = [eng.run_team(args.model, params, prepared, args.team, decode=False)[1] for _ in range(steps)]
     barrier_sync(dist, torch)
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, torch)
-    est, _ = eng.run_team(args.model, params, prepared, args.team)
-    whole, _ = eng.run(args.model, params, eng.prepare(batch))
-    same = all(a.path_group_sets == b.path_group_sets and np.allclose(a.posteriors, b.posteriors, rtol=1e-9, atol=1e-12)
-               and np.allclose(a.abundances, b.abundances, rtol=1e-9, atol=1e-9) and a.em_iters == b.em_iters for a, b in zip(est, whole))
+    est = same = None
+    if args.full or args.dump_outputs:  # (one more pass, decoded: the estimates do not depend on how the calls were joined)
+        est, _ = eng.run_team(args.model, params, prepared, args.team)
+    if args.full:
+        whole, _ = eng.run(args.model, params, eng.prepare(batch))
+        same = bool(all(a.path_group_sets == b.path_group_sets and np.allclose(a.posteriors, b.posteriors, rtol=1e-9, atol=1e-12)
+                        and np.allclose(a.abundances, b.abundances, rtol=1e-9, atol=1e-9) and a.em_iters == b.em_iters for a, b in zip(est, whole)))
     reads_all = sum_over_ranks(float(batch.total_reads), dist, torch)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, estimate_arrays(est))
     ms = elapsed / steps * 1e3
     return dict(metric="read-pairs quantified/sec", value=reads_all / (ms / 1e3), unit="read-pairs/s", n_gpus=world, steps=steps, warmup=warmup,
                 ms_per_step=ms, higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f64", data="synthetic",
@@ -1019,7 +1093,7 @@ def run_a1(args, rank, local_rank, world, dist, torch):
                                      f"configs[2]), -i {args.model}, reference defaults — through PathEstimator::estimate(), one call per cluster "
                                      f"from an OpenMP team of {args.team} threads (the reference's loop, src/main.cpp:829,976-977)",
                             team_threads=args.team, clusters_per_gpu=K),
-                ms_per_step_in_order=[round(x * 1e3, 2) for x in step_s], estimates_equal_estimate_batch=bool(same), prepare_seconds=prepare_s,
+                ms_per_step_in_order=[round(x * 1e3, 2) for x in step_s], estimates_equal_estimate_batch=same, prepare_seconds=prepare_s,
                 note="every call flattens its cluster on its own thread; the calls in flight are joined into batches of up to 256 clusters behind "
                      "the interface (PathEstimator::CallCombiner), up to three batches on the GPU at once; rows start on the host, uploads inside")
 
@@ -1029,8 +1103,8 @@ def gibbs_line(args, local_rank, steps=16):
     driver's record carries it: a short run of the --workload s5 bench as a child process (its own engines, its own memory)."""
     import subprocess
     env = dict(os.environ, RPVG_BENCH_NO_SINGLE="1")
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "s5", "--steps", str(steps), "--warmup", "4", "--no-cpu-baseline"],
-                         env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "s5", "--steps", str(steps), "--warmup", "4", "--no-cpu-baseline",
+                          "--full"], env=env, capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
         raise RuntimeError(out.stderr[-400:])
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1041,7 +1115,7 @@ def gibbs_line(args, local_rank, steps=16):
                 gpu_active_frac=d.get("gpu_active_frac"), host_cpu_ms_per_step=d.get("host_cpu_ms_per_step"), mass_conserved=d.get("mass_conserved"),
                 pipeline=d.get("pipeline", {}).get("workers"),
                 line_note="the configs[4] workload through the same batch pipeline, every batch uploaded inside the clock; python bench.py --workload s5 "
-                          "prints the full line")
+                          "--full prints the full line")
     return keep
 
 
@@ -1129,6 +1203,9 @@ def run_rows(args, rank, local_rank, world, dist, torch):
     reads_all = sum_over_ranks(float(aligns.total_reads), dist, torch)
     if rank != 0:
         return None
+    if args.dump_outputs:  # the merged rows of the last step
+        dump_outputs(args.dump_outputs, {name: getattr(rows, name) for name in ("cluster_row_off", "row_count", "row_noise", "row_grp_off",
+                                                                                "grp_prob", "grp_idx_off", "path_idx")})
     E = int(aligns.align_path_off[-1])
     A = int(aligns.read_align_off[-1])
     N = aligns.num_reads
@@ -1151,6 +1228,8 @@ def run_rows(args, rank, local_rank, world, dist, torch):
         kernels=dict(row_kernels_ms_per_step=build_ms / args.steps, sort_merge_pack_ms_per_step=merge_ms / args.steps),
         rows_out=int(rows.num_rows), rows_match_generator=same_structure, upload_ms=upload_ms, download_ms=download_ms,
         value_including_upload_and_download=float(aligns.total_reads) / ((elapsed / args.steps) + (upload_ms + download_ms) / 1e3) * world)
+    if not args.full:
+        return line
     # path clustering (PathClusters) of the same reads: the paths of all alignments of a read are one
     # id set over global path ids (src/path_clusters.cpp:31-47); the components must refine the generator's clusters
     per_align = np.diff(aligns.align_path_off.astype(np.int64))
@@ -1214,6 +1293,8 @@ def run_e2e(args, rank, local_rank, world, dist, torch):
     mass_ok = all(abs(e.abundances.sum() + e.noise_count - e.total_count) <= 1e-6 * max(1.0, e.total_count) for e in est)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, estimate_arrays(est))
     line = dict(
         metric="read-pairs quantified/sec from alignment-path lists", value=reads_all / (elapsed / args.steps), unit="read-pairs/s",
         n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3, higher_is_better=True,
@@ -1223,7 +1304,7 @@ def run_e2e(args, rank, local_rank, world, dist, torch):
                     parallelism=f"clusters sharded, {world} rank(s), no collective"),
         stages=dict(row_construction_ms_per_step=rows_s / args.steps * 1e3, estimates_ms_per_step=est_s / args.steps * 1e3),
         mass_conserved=bool(mass_ok))
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import pyoracle
         cores = pyoracle.max_threads()
         v = np.arange(65536, dtype=np.float64)
@@ -1297,6 +1378,8 @@ def run_c2(args, rank, local_rank, world, dist, torch):
     reads_all = sum_over_ranks(float(R), dist, torch)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(abundances=ab, noise_count=[noise], em_iters=[done]))
     it_ms = stats["em_dense_ms"] / max(1, stats["em_dense_launches"])  # HIP events around the streaming-pass launches
     it_bytes = stats["em_dense_alg_bytes"] / max(1, stats["em_dense_launches"])
     achieved = (it_bytes / 1e9) / (it_ms / 1e3)
@@ -1326,7 +1409,7 @@ def run_c2(args, rank, local_rank, world, dist, torch):
                                note="streaming_passes = HIP-event spans of the iterations' streaming-pass launches; build_and_compaction = the "
                                     "spans of the kernels in front of them (the rows counted and normalised straight into the dense matrix: fillDenseRowsKernel); the rest of a step is "
                                     "the reduce / update / control launches and the host's waits between chunks of iterations"))
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # reference-shaped CPU EM on a row sample of the same matrix, one core (a single cluster is serial
         # in the reference: SURVEY.md F4)
         from oracle import pyoracle

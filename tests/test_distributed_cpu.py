@@ -222,6 +222,51 @@ def test_bench_refuses_a_rank_count_that_differs_from_gpus():
     assert out.returncode != 0 and "--gpus 2" in (out.stderr + out.stdout)
 
 
+def test_bench_dumps_the_estimates_of_its_last_step(tmp_path):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float64 .npy files; the same arguments give the
+    same inputs, so two runs write the same arrays.  --steps is the number of timed steps the line reports."""
+    first, second = tmp_path / "first", tmp_path / "second"
+    line = _run_bench(["--gpus", "1", "--dump-outputs", str(first)])
+    _run_bench(["--gpus", "1", "--dump-outputs", str(second)])
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    names = sorted(f.name for f in first.iterdir())
+    assert names == sorted(f.name for f in second.iterdir())
+    assert {"abundances.npy", "posteriors.npy", "noise_count.npy", "total_count.npy", "em_iters.npy"} <= set(names)
+    for name in names:
+        a, b = np.load(first / name), np.load(second / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    clusters = line["config"]["clusters_per_gpu"]
+    assert len(np.load(first / "total_count.npy")) == clusters and len(np.load(first / "group_sets_per_cluster.npy")) == clusters
+    assert np.load(first / "abundances.npy").sum() + np.load(first / "noise_count.npy").sum() == pytest.approx(
+        np.load(first / "total_count.npy").sum(), rel=1e-9)
+
+
+def _load_bench():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_dump_stays_within_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """Past the budget, short arrays are written whole and the long ones as the same seeded sample of their elements."""
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    arrays = dict(long=np.arange(400000, dtype=np.float64), longer=np.arange(600000, dtype=np.int64), short=[3, 1, 2])
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 1 << 20
+    for name in ("long", "longer", "short"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "short.npy").tolist() == [3.0, 1.0, 2.0]
+    for name, n in (("long", 400000), ("longer", 600000)):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert 0 < len(a) < n and np.all(np.diff(a) > 0) and a[-1] < n  # sorted positions of the original elements
+
+
 def test_numa_binding_leaves_the_process_alone_when_it_cannot_be_read(monkeypatch):
     """bench.py binds a rank of a multi-rank run to the CPUs of its GPU's NUMA node; a GPU whose node cannot be read (no such
     PCI device here), or a node with too few of the process's CPUs, changes nothing."""

@@ -2,8 +2,8 @@
 """Phase breakdown of the drop-in path (PathEstimator::estimate() once per cluster from an OpenMP team, bench.py --workload a1)
 from the host layer's own traces:
 
-    RPVG_AMD_TRACE=1    python bench.py --workload a1 ...  2> phase_totals.txt     (per pass: seconds summed over threads)
-    RPVG_AMD_TIMELINE=1 python bench.py --workload a1 ...  2> host_timeline.txt    (every phase of every batch with its thread)
+    RPVG_AMD_TRACE=1    python bench.py --full --workload a1 ...  2> phase_totals.txt     (per pass: seconds summed over threads)
+    RPVG_AMD_TIMELINE=1 python bench.py --full --workload a1 ...  2> host_timeline.txt    (every phase of every batch with its thread)
 
     python tools/a1_phase_breakdown.py phase_totals.txt host_timeline.txt [team]
 

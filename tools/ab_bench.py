@@ -26,7 +26,7 @@ for rnd in range(args.rounds):
         for kv in envs.split():
             k, _, val = kv.partition("=")
             env[k] = val
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", args.workload, "--steps", str(args.steps), "--warmup", "5",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--workload", args.workload, "--steps", str(args.steps), "--warmup", "5",
                               "--no-cpu-baseline"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

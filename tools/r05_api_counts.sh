@@ -5,7 +5,7 @@ cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/prof_api
 STEPS=${STEPS:-40}
-RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 600 rocprofv3 --hip-trace --stats --output-format csv -d /tmp/prof_api -- python $R/bench.py --steps $STEPS --warmup 4 --no-cpu-baseline > /dev/null 2>&1
+RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 600 rocprofv3 --hip-trace --stats --output-format csv -d /tmp/prof_api -- python $R/bench.py --full --steps $STEPS --warmup 4 --no-cpu-baseline > /dev/null 2>&1
 f=$(ls /tmp/prof_api/*/*hip_api_stats.csv 2>/dev/null | tail -1)
 [ -z "$f" ] && f=$(ls /tmp/prof_api/*/*stats*.csv | head -1)
 cp $f $R/$out/hip_api_stats.csv

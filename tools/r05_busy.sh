@@ -3,7 +3,7 @@
 out=gpurun_out/r05/busy; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_busy -- python $R/bench.py --steps 24 --warmup 4 --no-cpu-baseline > $R/$out/bench.json 2>/dev/null
+RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_busy -- python $R/bench.py --full --steps 24 --warmup 4 --no-cpu-baseline > $R/$out/bench.json 2>/dev/null
 python $R/tools/gpu_busy_union.py /tmp/prof_busy 16 | tee $R/$out/gpu_busy_s3_pipeline.txt
 python $R/tools/r05_pipe_timeline.py /tmp/prof_busy 14 25 > $R/$out/kernel_timeline_s3_pipeline.txt
 python - <<PY

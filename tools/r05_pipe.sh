@@ -1,6 +1,6 @@
 #!/bin/bash
 # pipeline bench variants: $@ = env assignments per run, separated by ---
-run() { env "$@" timeout 300 python bench.py --steps ${STEPS:-60} --no-cpu-baseline 2>/tmp/bench.err > /tmp/bench.json; tail -2 /tmp/bench.err | grep -v amdgpu.ids; python - "$*" <<PY
+run() { env "$@" timeout 300 python bench.py --full --steps ${STEPS:-60} --no-cpu-baseline 2>/tmp/bench.err > /tmp/bench.json; tail -2 /tmp/bench.err | grep -v amdgpu.ids; python - "$*" <<PY
 import json,sys
 d=json.load(open("/tmp/bench.json"))
 sp=d["ms_per_step_spread"]

@@ -7,7 +7,7 @@ i=0
 while IFS= read -r variant; do
   [ -z "$variant" ] && continue
   i=$((i+1))
-  env $variant timeout ${PER_RUN_TIMEOUT:-150} python $R/bench.py --workload a1 --team ${TEAM:-64} --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
+  env $variant timeout ${PER_RUN_TIMEOUT:-150} python $R/bench.py --full --workload a1 --team ${TEAM:-64} --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
   python - "$variant" $R/$out/v$i.json <<'PY'
 import json,sys
 try:

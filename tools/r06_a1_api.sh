@@ -4,7 +4,7 @@ out=gpurun_out/r06/a1_api; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/prof_api
-timeout 600 rocprofv3 --hip-trace --stats --output-format csv -d /tmp/prof_api -- python $R/bench.py --workload a1 --team 64 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+timeout 600 rocprofv3 --hip-trace --stats --output-format csv -d /tmp/prof_api -- python $R/bench.py --full --workload a1 --team 64 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 f=$(ls /tmp/prof_api/*/*hip_api_stats.csv 2>/dev/null | tail -1)
 [ -z "$f" ] && f=$(ls /tmp/prof_api/*/*stats*.csv | head -1)
 cp $f $R/$out/hip_api_stats.csv

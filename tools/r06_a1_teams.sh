@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/r06/a1_teams; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
 for t in ${TEAMS:-64 96 128 192 256 384 512 64}; do
-timeout 300 python $R/bench.py --workload a1 --team $t --steps 6 --warmup 2 --no-cpu-baseline > $out/team_$t.json 2>/dev/null
+timeout 300 python $R/bench.py --full --workload a1 --team $t --steps 6 --warmup 2 --no-cpu-baseline > $out/team_$t.json 2>/dev/null
 python - $t $out/team_$t.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 out=gpurun_out/r06/bench${TAG:+_$TAG}; mkdir -p $out
 R=$GRAFT_REPO_ROOT
 cd /tmp; export TMPDIR=/tmp
-timeout 400 python $R/bench.py --steps ${STEPS:-60} --warmup 8 ${BENCH_ARGS} > $R/$out/bench_s3.json 2> $R/$out/bench_s3.err
+timeout 400 python $R/bench.py --full --steps ${STEPS:-60} --warmup 8 ${BENCH_ARGS} > $R/$out/bench_s3.json 2> $R/$out/bench_s3.err
 python - $R/$out/bench_s3.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

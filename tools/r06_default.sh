@@ -4,7 +4,7 @@ out=gpurun_out/r06/default${TAG:+_$TAG}; mkdir -p $out
 R=$GRAFT_REPO_ROOT
 cd /tmp; export TMPDIR=/tmp
 start=$(date +%s.%N)
-python $R/bench.py > $R/$out/bench_default.json 2> $R/$out/bench_default.err
+python $R/bench.py --full > $R/$out/bench_default.json 2> $R/$out/bench_default.err
 end=$(date +%s.%N)
 echo "wall seconds $(echo "$end - $start" | bc)"
 python - $R/$out/bench_default.json <<'PY'

@@ -7,7 +7,7 @@ i=0
 while IFS= read -r variant; do
   [ -z "$variant" ] && continue
   i=$((i+1))
-  env $variant RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 RPVG_BENCH_NO_SINGLE_DATASET=1 timeout 300 python $R/bench.py --steps ${STEPS:-40} --warmup 6 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
+  env $variant RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 RPVG_BENCH_NO_SINGLE_DATASET=1 timeout 300 python $R/bench.py --full --steps ${STEPS:-40} --warmup 6 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
   python - "$variant" $R/$out/v$i.json <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ i=0
 while IFS= read -r variant; do
   [ -z "$variant" ] && continue
   i=$((i+1))
-  env $variant RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 200 python $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
+  env $variant RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 200 python $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline > $R/$out/v$i.json 2> $R/$out/v$i.err
   python - "$variant" $R/$out/v$i.json <<'PY'
 import json,sys
 try:

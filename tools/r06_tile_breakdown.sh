@@ -6,9 +6,9 @@
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/r06/tiledbg; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-RPVG_HIP_SEARCH_CLASSES=1 RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 300 python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline 2>&1 | grep "search classes" | head -9 > $out/pair_tile_breakdown.txt
+RPVG_HIP_SEARCH_CLASSES=1 RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 300 python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline 2>&1 | grep "search classes" | head -9 > $out/pair_tile_breakdown.txt
 for dbg in ${DBG:-0 1 2 4 8 15 16 31 63 95 159}; do
-RPVG_HIP_PAIR_DEBUG=$dbg RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/p$dbg -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/log$dbg 2>&1
+RPVG_HIP_PAIR_DEBUG=$dbg RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_DROP_IN_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/p$dbg -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/log$dbg 2>&1
 python - <<PY >> $out/pair_tile_breakdown.txt
 import csv,glob
 f=glob.glob("$out/p$dbg/*/*kernel_stats.csv")[0]

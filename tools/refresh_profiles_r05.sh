@@ -20,16 +20,16 @@ except Exception as e:
 PY
 }
 # the driver's line (everything inside: one batch at a time, the pipeline, host bound, configs[4], dense EM, CPU baseline)
-timeout 900 python bench.py 2>$out/bench_s3.err | tail -1 > $out/bench_s3_n1.json; stamp $out/bench_s3_n1.json
-timeout 900 python bench.py --steps 200 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_200_steps.json; stamp $out/bench_s3_n1_200_steps.json
-RPVG_AMD_PIPELINE_WORKERS=1 timeout 900 python bench.py --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_one_worker.json; stamp $out/bench_s3_n1_one_worker.json
-RPVG_AMD_PIPELINE_WORKERS=2 timeout 900 python bench.py --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_two_workers.json; stamp $out/bench_s3_n1_two_workers.json
-RPVG_AMD_HOST_SOURCE_GROUPS=1 timeout 900 python bench.py --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_host_source_groups.json; stamp $out/bench_s3_n1_host_source_groups.json
-RPVG_HIP_SPIN_WAITS=1 timeout 900 python bench.py --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_spin_waits.json; stamp $out/bench_s3_n1_spin_waits.json
+timeout 900 python bench.py --full 2>$out/bench_s3.err | tail -1 > $out/bench_s3_n1.json; stamp $out/bench_s3_n1.json
+timeout 900 python bench.py --full --steps 200 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_200_steps.json; stamp $out/bench_s3_n1_200_steps.json
+RPVG_AMD_PIPELINE_WORKERS=1 timeout 900 python bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_one_worker.json; stamp $out/bench_s3_n1_one_worker.json
+RPVG_AMD_PIPELINE_WORKERS=2 timeout 900 python bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_two_workers.json; stamp $out/bench_s3_n1_two_workers.json
+RPVG_AMD_HOST_SOURCE_GROUPS=1 timeout 900 python bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_host_source_groups.json; stamp $out/bench_s3_n1_host_source_groups.json
+RPVG_HIP_SPIN_WAITS=1 timeout 900 python bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_spin_waits.json; stamp $out/bench_s3_n1_spin_waits.json
 # the switches between two correct implementations of the second half of the round (docs/design/history-r05.md), one at a time, no one-batch leg
 ab() {  # name, env...
   name=$1; shift
-  env "$@" RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 900 python bench.py --steps 120 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_120_steps_$name.json; stamp $out/bench_s3_n1_120_steps_$name.json
+  env "$@" RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 RPVG_BENCH_NO_HOST_BOUND=1 timeout 900 python bench.py --full --steps 120 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_s3_n1_120_steps_$name.json; stamp $out/bench_s3_n1_120_steps_$name.json
 }
 ab default RPVG_X=1
 ab pooled_main_queue RPVG_HIP_POOLED_MAIN_QUEUE=1
@@ -37,32 +37,32 @@ ab register_bins_in_five_launches RPVG_HIP_EM_REGISTER_LAUNCHES=5
 ab collapse_before_search RPVG_HIP_COLLAPSE_BEFORE_SEARCH=1
 ab mask_build RPVG_HIP_BUILD_MASKS=1
 ab default_again RPVG_X=2
-timeout 900 python bench.py --workload c2 --steps 4 --warmup 1 2>$out/bench_c2.err | tail -1 > $out/bench_c2_n1.json; stamp $out/bench_c2_n1.json
-timeout 900 python bench.py --workload s5 --steps 40 --warmup 6 2>$out/bench_s5.err | tail -1 > $out/bench_s5_n1.json; stamp $out/bench_s5_n1.json
-timeout 900 python bench.py --workload rows --steps 10 --warmup 2 2>$out/bench_rows.err | tail -1 > $out/bench_rows_n1.json; stamp $out/bench_rows_n1.json
-timeout 900 python bench.py --workload e2e --steps 10 --warmup 2 2>$out/bench_e2e.err | tail -1 > $out/bench_e2e_n1.json; stamp $out/bench_e2e_n1.json
-for t in 64 256; do timeout 900 python bench.py --workload a1 --team $t --steps 5 2>/dev/null | tail -1 > $out/bench_a1_n1_team_$t.json; stamp $out/bench_a1_n1_team_$t.json; done
-RPVG_AMD_NO_COMBINER=1 timeout 900 python bench.py --workload a1 --team 64 --steps 1 --warmup 1 2>/dev/null | tail -1 > $out/bench_a1_n1_team_64_no_combiner.json; stamp $out/bench_a1_n1_team_64_no_combiner.json
+timeout 900 python bench.py --full --workload c2 --steps 4 --warmup 1 2>$out/bench_c2.err | tail -1 > $out/bench_c2_n1.json; stamp $out/bench_c2_n1.json
+timeout 900 python bench.py --full --workload s5 --steps 40 --warmup 6 2>$out/bench_s5.err | tail -1 > $out/bench_s5_n1.json; stamp $out/bench_s5_n1.json
+timeout 900 python bench.py --full --workload rows --steps 10 --warmup 2 2>$out/bench_rows.err | tail -1 > $out/bench_rows_n1.json; stamp $out/bench_rows_n1.json
+timeout 900 python bench.py --full --workload e2e --steps 10 --warmup 2 2>$out/bench_e2e.err | tail -1 > $out/bench_e2e_n1.json; stamp $out/bench_e2e_n1.json
+for t in 64 256; do timeout 900 python bench.py --full --workload a1 --team $t --steps 5 2>/dev/null | tail -1 > $out/bench_a1_n1_team_$t.json; stamp $out/bench_a1_n1_team_$t.json; done
+RPVG_AMD_NO_COMBINER=1 timeout 900 python bench.py --full --workload a1 --team 64 --steps 1 --warmup 1 2>/dev/null | tail -1 > $out/bench_a1_n1_team_64_no_combiner.json; stamp $out/bench_a1_n1_team_64_no_combiner.json
 python tools/em_iter_latency.py 20000 > $out/em_iteration_latency.txt 2>&1
 cd /tmp; export TMPDIR=/tmp
 prof() {  # name, env + bench args...
   name=$1; shift
-  RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$name -- python $R/bench.py "$@" --no-cpu-baseline 2>$out/prof_$name.err | tail -1 > $out/bench_${name}_n1_profiled.json
+  RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$name -- python $R/bench.py --full "$@" --no-cpu-baseline 2>$out/prof_$name.err | tail -1 > $out/bench_${name}_n1_profiled.json
   cp $out/prof_$name/*/*kernel_stats.csv $out/rocprofv3_${name}_kernel_stats.csv; rm -rf $out/prof_$name
   stamp $out/bench_${name}_n1_profiled.json
 }
 prof s3 --steps 40 --warmup 8
 prof c2 --workload c2 --steps 4 --warmup 1
 prof s5 --workload s5 --steps 10 --warmup 2
-RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $out/prof_tl -- python $R/bench.py --steps 24 --warmup 4 --no-cpu-baseline > /dev/null 2>&1
+RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $out/prof_tl -- python $R/bench.py --full --steps 24 --warmup 4 --no-cpu-baseline > /dev/null 2>&1
 python $R/tools/gpu_busy_union.py $out/prof_tl 16 > $out/gpu_busy_s3_pipeline.txt 2>&1
 python $R/tools/r05_pipe_timeline.py $out/prof_tl 14 25 > $out/kernel_timeline_s3_pipeline.txt 2>&1; rm -rf $out/prof_tl
-RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $out/prof_tl1 -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+RPVG_BENCH_NO_PIPELINE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $out/prof_tl1 -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 python $R/tools/kernel_timeline.py $out/prof_tl1 15 > $out/kernel_timeline_s3_one_batch.txt 2>&1; rm -rf $out/prof_tl1
 # PMC passes (each in its own run: counter slots; --kernel-trace only).  One host lane, the pipeline only: every launch holds a whole batch.
 pmc() {  # dir, counters, bench args...
   d=$1; c=$2; shift 2
-  RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$d -- python $R/bench.py "$@" --no-cpu-baseline > $out/$d.log 2>&1
+  RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_SINGLE=1 RPVG_BENCH_NO_GIBBS_LINE=1 timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$d -- python $R/bench.py --full "$@" --no-cpu-baseline > $out/$d.log 2>&1
 }
 pmc pmc_s3_fetch FETCH_SIZE --steps 2 --warmup 1
 pmc pmc_s3_write WRITE_SIZE --steps 2 --warmup 1
@@ -75,10 +75,10 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE" "SQ_ACTIVE_I
 done
 cd $R
 python tools/pmc_traffic.py --fetch-dir $out/pmc_s3_fetch --write-dir $out/pmc_s3_write --kernel emSparseKernel,emRegisterKernel --steps 1 --commit $commit \
-  --command "RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_SINGLE=1 rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline (two separate passes; every launch holds the EM problems of a whole batch; per-launch figures only)" \
+  --command "RPVG_AMD_SINGLE_LANE=1 RPVG_BENCH_NO_SINGLE=1 rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (two separate passes; every launch holds the EM problems of a whole batch; per-launch figures only)" \
   --out $out/pmc_traffic_s3.json > /dev/null
 python tools/pmc_traffic.py --fetch-dir $out/pmc_c2_fetch --write-dir $out/pmc_c2_write --kernel emDenseAccum --steps 150 --double-fetch --shape 1000000,2001,2002 --commit $commit \
-  --command "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python bench.py --workload c2 --steps 1 --warmup 1 --no-cpu-baseline (two separate passes; 3 estimator calls x 50 EM iterations = 150 launches)" \
+  --command "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python bench.py --full --workload c2 --steps 1 --warmup 1 --no-cpu-baseline (two separate passes; 3 estimator calls x 50 EM iterations = 150 launches)" \
   --out $out/pmc_traffic_c2.json > /dev/null
 python tools/pmc_kernels.py $out/pmc_search_1 $out/pmc_search_2 $out/pmc_search_3 $out/pmc_search_4 --kernel pairTile,resolveTable,groupsBuild,fillSegments,subsetSelect,subsetMerge,sourceColumns,emRegister,emSparse,collapse,partitionRows,expandGroups,validateRows > $out/pmc_s3_throughput_kernels.txt
 (cd $out && python $R/tools/pmc_search_summary.py pmc_s3_throughput_kernels.txt 4573105636 pmc_search_s3.json $commit pairTile2Kernel > /dev/null)
