@@ -287,6 +287,26 @@ int rpvg_hip_group_conditionals(rpvg_hip_ctx * ctx, const rpvg_hip_groups * grou
                                 const uint32_t * matrix, const uint32_t * others, uint32_t width, double divisor,
                                 double * out);
 
+/* ---- full enumeration of the group posteriors, on the device ---------------------- */
+/* calculatePathGroupPosteriorsFull (src/path_estimator.cpp:332-377) for group sizes 1 .. 8: for every problem q (matrix[q]
+ * of `groups`, G_q columns) the posterior of every multiset of group_size columns,
+ *   exp( sum_i count_i * log( noise_i + sum_m M[i][m] / group_size ) + sum_m log_freq[m] + log(numPermutations) - logsum ),
+ * in lexicographic order of the non-decreasing member lists (the order of PathClusterEstimates::generateGroups), the
+ * rpvg_hip_full_set_count(G_q, group_size) sets of each problem back to back in `posteriors`.  The sets are enumerated
+ * on the device from their ranks; log_freq holds calcPathLogFrequences of every column, problems back to back.
+ * numPermutations is the reference's n! / (n - u + 1)! truncated to an integer (src/utils.hpp:95-117, u distinct members:
+ * the multinomial only up to n = 3).  logsum is formed per problem as max + log(sum exp(x - max)) in a fixed order (two
+ * calls give the same bits; the reference folds add_log set by set: the last bits may differ).
+ * Returns RPVG_HIP_ERR_UNSUPPORTED, having changed nothing, when a problem has more than RPVG_HIP_FULL_MAX_SETS sets.
+ * A batch is split into launches of at most 2^27 sets (one larger problem alone). */
+#define RPVG_HIP_FULL_MAX_SETS 0x7fffffffull
+int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t num_problems,
+                                   const uint32_t * matrix, uint32_t group_size, const double * log_freq,
+                                   double * posteriors);
+/* C(columns + group_size - 1, group_size): the multisets of group_size out of `columns` (0 for no columns); UINT64_MAX when
+ * it does not fit in 64 bits. */
+uint64_t rpvg_hip_full_set_count(uint32_t columns, uint32_t group_size);
+
 /* ---- the Gibbs sampler of the group posteriors, on the device ---------------------- */
 /* estimatePathGroupPosteriorsGibbs (src/path_estimator.cpp:475-589) for group sizes 1 and 2, draw for draw up to the
  * floating-point reduction order of a distribution's sums (the conditional's log-sum-exp, the weight sum and the partial sums

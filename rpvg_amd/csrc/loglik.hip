@@ -1404,7 +1404,7 @@ extern "C" int rpvg_hip_group_loglik(rpvg_hip_ctx * ctx, const rpvg_hip_groups *
     RPVG_REQUIRE(ctx && groups, "rpvg_hip_group_loglik: NULL argument");
     if (num_requests == 0) return RPVG_HIP_OK;
     RPVG_REQUIRE(matrix && members && out, "rpvg_hip_group_loglik: NULL request arrays");
-    RPVG_REQUIRE(width >= 1 && width <= 4, "rpvg_hip_group_loglik: width %u outside [1, 4]", width);
+    RPVG_REQUIRE(width >= 1 && width <= 8, "rpvg_hip_group_loglik: width %u outside [1, 8]", width);
     RPVG_REQUIRE(divisor > 0, "rpvg_hip_group_loglik: divisor must be positive");
     double evals = 0;
     for (uint32_t q = 0; q < num_requests; ++q) {
@@ -1444,7 +1444,11 @@ extern "C" int rpvg_hip_group_loglik(rpvg_hip_ctx * ctx, const rpvg_hip_groups *
         case 1: RPVG_LAUNCH_LOGLIK(1); break;
         case 2: RPVG_LAUNCH_LOGLIK(2); break;
         case 3: RPVG_LAUNCH_LOGLIK(3); break;
-        default: RPVG_LAUNCH_LOGLIK(4); break;
+        case 4: RPVG_LAUNCH_LOGLIK(4); break;
+        case 5: RPVG_LAUNCH_LOGLIK(5); break;
+        case 6: RPVG_LAUNCH_LOGLIK(6); break;
+        case 7: RPVG_LAUNCH_LOGLIK(7); break;
+        default: RPVG_LAUNCH_LOGLIK(8); break;
     }
 #undef RPVG_LAUNCH_LOGLIK
     ctx->spanEnd(span);
@@ -1462,7 +1466,7 @@ extern "C" int rpvg_hip_group_conditionals(rpvg_hip_ctx * ctx, const rpvg_hip_gr
     RPVG_REQUIRE(ctx && groups, "rpvg_hip_group_conditionals: NULL argument");
     if (num_requests == 0) return RPVG_HIP_OK;
     RPVG_REQUIRE(matrix && out && (others || width == 1), "rpvg_hip_group_conditionals: NULL request arrays");
-    RPVG_REQUIRE(width >= 1 && width <= 4, "rpvg_hip_group_conditionals: width %u outside [1, 4]", width);
+    RPVG_REQUIRE(width >= 1 && width <= 8, "rpvg_hip_group_conditionals: width %u outside [1, 8]", width);
     RPVG_REQUIRE(divisor > 0, "rpvg_hip_group_conditionals: divisor must be positive");
     std::vector<uint64_t> item_off(num_requests + 1, 0), out_off(num_requests + 1, 0);
     double evals = 0;
@@ -1511,7 +1515,11 @@ extern "C" int rpvg_hip_group_conditionals(rpvg_hip_ctx * ctx, const rpvg_hip_gr
         case 1: RPVG_LAUNCH_COND(1); break;
         case 2: RPVG_LAUNCH_COND(2); break;
         case 3: RPVG_LAUNCH_COND(3); break;
-        default: RPVG_LAUNCH_COND(4); break;
+        case 4: RPVG_LAUNCH_COND(4); break;
+        case 5: RPVG_LAUNCH_COND(5); break;
+        case 6: RPVG_LAUNCH_COND(6); break;
+        case 7: RPVG_LAUNCH_COND(7); break;
+        default: RPVG_LAUNCH_COND(8); break;
     }
 #undef RPVG_LAUNCH_COND
     ctx->spanEnd(span);

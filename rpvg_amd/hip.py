@@ -34,6 +34,7 @@ EXPORTS = [
     "rpvg_hip_batch_source_columns_get", "rpvg_hip_groups_build_from_sources", "rpvg_hip_groups_build_single_paths", "rpvg_hip_batch_upload_begin", "rpvg_hip_batch_upload_finish", "rpvg_hip_create_with_streams",
     "rpvg_hip_batch_upload_finish_queue", "rpvg_hip_batch_upload_finish_wait",
     "rpvg_hip_batch_upload_segments", "rpvg_hip_pinned_alloc", "rpvg_hip_pinned_free", "rpvg_hip_thread_wait_spin_us",
+    "rpvg_hip_group_full_posteriors", "rpvg_hip_full_set_count",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -123,6 +124,7 @@ def lib() -> C.CDLL:
                               "(there is no CPU fallback)")
         L = C.CDLL(LIB_PATH)
         L.rpvg_hip_last_error.restype = C.c_char_p
+        L.rpvg_hip_full_set_count.restype = C.c_uint64
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -404,6 +406,20 @@ class DeviceGroups:
                                                  C.c_void_p(oth.ctypes.data if oth.size else None), C.c_uint32(width),
                                                  C.c_double(divisor), C.c_void_p(out.ctypes.data)),
                "rpvg_hip_group_conditionals")
+        return np.split(out, np.cumsum(sizes)[:-1]) if sizes else []
+
+    def full_posteriors(self, matrix, group_size: int, log_freq, num_cols) -> List[np.ndarray]:
+        """rpvg_hip_group_full_posteriors: per problem, the posterior of every multiset of group_size columns of its matrix
+        (num_cols[m] columns), in lexicographic order of the member lists; log_freq[q] = the log frequencies of problem q's
+        columns."""
+        mt = np.ascontiguousarray(matrix, dtype=np.uint32)
+        lf = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in log_freq]) if len(log_freq) else np.zeros(0))
+        sizes = [int(lib().rpvg_hip_full_set_count(C.c_uint32(int(num_cols[int(m)])), C.c_uint32(group_size))) for m in mt]
+        out = np.zeros(sum(s for s in sizes if s <= 0x7fffffff), dtype=np.float64)
+        _check(lib().rpvg_hip_group_full_posteriors(self.ctx.handle, self.handle, C.c_uint32(len(mt)), C.c_void_p(mt.ctypes.data),
+                                                    C.c_uint32(group_size), C.c_void_p(lf.ctypes.data if lf.size else None),
+                                                    C.c_void_p(out.ctypes.data if out.size else None)),
+               "rpvg_hip_group_full_posteriors")
         return np.split(out, np.cumsum(sizes)[:-1]) if sizes else []
 
     def gibbs(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):

@@ -333,7 +333,7 @@ void MinimumPathAbundanceEstimator::estimateBatch(std::vector<PathClusterEstimat
     }
 }
 
-NestedPathAbundanceEstimator::NestedPathAbundanceEstimator(const uint32_t group_size_in, const double min_hap_prob_in, const bool infer_collapsed_in, const bool use_group_post_gibbs_in, const uint32_t max_em_its, const double max_rel_em_conv, const uint32_t num_gibbs_samples, const uint32_t gibbs_thin_its, const double prob_precision, std::shared_ptr<HipEngine> engine) : PathAbundanceEstimator(max_em_its, max_rel_em_conv, num_gibbs_samples, gibbs_thin_its, prob_precision, engine), group_size(group_size_in), min_hap_prob(min_hap_prob_in), infer_collapsed(infer_collapsed_in), use_group_post_gibbs(use_group_post_gibbs_in) {}
+NestedPathAbundanceEstimator::NestedPathAbundanceEstimator(const uint32_t group_size_in, const double min_hap_prob_in, const bool infer_collapsed_in, const bool use_group_post_gibbs_in, const uint32_t max_em_its, const double max_rel_em_conv, const uint32_t num_gibbs_samples, const uint32_t gibbs_thin_its, const double prob_precision, std::shared_ptr<HipEngine> engine) : PathAbundanceEstimator(max_em_its, max_rel_em_conv, num_gibbs_samples, gibbs_thin_its, prob_precision, engine), group_size(checkGroupSize(group_size_in)), min_hap_prob(min_hap_prob_in), infer_collapsed(infer_collapsed_in), use_group_post_gibbs(use_group_post_gibbs_in) {}
 
 // src/path_abundance_estimator.cpp:344-471 over a batch of clusters: posteriors of
 // all clusters first (one set of GPU calls), then the EM solves of every retained
@@ -943,8 +943,12 @@ void NestedPathAbundanceEstimator::sampleGroupPathIndices(std::vector<std::vecto
     const std::vector<double> & weights = group_posteriors.posteriors;
     std::discrete_distribution<uint32_t> draw_set(weights.begin(), weights.end());
 
-    uint32_t columns[8];
-    assert(group_size <= 8);
+    uint32_t columns[max_group_size];
+
+    if (group_size > max_group_size) {
+
+        throw EngineError("sampleGroupPathIndices: group size " + std::to_string(group_size) + " above " + std::to_string(max_group_size));
+    }
 
     for (size_t slot = 0; slot < path_subset_samples->size(); ++slot) {
 
@@ -1011,12 +1015,13 @@ void NestedPathAbundanceEstimator::mergeSubsetSolutions(std::vector<PathClusterE
 
     ScopedPhase merge_phase("nested: weighted merge");
 
-    // (the device path is the diploid one; the keys below hold up to four paths: ploidy <= 4, as everywhere on the device)
-    constexpr uint32_t max_group_size = 4;
+    // (rpvg_hip_nested_subset_em is the diploid route — estimateClusters calls it at group size 2 only —: the keys below hold
+    // up to four paths of a transcript; every other ploidy merges through the ordered map of the separate calls)
+    constexpr uint32_t max_key_paths = 4;
 
-    if (group_size > max_group_size) {
+    if (group_size > max_key_paths) {
 
-        throw EngineError("weighted merge of device-built subsets: group size above 4");
+        throw EngineError("weighted merge of device-built subsets: group size " + std::to_string(group_size) + " above " + std::to_string(max_key_paths) + " (the device subsets serve ploidy 2)");
     }
 
     #pragma omp parallel for schedule(static, clusterChunk()) num_threads(hostThreads())
@@ -1040,10 +1045,10 @@ void NestedPathAbundanceEstimator::mergeSubsetSolutions(std::vector<PathClusterE
         // 5 000-cluster batch.
         struct Entry {
 
-            std::array<uint32_t, max_group_size> key;
+            std::array<uint32_t, max_key_paths> key;
             uint32_t size;
             double weight;
-            std::array<double, max_group_size> abundance;
+            std::array<double, max_key_paths> abundance;
         };
 
         static thread_local std::vector<Entry> entries;
@@ -1104,7 +1109,7 @@ void NestedPathAbundanceEstimator::mergeSubsetSolutions(std::vector<PathClusterE
                     ++g1;
                 }
 
-                assert(g1 - g0 <= group_size && g1 - g0 <= max_group_size);
+                assert(g1 - g0 <= group_size && g1 - g0 <= max_key_paths);
 
                 Entry entry;
                 entry.key.fill(0);
@@ -1136,7 +1141,7 @@ void NestedPathAbundanceEstimator::mergeSubsetSolutions(std::vector<PathClusterE
 
             size_t e1 = e0;
             double posterior = 0;
-            std::array<double, max_group_size> sums;
+            std::array<double, max_key_paths> sums;
             sums.fill(0);
 
             while (e1 < entries.size() && entries[e1].key == entries[e0].key) {

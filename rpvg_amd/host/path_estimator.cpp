@@ -182,6 +182,16 @@ class GroupMatrices {
             }
         }
 
+        // Posteriors of every multiset of group_size columns of each matrix (lexicographic order), enumerated and normalised on
+        // the device: `posteriors` receives the sets of the matrices back to back.
+        void fullPosteriors(std::vector<double> * posteriors, const std::vector<uint32_t> & matrix, const uint32_t group_size, const std::vector<double> & log_freqs, const size_t num_sets) const {
+
+            ScopedPhase phase("posteriors: full enumeration device call");
+
+            posteriors->assign(num_sets, 0);
+            HipEngine::check(rpvg_hip_group_full_posteriors(engine->ctx(), groups, matrix.size(), matrix.data(), group_size, log_freqs.data(), posteriors->data()), "rpvg_hip_group_full_posteriors");
+        }
+
         // Whole conditionals (every candidate column given the other members), request after request.
         void conditionals(std::vector<double> * out, const std::vector<uint32_t> & matrix, const std::vector<uint32_t> & others, const size_t num_values, const uint32_t width, const double divisor) const {
 
@@ -1089,6 +1099,16 @@ void PathEstimator::estimateBatchSeeded(std::vector<PathClusterEstimates> * path
     estimateBatch(path_cluster_estimates, cluster_batch, &rngs);
 }
 
+uint32_t checkGroupSize(const uint32_t group_size) {
+
+    if (group_size < 1 || group_size > max_group_size) {
+
+        throw EngineError("ploidy (-y, --ploidy) " + std::to_string(group_size) + " is outside the supported range 1 .. " + std::to_string(max_group_size));
+    }
+
+    return group_size;
+}
+
 std::vector<double> PathEstimator::calcPathLogFrequences(const std::vector<uint32_t> & path_counts) {
 
     const uint32_t count_sum = std::accumulate(path_counts.begin(), path_counts.end(), 0u);
@@ -1130,15 +1150,20 @@ void PathEstimator::calculatePathGroupPosteriorsFull(std::vector<GroupPosteriors
 
     assert(group_size > 0);
 
-    if (group_size > 4) {
-
-        throw EngineError("calculatePathGroupPosteriorsFull: group sizes above 4 are not supported by the GPU log-likelihood kernel");
-    }
+    checkGroupSize(group_size);
 
     group_posteriors->assign(problems.size(), GroupPosteriors());
 
     if (problems.empty()) {
 
+        return;
+    }
+
+    // group sizes 5 .. 8: the sets are enumerated, evaluated and normalised on the device (rpvg_hip_group_full_posteriors);
+    // 1, 3 and 4 keep the request route below
+    if (group_size > 4) {
+
+        calculatePathGroupPosteriorsFullOnDevice(group_posteriors, cluster_batch, problems, group_size, normalise);
         return;
     }
 
@@ -1204,6 +1229,73 @@ void PathEstimator::calculatePathGroupPosteriorsFull(std::vector<GroupPosteriors
         for (auto & posterior: result.posteriors) {
 
             posterior = std::exp(posterior - sum_log_posterior);
+        }
+    }
+}
+
+void PathEstimator::calculatePathGroupPosteriorsFullOnDevice(std::vector<GroupPosteriors> * group_posteriors, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const bool normalise) const {
+
+    std::vector<uint64_t> num_sets(problems.size());
+    std::vector<uint32_t> problem_matrix(problems.size());
+    std::vector<double> log_freqs;
+    size_t total_sets = 0;
+
+    for (size_t i = 0; i < problems.size(); ++i) {
+
+        num_sets[i] = rpvg_hip_full_set_count(problems[i].numColumns(), group_size);
+
+        if (num_sets[i] > RPVG_HIP_FULL_MAX_SETS) {
+
+            throw EngineError("cluster " + std::to_string(problems[i].cluster) + ": full enumeration of the haplotype sets of ploidy " + std::to_string(group_size) + " over " + std::to_string(problems[i].numColumns()) + " columns exceeds " + std::to_string(RPVG_HIP_FULL_MAX_SETS) + " sets (use --use-hap-gibbs)");
+        }
+
+        problem_matrix[i] = i;
+        total_sets += num_sets[i];
+
+        const auto path_log_freqs = calcPathLogFrequences(problems[i].column_counts);
+        log_freqs.insert(log_freqs.end(), path_log_freqs.begin(), path_log_freqs.end());
+    }
+
+    const GroupMatrices matrices(engine, cluster_batch, problems, normalise, prob_precision);
+
+    std::vector<double> posteriors;
+    matrices.fullPosteriors(&posteriors, problem_matrix, group_size, log_freqs, total_sets);
+
+    std::vector<size_t> first_set(problems.size() + 1, 0);
+
+    for (size_t i = 0; i < problems.size(); ++i) {
+
+        first_set[i + 1] = first_set[i] + num_sets[i];
+    }
+
+    #pragma omp parallel for schedule(dynamic, 8) num_threads(hostThreads())
+    for (size_t i = 0; i < problems.size(); ++i) {
+
+        auto & result = group_posteriors->at(i);
+        result.group_size = group_size;
+        result.posteriors.assign(posteriors.begin() + first_set[i], posteriors.begin() + first_set[i + 1]);
+        result.members.resize(num_sets[i] * group_size);
+
+        // the members of the sets in rank order: lexicographic, non-decreasing (PathClusterEstimates::generateGroups)
+        std::vector<uint32_t> set(group_size, 0);
+
+        for (size_t j = 0; j < num_sets[i]; ++j) {
+
+            std::copy(set.begin(), set.end(), result.members.begin() + j * group_size);
+
+            int k = static_cast<int>(group_size) - 1;
+
+            while (k >= 0 && set[k] + 1 == problems[i].numColumns()) {
+
+                --k;
+            }
+
+            if (k < 0) {
+
+                break;
+            }
+
+            std::fill(set.begin() + k, set.end(), set[k] + 1);
         }
     }
 }
@@ -1744,10 +1836,7 @@ void PathEstimator::estimatePathGroupPosteriorsGibbs(std::vector<GroupPosteriors
     assert(group_size > 0);
     assert(rngs.size() == problems.size());
 
-    if (group_size > 4) {
-
-        throw EngineError("estimatePathGroupPosteriorsGibbs: group sizes above 4 are not supported by the GPU log-likelihood kernel");
-    }
+    checkGroupSize(group_size);
 
     group_posteriors->assign(problems.size(), GroupPosteriors());
 

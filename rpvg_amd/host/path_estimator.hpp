@@ -107,6 +107,13 @@ struct GroupPosteriorProblem {
     const uint32_t * columnEnd(const uint32_t column) const { return column_path.data() + column_path_off[column + 1]; }
 };
 
+// Largest ploidy (-y) the haplotype models take: the widest template of the device kernels.
+constexpr uint32_t max_group_size = 8;
+
+// group_size; throws EngineError naming the value and the limit unless 1 <= group_size <= max_group_size (the
+// haplotype estimators check their ploidy with it when they are constructed).
+uint32_t checkGroupSize(const uint32_t group_size);
+
 // Group sets (multisets of `group_size` column indices, flat) and their posteriors.
 struct GroupPosteriors {
 
@@ -173,8 +180,14 @@ class PathEstimator {
         void runInLanes(const std::vector<uint32_t> & clusters, const std::function<void(const std::vector<uint32_t> &, const std::function<void()> &)> & work) const;
 
         // calculatePathGroupPosteriorsFull (src/path_estimator.cpp:332-377) for many
-        // problems at once; log-likelihood contractions on the GPU.
+        // problems at once; log-likelihood contractions on the GPU.  Group sizes 5 .. 8 go
+        // through calculatePathGroupPosteriorsFullOnDevice.
         void calculatePathGroupPosteriorsFull(std::vector<GroupPosteriors> * group_posteriors, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const bool normalise) const;
+
+        // The same with the sets enumerated, evaluated and normalised on the device (rpvg_hip_group_full_posteriors):
+        // only the posteriors come back; the members are listed here in rank order.  Throws EngineError naming the
+        // cluster when a problem has more than RPVG_HIP_FULL_MAX_SETS sets.
+        void calculatePathGroupPosteriorsFullOnDevice(std::vector<GroupPosteriors> * group_posteriors, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const bool normalise) const;
 
         // calculatePathGroupPosteriorsBounded (src/path_estimator.cpp:379-473) for many
         // problems at once: one GPU workgroup per problem walks the branch-and-bound in

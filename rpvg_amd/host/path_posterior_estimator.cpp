@@ -80,7 +80,7 @@ void PathPosteriorEstimator::estimateBatch(std::vector<PathClusterEstimates> * p
     }
 }
 
-PathGroupPosteriorEstimator::PathGroupPosteriorEstimator(const uint32_t group_size_in, const bool use_group_post_gibbs_in, const double prob_precision, std::shared_ptr<HipEngine> engine) : PathPosteriorEstimator(prob_precision, engine), group_size(group_size_in), use_group_post_gibbs(use_group_post_gibbs_in) {}
+PathGroupPosteriorEstimator::PathGroupPosteriorEstimator(const uint32_t group_size_in, const bool use_group_post_gibbs_in, const double prob_precision, std::shared_ptr<HipEngine> engine) : PathPosteriorEstimator(prob_precision, engine), group_size(checkGroupSize(group_size_in)), use_group_post_gibbs(use_group_post_gibbs_in) {}
 
 // src/path_posterior_estimator.cpp:35-71 over a batch of clusters.
 void PathGroupPosteriorEstimator::estimateBatch(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, std::vector<std::mt19937> * rngs) {
