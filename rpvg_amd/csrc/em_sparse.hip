@@ -121,7 +121,7 @@ __device__ __forceinline__ void blockExclusiveScanPair(uint32_t & a, uint32_t & 
 //   4-6 register-resident dense, one wave: at most 16 columns and 64 / 128 / 256 rows (emRegisterKernel)
 //   7  LDS-resident, sixteen waves  CSR + vectors fit 152 KB (one workgroup per CU: the whole LDS)
 //   8-9 register-resident dense, one wave: 17 to 32 columns and 64 / 128 rows
-//   10 too many columns for LDS-resident vectors (> ~9 700): vectors in global memory, 16 waves
+//   10 too many columns for LDS-resident vectors (C >= 3 993): vectors in global memory, 16 waves
 //   11 the grid bin: rows + entries at or above EmBinRule::grid_min_work — not one workgroup but the whole GPU, one round
 //      of launches per EM iteration, driven by the host (em_grid.hip); no kernel of this file serves it
 constexpr int kEmBins = RPVG_HIP_EM_KERNELS;
@@ -844,7 +844,7 @@ __device__ __forceinline__ uint32_t nextProblem(const EmLaunchArgs & args, uint3
 // RESIDENT: the problem's compacted CSR is copied into LDS once and every EM iteration runs out of LDS
 // (small problems need up to thousands of iterations; from L2 each costs ~1.7 us of dependent-load
 // latency, from LDS a fraction of that).
-// WIDE: the abundance and accumulator vectors do not fit LDS (more than ~10 000 columns: the reference's EM has no
+// WIDE: the abundance and accumulator vectors do not fit LDS (C >= 3 993 columns: the reference's EM has no
 // size limit, and clusters such as HLA exceed this): they live in global memory (L2), the M-step uses global FP64 atomics.
 template <int BLOCK, bool RESIDENT, bool WIDE>
 __device__ __forceinline__ void emSparseProblem(const EmLaunchArgs & args, const uint32_t p, unsigned char * smem_raw) {

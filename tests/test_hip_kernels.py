@@ -100,7 +100,7 @@ def test_register_em_in_copies_equals_one_copy_to_the_bit(hip_ctx):
 
 
 def test_em_solve_cluster_wider_than_lds(hip_ctx):
-    """A cluster with more paths than LDS-resident abundance vectors hold (~9 700 columns): the reference's EM has no
+    """A cluster with more paths than LDS-resident abundance vectors hold (C >= 3 993 columns: the wide bin): the reference's EM has no
     size limit (src/path_abundance_estimator.cpp:47-114); its vectors then live in global memory.  Next to small
     clusters in the same call."""
     rng = np.random.default_rng(431)
