@@ -331,7 +331,7 @@ uint64_t rpvg_hip_full_set_count(uint32_t columns, uint32_t group_size);
  * the caller then drives the sampler itself through rpvg_hip_group_conditionals. */
 typedef struct rpvg_hip_gibbs_spec {
     uint32_t num_problems;
-    uint32_t group_size;                    /* 1 or 2                                                                  */
+    uint32_t group_size;                    /* rpvg_hip_group_gibbs: 1 or 2; rpvg_hip_group_gibbs_polyploid: 3 .. 8    */
     const uint32_t * matrix;                /* [P]   matrix of `groups` the problem samples on                         */
     const uint32_t * num_chains;            /* [P]   :501                                                              */
     const uint32_t * num_burn_its;          /* [P]   :502                                                              */
@@ -348,8 +348,8 @@ typedef struct rpvg_hip_gibbs_sets_view {
     uint32_t num_problems;
     uint32_t group_size;
     const uint64_t * set_off;        /* [P+1] sampled sets of each problem                                             */
-    const uint32_t * first;          /* [sets] smaller member (the member, for group size 1)                           */
-    const uint32_t * second;         /* [sets] larger member                                                           */
+    const uint32_t * first;          /* [sets] smaller member (the member, for group size 1); NULL for group sizes 3 .. 8 */
+    const uint32_t * second;         /* [sets] larger member; NULL for group sizes 3 .. 8                              */
     const uint32_t * count;          /* [sets] samples that produced the set (:573); posterior = count / (chains x its) */
     const uint64_t * words_consumed; /* [NG]  32-bit words the sampler took from each generator                        */
     const uint32_t * generator_state;/* [NG x 624] for a generator that gave at least 624 words: the state words before its
@@ -358,10 +358,30 @@ typedef struct rpvg_hip_gibbs_sets_view {
                                       * the stream at output words_consumed[g]; others are moved by discard()          */
     uint32_t rounds;                 /* rounds of (advance, conditionals) the call queued                              */
     uint64_t conditionals;           /* conditional distributions evaluated                                            */
+    const uint32_t * members;        /* [sets x group_size] rpvg_hip_group_gibbs_polyploid: every set ascending, the sets of
+                                      * a problem in order of first appearance; NULL from rpvg_hip_group_gibbs          */
 } rpvg_hip_gibbs_sets_view;
 
 int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
                          rpvg_hip_gibbs_sets ** result_out);
+/* The same sampler for group sizes 3 .. 8 (same spec, same result type; the view's `members` instead of `first` / `second`),
+ * draw for draw on the caller's generators: group_size start draws per chain, two words per conditional draw.
+ * The conditional of a slot depends on the multiset of the other group_size - 1 members, so the memo of a problem is a hash
+ * table keyed by those members, sorted and packed into 64 bits, floor(64 / group_size) bits each with all-ones reserved: a
+ * problem may have at most 2 097 151 columns at group size 3, 65 535 at 4, 4 095 at 5, 1 023 at 6, 511 at 7 and 255 at 8.
+ * The others are added to a row's noise in ascending column order (the reference adds them in the slot order of whichever
+ * chain asks first): a distribution's bits do not depend on which chain got there first, and can differ from the
+ * host-driven sampler's in the last bit of a row's base.
+ * Both tables of a problem are sized from what its chains can make — sampled sets: min(multisets of group_size columns,
+ * chains x its); conditionals: min(multisets of group_size - 1 columns, chains x (burn + its) x group_size) — times two,
+ * rounded up to a power of two; 16 bytes per set slot, 48 per conditional slot, together at most a quarter of the free
+ * device memory and 16 GiB.  The distributions (32 bytes per column each) are handed out of RPVG_HIP_GIBBS_BYTES (default: a
+ * quarter of the free device memory, at most 32 GiB) as they are asked for.
+ * Returns RPVG_HIP_ERR_UNSUPPORTED, having changed nothing, for other group sizes, a problem with more columns than the key
+ * holds, tables or distributions that outgrow their memory and chains not done after 8 192 rounds: the caller then drives
+ * the sampler itself through rpvg_hip_group_conditionals.  RPVG_HIP_ERR_INVALID for a matrix index out of range. */
+int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
+                                   rpvg_hip_gibbs_sets ** result_out);
 int rpvg_hip_gibbs_sets_get(const rpvg_hip_gibbs_sets * result, rpvg_hip_gibbs_sets_view * view_out);
 void rpvg_hip_gibbs_sets_free(rpvg_hip_gibbs_sets * result);
 
@@ -562,13 +582,16 @@ typedef struct rpvg_hip_kernel_stats {
     /* length of the union of all timed spans of this context (kernels and copies; a span runs from the first command of
      * a stage to its last on the stage's stream, so this is an upper bound of the time the GPU worked for the context) */
     double busy_ms;
-    /* rpvg_hip_group_gibbs: the span from the sampler's first kernel to its last (chains, request bookkeeping, distributions AND the
+    /* rpvg_hip_group_gibbs, rpvg_hip_group_gibbs_polyploid: the span from the sampler's first kernel to its last (chains, request bookkeeping, distributions AND the
      * conditionals, whose own spans are in loglik_ms: gibbs_ms - loglik_ms is what the chains and their bookkeeping take) */
     double gibbs_ms;
     /* pairTile2Kernel alone (round 6): its own HIP-event spans on the stream it runs on and its launches — the kernel the row-pair
      * evaluations of loglik_evals belong to on the diploid search's table path (loglik_ms also holds the kernels behind it, and the
      * spans of batches in flight overlap); timed by contexts that time every kernel family (RPVG_HIP_SPANS=2) */
     double search_tile_ms;    uint64_t search_tile_launches;
+    /* calls of rpvg_hip_group_gibbs and rpvg_hip_group_gibbs_polyploid that returned their sets (RPVG_HIP_OK with at least one
+     * problem): a call that gave up on the way (RPVG_HIP_ERR_UNSUPPORTED) has a span in gibbs_ms and no count here */
+    uint64_t gibbs_calls_completed;
 } rpvg_hip_kernel_stats;
 
 int rpvg_hip_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_kernel_stats * stats_out);

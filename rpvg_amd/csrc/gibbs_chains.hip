@@ -14,7 +14,9 @@
 // a round are evaluated together — groupConditionalKernel's arithmetic over all candidate columns, then the
 // distribution's partial sums — and the chains go on.  Nothing crosses to the host inside the loop: the host queues rounds
 // and looks at a counter of unfinished chains every few rounds.  Group sizes 1 and 2 (a conditional is indexed by one
-// other member); larger groups stay with the host-driven sampler (rpvg_hip_group_conditionals).
+// other member) through rpvg_hip_group_gibbs; group sizes 3 .. 8 (a conditional is indexed by the multiset of the others:
+// a hash table per problem) through rpvg_hip_group_gibbs_polyploid, further down.  What neither takes is left to the
+// caller's host-driven sampler (rpvg_hip_group_conditionals).
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -31,6 +33,7 @@ struct rpvg_hip_gibbs_sets {
     void * state_block = nullptr;  // pinned: [NG x 624] state words
     void * block = nullptr;  // pinned: first | second | count | sequence
     const uint32_t * first = nullptr, * second = nullptr, * count = nullptr;
+    const uint32_t * members = nullptr;  // [sets x group_size], rpvg_hip_group_gibbs_polyploid
     uint32_t rounds = 0;
     uint64_t conditionals = 0;
     ~rpvg_hip_gibbs_sets() {
@@ -45,7 +48,8 @@ constexpr uint32_t kMaxRounds = 8192;
 constexpr uint32_t kPending = 0xffffffffu;
 constexpr uint32_t kChainDone = 0x80000000u;
 constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr uint32_t kErrStream = 1, kErrDistributions = 2;
+constexpr uint32_t kErrStream = 1, kErrDistributions = 2, kErrTable = 4;
+constexpr uint32_t kMaxGroupSize = 8;
 constexpr uint32_t kCondCands = 64, kCondRows = 64, kCondStride = 70;  // gibbsConditionalTileKernel: doubles per staged row = 4 + 64 + noise + count
 constexpr uint32_t kWordWindow = 16;  // generator words a chain keeps in LDS
 constexpr uint32_t kRankInLds = 2048;  // sets of a problem ordered by first appearance inside the collect kernel up to this many
@@ -68,7 +72,9 @@ struct GibbsHeader {
 struct GibbsProblems {  // device arrays over the problems
     const uint32_t * matrix, * chains, * burn, * its;
     const uint64_t * chain_off;  // [P+1]
-    const uint64_t * col_off;    // [P+1] columns before the problem: log frequencies, memo
+    const uint64_t * col_off;    // [P+1] columns before the problem: log frequencies
+    const uint64_t * rec_off;    // [P+1] records before the problem's: its columns (group sizes 1 and 2: the memo is indexed by the other
+                                 //       member), the slots of its memo table (group sizes 3 .. 8: a power of two)
     const uint64_t * tab_off;    // [P+1] slots of the problems' sample tables (powers of two)
     const double * log_freq;
 };
@@ -76,7 +82,7 @@ struct GibbsProblems {  // device arrays over the problems
 struct GibbsChains {  // device arrays over the chains
     uint32_t * problem;
     unsigned long long * pos;  // next word of the chain in `stream`
-    uint32_t * cur;            // [2 x chains]
+    uint32_t * cur;            // [max(2, group size) x chains]
     uint32_t * iter;
     uint32_t * flag;           // slot | kChainDone
 };
@@ -107,6 +113,7 @@ __global__ __launch_bounds__(256) void gibbsStreamKernel(const uint32_t * __rest
     const uint32_t tid = threadIdx.x;
     const uint64_t off = stream_off[g];
     const uint64_t capacity = stream_off[g + 1] - off;
+    const uint32_t cur_stride = group_size < 2 ? 2 : group_size;  // members a chain keeps in ch.cur
     for (uint32_t i = tid; i < kMtWords; i += 256) {
         const uint32_t w = gen_words[static_cast<uint64_t>(g) * kMtWords + i];
         stream[off + i] = w;
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(256) void gibbsStreamKernel(const uint32_t * __rest
             const uint64_t c0 = pr.chain_off[p];
             const uint32_t chains = pr.chains[p];
             for (uint32_t c = 0; c < chains; ++c) {
-                uint32_t start[2] = {0, 0};
+                uint32_t start[kMaxGroupSize] = {0, 0, 0, 0, 0, 0, 0, 0};
                 for (uint32_t s = 0; s < group_size; ++s) {
                     start[s] = uniformBelow(G, [&]() {
                         if (pos >= capacity) {
@@ -166,8 +173,7 @@ __global__ __launch_bounds__(256) void gibbsStreamKernel(const uint32_t * __rest
                 }
                 ch.problem[c0 + c] = p;
                 ch.pos[c0 + c] = off + pos;
-                ch.cur[2 * (c0 + c)] = start[0];
-                ch.cur[2 * (c0 + c) + 1] = start[1];
+                for (uint32_t s = 0; s < cur_stride; ++s) ch.cur[cur_stride * (c0 + c) + s] = start[s];
                 ch.iter[c0 + c] = 0;
                 ch.flag[c0 + c] = 0;
                 pos += words_per_chain;
@@ -237,7 +243,7 @@ __global__ __launch_bounds__(256) void gibbsAdvanceKernel(const uint32_t num_cha
     uint32_t cur0 = ch.cur[2 * ci], cur1 = ch.cur[2 * ci + 1];
     uint32_t iter = ch.iter[ci];
     uint32_t slot = flag & 1u;
-    const uint64_t col0 = pr.col_off[p];
+    const uint64_t col0 = pr.rec_off[p];
     RequestInfo * records_p = records + col0;
     const uint64_t tab = pr.tab_off[p];
     const uint64_t tab_mask = pr.tab_off[p + 1] - tab - 1;
@@ -460,7 +466,7 @@ __global__ __launch_bounds__(1024) void gibbsRequestOffsetsKernel(const GibbsPro
             // past the capacity nothing of this round is evaluated (the host reads the error): the records stay harmless
             const bool fits = e.dist_off + cols <= dist_capacity;
             entries[a] = e;
-            const uint64_t col0 = pr.col_off[p];
+            const uint64_t col0 = pr.rec_off[p];
             for (uint32_t j = 0; j < e.count; ++j) {
                 const uint32_t id = static_cast<uint32_t>(col0) + first + j;
                 const uint32_t record = static_cast<uint32_t>(col0) + req_other[id];
@@ -871,7 +877,7 @@ __global__ __launch_bounds__(256) void gibbsDistributionKernel(const GibbsProble
         const uint32_t id = new_req[q];  // the request's record
         const uint32_t p = records[id].mode;
         const uint32_t G = mat_cols[pr.matrix[p]];
-        const uint64_t col0 = pr.col_off[p];
+        const uint64_t col0 = pr.rec_off[p];
         const uint32_t done = prob_done[p];
         double * v = dist + records[id].dist_off;
         double largest = -INFINITY;
@@ -1049,10 +1055,395 @@ __global__ __launch_bounds__(256) void gibbsCollectKernel(const GibbsProblems pr
     }
 }
 
+// ---- group sizes 3 .. 8 (rpvg_hip_group_gibbs_polyploid) ---------------------------------------------------------
+// The conditional of a slot depends on the MULTISET of the GS - 1 other members (src/path_estimator.cpp:518-523: the group
+// with the slot set to the sentinel, sorted), so the memo of a problem is an open-addressing table keyed by the sorted
+// others packed into one 64-bit word, 64 / GS bits per member (21 bits at group size 3, 8 at group size 8; the same
+// packing holds the GS sorted members of a sampled set, and all-ones stays the empty key: a problem has at most
+// 2^bits - 1 columns).  Slot h of a problem's table is record rec_off[p] + h; a chain that claims a key (one atomicCAS)
+// numbers the request, a chain that finds the key reads the record: state 0 = claimed, not numbered yet.  Probes are
+// counted: a table is sized for twice the keys its problem can make, and one that is full all the same ends the chain
+// and raises kErrTable instead of spinning.
+template <int N>
+__device__ __forceinline__ void sortAscending(uint32_t (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i + 1 < N; ++i) {
+#pragma unroll
+        for (int j = 0; j + 1 < N - i; ++j) {
+            const uint32_t lo = min(v[j], v[j + 1]), hi = max(v[j], v[j + 1]);
+            v[j] = lo;
+            v[j + 1] = hi;
+        }
+    }
+}
+
+__host__ __device__ inline uint32_t memberBits(const uint32_t group_size) { return 64u / group_size; }
+
+// One thread per chain, as gibbsAdvanceKernel; the slots of an iteration are unrolled so that the members, the key and
+// the record each slot drew from last (a slot's conditional changes only when another slot's member changed) stay in
+// registers under constant indices.
+template <int GS>
+__global__ __launch_bounds__(256) void gibbsAdvancePolyKernel(const uint32_t num_chains, const uint32_t round, const GibbsProblems pr,
+                                                              const uint32_t * __restrict__ mat_cols, const GibbsChains ch,
+                                                              const uint32_t * __restrict__ stream, unsigned long long * memo_key,
+                                                              RequestInfo * records, uint32_t * prob_count,
+                                                              const uint32_t * __restrict__ prob_done, GibbsHeader * hdr, uint32_t * remaining,
+                                                              uint32_t * active_problem, uint32_t * req_slot, const double * __restrict__ dist,
+                                                              unsigned long long * tab_key, uint32_t * tab_count, uint32_t * tab_first,
+                                                              const uint32_t chains_per_wave) {
+    constexpr uint32_t kBits = 64 / GS;
+    if ((threadIdx.x & 63u) >= chains_per_wave) return;
+    const uint32_t ci = ((blockIdx.x * 256 + threadIdx.x) >> 6) * chains_per_wave + (threadIdx.x & 63u);
+    if (ci >= num_chains) return;
+    uint32_t flag = ch.flag[ci];
+    if (flag & kChainDone) return;
+    const uint32_t p = ch.problem[ci];
+    const uint32_t G = mat_cols[pr.matrix[p]];
+    const uint32_t done = prob_done[p];
+    const uint32_t burn = pr.burn[p], its = pr.its[p];
+    const uint32_t total_its = burn + its;
+    unsigned long long pos = ch.pos[ci];
+    uint32_t cur[GS];
+#pragma unroll
+    for (int k = 0; k < GS; ++k) cur[k] = ch.cur[static_cast<uint64_t>(GS) * ci + k];
+    uint32_t iter = ch.iter[ci];
+    uint32_t slot = flag & 7u;
+    const uint64_t memo = pr.rec_off[p];
+    const uint64_t memo_mask = pr.rec_off[p + 1] - memo - 1;
+    const uint64_t tab = pr.tab_off[p];
+    const uint64_t tab_mask = pr.tab_off[p + 1] - tab - 1;
+    const uint32_t chain_in_problem = ci - static_cast<uint32_t>(pr.chain_off[p]);
+    unsigned long long held_key[GS];
+    RequestInfo held[GS];
+#pragma unroll
+    for (int k = 0; k < GS; ++k) held_key[k] = kEmptyKey;
+    unsigned long long run_key = kEmptyKey;
+    uint32_t run_length = 0;
+    uint64_t run_at = 0;
+    bool waiting = false, failed = false;
+    constexpr int kAheadDraws = 4;  // (as gibbsAdvanceKernel: the words of the next four draws wait in registers)
+    uint32_t ahead_first[kAheadDraws], ahead_second[kAheadDraws];
+#pragma unroll
+    for (int d = 0; d < kAheadDraws; ++d) {
+        ahead_first[d] = (G >= 2) ? stream[pos + 2 * d] : 0u;
+        ahead_second[d] = (G >= 2) ? stream[pos + 2 * d + 1] : 0u;
+    }
+    while (true) {
+#pragma unroll
+        for (int s = 0; s < GS; ++s) {
+            if (waiting || failed || static_cast<uint32_t>(s) < slot) continue;  // (a chain goes on at the slot it waited at)
+            uint32_t drawn = 0;
+            if (G >= 2) {
+                uint32_t others[GS];
+#pragma unroll
+                for (int k = 0; k < GS; ++k) others[k] = (k == s) ? 0xffffffffu : cur[k];  // the reference's sentinel: sorts last
+                sortAscending(others);
+                unsigned long long key = 0;
+#pragma unroll
+                for (int k = 0; k + 1 < GS; ++k) key |= static_cast<unsigned long long>(others[k]) << (kBits * k);
+                if (held_key[s] != key) {
+                    uint64_t h = mixKey(key) & memo_mask;
+                    uint64_t probes = 0;
+                    bool found = false;
+                    while (true) {
+                        unsigned long long old = __hip_atomic_load(memo_key + memo + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (old == kEmptyKey) old = atomicCAS(memo_key + memo + h, kEmptyKey, key);
+                        if (old == kEmptyKey) {  // this chain's to ask for
+                            const uint32_t k = atomicAdd(prob_count + p, 1u);
+                            req_slot[memo + k] = static_cast<uint32_t>(h);
+                            atomicExch(&records[memo + h].state, k + 1);
+                            if (k == done) active_problem[atomicAdd(&hdr->num_active, 1u)] = p;  // the problem's first request of this round
+                            break;
+                        }
+                        if (old == key) {
+                            found = true;
+                            break;
+                        }
+                        h = (h + 1) & memo_mask;
+                        if (++probes > memo_mask) {
+                            failed = true;
+                            break;
+                        }
+                    }
+                    if (failed) continue;
+                    if (!found) {
+                        waiting = true;
+                        slot = s;
+                        continue;
+                    }
+                    const RequestInfo record = records[memo + h];  // (fields behind a state below `done` were written by earlier launches)
+                    if (record.state == 0 || record.state - 1 >= done) {
+                        waiting = true;
+                        slot = s;
+                        continue;
+                    }
+                    held[s] = record;
+                    held_key[s] = key;
+                }
+                const double u = rpvg_streams::canonicalFromWords(ahead_first[0], ahead_second[0]);
+#pragma unroll
+                for (int d = 0; d + 1 < kAheadDraws; ++d) {
+                    ahead_first[d] = ahead_first[d + 1];
+                    ahead_second[d] = ahead_second[d + 1];
+                }
+                ahead_first[kAheadDraws - 1] = stream[pos + 2 * kAheadDraws];
+                ahead_second[kAheadDraws - 1] = stream[pos + 2 * kAheadDraws + 1];
+                pos += 2;
+                if (held[s].mode_below < u && u <= held[s].mode_upto) {
+                    drawn = held[s].mode;
+                } else {  // std::lower_bound over the partial sums from the bucket's column (see gibbsAdvanceKernel)
+                    const double * cp = dist + held[s].dist_off;
+                    const DrawBucket bucket = reinterpret_cast<const DrawBucket *>(cp + G)[min(static_cast<uint32_t>(u * static_cast<double>(G)), G - 1)];
+                    uint32_t k = static_cast<uint32_t>(bucket.column);
+                    if (!(bucket.below < u && u <= bucket.upto)) {
+                        while (k > 0 && cp[k - 1] >= u) --k;
+                        while (cp[k] < u) ++k;
+                    }
+                    drawn = k;
+                }
+            }
+            cur[s] = drawn;
+        }
+        if (waiting || failed) break;
+        slot = 0;
+        if (iter >= burn) {
+            uint32_t sorted[GS];
+#pragma unroll
+            for (int k = 0; k < GS; ++k) sorted[k] = cur[k];
+            sortAscending(sorted);
+            unsigned long long key = 0;
+#pragma unroll
+            for (int k = 0; k < GS; ++k) key |= static_cast<unsigned long long>(sorted[k]) << (kBits * k);
+            if (key == run_key) {
+                ++run_length;
+            } else {
+                if (run_length) atomicAdd(tab_count + run_at, run_length);
+                run_length = 0;
+                run_key = kEmptyKey;
+                uint64_t h = mixKey(key) & tab_mask;
+                uint64_t probes = 0;
+                while (true) {
+                    const unsigned long long old = atomicCAS(tab_key + tab + h, kEmptyKey, key);
+                    if (old == kEmptyKey || old == key) break;
+                    h = (h + 1) & tab_mask;
+                    if (++probes > tab_mask) {
+                        failed = true;
+                        break;
+                    }
+                }
+                if (failed) break;
+                run_key = key;
+                run_at = tab + h;
+                run_length = 1;
+                atomicMin(tab_first + run_at, chain_in_problem * its + (iter - burn));  // later samples of the run come later
+            }
+        }
+        ++iter;
+        if (iter == total_its) {
+            flag = kChainDone;
+            break;
+        }
+    }
+    if (run_length) atomicAdd(tab_count + run_at, run_length);
+    if (failed) {  // a full table: the call is given up (the host reads the error), the chain must not be looked at again
+        atomicOr(&hdr->error, kErrTable);
+        flag = kChainDone;
+    }
+    ch.pos[ci] = pos;
+#pragma unroll
+    for (int k = 0; k < GS; ++k) ch.cur[static_cast<uint64_t>(GS) * ci + k] = cur[k];
+    ch.iter[ci] = iter;
+    ch.flag[ci] = (flag & kChainDone) | slot;
+    if (waiting) atomicAdd(remaining + round, 1u);
+}
+
+// The conditionals of a round's requests: groupConditionalKernel's arithmetic (loglik.hip: sumCountLogsMulti over four
+// candidate columns) + log frequency, with the others added to the noise IN ASCENDING COLUMN ORDER — the order of the
+// packed key.  The reference adds them in the slot order of whichever chain misses the memo first; here "first" is
+// whoever wins the atomicCAS, and a fixed order keeps the bits of a distribution independent of scheduling.  The work items
+// are gibbsRequestOffsetsKernel's (up to four requests of a problem x four candidate columns, turns by the matrix's rows);
+// a wave takes the requests of an item one after the other: with up to seven others per request the rows are read per
+// request anyway, and the rounds behind the first hold a few requests per problem.  The first round goes through here too:
+// at these group sizes the starts of a problem's chains are nearly all distinct multisets, so there is no block of requests
+// sharing their others for a staged tile to amortise.
+template <int GS>
+__global__ __launch_bounds__(256) void gibbsConditionalPolyKernel(const GibbsProblems pr, const GibbsHeader * __restrict__ hdr,
+                                                                  const ActiveEntry * __restrict__ entries, const uint32_t * __restrict__ req_slot,
+                                                                  const unsigned long long * __restrict__ memo_key,
+                                                                  const uint64_t * __restrict__ mat_val_off, const uint64_t * __restrict__ mat_row_off,
+                                                                  const uint32_t * __restrict__ mat_fast, const uint32_t * __restrict__ mat_mid,
+                                                                  const uint64_t * __restrict__ mat_rows, const uint32_t * __restrict__ mat_cols,
+                                                                  const double * __restrict__ values, const double * __restrict__ row_count,
+                                                                  const double * __restrict__ row_noise, double * __restrict__ dist) {
+    constexpr int kCand = 4;
+    constexpr uint32_t kBits = 64 / GS;
+    constexpr unsigned long long kMask = (1ull << kBits) - 1;
+    constexpr double divisor = static_cast<double>(GS);
+    const unsigned long long num_items = hdr->num_items;
+    if (num_items == 0) return;
+    __shared__ LogTableEntry lt[kLogTableSize];
+    loadLogTable(lt);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint32_t num_active = hdr->cur_active;
+    const unsigned long long num_waves = static_cast<unsigned long long>(gridDim.x) * 4;
+    for (unsigned long long turn = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6); turn < num_items; turn += num_waves) {
+        uint32_t lo = 0, hi = num_active - 1;  // last entry with item_off <= turn
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+            if (entries[mid].item_off <= turn) lo = mid; else hi = mid - 1;
+        }
+        const ActiveEntry e = entries[lo];
+        const uint32_t p = e.problem;
+        const uint32_t m = pr.matrix[p];
+        const uint64_t R = mat_rows[m];
+        const uint32_t G = mat_cols[m];
+        const double * M = values + mat_val_off[m];
+        const double * cnt = row_count + mat_row_off[m];
+        const double * nz = row_noise + mat_row_off[m];
+        const double * lf = pr.log_freq + pr.col_off[p];
+        const uint64_t memo = pr.rec_off[p];
+        const uint64_t fast_end = mat_fast[m], mid_end = mat_mid[m];
+        const uint32_t other_groups = (e.count + 3) / 4;
+        const uint32_t work_items = other_groups * ((G + 3) / 4);
+        const uint32_t per_turn = itemsPerTurn(R);
+        const uint32_t local_begin = static_cast<uint32_t>(turn - e.item_off) * per_turn;
+        const uint32_t local_end = min(work_items, local_begin + per_turn);
+        for (uint32_t local = local_begin; local < local_end; ++local) {
+            const uint32_t j0 = (local % other_groups) * 4;  // first request of the item among the problem's new ones
+            const uint32_t k0 = (local / other_groups) * 4;
+            const uint32_t j_end = min(e.count, j0 + 4);
+            const double * cand[kCand];
+#pragma unroll
+            for (int c = 0; c < kCand; ++c) cand[c] = M + static_cast<uint64_t>(min(k0 + c, G - 1)) * R;
+            for (uint32_t j = j0; j < j_end; ++j) {
+                const unsigned long long key = memo_key[memo + req_slot[memo + e.first + j]];
+                const double * other[GS - 1];
+#pragma unroll
+                for (int w = 0; w + 1 < GS; ++w) other[w] = M + min(static_cast<uint64_t>((key >> (kBits * w)) & kMask), static_cast<uint64_t>(G - 1)) * R;
+                double acc[kCand] = {0.0, 0.0, 0.0, 0.0};
+                LogProduct prod[kCand];
+                auto x = [&](const uint64_t i, double (&xs)[kCand]) {
+                    double base = nz[i];
+#pragma unroll
+                    for (int w = 0; w + 1 < GS; ++w) base += other[w][i] / divisor;
+#pragma unroll
+                    for (int c = 0; c < kCand; ++c) xs[c] = base + cand[c][i] / divisor;
+                };
+                sumCountLogsMulti<kCand, 64, uint64_t>(lt, cnt, x, 0, fast_end, mid_end, R, lane, prod, acc);
+                if (mid_end) {
+#pragma unroll
+                    for (int c = 0; c < kCand; ++c) acc[c] += prod[c].value(lt);
+                }
+                double * out = dist + e.dist_off + static_cast<unsigned long long>(j) * distributionDoubles(G);
+#pragma unroll
+                for (int c = 0; c < kCand; ++c) {
+                    const double total = waveSumF64(acc[c]);
+                    if (lane == 0 && k0 + c < G) out[k0 + c] = total + lf[k0 + c];
+                }
+            }
+        }
+    }
+}
+
+// gibbsCollectKernel for sets of group_size members: [sets x group_size], every set ascending.
+__global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblems pr, const uint32_t group_size,
+                                                              const unsigned long long * __restrict__ tab_key,
+                                                              const uint32_t * __restrict__ tab_count, const uint32_t * __restrict__ tab_first,
+                                                              const unsigned long long * __restrict__ set_off, uint32_t * __restrict__ out_members,
+                                                              uint32_t * __restrict__ out_count, uint32_t * __restrict__ out_seq, GibbsHeader * hdr) {
+    __shared__ uint32_t seqs[kRankInLds];
+    __shared__ uint32_t slots[kRankInLds];
+    __shared__ uint32_t cursor;
+    const uint32_t p = blockIdx.x;
+    const unsigned long long out0 = set_off[p];
+    const uint32_t n = static_cast<uint32_t>(set_off[p + 1] - out0);
+    if (n == 0) return;
+    if (threadIdx.x == 0) cursor = 0;
+    __syncthreads();
+    const uint32_t bits = memberBits(group_size);
+    const unsigned long long mask = (1ull << bits) - 1;
+    const uint64_t tab = pr.tab_off[p], size = pr.tab_off[p + 1] - tab;
+    const bool in_lds = n <= kRankInLds;
+    auto write = [&](const unsigned long long at, const uint64_t s, const uint32_t seq) {
+        const unsigned long long key = tab_key[tab + s];
+        for (uint32_t k = 0; k < group_size; ++k) out_members[at * group_size + k] = static_cast<uint32_t>((key >> (bits * k)) & mask);
+        out_count[at] = tab_count[tab + s];
+        out_seq[at] = seq;
+    };
+    for (uint64_t s = threadIdx.x; s < size; s += 256) {
+        if (tab_key[tab + s] == kEmptyKey) continue;
+        const uint32_t at = atomicAdd(&cursor, 1u);
+        if (in_lds) {
+            seqs[at] = tab_first[tab + s];
+            slots[at] = static_cast<uint32_t>(s);
+        } else {
+            write(out0 + at, s, tab_first[tab + s]);
+        }
+    }
+    __syncthreads();
+    if (!in_lds) {
+        if (threadIdx.x == 0) atomicAdd(&hdr->unsorted, 1u);
+        return;
+    }
+    for (uint32_t e = threadIdx.x; e < n; e += 256) {
+        const uint32_t mine = seqs[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < n; ++j) rank += seqs[j] < mine;  // sequence numbers are distinct: one sample each
+        write(out0 + rank, slots[e], mine);
+    }
+}
+
 uint64_t nextPowerOfTwo(uint64_t v) {
     uint64_t p = 16;
     while (p < v) p <<= 1;
     return p;
+}
+
+// The generators' lists of problems, checked, and where each generator's words lie in the stream: whole blocks of 624, with
+// room for the rejections of the start draws.  Shared by both entry points (`entry` names the caller in the messages).
+int gibbsStreamLayout(const rpvg_hip_gibbs_spec * spec, const std::vector<uint64_t> & words_needed, const char * entry,
+                      std::vector<uint64_t> * stream_off_out) {
+    const uint32_t P = spec->num_problems, NG = spec->num_generators;
+    std::vector<uint64_t> & stream_off = *stream_off_out;
+    stream_off.assign(static_cast<size_t>(NG) + 1, 0);
+    std::vector<uint8_t> seen(P, 0);
+    for (uint32_t g = 0; g < NG; ++g) {
+        RPVG_REQUIRE(spec->generator_problem_off[g] <= spec->generator_problem_off[g + 1] && spec->generator_problem_off[g + 1] <= P,
+                     "%s: generator %u has inconsistent offsets", entry, g);
+        uint64_t needed = 0;
+        for (uint32_t j = spec->generator_problem_off[g]; j < spec->generator_problem_off[g + 1]; ++j) {
+            const uint32_t p = spec->generator_problem[j];
+            RPVG_REQUIRE(p < P && !seen[p], "%s: generator %u lists problem %u (out of range or listed twice)", entry, g, p);
+            seen[p] = 1;
+            needed += words_needed[p];
+        }
+        // room for the start draws' rejections (one more word each, probability columns / 2^32 per draw)
+        const uint64_t blocks = std::max<uint64_t>(1, (needed + 64 + rpvg_streams::kMtWords - 1) / rpvg_streams::kMtWords);
+        stream_off[g + 1] = stream_off[g] + blocks * rpvg_streams::kMtWords;
+    }
+    RPVG_REQUIRE(spec->generator_problem_off[0] == 0 && spec->generator_problem_off[NG] == P, "%s: the generators list %u of %u problems", entry,
+                 spec->generator_problem_off[NG], P);
+    return RPVG_HIP_OK;
+}
+
+// The problems with more sets than the collect kernels rank in LDS left them in table order with the sequence numbers of
+// their first samples: ordered here.  `columns`: the arrays over the sets to permute, each with its values per set.
+void orderUnsortedSets(const std::vector<uint64_t> & set_off, const uint32_t * seq, const std::vector<std::pair<uint32_t *, uint32_t>> & columns) {
+    std::vector<uint32_t> order, scratch;
+    for (size_t p = 0; p + 1 < set_off.size(); ++p) {
+        const uint64_t begin = set_off[p], n = set_off[p + 1] - begin;
+        if (n <= kRankInLds) continue;
+        order.resize(n);
+        std::iota(order.begin(), order.end(), 0u);
+        std::sort(order.begin(), order.end(), [&](const uint32_t a, const uint32_t b) { return seq[begin + a] < seq[begin + b]; });
+        for (const auto & column : columns) {
+            const uint64_t width = column.second;
+            scratch.resize(n * width);
+            for (uint64_t e = 0; e < n; ++e) std::copy_n(column.first + (begin + order[e]) * width, width, scratch.begin() + e * width);
+            std::copy(scratch.begin(), scratch.end(), column.first + begin * width);
+        }
+    }
 }
 
 }  // namespace
@@ -1106,24 +1497,11 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
     const uint64_t num_chains = chain_off[P], num_cols = col_off[P], num_slots = tab_off[P];
     RPVG_REQUIRE(num_chains < 0x7fffffffull, "rpvg_hip_group_gibbs: %llu chains exceed one launch", static_cast<unsigned long long>(num_chains));
     RPVG_REQUIRE(num_cols < 0xfffffff0ull, "rpvg_hip_group_gibbs: %llu columns", static_cast<unsigned long long>(num_cols));
-    std::vector<uint64_t> stream_off(static_cast<size_t>(NG) + 1, 0);
-    std::vector<uint8_t> seen(P, 0);
-    for (uint32_t g = 0; g < NG; ++g) {
-        RPVG_REQUIRE(spec->generator_problem_off[g] <= spec->generator_problem_off[g + 1] && spec->generator_problem_off[g + 1] <= P,
-                     "rpvg_hip_group_gibbs: generator %u has inconsistent offsets", g);
-        uint64_t needed = 0;
-        for (uint32_t j = spec->generator_problem_off[g]; j < spec->generator_problem_off[g + 1]; ++j) {
-            const uint32_t p = spec->generator_problem[j];
-            RPVG_REQUIRE(p < P && !seen[p], "rpvg_hip_group_gibbs: generator %u lists problem %u (out of range or listed twice)", g, p);
-            seen[p] = 1;
-            needed += words_needed[p];
-        }
-        // room for the start draws' rejections (one more word each, probability columns / 2^32 per draw)
-        const uint64_t blocks = std::max<uint64_t>(1, (needed + 64 + rpvg_streams::kMtWords - 1) / rpvg_streams::kMtWords);
-        stream_off[g + 1] = stream_off[g] + blocks * rpvg_streams::kMtWords;
+    std::vector<uint64_t> stream_off;
+    {
+        const int layout_status = gibbsStreamLayout(spec, words_needed, "rpvg_hip_group_gibbs", &stream_off);
+        if (layout_status != RPVG_HIP_OK) return layout_status;
     }
-    RPVG_REQUIRE(spec->generator_problem_off[0] == 0 && spec->generator_problem_off[NG] == P,
-                 "rpvg_hip_group_gibbs: the generators list %u of %u problems", spec->generator_problem_off[NG], P);
 
     std::lock_guard<std::mutex> lock(ctx->mutex);
     RPVG_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1198,7 +1576,7 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
     RPVG_HIP_CHECK(hipMemsetAsync(d_tab_key.ptr, 0xff, num_slots * sizeof(unsigned long long), st));
     RPVG_HIP_CHECK(hipMemsetAsync(d_tab_first.ptr, 0xff, num_slots * sizeof(uint32_t), st));
 
-    const GibbsProblems pr{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
+    const GibbsProblems pr{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_col_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
     const GibbsChains ch{d_chain_problem.ptr, d_chain_pos.ptr, d_chain_cur.ptr, d_chain_iter.ptr, d_chain_flag.ptr};
     const int sampler_span = ctx->spanBegin(FAM_GIBBS);
     struct SamplerSpan {  // (closed on every way out)
@@ -1368,20 +1746,7 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
         }
         RPVG_HIP_CHECK(waitStream(st));
         if (progress->hdr.unsorted) {  // the few problems with more sets than the collect kernel ranks in LDS
-            uint32_t * seq = host + 3 * total_sets;
-            std::vector<uint32_t> order, scratch;
-            for (uint32_t p = 0; p < P; ++p) {
-                const uint64_t begin = result->set_off[p], n = result->set_off[p + 1] - begin;
-                if (n <= kRankInLds) continue;
-                order.resize(n);
-                std::iota(order.begin(), order.end(), 0u);
-                std::sort(order.begin(), order.end(), [&](const uint32_t a, const uint32_t b) { return seq[begin + a] < seq[begin + b]; });
-                scratch.resize(n);
-                for (uint32_t * column : {host, host + total_sets, host + 2 * total_sets}) {
-                    for (uint64_t e = 0; e < n; ++e) scratch[e] = column[begin + order[e]];
-                    std::copy(scratch.begin(), scratch.end(), column + begin);
-                }
-            }
+            orderUnsortedSets(result->set_off, host + 3 * total_sets, {{host, 1u}, {host + total_sets, 1u}, {host + 2 * total_sets, 1u}});
         }
         result->first = host;
         result->second = host + total_sets;
@@ -1389,6 +1754,307 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
     }
     const int build_status = groups->buildError(st);  // the matrices were built without a host sync
     if (build_status != RPVG_HIP_OK) return build_status;
+    ctx->stats.gibbs_calls_completed += 1;
+    *result_out = result.release();
+    return RPVG_HIP_OK;
+}
+
+// Group sizes 3 .. 8: the same rounds (advance -> request offsets -> conditionals -> distributions) over a memo TABLE per
+// problem.  Both tables of a problem are sized from what its chains can make — sets: min(multisets of GS columns, chains x
+// its); conditionals: min(multisets of GS - 1 columns, chains x (burn + its) x GS) — doubled and rounded up to a power of
+// two, so they cannot fill; together they must fit a quarter of the free device memory (at most 16 GiB), or the call is the
+// caller's.  The distributions are handed out of RPVG_HIP_GIBBS_BYTES as the requests come.
+extern "C" int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
+                                              rpvg_hip_gibbs_sets ** result_out) {
+    RPVG_REQUIRE(ctx && groups && spec && result_out, "rpvg_hip_group_gibbs_polyploid: NULL argument");
+    *result_out = nullptr;
+    const uint32_t P = spec->num_problems, NG = spec->num_generators, GS = spec->group_size;
+    if (GS < 3 || GS > kMaxGroupSize) {
+        setError("rpvg_hip_group_gibbs_polyploid: group size %u (this entry point takes 3 .. 8, rpvg_hip_group_gibbs 1 and 2)", GS);
+        return RPVG_HIP_ERR_UNSUPPORTED;
+    }
+    RPVG_REQUIRE(P == 0 || (spec->matrix && spec->num_chains && spec->num_burn_its && spec->num_gibbs_its && spec->log_freq &&
+                            spec->generator_problem_off && spec->generator_problem && spec->generator_words),
+                 "rpvg_hip_group_gibbs_polyploid: NULL array");
+    RPVG_REQUIRE(P == 0 || NG >= 1, "rpvg_hip_group_gibbs_polyploid: no generators");
+    auto result = std::make_unique<rpvg_hip_gibbs_sets>();
+    result->num_problems = P;
+    result->group_size = GS;
+    result->set_off.assign(static_cast<size_t>(P) + 1, 0);
+    result->words_consumed.assign(NG, 0);
+    if (P == 0) {
+        *result_out = result.release();
+        return RPVG_HIP_OK;
+    }
+
+    std::unique_ptr<HostScope> scope(new HostScope("group_gibbs_polyploid: host sizes"));
+    const uint64_t max_columns = (1ull << memberBits(GS)) - 1;  // all-ones is the empty key
+    std::vector<uint64_t> chain_off(static_cast<size_t>(P) + 1, 0), col_off(static_cast<size_t>(P) + 1, 0), tab_off(static_cast<size_t>(P) + 1, 0),
+        memo_off(static_cast<size_t>(P) + 1, 0);
+    std::vector<uint64_t> words_needed(P, 0);
+    long double dist_bound = 0;
+    uint64_t out_capacity = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        RPVG_REQUIRE(spec->matrix[p] < groups->num_matrices, "rpvg_hip_group_gibbs_polyploid: problem %u refers to matrix %u of %u", p,
+                     spec->matrix[p], groups->num_matrices);
+        const uint64_t G = groups->h_num_cols[spec->matrix[p]];
+        RPVG_REQUIRE(G >= 1, "rpvg_hip_group_gibbs_polyploid: problem %u has no columns", p);
+        const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
+        RPVG_REQUIRE(chains * its < 0x40000000ull, "rpvg_hip_group_gibbs_polyploid: problem %u draws %llu samples", p,
+                     static_cast<unsigned long long>(chains * its));
+        chain_off[p + 1] = chain_off[p] + chains;
+        col_off[p + 1] = col_off[p] + G;
+        const uint64_t draws = chains * all_its * GS;
+        words_needed[p] = chains * GS + (G >= 2 ? 2 * draws : 0);
+    }
+    for (uint32_t p = 0; p < P; ++p) {  // (behind the invalid arguments: those are errors whatever else the call holds)
+        const uint64_t G = groups->h_num_cols[spec->matrix[p]];
+        if (G > max_columns) {
+            setError("rpvg_hip_group_gibbs_polyploid: problem %u has %llu columns, the device sampler takes at most %llu at group size %u "
+                     "(%u bits per member of a packed key)", p, static_cast<unsigned long long>(G), static_cast<unsigned long long>(max_columns),
+                     GS, memberBits(GS));
+            return RPVG_HIP_ERR_UNSUPPORTED;
+        }
+        const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
+        // A chain waits at most once per draw: all_its x GS rounds at the worst (a flat posterior over many columns comes
+        // close to it).  A problem whose worst case is past twice kMaxRounds is not tried: it would queue thousands of rounds
+        // before the answer is "unsupported" all the same.
+        if (G >= 2 && all_its * GS > 2ull * kMaxRounds) {
+            setError("rpvg_hip_group_gibbs_polyploid: problem %u can take %llu rounds of requests (iterations x group size), the device sampler queues at most %u",
+                     p, static_cast<unsigned long long>(all_its * GS), kMaxRounds);
+            return RPVG_HIP_ERR_UNSUPPORTED;
+        }
+        const uint64_t sets_bound = std::min<uint64_t>(rpvg_hip_full_set_count(static_cast<uint32_t>(G), GS), chains * its);
+        const uint64_t memo_bound = G >= 2 ? std::min<uint64_t>(rpvg_hip_full_set_count(static_cast<uint32_t>(G), GS - 1), chains * all_its * GS) : 0;
+        tab_off[p + 1] = tab_off[p] + nextPowerOfTwo(2 * sets_bound);
+        memo_off[p + 1] = memo_off[p] + nextPowerOfTwo(2 * memo_bound);
+        out_capacity += sets_bound;
+        dist_bound += static_cast<long double>(distributionDoubles(G)) * static_cast<long double>(memo_bound);
+    }
+    const uint64_t num_chains = chain_off[P], num_cols = col_off[P], num_slots = tab_off[P], num_records = memo_off[P];
+    RPVG_REQUIRE(num_chains < 0x7fffffffull, "rpvg_hip_group_gibbs_polyploid: %llu chains exceed one launch", static_cast<unsigned long long>(num_chains));
+    RPVG_REQUIRE(num_cols < 0xfffffff0ull, "rpvg_hip_group_gibbs_polyploid: %llu columns", static_cast<unsigned long long>(num_cols));
+    std::vector<uint64_t> stream_off;
+    {
+        const int layout_status = gibbsStreamLayout(spec, words_needed, "rpvg_hip_group_gibbs_polyploid", &stream_off);
+        if (layout_status != RPVG_HIP_OK) return layout_status;
+    }
+
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    scope.reset(new HostScope("group_gibbs_polyploid: uploads, allocations"));
+
+    uint64_t dist_capacity = 0;
+    {
+        const char * env = std::getenv("RPVG_HIP_GIBBS_BYTES");  // (read per call: a test switches it)
+        size_t free_bytes = 0, total_bytes = 0;
+        RPVG_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+        // per set slot: key, count, first sample; per memo slot: key, record, request list, round list
+        const long double table_bytes = 16.0L * num_slots + (8.0L + sizeof(RequestInfo) + 8.0L) * num_records;
+        const long double table_budget = std::min<long double>(0.25L * free_bytes, 16.0L * (1ull << 30));
+        if (table_bytes > table_budget || num_records >= 0xfffffff0ull) {
+            setError("rpvg_hip_group_gibbs_polyploid: the tables of the sampled sets and of the conditionals take %.0Lf bytes, more than the %.0Lf set aside for them",
+                     table_bytes, table_budget);
+            return RPVG_HIP_ERR_UNSUPPORTED;
+        }
+        long double budget = env ? std::strtold(env, nullptr) : std::min<long double>(0.25L * free_bytes, 32.0L * (1ull << 30));
+        dist_capacity = static_cast<uint64_t>(std::min<long double>(dist_bound, budget / 8));
+        dist_capacity = std::max<uint64_t>(dist_capacity, 1);
+    }
+
+    DeviceBuffer<uint32_t> d_matrix, d_chains, d_burn, d_its, d_gen_prob_off, d_gen_prob, d_gen_words;
+    DeviceBuffer<uint64_t> d_chain_off, d_col_off, d_tab_off, d_memo_off, d_stream_off;
+    DeviceBuffer<double> d_log_freq;
+    DeviceBuffer<uint32_t> d_remaining, d_tab_count, d_prob_count, d_prob_done;
+    DeviceBuffer<RequestInfo> d_records;
+    DeviceBuffer<GibbsHeader> d_hdr;
+    DeviceBuffer<unsigned long long> d_words, d_set_off;
+    UploadPack pack;
+    pack.add(d_matrix, spec->matrix, P);
+    pack.add(d_chains, spec->num_chains, P);
+    pack.add(d_burn, spec->num_burn_its, P);
+    pack.add(d_its, spec->num_gibbs_its, P);
+    pack.add(d_gen_prob_off, spec->generator_problem_off, static_cast<size_t>(NG) + 1);
+    pack.add(d_gen_prob, spec->generator_problem, P);
+    pack.add(d_gen_words, spec->generator_words, static_cast<size_t>(NG) * rpvg_streams::kMtWords);
+    pack.add(d_chain_off, chain_off.data(), chain_off.size());
+    pack.add(d_col_off, col_off.data(), col_off.size());
+    pack.add(d_tab_off, tab_off.data(), tab_off.size());
+    pack.add(d_memo_off, memo_off.data(), memo_off.size());
+    pack.add(d_stream_off, stream_off.data(), stream_off.size());
+    pack.add(d_log_freq, spec->log_freq, num_cols);
+    pack.addZero(d_prob_count, P);
+    pack.addZero(d_prob_done, P);
+    pack.addZero(d_remaining, kMaxRounds);
+    pack.addZero(d_hdr, 1);
+    pack.addZero(d_words, NG);
+    pack.addZero(d_set_off, static_cast<size_t>(P) + 1);
+    int span = ctx->spanBegin(FAM_H2D);
+    RPVG_HIP_CHECK(pack.commit(st));
+    ctx->spanEnd(span);
+    ctx->stats.h2d_bytes += static_cast<double>(pack.copied_bytes);
+
+    DeviceBuffer<uint32_t> d_stream, d_chain_problem, d_chain_cur, d_chain_iter, d_chain_flag, d_active_problem, d_req_slot, d_new_req, d_tab_first;
+    DeviceBuffer<unsigned long long> d_chain_pos, d_tab_key, d_memo_key;
+    DeviceBuffer<ActiveEntry> d_entries;
+    DeviceBuffer<double> d_dist;
+    DeviceBuffer<uint32_t> d_out;  // members | count | sequence
+    DeviceBuffer<uint32_t> d_final_state;
+    RPVG_HIP_CHECK(d_final_state.alloc(static_cast<size_t>(NG) * rpvg_streams::kMtWords));
+    RPVG_HIP_CHECK(d_stream.alloc(stream_off[NG] + kWordWindow));  // (the chains fetch their words four draws ahead)
+    RPVG_HIP_CHECK(d_chain_problem.alloc(num_chains));
+    RPVG_HIP_CHECK(d_chain_cur.alloc(GS * num_chains));
+    RPVG_HIP_CHECK(d_chain_iter.alloc(num_chains));
+    RPVG_HIP_CHECK(d_chain_flag.alloc(num_chains));
+    RPVG_HIP_CHECK(d_chain_pos.alloc(num_chains));
+    RPVG_HIP_CHECK(d_active_problem.alloc(P));
+    RPVG_HIP_CHECK(d_entries.alloc(P));
+    RPVG_HIP_CHECK(d_records.alloc(num_records));
+    RPVG_HIP_CHECK(d_req_slot.alloc(num_records));
+    RPVG_HIP_CHECK(d_new_req.alloc(num_records));
+    RPVG_HIP_CHECK(d_memo_key.alloc(num_records));
+    RPVG_HIP_CHECK(d_tab_key.alloc(num_slots));
+    RPVG_HIP_CHECK(d_tab_first.alloc(num_slots));
+    RPVG_HIP_CHECK(d_tab_count.alloc(num_slots));
+    RPVG_HIP_CHECK(d_dist.alloc(dist_capacity));
+    RPVG_HIP_CHECK(hipMemsetAsync(d_records.ptr, 0, num_records * sizeof(RequestInfo), st));
+    RPVG_HIP_CHECK(hipMemsetAsync(d_memo_key.ptr, 0xff, num_records * sizeof(unsigned long long), st));
+    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_key.ptr, 0xff, num_slots * sizeof(unsigned long long), st));
+    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_first.ptr, 0xff, num_slots * sizeof(uint32_t), st));
+    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_count.ptr, 0, num_slots * sizeof(uint32_t), st));
+
+    const GibbsProblems pr{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_memo_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
+    const GibbsChains ch{d_chain_problem.ptr, d_chain_pos.ptr, d_chain_cur.ptr, d_chain_iter.ptr, d_chain_flag.ptr};
+    const int sampler_span = ctx->spanBegin(FAM_GIBBS);
+    struct SamplerSpan {  // (closed on every way out)
+        rpvg_hip_ctx * ctx;
+        int span;
+        ~SamplerSpan() { ctx->spanEnd(span); }
+    } sampler_span_guard{ctx, sampler_span};
+    gibbsStreamKernel<<<dim3(NG), dim3(256), 0, st>>>(d_gen_words.ptr, d_gen_prob_off.ptr, d_gen_prob.ptr, d_stream_off.ptr, pr, groups->mat_cols.ptr, GS,
+                                                      d_stream.ptr, ch, d_words.ptr, d_final_state.ptr, d_hdr.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    RPVG_HIP_CHECK(pinnedAlloc(&result->state_block, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t)));
+    RPVG_HIP_CHECK(hipMemcpyAsync(result->state_block, d_final_state.ptr, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(groups->waitCollapse(st));
+
+    struct Progress {
+        uint32_t remaining;
+        uint32_t pad[15];
+        GibbsHeader hdr;
+    };
+    void * pinned = nullptr;
+    RPVG_HIP_CHECK(pinnedAlloc(&pinned, sizeof(Progress)));
+    std::shared_ptr<void> pinned_guard(pinned, [](void * ptr) { pinnedFree(ptr); });
+    Progress * progress = static_cast<Progress *>(pinned);
+
+    scope.reset(new HostScope("group_gibbs_polyploid: rounds"));
+    const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
+    const uint32_t chains_per_wave = 8;  // (as at group size 2: a wave runs the union of its chains' paths)
+    const uint32_t advance_blocks = static_cast<uint32_t>((num_chains + 4 * chains_per_wave - 1) / (4 * chains_per_wave));
+    const uint32_t work_blocks = cus * 8;
+    uint32_t round = 0;
+    bool finished = false;
+    uint32_t chunk = 6;
+    while (!finished) {
+        if (round + chunk >= kMaxRounds) {
+            RPVG_HIP_CHECK(waitStream(st));
+            setError("rpvg_hip_group_gibbs_polyploid: the chains are not done after %u rounds", round);
+            return RPVG_HIP_ERR_UNSUPPORTED;
+        }
+        for (uint32_t r = 0; r < chunk; ++r, ++round) {
+#define RPVG_GIBBS_POLY_ROUND(W)                                                                                                       \
+    gibbsAdvancePolyKernel<W><<<dim3(advance_blocks), dim3(256), 0, st>>>(                                                             \
+        static_cast<uint32_t>(num_chains), round, pr, groups->mat_cols.ptr, ch, d_stream.ptr, d_memo_key.ptr, d_records.ptr,           \
+        d_prob_count.ptr, d_prob_done.ptr, d_hdr.ptr, d_remaining.ptr, d_active_problem.ptr, d_req_slot.ptr, d_dist.ptr,               \
+        d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, chains_per_wave);                                                             \
+    gibbsRequestOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(pr, groups->mat_cols.ptr, groups->mat_rows.ptr, d_hdr.ptr,               \
+                                                              d_active_problem.ptr, d_prob_count.ptr, d_prob_done.ptr, d_entries.ptr,  \
+                                                              d_new_req.ptr, d_req_slot.ptr, d_records.ptr, dist_capacity, 0u);        \
+    span = ctx->spanBegin(FAM_LOGLIK);                                                                                                 \
+    gibbsConditionalPolyKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(                                                            \
+        pr, d_hdr.ptr, d_entries.ptr, d_req_slot.ptr, d_memo_key.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,                \
+        groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr,                     \
+        groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);                                                                     \
+    ctx->spanEnd(span)
+            switch (GS) {
+                case 3: RPVG_GIBBS_POLY_ROUND(3); break;
+                case 4: RPVG_GIBBS_POLY_ROUND(4); break;
+                case 5: RPVG_GIBBS_POLY_ROUND(5); break;
+                case 6: RPVG_GIBBS_POLY_ROUND(6); break;
+                case 7: RPVG_GIBBS_POLY_ROUND(7); break;
+                default: RPVG_GIBBS_POLY_ROUND(8); break;
+            }
+#undef RPVG_GIBBS_POLY_ROUND
+            // (ask-ahead share 2: never — it numbers requests by the other COLUMN, which is group size 2's memo)
+            gibbsDistributionKernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_new_req.ptr, groups->mat_cols.ptr, d_records.ptr, d_dist.ptr,
+                                                                            2.0, d_prob_count.ptr, d_prob_done.ptr, d_active_problem.ptr,
+                                                                            d_req_slot.ptr, d_hdr.ptr);
+        }
+        RPVG_HIP_CHECK(hipGetLastError());
+        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->remaining, d_remaining.ptr + (round - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(waitStream(st));
+        if (progress->hdr.error) {
+            const uint32_t err = progress->hdr.error;
+            if (err & kErrDistributions) {
+                setError("rpvg_hip_group_gibbs_polyploid: the conditional distributions need more than the %llu bytes reserved for them (RPVG_HIP_GIBBS_BYTES)",
+                         static_cast<unsigned long long>(dist_capacity * 8));
+                return RPVG_HIP_ERR_UNSUPPORTED;
+            }
+            if (err & kErrTable) {
+                setError("rpvg_hip_group_gibbs_polyploid: a table of sampled sets or of conditionals is full");
+                return RPVG_HIP_ERR_UNSUPPORTED;
+            }
+            setError("rpvg_hip_group_gibbs_polyploid: a generator's start draws ran past the words generated for it");
+            return RPVG_HIP_ERR_RUNTIME;
+        }
+        finished = progress->remaining == 0;
+        // a flat posterior asks for a new conditional at nearly every draw: rounds by the hundred, looked at less and less often
+        chunk = std::min<uint32_t>(32, std::max<uint32_t>(4, round / 4));
+    }
+    ctx->stats.loglik_launches += round;
+    ctx->stats.loglik_evals += progress->hdr.evals;
+    result->rounds = round;
+    result->conditionals = progress->hdr.total_requests;
+
+    // the sets
+    scope.reset(new HostScope("group_gibbs_polyploid: sets"));
+    RPVG_HIP_CHECK(d_out.alloc((GS + 2) * out_capacity));
+    uint32_t * out_members = d_out.ptr, * out_count = d_out.ptr + GS * out_capacity, * out_seq = d_out.ptr + (GS + 1) * out_capacity;
+    gibbsCountSetsKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_set_off.ptr);
+    gibbsSetOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(P, d_set_off.ptr, d_hdr.ptr);
+    gibbsCollectPolyKernel<<<dim3(P), dim3(256), 0, st>>>(pr, GS, d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, d_set_off.ptr, out_members, out_count,
+                                                          out_seq, d_hdr.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    RPVG_HIP_CHECK(hipMemcpyAsync(result->set_off.data(), d_set_off.ptr, (static_cast<size_t>(P) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(result->words_consumed.data(), d_words.ptr, static_cast<size_t>(NG) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(waitStream(st));
+    const uint64_t total_sets = progress->hdr.total_sets;
+    RPVG_REQUIRE(total_sets <= out_capacity, "rpvg_hip_group_gibbs_polyploid: %llu sets in room for %llu", static_cast<unsigned long long>(total_sets),
+                 static_cast<unsigned long long>(out_capacity));
+    if (total_sets > 0) {
+        RPVG_HIP_CHECK(pinnedAlloc(&result->block, (GS + 2) * total_sets * sizeof(uint32_t)));
+        uint32_t * host = static_cast<uint32_t *>(result->block);
+        uint32_t * host_count = host + GS * total_sets, * host_seq = host + (GS + 1) * total_sets;
+        RPVG_HIP_CHECK(hipMemcpyAsync(host, out_members, GS * total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(host_count, out_count, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (progress->hdr.unsorted) {
+            RPVG_HIP_CHECK(hipMemcpyAsync(host_seq, out_seq, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        RPVG_HIP_CHECK(waitStream(st));
+        if (progress->hdr.unsorted) {  // the problems with more sets than the collect kernel ranks in LDS
+            orderUnsortedSets(result->set_off, host_seq, {{host, GS}, {host_count, 1u}});
+        }
+        result->members = host;
+        result->count = host_count;
+    }
+    const int build_status = groups->buildError(st);  // the matrices were built without a host sync
+    if (build_status != RPVG_HIP_OK) return build_status;
+    ctx->stats.gibbs_calls_completed += 1;
     *result_out = result.release();
     return RPVG_HIP_OK;
 }
@@ -1405,6 +2071,7 @@ extern "C" int rpvg_hip_gibbs_sets_get(const rpvg_hip_gibbs_sets * result, rpvg_
     view_out->generator_state = static_cast<const uint32_t *>(result->state_block);
     view_out->rounds = result->rounds;
     view_out->conditionals = result->conditionals;
+    view_out->members = result->members;
     return RPVG_HIP_OK;
 }
 

@@ -26,7 +26,7 @@ EXPORTS = [
     "rpvg_hip_gibbs_read_counts", "rpvg_hip_min_path_cover", "rpvg_hip_bounded_pair_posteriors", "rpvg_hip_pair_posteriors_get", "rpvg_hip_pair_posteriors_free",
     "rpvg_hip_em_dense_sharded", "rpvg_hip_synth_dense_rows", "rpvg_hip_synth_dense_cluster_batch", "rpvg_hip_comm_unique_id", "rpvg_hip_comm_init",
     "rpvg_hip_comm_destroy", "rpvg_hip_comm_allreduce_sum_f64", "rpvg_hip_comm_init_all", "rpvg_hip_gather", "rpvg_hip_host_register", "rpvg_hip_host_unregister", "rpvg_hip_group_conditionals",
-    "rpvg_hip_group_gibbs", "rpvg_hip_gibbs_sets_get", "rpvg_hip_gibbs_sets_free",
+    "rpvg_hip_group_gibbs", "rpvg_hip_group_gibbs_polyploid", "rpvg_hip_gibbs_sets_get", "rpvg_hip_gibbs_sets_free",
     "rpvg_hip_alignments_upload", "rpvg_hip_alignments_free", "rpvg_hip_read_rows_build", "rpvg_hip_read_rows_to_batch",
     "rpvg_hip_read_rows_view", "rpvg_hip_read_rows_sizes", "rpvg_hip_read_rows_free", "rpvg_hip_path_clusters", "rpvg_hip_debug_log",
     "rpvg_hip_nested_subset_em", "rpvg_hip_subset_em_get", "rpvg_hip_subset_em_free",
@@ -70,7 +70,7 @@ class CGibbsSetsView(C.Structure):
     _fields_ = [("num_problems", C.c_uint32), ("group_size", C.c_uint32), ("set_off", C.POINTER(C.c_uint64)),
                 ("first", C.POINTER(C.c_uint32)), ("second", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint32)),
                 ("words_consumed", C.POINTER(C.c_uint64)), ("generator_state", C.POINTER(C.c_uint32)), ("rounds", C.c_uint32),
-                ("conditionals", C.c_uint64)]
+                ("conditionals", C.c_uint64), ("members", C.POINTER(C.c_uint32))]
 
 
 class CPairPosteriorsView(C.Structure):
@@ -98,6 +98,7 @@ class CKernelStats(C.Structure):
         ("em_kernel", CEmKernelStats * EM_KERNELS),
         ("collapse_ms", C.c_double), ("busy_ms", C.c_double), ("gibbs_ms", C.c_double),
         ("search_tile_ms", C.c_double), ("search_tile_launches", C.c_uint64),
+        ("gibbs_calls_completed", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -425,6 +426,16 @@ class DeviceGroups:
     def gibbs(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
         """rpvg_hip_group_gibbs: per problem ([sorted member tuples in order of first appearance], counts); plus the words each
         generator gave, the state words of the generators that gave at least 624, and (rounds, conditionals)."""
+        return self._gibbs("rpvg_hip_group_gibbs", matrix, group_size, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems,
+                           generator_words)
+
+    def gibbs_polyploid(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
+        """rpvg_hip_group_gibbs_polyploid (group sizes 3 .. 8): the arguments and the return shape of gibbs(), member tuples of
+        length group_size."""
+        return self._gibbs("rpvg_hip_group_gibbs_polyploid", matrix, group_size, num_chains, num_burn_its, num_gibbs_its, log_freq,
+                           generator_problems, generator_words)
+
+    def _gibbs(self, entry, matrix, group_size, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
         mt = np.ascontiguousarray(matrix, dtype=np.uint32)
         ch = np.ascontiguousarray(num_chains, dtype=np.uint32)
         bu = np.ascontiguousarray(num_burn_its, dtype=np.uint32)
@@ -436,14 +447,18 @@ class DeviceGroups:
         spec = CGibbsSpec(len(mt), group_size, mt.ctypes.data, ch.ctypes.data, bu.ctypes.data, it.ctypes.data, lf.ctypes.data,
                           len(generator_problems), goff.ctypes.data, gp.ctypes.data, gw.ctypes.data)
         h = C.c_void_p()
-        _check(lib().rpvg_hip_group_gibbs(self.ctx.handle, self.handle, C.byref(spec), C.byref(h)), "rpvg_hip_group_gibbs")
+        _check(getattr(lib(), entry)(self.ctx.handle, self.handle, C.byref(spec), C.byref(h)), entry)
         try:
             v = CGibbsSetsView()
             _check(lib().rpvg_hip_gibbs_sets_get(h, C.byref(v)), "rpvg_hip_gibbs_sets_get")
             off = np.ctypeslib.as_array(v.set_off, shape=(len(mt) + 1,)).copy()
             total = int(off[-1])
-            first = np.ctypeslib.as_array(v.first, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
-            second = np.ctypeslib.as_array(v.second, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+            by_members = bool(v.members)
+            if by_members:
+                members = np.ctypeslib.as_array(v.members, shape=(total, group_size)).copy()
+            else:
+                first = np.ctypeslib.as_array(v.first, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+                second = np.ctypeslib.as_array(v.second, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
             count = np.ctypeslib.as_array(v.count, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
             if len(generator_problems):
                 words = np.ctypeslib.as_array(v.words_consumed, shape=(len(generator_problems),)).copy()
@@ -453,7 +468,10 @@ class DeviceGroups:
             out = []
             for i in range(len(mt)):
                 a, b = int(off[i]), int(off[i + 1])
-                sets = [(int(x),) if group_size == 1 else (int(x), int(y)) for x, y in zip(first[a:b], second[a:b])]
+                if by_members:
+                    sets = [tuple(int(x) for x in row) for row in members[a:b]]
+                else:
+                    sets = [(int(x),) if group_size == 1 else (int(x), int(y)) for x, y in zip(first[a:b], second[a:b])]
                 out.append((sets, [int(c) for c in count[a:b]]))
             return out, words, state, (int(v.rounds), int(v.conditionals))
         finally:

@@ -1699,19 +1699,27 @@ bool estimatePathGroupPosteriorsGibbsOnDevice(std::vector<GroupPosteriors> * gro
     spec.generator_problem = generator_problem.data();
     spec.generator_words = generator_words.data();
 
-    ScopedPhase call_phase("gibbs: rpvg_hip_group_gibbs");
+    // group sizes 3 .. 8 have an entry point of their own (the memo of the conditionals is a hash table there)
+    const char * const entry_point = (group_size > 2) ? "rpvg_hip_group_gibbs_polyploid" : "rpvg_hip_group_gibbs";
+
+    ScopedPhase call_phase((group_size > 2) ? "gibbs: rpvg_hip_group_gibbs_polyploid" : "gibbs: rpvg_hip_group_gibbs");
 
     rpvg_hip_gibbs_sets * sets = nullptr;
-    const int status = rpvg_hip_group_gibbs(engine->ctx(), groups, &spec, &sets);
+    const int status = (group_size > 2) ? rpvg_hip_group_gibbs_polyploid(engine->ctx(), groups, &spec, &sets) : rpvg_hip_group_gibbs(engine->ctx(), groups, &spec, &sets);
 
     call_phase.stop();
 
     if (status == RPVG_HIP_ERR_UNSUPPORTED) {
 
+        if (PhaseTrace::enabled()) {
+
+            std::fprintf(stderr, "[rpvg_amd trace] gibbs: the device sampler leaves the call to the host-driven one: %s\n", rpvg_hip_last_error());
+        }
+
         return false;
     }
 
-    HipEngine::check(status, "rpvg_hip_group_gibbs");
+    HipEngine::check(status, entry_point);
     std::shared_ptr<rpvg_hip_gibbs_sets> sets_holder(sets, rpvg_hip_gibbs_sets_free);
 
     rpvg_hip_gibbs_sets_view view;
@@ -1755,11 +1763,18 @@ bool estimatePathGroupPosteriorsGibbsOnDevice(std::vector<GroupPosteriors> * gro
 
             for (uint64_t s = first_set; s < first_set + num_sets; ++s) {
 
-                result.members.emplace_back(view.first[s]);
+                if (group_size > 2) {
 
-                if (group_size == 2) {
+                    result.members.insert(result.members.end(), view.members + s * group_size, view.members + (s + 1) * group_size);
 
-                    result.members.emplace_back(view.second[s]);
+                } else {
+
+                    result.members.emplace_back(view.first[s]);
+
+                    if (group_size == 2) {
+
+                        result.members.emplace_back(view.second[s]);
+                    }
                 }
 
                 // src/path_estimator.cpp:583-586
@@ -1847,10 +1862,11 @@ void PathEstimator::estimatePathGroupPosteriorsGibbs(std::vector<GroupPosteriors
 
     const GroupMatrices matrices(engine, cluster_batch, problems, normalise, prob_precision);
 
-    // group sizes 1 and 2: the chains themselves run on the device (rpvg_hip_group_gibbs), draw for draw
+    // the chains themselves run on the device, draw for draw (rpvg_hip_group_gibbs for group sizes 1 and 2,
+    // rpvg_hip_group_gibbs_polyploid for 3 .. 8); what it does not take is left to the host-driven sampler below
     static const bool host_sampler = std::getenv("RPVG_AMD_HOST_GIBBS") != nullptr;
 
-    if (group_size <= 2 && !host_sampler && estimatePathGroupPosteriorsGibbsOnDevice(group_posteriors, engine, matrices.handle(), problems, group_size, rngs, &PathEstimator::calcPathLogFrequences)) {
+    if (!host_sampler && estimatePathGroupPosteriorsGibbsOnDevice(group_posteriors, engine, matrices.handle(), problems, group_size, rngs, &PathEstimator::calcPathLogFrequences)) {
 
         return;
     }
