@@ -15,8 +15,11 @@
 // distribution's partial sums — and the chains go on.  Nothing crosses to the host inside the loop: the host queues rounds
 // and looks at a counter of unfinished chains every few rounds.  Group sizes 1 and 2 (a conditional is indexed by one
 // other member) through rpvg_hip_group_gibbs; group sizes 3 .. 8 (a conditional is indexed by the multiset of the others:
-// a hash table per problem) through rpvg_hip_group_gibbs_polyploid, further down.  What neither takes is left to the
-// caller's host-driven sampler (rpvg_hip_group_conditionals).
+// a hash table per problem) through rpvg_hip_group_gibbs_polyploid.  What neither takes is left to the caller's
+// host-driven sampler (rpvg_hip_group_conditionals).
+// The file: the kernels every group size shares, the chains' and conditionals' kernels of group sizes 1 and 2, those of
+// 3 .. 8, the collect kernels; then the host side — ONE driver (runGibbs: sizes, uploads, streams, rounds, sets over a
+// GibbsRun) behind both entry points, with what differs between them in PairVariant and PolyVariant.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -1004,57 +1007,6 @@ __global__ __launch_bounds__(1024) void gibbsSetOffsetsKernel(const uint32_t num
     }
 }
 
-// One workgroup per problem: its sets ordered by the sample that produced them first (the reference appends a set to
-// path_group_sets when it first meets it, src/path_estimator.cpp:566-568) — rank by counting in LDS; a problem with more
-// sets than fit leaves in table order with the sequence numbers, and the host orders it.
-__global__ __launch_bounds__(256) void gibbsCollectKernel(const GibbsProblems pr, const unsigned long long * __restrict__ tab_key,
-                                                          const uint32_t * __restrict__ tab_count, const uint32_t * __restrict__ tab_first,
-                                                          const unsigned long long * __restrict__ set_off, uint32_t * __restrict__ out_first,
-                                                          uint32_t * __restrict__ out_second, uint32_t * __restrict__ out_count,
-                                                          uint32_t * __restrict__ out_seq, GibbsHeader * hdr) {
-    __shared__ uint32_t seqs[kRankInLds];
-    __shared__ uint32_t slots[kRankInLds];
-    __shared__ uint32_t cursor;
-    const uint32_t p = blockIdx.x;
-    const unsigned long long out0 = set_off[p];
-    const uint32_t n = static_cast<uint32_t>(set_off[p + 1] - out0);
-    if (n == 0) return;
-    if (threadIdx.x == 0) cursor = 0;
-    __syncthreads();
-    const uint64_t tab = pr.tab_off[p], size = pr.tab_off[p + 1] - tab;
-    const bool in_lds = n <= kRankInLds;
-    for (uint64_t s = threadIdx.x; s < size; s += 256) {
-        const unsigned long long key = tab_key[tab + s];
-        if (key == kEmptyKey) continue;
-        const uint32_t at = atomicAdd(&cursor, 1u);
-        if (in_lds) {
-            seqs[at] = tab_first[tab + s];
-            slots[at] = static_cast<uint32_t>(s);
-        } else {
-            out_first[out0 + at] = static_cast<uint32_t>(key >> 32);
-            out_second[out0 + at] = static_cast<uint32_t>(key);
-            out_count[out0 + at] = tab_count[tab + s];
-            out_seq[out0 + at] = tab_first[tab + s];
-        }
-    }
-    __syncthreads();
-    if (!in_lds) {
-        if (threadIdx.x == 0) atomicAdd(&hdr->unsorted, 1u);
-        return;
-    }
-    for (uint32_t e = threadIdx.x; e < n; e += 256) {
-        const uint32_t mine = seqs[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < n; ++j) rank += seqs[j] < mine;  // sequence numbers are distinct: one sample each
-        const uint64_t s = slots[e];
-        const unsigned long long key = tab_key[tab + s];
-        out_first[out0 + rank] = static_cast<uint32_t>(key >> 32);
-        out_second[out0 + rank] = static_cast<uint32_t>(key);
-        out_count[out0 + rank] = tab_count[tab + s];
-        out_seq[out0 + rank] = mine;
-    }
-}
-
 // ---- group sizes 3 .. 8 (rpvg_hip_group_gibbs_polyploid) ---------------------------------------------------------
 // The conditional of a slot depends on the MULTISET of the GS - 1 other members (src/path_estimator.cpp:518-523: the group
 // with the slot set to the sentinel, sorted), so the memo of a problem is an open-addressing table keyed by the sorted
@@ -1346,12 +1298,15 @@ __global__ __launch_bounds__(256) void gibbsConditionalPolyKernel(const GibbsPro
     }
 }
 
-// gibbsCollectKernel for sets of group_size members: [sets x group_size], every set ascending.
-__global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblems pr, const uint32_t group_size,
-                                                              const unsigned long long * __restrict__ tab_key,
-                                                              const uint32_t * __restrict__ tab_count, const uint32_t * __restrict__ tab_first,
-                                                              const unsigned long long * __restrict__ set_off, uint32_t * __restrict__ out_members,
-                                                              uint32_t * __restrict__ out_count, uint32_t * __restrict__ out_seq, GibbsHeader * hdr) {
+// ---- the sampled sets collected, for every group size ------------------------------------------------------------
+// One workgroup per problem: its sets ordered by the sample that produced them first (the reference appends a set to
+// path_group_sets when it first meets it, src/path_estimator.cpp:566-568) — rank by counting in LDS; a problem with more
+// sets than fit leaves in table order with the sequence numbers, and the host orders it.  write(at, slot, seq) places the
+// set in slot `slot` of the sample tables at position `at` of the output: all that differs between the group sizes.
+template <typename Writer>
+__device__ __forceinline__ void collectSets(const GibbsProblems & pr, const unsigned long long * __restrict__ tab_key,
+                                            const uint32_t * __restrict__ tab_first, const unsigned long long * __restrict__ set_off,
+                                            GibbsHeader * hdr, const Writer & write) {
     __shared__ uint32_t seqs[kRankInLds];
     __shared__ uint32_t slots[kRankInLds];
     __shared__ uint32_t cursor;
@@ -1361,16 +1316,8 @@ __global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblem
     if (n == 0) return;
     if (threadIdx.x == 0) cursor = 0;
     __syncthreads();
-    const uint32_t bits = memberBits(group_size);
-    const unsigned long long mask = (1ull << bits) - 1;
     const uint64_t tab = pr.tab_off[p], size = pr.tab_off[p + 1] - tab;
     const bool in_lds = n <= kRankInLds;
-    auto write = [&](const unsigned long long at, const uint64_t s, const uint32_t seq) {
-        const unsigned long long key = tab_key[tab + s];
-        for (uint32_t k = 0; k < group_size; ++k) out_members[at * group_size + k] = static_cast<uint32_t>((key >> (bits * k)) & mask);
-        out_count[at] = tab_count[tab + s];
-        out_seq[at] = seq;
-    };
     for (uint64_t s = threadIdx.x; s < size; s += 256) {
         if (tab_key[tab + s] == kEmptyKey) continue;
         const uint32_t at = atomicAdd(&cursor, 1u);
@@ -1378,7 +1325,7 @@ __global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblem
             seqs[at] = tab_first[tab + s];
             slots[at] = static_cast<uint32_t>(s);
         } else {
-            write(out0 + at, s, tab_first[tab + s]);
+            write(out0 + at, tab + s, tab_first[tab + s]);
         }
     }
     __syncthreads();
@@ -1390,8 +1337,39 @@ __global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblem
         const uint32_t mine = seqs[e];
         uint32_t rank = 0;
         for (uint32_t j = 0; j < n; ++j) rank += seqs[j] < mine;  // sequence numbers are distinct: one sample each
-        write(out0 + rank, slots[e], mine);
+        write(out0 + rank, tab + slots[e], mine);
     }
+}
+
+// group sizes 1 and 2: the two members of a key (the same twice at group size 1)
+__global__ __launch_bounds__(256) void gibbsCollectKernel(const GibbsProblems pr, const unsigned long long * __restrict__ tab_key,
+                                                          const uint32_t * __restrict__ tab_count, const uint32_t * __restrict__ tab_first,
+                                                          const unsigned long long * __restrict__ set_off, uint32_t * __restrict__ out_first,
+                                                          uint32_t * __restrict__ out_second, uint32_t * __restrict__ out_count,
+                                                          uint32_t * __restrict__ out_seq, GibbsHeader * hdr) {
+    collectSets(pr, tab_key, tab_first, set_off, hdr, [&](const unsigned long long at, const uint64_t slot, const uint32_t seq) {
+        const unsigned long long key = tab_key[slot];
+        out_first[at] = static_cast<uint32_t>(key >> 32);
+        out_second[at] = static_cast<uint32_t>(key);
+        out_count[at] = tab_count[slot];
+        out_seq[at] = seq;
+    });
+}
+
+// group sizes 3 .. 8: [sets x group_size], every set ascending
+__global__ __launch_bounds__(256) void gibbsCollectPolyKernel(const GibbsProblems pr, const uint32_t group_size,
+                                                              const unsigned long long * __restrict__ tab_key,
+                                                              const uint32_t * __restrict__ tab_count, const uint32_t * __restrict__ tab_first,
+                                                              const unsigned long long * __restrict__ set_off, uint32_t * __restrict__ out_members,
+                                                              uint32_t * __restrict__ out_count, uint32_t * __restrict__ out_seq, GibbsHeader * hdr) {
+    const uint32_t bits = memberBits(group_size);
+    const unsigned long long mask = (1ull << bits) - 1;
+    collectSets(pr, tab_key, tab_first, set_off, hdr, [&](const unsigned long long at, const uint64_t slot, const uint32_t seq) {
+        const unsigned long long key = tab_key[slot];
+        for (uint32_t k = 0; k < group_size; ++k) out_members[at * group_size + k] = static_cast<uint32_t>((key >> (bits * k)) & mask);
+        out_count[at] = tab_count[slot];
+        out_seq[at] = seq;
+    });
 }
 
 uint64_t nextPowerOfTwo(uint64_t v) {
@@ -1401,7 +1379,7 @@ uint64_t nextPowerOfTwo(uint64_t v) {
 }
 
 // The generators' lists of problems, checked, and where each generator's words lie in the stream: whole blocks of 624, with
-// room for the rejections of the start draws.  Shared by both entry points (`entry` names the caller in the messages).
+// room for the rejections of the start draws (`entry` names the caller in the messages).
 int gibbsStreamLayout(const rpvg_hip_gibbs_spec * spec, const std::vector<uint64_t> & words_needed, const char * entry,
                       std::vector<uint64_t> * stream_off_out) {
     const uint32_t P = spec->num_problems, NG = spec->num_generators;
@@ -1446,80 +1424,38 @@ void orderUnsortedSets(const std::vector<uint64_t> & set_off, const uint32_t * s
     }
 }
 
-}  // namespace
+// ---- the host side: one driver, two variants ---------------------------------------------------------------
+// A call is five stages over one GibbsRun — sizes, uploads and allocations, the generators' streams, the rounds, the sets.
+// What the two entry points do differently is in PairVariant (group sizes 1 and 2) and PolyVariant (3 .. 8) behind it: the
+// memo of the conditionals and what it needs, the refusals, the kernels of a round, how often the host looks, the output.
+struct Progress {  // pinned: what the host reads between two chunks of rounds
+    uint32_t remaining;
+    uint32_t pad[15];
+    GibbsHeader hdr;
+};
 
-extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
-                                    rpvg_hip_gibbs_sets ** result_out) {
-    RPVG_REQUIRE(ctx && groups && spec && result_out, "rpvg_hip_group_gibbs: NULL argument");
-    *result_out = nullptr;
-    const uint32_t P = spec->num_problems, NG = spec->num_generators, GS = spec->group_size;
-    if (GS < 1 || GS > 2) {
-        setError("rpvg_hip_group_gibbs: group size %u (the device sampler takes 1 and 2)", GS);
-        return RPVG_HIP_ERR_UNSUPPORTED;
-    }
-    RPVG_REQUIRE(P == 0 || (spec->matrix && spec->num_chains && spec->num_burn_its && spec->num_gibbs_its && spec->log_freq &&
-                            spec->generator_problem_off && spec->generator_problem && spec->generator_words),
-                 "rpvg_hip_group_gibbs: NULL array");
-    RPVG_REQUIRE(P == 0 || NG >= 1, "rpvg_hip_group_gibbs: no generators");
-    auto result = std::make_unique<rpvg_hip_gibbs_sets>();
-    result->num_problems = P;
-    result->group_size = GS;
-    result->set_off.assign(static_cast<size_t>(P) + 1, 0);
-    result->words_consumed.assign(NG, 0);
-    if (P == 0) {
-        *result_out = result.release();
-        return RPVG_HIP_OK;
-    }
+struct SamplerSpan {  // FAM_GIBBS (closed on every way out)
+    rpvg_hip_ctx * ctx = nullptr;
+    int span = 0;
+    ~SamplerSpan() { if (ctx) ctx->spanEnd(span); }
+};
 
-    std::unique_ptr<HostScope> scope(new HostScope("group_gibbs: host sizes"));
-    // sizes: chains, columns, sample tables, stream capacities
-    std::vector<uint64_t> chain_off(static_cast<size_t>(P) + 1, 0), col_off(static_cast<size_t>(P) + 1, 0), tab_off(static_cast<size_t>(P) + 1, 0);
-    std::vector<uint64_t> words_needed(P, 0);
-    long double dist_bound = 0;
-    uint64_t out_capacity = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        RPVG_REQUIRE(spec->matrix[p] < groups->num_matrices, "rpvg_hip_group_gibbs: problem %u refers to matrix %u of %u", p,
-                     spec->matrix[p], groups->num_matrices);
-        const uint64_t G = groups->h_num_cols[spec->matrix[p]];
-        RPVG_REQUIRE(G >= 1, "rpvg_hip_group_gibbs: problem %u has no columns", p);
-        const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
-        RPVG_REQUIRE(chains * its < 0x40000000ull, "rpvg_hip_group_gibbs: problem %u draws %llu samples", p,
-                     static_cast<unsigned long long>(chains * its));
-        chain_off[p + 1] = chain_off[p] + chains;
-        col_off[p + 1] = col_off[p] + G;
-        const uint64_t sets_bound = std::min<uint64_t>(GS == 2 ? G * (G + 1) / 2 : G, chains * its);
-        tab_off[p + 1] = tab_off[p] + nextPowerOfTwo(2 * sets_bound);
-        out_capacity += sets_bound;
-        const uint64_t draws = chains * all_its * GS;
-        words_needed[p] = chains * GS + (G >= 2 ? 2 * draws : 0);
-        dist_bound += static_cast<long double>(distributionDoubles(G)) * static_cast<long double>(GS == 2 ? G : 1);  // every column as the other member once
-    }
-    const uint64_t num_chains = chain_off[P], num_cols = col_off[P], num_slots = tab_off[P];
-    RPVG_REQUIRE(num_chains < 0x7fffffffull, "rpvg_hip_group_gibbs: %llu chains exceed one launch", static_cast<unsigned long long>(num_chains));
-    RPVG_REQUIRE(num_cols < 0xfffffff0ull, "rpvg_hip_group_gibbs: %llu columns", static_cast<unsigned long long>(num_cols));
-    std::vector<uint64_t> stream_off;
-    {
-        const int layout_status = gibbsStreamLayout(spec, words_needed, "rpvg_hip_group_gibbs", &stream_off);
-        if (layout_status != RPVG_HIP_OK) return layout_status;
-    }
+using SetColumns = std::vector<std::pair<uint32_t *, uint32_t>>;  // (array over the sets, its values per set)
 
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    scope.reset(new HostScope("group_gibbs: uploads, allocations"));
-
-    // storage of the distributions: by the bound when it fits the budget, else the budget (a call that runs out of it
-    // reports RPVG_HIP_ERR_UNSUPPORTED: the caller has the host-driven sampler)
-    uint64_t dist_capacity = 0;
-    {
-        const char * env = std::getenv("RPVG_HIP_GIBBS_BYTES");  // (read per call: a test switches it)
-        size_t free_bytes = 0, total_bytes = 0;
-        RPVG_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
-        long double budget = env ? std::strtold(env, nullptr) : std::min<long double>(0.25L * free_bytes, 32.0L * (1ull << 30));  // (two host lanes ask at the same time)
-        dist_capacity = static_cast<uint64_t>(std::min<long double>(dist_bound, budget / 8));
-        dist_capacity = std::max<uint64_t>(dist_capacity, 1);
-    }
-
+template <typename V>  // V: the variant, derived from GibbsRun<V>
+struct GibbsRun {
+    std::unique_ptr<rpvg_hip_gibbs_sets> result;
+    std::unique_lock<std::mutex> lock;  // the context's, from the uploads on (in front of the buffers: released behind them)
+    rpvg_hip_ctx * const ctx;
+    const rpvg_hip_groups * const groups;
+    const rpvg_hip_gibbs_spec * const spec;
+    const char * const entry;  // the entry point's name, for the messages
+    const uint32_t P, NG, GS;
+    hipStream_t st = nullptr;
+    std::vector<uint64_t> chain_off, col_off, tab_off, words_needed, stream_off;
+    long double dist_bound = 0;  // doubles of distribution storage the call can need
+    uint64_t out_capacity = 0, num_chains = 0, num_cols = 0, num_slots = 0, dist_capacity = 0;
+    uint64_t num_records = 0;  // memo records, counted by the variant's sizeProblem: the columns (1 and 2), the slots of the memo tables (3 .. 8)
     DeviceBuffer<uint32_t> d_matrix, d_chains, d_burn, d_its, d_gen_prob_off, d_gen_prob, d_gen_words;
     DeviceBuffer<uint64_t> d_chain_off, d_col_off, d_tab_off, d_stream_off;
     DeviceBuffer<double> d_log_freq;
@@ -1528,182 +1464,304 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
     DeviceBuffer<GibbsHeader> d_hdr;
     DeviceBuffer<unsigned long long> d_words, d_set_off;
     UploadPack pack;
-    pack.add(d_matrix, spec->matrix, P);
-    pack.add(d_chains, spec->num_chains, P);
-    pack.add(d_burn, spec->num_burn_its, P);
-    pack.add(d_its, spec->num_gibbs_its, P);
-    pack.add(d_gen_prob_off, spec->generator_problem_off, static_cast<size_t>(NG) + 1);
-    pack.add(d_gen_prob, spec->generator_problem, P);
-    pack.add(d_gen_words, spec->generator_words, static_cast<size_t>(NG) * rpvg_streams::kMtWords);
-    pack.add(d_chain_off, chain_off.data(), chain_off.size());
-    pack.add(d_col_off, col_off.data(), col_off.size());
-    pack.add(d_tab_off, tab_off.data(), tab_off.size());
-    pack.add(d_stream_off, stream_off.data(), stream_off.size());
-    pack.add(d_log_freq, spec->log_freq, num_cols);
-    pack.addZero(d_records, num_cols);
-    pack.addZero(d_prob_count, P);
-    pack.addZero(d_prob_done, P);
-    pack.addZero(d_remaining, kMaxRounds);
-    pack.addZero(d_tab_count, num_slots);
-    pack.addZero(d_hdr, 1);
-    pack.addZero(d_words, NG);
-    pack.addZero(d_set_off, static_cast<size_t>(P) + 1);
-    int span = ctx->spanBegin(FAM_H2D);
-    RPVG_HIP_CHECK(pack.commit(st));
-    ctx->spanEnd(span);
-    ctx->stats.h2d_bytes += static_cast<double>(pack.copied_bytes);
-
-    DeviceBuffer<uint32_t> d_stream, d_chain_problem, d_chain_cur, d_chain_iter, d_chain_flag, d_active_problem, d_req_other, d_new_req, d_tab_first;
+    DeviceBuffer<uint32_t> d_stream, d_chain_problem, d_chain_cur, d_chain_iter, d_chain_flag, d_active_problem, d_new_req, d_tab_first;
+    DeviceBuffer<uint32_t> d_req;  // a problem's requests as they were numbered: the other member (1 and 2), the memo slot (3 .. 8)
     DeviceBuffer<unsigned long long> d_chain_pos, d_tab_key;
     DeviceBuffer<ActiveEntry> d_entries;
     DeviceBuffer<double> d_dist;
-    DeviceBuffer<uint32_t> d_out;  // first | second | count | sequence, out_capacity each
+    DeviceBuffer<uint32_t> d_out;  // the variant's columns over the sets | sequence, out_capacity sets each
     DeviceBuffer<uint32_t> d_final_state;
-    RPVG_HIP_CHECK(d_final_state.alloc(static_cast<size_t>(NG) * rpvg_streams::kMtWords));
-    RPVG_HIP_CHECK(d_stream.alloc(stream_off[NG] + kWordWindow));  // (the chains fetch their words four draws ahead)
-    RPVG_HIP_CHECK(d_chain_problem.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_cur.alloc(2 * num_chains));
-    RPVG_HIP_CHECK(d_chain_iter.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_flag.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_pos.alloc(num_chains));
-    RPVG_HIP_CHECK(d_active_problem.alloc(P));
-    RPVG_HIP_CHECK(d_entries.alloc(P));
-    RPVG_HIP_CHECK(d_req_other.alloc(num_cols));
-    RPVG_HIP_CHECK(d_new_req.alloc(num_cols));
-    RPVG_HIP_CHECK(d_tab_key.alloc(num_slots));
-    RPVG_HIP_CHECK(d_tab_first.alloc(num_slots));
-    RPVG_HIP_CHECK(d_dist.alloc(dist_capacity));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_key.ptr, 0xff, num_slots * sizeof(unsigned long long), st));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_first.ptr, 0xff, num_slots * sizeof(uint32_t), st));
+    GibbsProblems pr{};
+    GibbsChains ch{};
+    SamplerSpan sampler_span;
+    std::shared_ptr<void> pinned_guard;
+    Progress * progress = nullptr;
+    uint32_t chains_per_wave = 8, advance_blocks = 0, work_blocks = 0, round = 0;
+    void (V::*queue_round)() = nullptr;  // V::queueRound<GS>
 
-    const GibbsProblems pr{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_col_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
-    const GibbsChains ch{d_chain_problem.ptr, d_chain_pos.ptr, d_chain_cur.ptr, d_chain_iter.ptr, d_chain_flag.ptr};
-    const int sampler_span = ctx->spanBegin(FAM_GIBBS);
-    struct SamplerSpan {  // (closed on every way out)
-        rpvg_hip_ctx * ctx;
-        int span;
-        ~SamplerSpan() { ctx->spanEnd(span); }
-    } sampler_span_guard{ctx, sampler_span};
-    gibbsStreamKernel<<<dim3(NG), dim3(256), 0, st>>>(d_gen_words.ptr, d_gen_prob_off.ptr, d_gen_prob.ptr, d_stream_off.ptr, pr, groups->mat_cols.ptr, GS,
-                                                      d_stream.ptr, ch, d_words.ptr, d_final_state.ptr, d_hdr.ptr);
-    RPVG_HIP_CHECK(hipGetLastError());
-    RPVG_HIP_CHECK(pinnedAlloc(&result->state_block, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t)));
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->state_block, d_final_state.ptr, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(groups->waitCollapse(st));
+    GibbsRun(rpvg_hip_ctx * c, const rpvg_hip_groups * g, const rpvg_hip_gibbs_spec * s)
+        : ctx(c), groups(g), spec(s), entry(V::kEntry), P(s->num_problems), NG(s->num_generators), GS(s->group_size),
+          chain_off(static_cast<size_t>(P) + 1, 0), col_off(chain_off), tab_off(chain_off), words_needed(P, 0) {}
+    V & variant() { return static_cast<V &>(*this); }
+    int refuseTables(size_t) { return RPVG_HIP_OK; }  // (what a variant does not name, it does not have)
+    int afterRounds() { return RPVG_HIP_OK; }
 
-    struct Progress {
-        uint32_t remaining;
-        uint32_t pad[15];
-        GibbsHeader hdr;
-    };
-    void * pinned = nullptr;
-    RPVG_HIP_CHECK(pinnedAlloc(&pinned, sizeof(Progress)));
-    std::shared_ptr<void> pinned_guard(pinned, [](void * ptr) { pinnedFree(ptr); });
-    Progress * progress = static_cast<Progress *>(pinned);
-
-    // share of a distribution from which a column's own conditional is asked for ahead of the chains (group size 2; above 1: never)
-    // (off by default: at 0.02 and 0.002 the fourth round has 750 / 220 chains left instead of 1 330, the dozen chains of a
-    // long-tailed posterior that make the last ten rounds are not helped, and the batch takes as long within the noise)
-    static const double ask_ahead_env = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_ASK_AHEAD") ? std::atof(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_ASK_AHEAD")) : 0.0;
-    const double ask_ahead = (GS == 2 && ask_ahead_env > 0) ? ask_ahead_env : 2.0;
-    // rounds (from the first) whose conditionals go through the tile kernel (A/B)
-    static const uint32_t tiled_rounds = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_TILED_ROUNDS") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_TILED_ROUNDS"))) : 1u;
-    static const uint32_t follow_modes = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_MODES") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_MODES"))) : 2u;
-    static const double follow_share = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_SHARE") ? std::atof(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_SHARE")) : 0.1;
-    static const bool debug = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_DEBUG") != nullptr;
-    DeviceBuffer<unsigned long long> d_debug;
-    if (debug) {
-        RPVG_HIP_CHECK(d_debug.alloc(8ull * kMaxRounds));
-        RPVG_HIP_CHECK(hipMemsetAsync(d_debug.ptr, 0, 8ull * kMaxRounds * sizeof(unsigned long long), st));
+    // sizes: chains, columns, sample tables, stream capacities — and every refusal that needs no device
+    int validateAndSize() {
+        for (uint32_t p = 0; p < P; ++p) {
+            RPVG_REQUIRE(spec->matrix[p] < groups->num_matrices, "%s: problem %u refers to matrix %u of %u", entry, p, spec->matrix[p], groups->num_matrices);
+            const uint64_t G = groups->h_num_cols[spec->matrix[p]];
+            RPVG_REQUIRE(G >= 1, "%s: problem %u has no columns", entry, p);
+            const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
+            RPVG_REQUIRE(chains * its < 0x40000000ull, "%s: problem %u draws %llu samples", entry, p, static_cast<unsigned long long>(chains * its));
+            chain_off[p + 1] = chain_off[p] + chains;
+            col_off[p + 1] = col_off[p] + G;
+            const uint64_t draws = chains * all_its * GS;
+            words_needed[p] = chains * GS + (G >= 2 ? 2 * draws : 0);
+        }
+        for (uint32_t p = 0; p < P; ++p) {  // (behind the invalid arguments: those are errors whatever else the call holds)
+            const uint64_t its = spec->num_gibbs_its[p];
+            const int refused = variant().sizeProblem(p, groups->h_num_cols[spec->matrix[p]], spec->num_chains[p], its, its + spec->num_burn_its[p]);
+            if (refused != RPVG_HIP_OK) return refused;
+        }
+        num_chains = chain_off[P];
+        num_cols = col_off[P];
+        num_slots = tab_off[P];
+        RPVG_REQUIRE(num_chains < 0x7fffffffull, "%s: %llu chains exceed one launch", entry, static_cast<unsigned long long>(num_chains));
+        RPVG_REQUIRE(num_cols < 0xfffffff0ull, "%s: %llu columns", entry, static_cast<unsigned long long>(num_cols));
+        return gibbsStreamLayout(spec, words_needed, entry, &stream_off);
     }
-    scope.reset(new HostScope("group_gibbs: rounds"));
-    const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
-    static const uint32_t chains_per_wave = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_CHAINS_PER_WAVE") ? std::min(64, std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_CHAINS_PER_WAVE")))) : 8u;  // (64 / 16 / 8 chains per wave: 3.7 / 3.2 / 2.6 ms for the five long rounds of a configs[4] lane)
-    const uint32_t advance_blocks = static_cast<uint32_t>((num_chains + 4 * chains_per_wave - 1) / (4 * chains_per_wave));
-    const uint32_t work_blocks = cus * 8;
-    uint32_t round = 0;
-    bool finished = false;
-    static const uint32_t first_rounds = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FIRST_ROUNDS") ? std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FIRST_ROUNDS"))) : 6;
-    uint32_t chunk = first_rounds;
-    while (!finished) {
-        if (round + chunk >= kMaxRounds) {  // (a round per column of a flat posterior over thousands of columns: the caller's sampler takes it)
-            RPVG_HIP_CHECK(waitStream(st));
-            setError("rpvg_hip_group_gibbs: the chains are not done after %u rounds", round);
-            return RPVG_HIP_ERR_UNSUPPORTED;
-        }
-        for (uint32_t r = 0; r < chunk; ++r, ++round) {
-#define RPVG_GIBBS_ROUND(W)                                                                                                            \
-    gibbsAdvanceKernel<W><<<dim3(advance_blocks), dim3(256), 0, st>>>(                                                                 \
-        static_cast<uint32_t>(num_chains), round, pr, groups->mat_cols.ptr, ch, d_stream.ptr, d_records.ptr, d_prob_count.ptr,         \
-        d_prob_done.ptr, d_hdr.ptr, d_remaining.ptr, d_active_problem.ptr, d_req_other.ptr, d_dist.ptr, d_tab_key.ptr,                 \
-        d_tab_count.ptr, d_tab_first.ptr, d_debug.ptr, chains_per_wave);                                                               \
-    gibbsRequestOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(pr, groups->mat_cols.ptr, groups->mat_rows.ptr, d_hdr.ptr,               \
-                                                              d_active_problem.ptr, d_prob_count.ptr, d_prob_done.ptr, d_entries.ptr,  \
-                                                              d_new_req.ptr, d_req_other.ptr, d_records.ptr, dist_capacity,            \
-                                                              (tiled_rounds > round) ? 1u : 0u);                                       \
-    span = ctx->spanBegin(FAM_LOGLIK);                                                                                                 \
-    if (tiled_rounds > round) {                                                                                                        \
-        gibbsConditionalTileKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(                                                        \
-            pr, d_hdr.ptr, d_entries.ptr, d_req_other.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr, groups->mat_fast.ptr,     \
-            groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr, groups->row_count.ptr,                \
-            groups->row_noise.ptr, d_dist.ptr);                                                                                        \
-    } else {                                                                                                                           \
-        gibbsConditionalKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(                                                            \
-            pr, d_hdr.ptr, d_entries.ptr, d_req_other.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr, groups->mat_fast.ptr,     \
-            groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr, groups->row_count.ptr,                \
-            groups->row_noise.ptr, d_dist.ptr);                                                                                        \
-    }                                                                                                                                  \
-    ctx->spanEnd(span)
-            if (GS == 1) {
-                RPVG_GIBBS_ROUND(1);
-            } else {
-                RPVG_GIBBS_ROUND(2);
-            }
-#undef RPVG_GIBBS_ROUND
-            const bool follows = round == 0 && GS == 2 && follow_modes > 0;
-            gibbsDistributionKernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_new_req.ptr, groups->mat_cols.ptr, d_records.ptr, d_dist.ptr,
-                                                                            follows ? follow_share : ask_ahead, d_prob_count.ptr, d_prob_done.ptr,
-                                                                            d_active_problem.ptr, d_req_other.ptr, d_hdr.ptr);
-            // Behind the first round the conditionals of the columns the chains are about to draw — the columns that hold a
-            // tenth or more of a distribution just evaluated — are evaluated twice over before the chains move again: a chain
-            // from a random start needs the conditional of its first draw, then that of its second, and each was a round of all
-            // 60 000 chains of a configs[4] lane (rounds 1-3: 1.3, 6.0 and 12.6 M draws; now 19.6 M draws in the first round
-            // behind the starts and 2 500 chains left after it).  The same conditionals as before, to 0.002 % of the
-            // evaluations: they are the ones the chains ask for anyway.  (RPVG_HIP_GIBBS_FOLLOW_MODES=n, _FOLLOW_SHARE=x)
-            for (uint32_t f = 0; follows && f < follow_modes; ++f) {
-                gibbsRequestOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(pr, groups->mat_cols.ptr, groups->mat_rows.ptr, d_hdr.ptr, d_active_problem.ptr,
-                                                                          d_prob_count.ptr, d_prob_done.ptr, d_entries.ptr, d_new_req.ptr, d_req_other.ptr,
-                                                                          d_records.ptr, dist_capacity, 0u);
-                span = ctx->spanBegin(FAM_LOGLIK);
-                gibbsConditionalKernel<2><<<dim3(work_blocks), dim3(256), 0, st>>>(
-                    pr, d_hdr.ptr, d_entries.ptr, d_req_other.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr, groups->mat_fast.ptr,
-                    groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr, groups->row_count.ptr,
-                    groups->row_noise.ptr, d_dist.ptr);
-                ctx->spanEnd(span);
-                gibbsDistributionKernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_new_req.ptr, groups->mat_cols.ptr, d_records.ptr, d_dist.ptr,
-                                                                                (f + 1 < follow_modes) ? follow_share : ask_ahead, d_prob_count.ptr,
-                                                                                d_prob_done.ptr, d_active_problem.ptr, d_req_other.ptr, d_hdr.ptr);
-            }
-        }
+
+    int uploadAndAllocate() {
+        // storage of the distributions: by the bound when it fits the budget, else the budget (a call that runs out of it
+        // reports RPVG_HIP_ERR_UNSUPPORTED: the caller has the host-driven sampler)
+        const char * env = std::getenv("RPVG_HIP_GIBBS_BYTES");  // (read per call: a test switches it)
+        size_t free_bytes = 0, total_bytes = 0;
+        RPVG_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+        const int refused = variant().refuseTables(free_bytes);
+        if (refused != RPVG_HIP_OK) return refused;
+        long double budget = env ? std::strtold(env, nullptr) : std::min<long double>(0.25L * free_bytes, 32.0L * (1ull << 30));  // (two host lanes ask at the same time)
+        dist_capacity = static_cast<uint64_t>(std::min<long double>(dist_bound, budget / 8));
+        dist_capacity = std::max<uint64_t>(dist_capacity, 1);
+
+        pack.add(d_matrix, spec->matrix, P);
+        pack.add(d_chains, spec->num_chains, P);
+        pack.add(d_burn, spec->num_burn_its, P);
+        pack.add(d_its, spec->num_gibbs_its, P);
+        pack.add(d_gen_prob_off, spec->generator_problem_off, static_cast<size_t>(NG) + 1);
+        pack.add(d_gen_prob, spec->generator_problem, P);
+        pack.add(d_gen_words, spec->generator_words, static_cast<size_t>(NG) * rpvg_streams::kMtWords);
+        pack.add(d_chain_off, chain_off.data(), chain_off.size());
+        pack.add(d_col_off, col_off.data(), col_off.size());
+        pack.add(d_tab_off, tab_off.data(), tab_off.size());
+        variant().addUploads();
+        pack.add(d_stream_off, stream_off.data(), stream_off.size());
+        pack.add(d_log_freq, spec->log_freq, num_cols);
+        pack.addZero(d_prob_count, P);
+        pack.addZero(d_prob_done, P);
+        pack.addZero(d_remaining, kMaxRounds);
+        pack.addZero(d_hdr, 1);
+        pack.addZero(d_words, NG);
+        pack.addZero(d_set_off, static_cast<size_t>(P) + 1);
+        const int span = ctx->spanBegin(FAM_H2D);
+        RPVG_HIP_CHECK(pack.commit(st));
+        ctx->spanEnd(span);
+        ctx->stats.h2d_bytes += static_cast<double>(pack.copied_bytes);
+
+        RPVG_HIP_CHECK(d_final_state.alloc(static_cast<size_t>(NG) * rpvg_streams::kMtWords));
+        RPVG_HIP_CHECK(d_stream.alloc(stream_off[NG] + kWordWindow));  // (the chains fetch their words four draws ahead)
+        RPVG_HIP_CHECK(d_chain_problem.alloc(num_chains));
+        RPVG_HIP_CHECK(d_chain_cur.alloc(std::max(2u, GS) * num_chains));  // (gibbsStreamKernel's cur_stride: the kernels of group size 1 keep two slots too)
+        RPVG_HIP_CHECK(d_chain_iter.alloc(num_chains));
+        RPVG_HIP_CHECK(d_chain_flag.alloc(num_chains));
+        RPVG_HIP_CHECK(d_chain_pos.alloc(num_chains));
+        RPVG_HIP_CHECK(d_active_problem.alloc(P));
+        RPVG_HIP_CHECK(d_entries.alloc(P));
+        RPVG_HIP_CHECK(d_req.alloc(num_records));
+        RPVG_HIP_CHECK(d_new_req.alloc(num_records));
+        RPVG_HIP_CHECK(d_tab_key.alloc(num_slots));
+        RPVG_HIP_CHECK(d_tab_first.alloc(num_slots));
+        RPVG_HIP_CHECK(d_dist.alloc(dist_capacity));
+        RPVG_HIP_CHECK(hipMemsetAsync(d_tab_key.ptr, 0xff, num_slots * sizeof(unsigned long long), st));
+        RPVG_HIP_CHECK(hipMemsetAsync(d_tab_first.ptr, 0xff, num_slots * sizeof(uint32_t), st));
+        pr = GibbsProblems{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_col_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
+        ch = GibbsChains{d_chain_problem.ptr, d_chain_pos.ptr, d_chain_cur.ptr, d_chain_iter.ptr, d_chain_flag.ptr};
+        return variant().allocateOwn();  // (what only the variant has; a memo table's offsets go into pr.rec_off)
+    }
+
+    // the generators' words and every chain's start, the generators' final state on its way back, the block the rounds report into
+    int startStreams() {
+        const size_t state_bytes = static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t);
+        sampler_span.span = ctx->spanBegin(FAM_GIBBS);
+        sampler_span.ctx = ctx;
+        gibbsStreamKernel<<<dim3(NG), dim3(256), 0, st>>>(d_gen_words.ptr, d_gen_prob_off.ptr, d_gen_prob.ptr, d_stream_off.ptr, pr, groups->mat_cols.ptr, GS,
+                                                          d_stream.ptr, ch, d_words.ptr, d_final_state.ptr, d_hdr.ptr);
         RPVG_HIP_CHECK(hipGetLastError());
-        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->remaining, d_remaining.ptr + (round - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(waitStream(st));
-        if (progress->hdr.error) {
-            const uint32_t err = progress->hdr.error;
-            if (err & kErrDistributions) {
-                setError("rpvg_hip_group_gibbs: the conditional distributions need more than the %llu bytes reserved for them (RPVG_HIP_GIBBS_BYTES)",
-                         static_cast<unsigned long long>(dist_capacity * 8));
+        RPVG_HIP_CHECK(pinnedAlloc(&result->state_block, state_bytes));
+        RPVG_HIP_CHECK(hipMemcpyAsync(result->state_block, d_final_state.ptr, state_bytes, hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(groups->waitCollapse(st));
+        void * pinned = nullptr;
+        RPVG_HIP_CHECK(pinnedAlloc(&pinned, sizeof(Progress)));
+        pinned_guard.reset(pinned, [](void * ptr) { pinnedFree(ptr); });
+        progress = static_cast<Progress *>(pinned);
+        return RPVG_HIP_OK;
+    }
+
+    // the launches every round of either variant has
+    void queueRequestOffsets(const uint32_t tiled) {
+        gibbsRequestOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(pr, groups->mat_cols.ptr, groups->mat_rows.ptr, d_hdr.ptr, d_active_problem.ptr,
+                                                                  d_prob_count.ptr, d_prob_done.ptr, d_entries.ptr, d_new_req.ptr, d_req.ptr,
+                                                                  d_records.ptr, dist_capacity, tiled);
+    }
+    void queueDistributions(const double ask_ahead) {
+        gibbsDistributionKernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_new_req.ptr, groups->mat_cols.ptr, d_records.ptr, d_dist.ptr,
+                                                                        ask_ahead, d_prob_count.ptr, d_prob_done.ptr, d_active_problem.ptr, d_req.ptr,
+                                                                        d_hdr.ptr);
+    }
+
+    // Rounds by the chunk, nothing of them waited for in between, until the last round of a chunk left no chain waiting.
+    int runRounds() {
+        queue_round = V::roundOfSize(GS);
+        advance_blocks = static_cast<uint32_t>((num_chains + 4 * chains_per_wave - 1) / (4 * chains_per_wave));
+        work_blocks = static_cast<uint32_t>(ctx->props.multiProcessorCount) * 8;
+        bool finished = false;
+        while (!finished) {
+            const uint32_t chunk = variant().chunk();
+            if (round + chunk >= kMaxRounds) {  // (a round per column of a flat posterior over thousands of columns: the caller's sampler takes it)
+                RPVG_HIP_CHECK(waitStream(st));
+                setError("%s: the chains are not done after %u rounds", entry, round);
                 return RPVG_HIP_ERR_UNSUPPORTED;
             }
-            setError("rpvg_hip_group_gibbs: a generator's start draws ran past the words generated for it");
-            return RPVG_HIP_ERR_RUNTIME;
+            for (uint32_t r = 0; r < chunk; ++r, ++round) (variant().*queue_round)();
+            RPVG_HIP_CHECK(hipGetLastError());
+            RPVG_HIP_CHECK(hipMemcpyAsync(&progress->remaining, d_remaining.ptr + (round - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
+            RPVG_HIP_CHECK(waitStream(st));
+            if (progress->hdr.error) {
+                const uint32_t err = progress->hdr.error;
+                if (err & kErrDistributions) {
+                    setError("%s: the conditional distributions need more than the %llu bytes reserved for them (RPVG_HIP_GIBBS_BYTES)", entry,
+                             static_cast<unsigned long long>(dist_capacity * 8));
+                    return RPVG_HIP_ERR_UNSUPPORTED;
+                }
+                if ((err & kErrTable) && V::kTablesCanFill) {
+                    setError("%s: a table of sampled sets or of conditionals is full", entry);
+                    return RPVG_HIP_ERR_UNSUPPORTED;
+                }
+                setError("%s: a generator's start draws ran past the words generated for it", entry);
+                return RPVG_HIP_ERR_RUNTIME;
+            }
+            finished = progress->remaining == 0;
         }
-        finished = progress->remaining == 0;
-        chunk = 4;
+        const int status = variant().afterRounds();
+        if (status != RPVG_HIP_OK) return status;
+        ctx->stats.loglik_launches += round;
+        ctx->stats.loglik_evals += progress->hdr.evals;
+        result->rounds = round;
+        result->conditionals = progress->hdr.total_requests;
+        return RPVG_HIP_OK;
     }
-    if (debug) {
+
+    // The sets of every problem in the order of their first samples: counted, their offsets, collected into the variant's columns
+    // (out_capacity sets each on the device, total_sets in the result's pinned block) with the sequence numbers behind them,
+    // which come back only when the collect kernel left problems for the host to order.
+    int collect() {
+        const uint32_t words = variant().wordsPerSet();  // the variant's columns and the sequence number
+        RPVG_HIP_CHECK(d_out.alloc(words * out_capacity));
+        uint32_t * out_seq = nullptr, * host_seq = nullptr;
+        const SetColumns out = variant().setColumns(d_out.ptr, out_capacity, out_seq);
+        gibbsCountSetsKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_set_off.ptr);
+        gibbsSetOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(P, d_set_off.ptr, d_hdr.ptr);
+        variant().queueCollect(out, out_seq);
+        RPVG_HIP_CHECK(hipGetLastError());
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are copied as they are");
+        RPVG_HIP_CHECK(hipMemcpyAsync(result->set_off.data(), d_set_off.ptr, (static_cast<size_t>(P) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(result->words_consumed.data(), d_words.ptr, static_cast<size_t>(NG) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(waitStream(st));
+        const uint64_t total_sets = progress->hdr.total_sets;
+        RPVG_REQUIRE(total_sets <= out_capacity, "%s: %llu sets in room for %llu", entry, static_cast<unsigned long long>(total_sets),
+                     static_cast<unsigned long long>(out_capacity));
+        if (total_sets > 0) {
+            RPVG_HIP_CHECK(pinnedAlloc(&result->block, words * total_sets * sizeof(uint32_t)));
+            const SetColumns host = variant().setColumns(static_cast<uint32_t *>(result->block), total_sets, host_seq);
+            for (size_t c = 0; c < host.size(); ++c) {
+                RPVG_HIP_CHECK(hipMemcpyAsync(host[c].first, out[c].first, host[c].second * total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            }
+            if (progress->hdr.unsorted) {
+                RPVG_HIP_CHECK(hipMemcpyAsync(host_seq, out_seq, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            }
+            RPVG_HIP_CHECK(waitStream(st));
+            if (progress->hdr.unsorted) orderUnsortedSets(result->set_off, host_seq, host);  // the few problems with more sets than the collect kernel ranks in LDS
+            variant().publish(host);
+        }
+        const int build_status = groups->buildError(st);  // the matrices were built without a host sync
+        if (build_status != RPVG_HIP_OK) return build_status;
+        ctx->stats.gibbs_calls_completed += 1;
+        return RPVG_HIP_OK;
+    }
+};
+
+// ---- group sizes 1 and 2: a conditional is indexed by the one other member, a record per column ------------------
+struct PairVariant : GibbsRun<PairVariant> {
+    using GibbsRun::GibbsRun;
+    static constexpr const char * kEntry = "rpvg_hip_group_gibbs";
+    static constexpr const char * kScopes[4] = {"group_gibbs: host sizes", "group_gibbs: uploads, allocations", "group_gibbs: rounds", "group_gibbs: sets"};
+    static constexpr bool kTablesCanFill = false;  // (kErrTable cannot occur)
+    bool debug = false;
+    DeviceBuffer<unsigned long long> d_debug;  // RPVG_HIP_GIBBS_DEBUG: eight counters per round
+
+    int sizeProblem(const uint32_t p, const uint64_t G, const uint64_t chains, const uint64_t its, const uint64_t) {
+        const uint64_t sets_bound = std::min<uint64_t>(GS == 2 ? G * (G + 1) / 2 : G, chains * its);
+        tab_off[p + 1] = tab_off[p] + nextPowerOfTwo(2 * sets_bound);
+        out_capacity += sets_bound;
+        num_records += G;
+        dist_bound += static_cast<long double>(distributionDoubles(G)) * static_cast<long double>(GS == 2 ? G : 1);  // every column as the other member once
+        return RPVG_HIP_OK;
+    }
+    void addUploads() {
+        pack.addZero(d_records, num_cols);
+        pack.addZero(d_tab_count, num_slots);
+    }
+    int allocateOwn() {
+        static const bool debug_env = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_DEBUG") != nullptr;
+        debug = debug_env;
+        if (debug) {
+            RPVG_HIP_CHECK(d_debug.alloc(8ull * kMaxRounds));
+            RPVG_HIP_CHECK(hipMemsetAsync(d_debug.ptr, 0, 8ull * kMaxRounds * sizeof(unsigned long long), st));
+        }
+        static const uint32_t chains_per_wave_env = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_CHAINS_PER_WAVE") ? std::min(64, std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_CHAINS_PER_WAVE")))) : 8u;  // (64 / 16 / 8 chains per wave: 3.7 / 3.2 / 2.6 ms for the five long rounds of a configs[4] lane)
+        chains_per_wave = chains_per_wave_env;
+        return RPVG_HIP_OK;
+    }
+    static auto roundOfSize(const uint32_t size) { return size == 1 ? &PairVariant::queueRound<1> : &PairVariant::queueRound<2>; }
+
+    template <int W>
+    void queueRound() {
+        // share of a distribution from which a column's own conditional is asked for ahead of the chains (group size 2; above 1: never)
+        // (off by default: at 0.02 and 0.002 the fourth round has 750 / 220 chains left instead of 1 330, the dozen chains of a
+        // long-tailed posterior that make the last ten rounds are not helped, and the batch takes as long within the noise)
+        static const double ask_ahead_env = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_ASK_AHEAD") ? std::atof(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_ASK_AHEAD")) : 0.0;
+        const double ask_ahead = (W == 2 && ask_ahead_env > 0) ? ask_ahead_env : 2.0;
+        // rounds (from the first) whose conditionals go through the tile kernel (A/B)
+        static const uint32_t tiled_rounds = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_TILED_ROUNDS") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_TILED_ROUNDS"))) : 1u;
+        static const uint32_t follow_modes = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_MODES") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_MODES"))) : 2u;
+        static const double follow_share = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_SHARE") ? std::atof(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FOLLOW_SHARE")) : 0.1;
+        gibbsAdvanceKernel<W><<<dim3(advance_blocks), dim3(256), 0, st>>>(
+            static_cast<uint32_t>(num_chains), round, pr, groups->mat_cols.ptr, ch, d_stream.ptr, d_records.ptr, d_prob_count.ptr,
+            d_prob_done.ptr, d_hdr.ptr, d_remaining.ptr, d_active_problem.ptr, d_req.ptr, d_dist.ptr, d_tab_key.ptr,
+            d_tab_count.ptr, d_tab_first.ptr, d_debug.ptr, chains_per_wave);
+        queueRequestOffsets((tiled_rounds > round) ? 1u : 0u);
+        queueConditionals((tiled_rounds > round) ? gibbsConditionalTileKernel<W> : gibbsConditionalKernel<W>);
+        const bool follows = round == 0 && W == 2 && follow_modes > 0;
+        queueDistributions(follows ? follow_share : ask_ahead);
+        // Behind the first round the conditionals of the columns the chains are about to draw — the columns that hold a
+        // tenth or more of a distribution just evaluated — are evaluated twice over before the chains move again: a chain
+        // from a random start needs the conditional of its first draw, then that of its second, and each was a round of all
+        // 60 000 chains of a configs[4] lane (rounds 1-3: 1.3, 6.0 and 12.6 M draws; now 19.6 M draws in the first round
+        // behind the starts and 2 500 chains left after it).  The same conditionals as before, to 0.002 % of the
+        // evaluations: they are the ones the chains ask for anyway.  (RPVG_HIP_GIBBS_FOLLOW_MODES=n, _FOLLOW_SHARE=x)
+        for (uint32_t f = 0; follows && f < follow_modes; ++f) {
+            queueRequestOffsets(0u);
+            queueConditionals(gibbsConditionalKernel<2>);
+            queueDistributions((f + 1 < follow_modes) ? follow_share : ask_ahead);
+        }
+    }
+    void queueConditionals(decltype(&gibbsConditionalKernel<2>) kernel) {  // (the tile kernel takes the same arguments)
+        const int span = ctx->spanBegin(FAM_LOGLIK);
+        kernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,
+                                                       groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr,
+                                                       groups->values.ptr, groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);
+        ctx->spanEnd(span);
+    }
+
+    uint32_t chunk() const {  // rounds queued before the host looks at the chains left
+        static const uint32_t first_rounds = RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FIRST_ROUNDS") ? std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_GIBBS_FIRST_ROUNDS"))) : 6;
+        return round == 0 ? first_rounds : 4;
+    }
+
+    int afterRounds() {
+        if (!debug) return RPVG_HIP_OK;
         std::vector<unsigned long long> counts(8ull * round);
         RPVG_HIP_CHECK(hipMemcpy(counts.data(), d_debug.ptr, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (uint32_t r = 0; r < round; ++r) {
@@ -1711,111 +1769,48 @@ extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * 
             std::fprintf(stderr, "[rpvg_hip gibbs] round %2u: %7llu chains ran, %9llu draws (most of one chain %6llu), %8llu record lookups, %8llu draws off the mode (%llu walked on), %8llu key changes\n",
                          r, c[0], c[1], c[2], c[3], c[4], c[5], c[6]);
         }
+        return RPVG_HIP_OK;
     }
-    ctx->stats.loglik_launches += round;
-    ctx->stats.loglik_evals += progress->hdr.evals;
-    result->rounds = round;
-    result->conditionals = progress->hdr.total_requests;
 
-    // the sets
-    scope.reset(new HostScope("group_gibbs: sets"));
-    RPVG_HIP_CHECK(d_out.alloc(4 * out_capacity));
-    uint32_t * out_first = d_out.ptr, * out_second = d_out.ptr + out_capacity, * out_count = d_out.ptr + 2 * out_capacity,
-             * out_seq = d_out.ptr + 3 * out_capacity;
-    gibbsCountSetsKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_set_off.ptr);
-    gibbsSetOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(P, d_set_off.ptr, d_hdr.ptr);
-    gibbsCollectKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, d_set_off.ptr, out_first, out_second,
-                                                      out_count, out_seq, d_hdr.ptr);
-    RPVG_HIP_CHECK(hipGetLastError());
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are copied as they are");
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->set_off.data(), d_set_off.ptr, (static_cast<size_t>(P) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->words_consumed.data(), d_words.ptr, static_cast<size_t>(NG) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(waitStream(st));
-    const uint64_t total_sets = progress->hdr.total_sets;
-    RPVG_REQUIRE(total_sets <= out_capacity, "rpvg_hip_group_gibbs: %llu sets in room for %llu", static_cast<unsigned long long>(total_sets),
-                 static_cast<unsigned long long>(out_capacity));
-    if (total_sets > 0) {
-        RPVG_HIP_CHECK(pinnedAlloc(&result->block, 4 * total_sets * sizeof(uint32_t)));
-        uint32_t * host = static_cast<uint32_t *>(result->block);
-        RPVG_HIP_CHECK(hipMemcpyAsync(host, out_first, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipMemcpyAsync(host + total_sets, out_second, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipMemcpyAsync(host + 2 * total_sets, out_count, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (progress->hdr.unsorted) {
-            RPVG_HIP_CHECK(hipMemcpyAsync(host + 3 * total_sets, out_seq, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        }
-        RPVG_HIP_CHECK(waitStream(st));
-        if (progress->hdr.unsorted) {  // the few problems with more sets than the collect kernel ranks in LDS
-            orderUnsortedSets(result->set_off, host + 3 * total_sets, {{host, 1u}, {host + total_sets, 1u}, {host + 2 * total_sets, 1u}});
-        }
-        result->first = host;
-        result->second = host + total_sets;
-        result->count = host + 2 * total_sets;
+    uint32_t wordsPerSet() const { return 4; }  // first | second | count | sequence
+    SetColumns setColumns(uint32_t * block, const uint64_t sets, uint32_t *& seq) const {
+        seq = block + 3 * sets;
+        return {{block, 1u}, {block + sets, 1u}, {block + 2 * sets, 1u}};
     }
-    const int build_status = groups->buildError(st);  // the matrices were built without a host sync
-    if (build_status != RPVG_HIP_OK) return build_status;
-    ctx->stats.gibbs_calls_completed += 1;
-    *result_out = result.release();
-    return RPVG_HIP_OK;
-}
+    void queueCollect(const SetColumns & out, uint32_t * out_seq) {
+        gibbsCollectKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, d_set_off.ptr, out[0].first, out[1].first,
+                                                          out[2].first, out_seq, d_hdr.ptr);
+    }
+    void publish(const SetColumns & host) {
+        result->first = host[0].first;
+        result->second = host[1].first;
+        result->count = host[2].first;
+    }
+};
 
-// Group sizes 3 .. 8: the same rounds (advance -> request offsets -> conditionals -> distributions) over a memo TABLE per
+// ---- group sizes 3 .. 8: the same rounds (advance -> request offsets -> conditionals -> distributions) over a memo TABLE per
 // problem.  Both tables of a problem are sized from what its chains can make — sets: min(multisets of GS columns, chains x
 // its); conditionals: min(multisets of GS - 1 columns, chains x (burn + its) x GS) — doubled and rounded up to a power of
 // two, so they cannot fill; together they must fit a quarter of the free device memory (at most 16 GiB), or the call is the
 // caller's.  The distributions are handed out of RPVG_HIP_GIBBS_BYTES as the requests come.
-extern "C" int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
-                                              rpvg_hip_gibbs_sets ** result_out) {
-    RPVG_REQUIRE(ctx && groups && spec && result_out, "rpvg_hip_group_gibbs_polyploid: NULL argument");
-    *result_out = nullptr;
-    const uint32_t P = spec->num_problems, NG = spec->num_generators, GS = spec->group_size;
-    if (GS < 3 || GS > kMaxGroupSize) {
-        setError("rpvg_hip_group_gibbs_polyploid: group size %u (this entry point takes 3 .. 8, rpvg_hip_group_gibbs 1 and 2)", GS);
-        return RPVG_HIP_ERR_UNSUPPORTED;
-    }
-    RPVG_REQUIRE(P == 0 || (spec->matrix && spec->num_chains && spec->num_burn_its && spec->num_gibbs_its && spec->log_freq &&
-                            spec->generator_problem_off && spec->generator_problem && spec->generator_words),
-                 "rpvg_hip_group_gibbs_polyploid: NULL array");
-    RPVG_REQUIRE(P == 0 || NG >= 1, "rpvg_hip_group_gibbs_polyploid: no generators");
-    auto result = std::make_unique<rpvg_hip_gibbs_sets>();
-    result->num_problems = P;
-    result->group_size = GS;
-    result->set_off.assign(static_cast<size_t>(P) + 1, 0);
-    result->words_consumed.assign(NG, 0);
-    if (P == 0) {
-        *result_out = result.release();
-        return RPVG_HIP_OK;
-    }
+struct PolyVariant : GibbsRun<PolyVariant> {
+    static constexpr const char * kEntry = "rpvg_hip_group_gibbs_polyploid";
+    static constexpr const char * kScopes[4] = {"group_gibbs_polyploid: host sizes", "group_gibbs_polyploid: uploads, allocations",
+                                                "group_gibbs_polyploid: rounds", "group_gibbs_polyploid: sets"};
+    static constexpr bool kTablesCanFill = true;  // (they are sized not to: kErrTable is "unsupported")
+    std::vector<uint64_t> memo_off;  // [P+1] slots of the problems' memo tables (powers of two)
+    DeviceBuffer<uint64_t> d_memo_off;
+    DeviceBuffer<unsigned long long> d_memo_key;
+    PolyVariant(rpvg_hip_ctx * c, const rpvg_hip_groups * g, const rpvg_hip_gibbs_spec * s) : GibbsRun(c, g, s), memo_off(chain_off) {}
 
-    std::unique_ptr<HostScope> scope(new HostScope("group_gibbs_polyploid: host sizes"));
-    const uint64_t max_columns = (1ull << memberBits(GS)) - 1;  // all-ones is the empty key
-    std::vector<uint64_t> chain_off(static_cast<size_t>(P) + 1, 0), col_off(static_cast<size_t>(P) + 1, 0), tab_off(static_cast<size_t>(P) + 1, 0),
-        memo_off(static_cast<size_t>(P) + 1, 0);
-    std::vector<uint64_t> words_needed(P, 0);
-    long double dist_bound = 0;
-    uint64_t out_capacity = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        RPVG_REQUIRE(spec->matrix[p] < groups->num_matrices, "rpvg_hip_group_gibbs_polyploid: problem %u refers to matrix %u of %u", p,
-                     spec->matrix[p], groups->num_matrices);
-        const uint64_t G = groups->h_num_cols[spec->matrix[p]];
-        RPVG_REQUIRE(G >= 1, "rpvg_hip_group_gibbs_polyploid: problem %u has no columns", p);
-        const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
-        RPVG_REQUIRE(chains * its < 0x40000000ull, "rpvg_hip_group_gibbs_polyploid: problem %u draws %llu samples", p,
-                     static_cast<unsigned long long>(chains * its));
-        chain_off[p + 1] = chain_off[p] + chains;
-        col_off[p + 1] = col_off[p] + G;
-        const uint64_t draws = chains * all_its * GS;
-        words_needed[p] = chains * GS + (G >= 2 ? 2 * draws : 0);
-    }
-    for (uint32_t p = 0; p < P; ++p) {  // (behind the invalid arguments: those are errors whatever else the call holds)
-        const uint64_t G = groups->h_num_cols[spec->matrix[p]];
+    int sizeProblem(const uint32_t p, const uint64_t G, const uint64_t chains, const uint64_t its, const uint64_t all_its) {
+        const uint64_t max_columns = (1ull << memberBits(GS)) - 1;  // all-ones is the empty key
         if (G > max_columns) {
             setError("rpvg_hip_group_gibbs_polyploid: problem %u has %llu columns, the device sampler takes at most %llu at group size %u "
                      "(%u bits per member of a packed key)", p, static_cast<unsigned long long>(G), static_cast<unsigned long long>(max_columns),
                      GS, memberBits(GS));
             return RPVG_HIP_ERR_UNSUPPORTED;
         }
-        const uint64_t chains = spec->num_chains[p], its = spec->num_gibbs_its[p], all_its = its + spec->num_burn_its[p];
         // A chain waits at most once per draw: all_its x GS rounds at the worst (a flat posterior over many columns comes
         // close to it).  A problem whose worst case is past twice kMaxRounds is not tried: it would queue thousands of rounds
         // before the answer is "unsupported" all the same.
@@ -1828,28 +1823,12 @@ extern "C" int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip
         const uint64_t memo_bound = G >= 2 ? std::min<uint64_t>(rpvg_hip_full_set_count(static_cast<uint32_t>(G), GS - 1), chains * all_its * GS) : 0;
         tab_off[p + 1] = tab_off[p] + nextPowerOfTwo(2 * sets_bound);
         memo_off[p + 1] = memo_off[p] + nextPowerOfTwo(2 * memo_bound);
+        num_records = memo_off[p + 1];
         out_capacity += sets_bound;
         dist_bound += static_cast<long double>(distributionDoubles(G)) * static_cast<long double>(memo_bound);
+        return RPVG_HIP_OK;
     }
-    const uint64_t num_chains = chain_off[P], num_cols = col_off[P], num_slots = tab_off[P], num_records = memo_off[P];
-    RPVG_REQUIRE(num_chains < 0x7fffffffull, "rpvg_hip_group_gibbs_polyploid: %llu chains exceed one launch", static_cast<unsigned long long>(num_chains));
-    RPVG_REQUIRE(num_cols < 0xfffffff0ull, "rpvg_hip_group_gibbs_polyploid: %llu columns", static_cast<unsigned long long>(num_cols));
-    std::vector<uint64_t> stream_off;
-    {
-        const int layout_status = gibbsStreamLayout(spec, words_needed, "rpvg_hip_group_gibbs_polyploid", &stream_off);
-        if (layout_status != RPVG_HIP_OK) return layout_status;
-    }
-
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    scope.reset(new HostScope("group_gibbs_polyploid: uploads, allocations"));
-
-    uint64_t dist_capacity = 0;
-    {
-        const char * env = std::getenv("RPVG_HIP_GIBBS_BYTES");  // (read per call: a test switches it)
-        size_t free_bytes = 0, total_bytes = 0;
-        RPVG_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+    int refuseTables(const size_t free_bytes) {
         // per set slot: key, count, first sample; per memo slot: key, record, request list, round list
         const long double table_bytes = 16.0L * num_slots + (8.0L + sizeof(RequestInfo) + 8.0L) * num_records;
         const long double table_budget = std::min<long double>(0.25L * free_bytes, 16.0L * (1ull << 30));
@@ -1858,205 +1837,116 @@ extern "C" int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip
                      table_bytes, table_budget);
             return RPVG_HIP_ERR_UNSUPPORTED;
         }
-        long double budget = env ? std::strtold(env, nullptr) : std::min<long double>(0.25L * free_bytes, 32.0L * (1ull << 30));
-        dist_capacity = static_cast<uint64_t>(std::min<long double>(dist_bound, budget / 8));
-        dist_capacity = std::max<uint64_t>(dist_capacity, 1);
+        return RPVG_HIP_OK;
+    }
+    void addUploads() { pack.add(d_memo_off, memo_off.data(), memo_off.size()); }
+    int allocateOwn() {
+        pr.rec_off = d_memo_off.ptr;
+        RPVG_HIP_CHECK(d_records.alloc(num_records));
+        RPVG_HIP_CHECK(d_memo_key.alloc(num_records));
+        RPVG_HIP_CHECK(d_tab_count.alloc(num_slots));
+        RPVG_HIP_CHECK(hipMemsetAsync(d_records.ptr, 0, num_records * sizeof(RequestInfo), st));
+        RPVG_HIP_CHECK(hipMemsetAsync(d_memo_key.ptr, 0xff, num_records * sizeof(unsigned long long), st));
+        RPVG_HIP_CHECK(hipMemsetAsync(d_tab_count.ptr, 0, num_slots * sizeof(uint32_t), st));
+        return RPVG_HIP_OK;
+    }
+    static auto roundOfSize(const uint32_t size) {  // (chains_per_wave stays 8, as at group size 2: a wave runs the union of its chains' paths)
+        static constexpr void (PolyVariant::*kRounds[])() = {&PolyVariant::queueRound<3>, &PolyVariant::queueRound<4>, &PolyVariant::queueRound<5>,
+                                                             &PolyVariant::queueRound<6>, &PolyVariant::queueRound<7>, &PolyVariant::queueRound<8>};
+        return kRounds[size - 3];
     }
 
-    DeviceBuffer<uint32_t> d_matrix, d_chains, d_burn, d_its, d_gen_prob_off, d_gen_prob, d_gen_words;
-    DeviceBuffer<uint64_t> d_chain_off, d_col_off, d_tab_off, d_memo_off, d_stream_off;
-    DeviceBuffer<double> d_log_freq;
-    DeviceBuffer<uint32_t> d_remaining, d_tab_count, d_prob_count, d_prob_done;
-    DeviceBuffer<RequestInfo> d_records;
-    DeviceBuffer<GibbsHeader> d_hdr;
-    DeviceBuffer<unsigned long long> d_words, d_set_off;
-    UploadPack pack;
-    pack.add(d_matrix, spec->matrix, P);
-    pack.add(d_chains, spec->num_chains, P);
-    pack.add(d_burn, spec->num_burn_its, P);
-    pack.add(d_its, spec->num_gibbs_its, P);
-    pack.add(d_gen_prob_off, spec->generator_problem_off, static_cast<size_t>(NG) + 1);
-    pack.add(d_gen_prob, spec->generator_problem, P);
-    pack.add(d_gen_words, spec->generator_words, static_cast<size_t>(NG) * rpvg_streams::kMtWords);
-    pack.add(d_chain_off, chain_off.data(), chain_off.size());
-    pack.add(d_col_off, col_off.data(), col_off.size());
-    pack.add(d_tab_off, tab_off.data(), tab_off.size());
-    pack.add(d_memo_off, memo_off.data(), memo_off.size());
-    pack.add(d_stream_off, stream_off.data(), stream_off.size());
-    pack.add(d_log_freq, spec->log_freq, num_cols);
-    pack.addZero(d_prob_count, P);
-    pack.addZero(d_prob_done, P);
-    pack.addZero(d_remaining, kMaxRounds);
-    pack.addZero(d_hdr, 1);
-    pack.addZero(d_words, NG);
-    pack.addZero(d_set_off, static_cast<size_t>(P) + 1);
-    int span = ctx->spanBegin(FAM_H2D);
-    RPVG_HIP_CHECK(pack.commit(st));
-    ctx->spanEnd(span);
-    ctx->stats.h2d_bytes += static_cast<double>(pack.copied_bytes);
-
-    DeviceBuffer<uint32_t> d_stream, d_chain_problem, d_chain_cur, d_chain_iter, d_chain_flag, d_active_problem, d_req_slot, d_new_req, d_tab_first;
-    DeviceBuffer<unsigned long long> d_chain_pos, d_tab_key, d_memo_key;
-    DeviceBuffer<ActiveEntry> d_entries;
-    DeviceBuffer<double> d_dist;
-    DeviceBuffer<uint32_t> d_out;  // members | count | sequence
-    DeviceBuffer<uint32_t> d_final_state;
-    RPVG_HIP_CHECK(d_final_state.alloc(static_cast<size_t>(NG) * rpvg_streams::kMtWords));
-    RPVG_HIP_CHECK(d_stream.alloc(stream_off[NG] + kWordWindow));  // (the chains fetch their words four draws ahead)
-    RPVG_HIP_CHECK(d_chain_problem.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_cur.alloc(GS * num_chains));
-    RPVG_HIP_CHECK(d_chain_iter.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_flag.alloc(num_chains));
-    RPVG_HIP_CHECK(d_chain_pos.alloc(num_chains));
-    RPVG_HIP_CHECK(d_active_problem.alloc(P));
-    RPVG_HIP_CHECK(d_entries.alloc(P));
-    RPVG_HIP_CHECK(d_records.alloc(num_records));
-    RPVG_HIP_CHECK(d_req_slot.alloc(num_records));
-    RPVG_HIP_CHECK(d_new_req.alloc(num_records));
-    RPVG_HIP_CHECK(d_memo_key.alloc(num_records));
-    RPVG_HIP_CHECK(d_tab_key.alloc(num_slots));
-    RPVG_HIP_CHECK(d_tab_first.alloc(num_slots));
-    RPVG_HIP_CHECK(d_tab_count.alloc(num_slots));
-    RPVG_HIP_CHECK(d_dist.alloc(dist_capacity));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_records.ptr, 0, num_records * sizeof(RequestInfo), st));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_memo_key.ptr, 0xff, num_records * sizeof(unsigned long long), st));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_key.ptr, 0xff, num_slots * sizeof(unsigned long long), st));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_first.ptr, 0xff, num_slots * sizeof(uint32_t), st));
-    RPVG_HIP_CHECK(hipMemsetAsync(d_tab_count.ptr, 0, num_slots * sizeof(uint32_t), st));
-
-    const GibbsProblems pr{d_matrix.ptr, d_chains.ptr, d_burn.ptr, d_its.ptr, d_chain_off.ptr, d_col_off.ptr, d_memo_off.ptr, d_tab_off.ptr, d_log_freq.ptr};
-    const GibbsChains ch{d_chain_problem.ptr, d_chain_pos.ptr, d_chain_cur.ptr, d_chain_iter.ptr, d_chain_flag.ptr};
-    const int sampler_span = ctx->spanBegin(FAM_GIBBS);
-    struct SamplerSpan {  // (closed on every way out)
-        rpvg_hip_ctx * ctx;
-        int span;
-        ~SamplerSpan() { ctx->spanEnd(span); }
-    } sampler_span_guard{ctx, sampler_span};
-    gibbsStreamKernel<<<dim3(NG), dim3(256), 0, st>>>(d_gen_words.ptr, d_gen_prob_off.ptr, d_gen_prob.ptr, d_stream_off.ptr, pr, groups->mat_cols.ptr, GS,
-                                                      d_stream.ptr, ch, d_words.ptr, d_final_state.ptr, d_hdr.ptr);
-    RPVG_HIP_CHECK(hipGetLastError());
-    RPVG_HIP_CHECK(pinnedAlloc(&result->state_block, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t)));
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->state_block, d_final_state.ptr, static_cast<size_t>(NG) * rpvg_streams::kMtWords * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(groups->waitCollapse(st));
-
-    struct Progress {
-        uint32_t remaining;
-        uint32_t pad[15];
-        GibbsHeader hdr;
-    };
-    void * pinned = nullptr;
-    RPVG_HIP_CHECK(pinnedAlloc(&pinned, sizeof(Progress)));
-    std::shared_ptr<void> pinned_guard(pinned, [](void * ptr) { pinnedFree(ptr); });
-    Progress * progress = static_cast<Progress *>(pinned);
-
-    scope.reset(new HostScope("group_gibbs_polyploid: rounds"));
-    const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
-    const uint32_t chains_per_wave = 8;  // (as at group size 2: a wave runs the union of its chains' paths)
-    const uint32_t advance_blocks = static_cast<uint32_t>((num_chains + 4 * chains_per_wave - 1) / (4 * chains_per_wave));
-    const uint32_t work_blocks = cus * 8;
-    uint32_t round = 0;
-    bool finished = false;
-    uint32_t chunk = 6;
-    while (!finished) {
-        if (round + chunk >= kMaxRounds) {
-            RPVG_HIP_CHECK(waitStream(st));
-            setError("rpvg_hip_group_gibbs_polyploid: the chains are not done after %u rounds", round);
-            return RPVG_HIP_ERR_UNSUPPORTED;
-        }
-        for (uint32_t r = 0; r < chunk; ++r, ++round) {
-#define RPVG_GIBBS_POLY_ROUND(W)                                                                                                       \
-    gibbsAdvancePolyKernel<W><<<dim3(advance_blocks), dim3(256), 0, st>>>(                                                             \
-        static_cast<uint32_t>(num_chains), round, pr, groups->mat_cols.ptr, ch, d_stream.ptr, d_memo_key.ptr, d_records.ptr,           \
-        d_prob_count.ptr, d_prob_done.ptr, d_hdr.ptr, d_remaining.ptr, d_active_problem.ptr, d_req_slot.ptr, d_dist.ptr,               \
-        d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, chains_per_wave);                                                             \
-    gibbsRequestOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(pr, groups->mat_cols.ptr, groups->mat_rows.ptr, d_hdr.ptr,               \
-                                                              d_active_problem.ptr, d_prob_count.ptr, d_prob_done.ptr, d_entries.ptr,  \
-                                                              d_new_req.ptr, d_req_slot.ptr, d_records.ptr, dist_capacity, 0u);        \
-    span = ctx->spanBegin(FAM_LOGLIK);                                                                                                 \
-    gibbsConditionalPolyKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(                                                            \
-        pr, d_hdr.ptr, d_entries.ptr, d_req_slot.ptr, d_memo_key.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,                \
-        groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr,                     \
-        groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);                                                                     \
-    ctx->spanEnd(span)
-            switch (GS) {
-                case 3: RPVG_GIBBS_POLY_ROUND(3); break;
-                case 4: RPVG_GIBBS_POLY_ROUND(4); break;
-                case 5: RPVG_GIBBS_POLY_ROUND(5); break;
-                case 6: RPVG_GIBBS_POLY_ROUND(6); break;
-                case 7: RPVG_GIBBS_POLY_ROUND(7); break;
-                default: RPVG_GIBBS_POLY_ROUND(8); break;
-            }
-#undef RPVG_GIBBS_POLY_ROUND
-            // (ask-ahead share 2: never — it numbers requests by the other COLUMN, which is group size 2's memo)
-            gibbsDistributionKernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_new_req.ptr, groups->mat_cols.ptr, d_records.ptr, d_dist.ptr,
-                                                                            2.0, d_prob_count.ptr, d_prob_done.ptr, d_active_problem.ptr,
-                                                                            d_req_slot.ptr, d_hdr.ptr);
-        }
-        RPVG_HIP_CHECK(hipGetLastError());
-        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->remaining, d_remaining.ptr + (round - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(waitStream(st));
-        if (progress->hdr.error) {
-            const uint32_t err = progress->hdr.error;
-            if (err & kErrDistributions) {
-                setError("rpvg_hip_group_gibbs_polyploid: the conditional distributions need more than the %llu bytes reserved for them (RPVG_HIP_GIBBS_BYTES)",
-                         static_cast<unsigned long long>(dist_capacity * 8));
-                return RPVG_HIP_ERR_UNSUPPORTED;
-            }
-            if (err & kErrTable) {
-                setError("rpvg_hip_group_gibbs_polyploid: a table of sampled sets or of conditionals is full");
-                return RPVG_HIP_ERR_UNSUPPORTED;
-            }
-            setError("rpvg_hip_group_gibbs_polyploid: a generator's start draws ran past the words generated for it");
-            return RPVG_HIP_ERR_RUNTIME;
-        }
-        finished = progress->remaining == 0;
-        // a flat posterior asks for a new conditional at nearly every draw: rounds by the hundred, looked at less and less often
-        chunk = std::min<uint32_t>(32, std::max<uint32_t>(4, round / 4));
+    template <int W>
+    void queueRound() {
+        gibbsAdvancePolyKernel<W><<<dim3(advance_blocks), dim3(256), 0, st>>>(
+            static_cast<uint32_t>(num_chains), round, pr, groups->mat_cols.ptr, ch, d_stream.ptr, d_memo_key.ptr, d_records.ptr,
+            d_prob_count.ptr, d_prob_done.ptr, d_hdr.ptr, d_remaining.ptr, d_active_problem.ptr, d_req.ptr, d_dist.ptr,
+            d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, chains_per_wave);
+        queueRequestOffsets(0u);
+        const int span = ctx->spanBegin(FAM_LOGLIK);
+        gibbsConditionalPolyKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(
+            pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, d_memo_key.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,
+            groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr,
+            groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);
+        ctx->spanEnd(span);
+        queueDistributions(2.0);  // (ask-ahead share 2: never — it numbers requests by the other COLUMN, which is group size 2's memo)
     }
-    ctx->stats.loglik_launches += round;
-    ctx->stats.loglik_evals += progress->hdr.evals;
-    result->rounds = round;
-    result->conditionals = progress->hdr.total_requests;
 
-    // the sets
-    scope.reset(new HostScope("group_gibbs_polyploid: sets"));
-    RPVG_HIP_CHECK(d_out.alloc((GS + 2) * out_capacity));
-    uint32_t * out_members = d_out.ptr, * out_count = d_out.ptr + GS * out_capacity, * out_seq = d_out.ptr + (GS + 1) * out_capacity;
-    gibbsCountSetsKernel<<<dim3(P), dim3(256), 0, st>>>(pr, d_tab_key.ptr, d_set_off.ptr);
-    gibbsSetOffsetsKernel<<<dim3(1), dim3(1024), 0, st>>>(P, d_set_off.ptr, d_hdr.ptr);
-    gibbsCollectPolyKernel<<<dim3(P), dim3(256), 0, st>>>(pr, GS, d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, d_set_off.ptr, out_members, out_count,
-                                                          out_seq, d_hdr.ptr);
-    RPVG_HIP_CHECK(hipGetLastError());
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->set_off.data(), d_set_off.ptr, (static_cast<size_t>(P) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(result->words_consumed.data(), d_words.ptr, static_cast<size_t>(NG) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(&progress->hdr, d_hdr.ptr, sizeof(GibbsHeader), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(waitStream(st));
-    const uint64_t total_sets = progress->hdr.total_sets;
-    RPVG_REQUIRE(total_sets <= out_capacity, "rpvg_hip_group_gibbs_polyploid: %llu sets in room for %llu", static_cast<unsigned long long>(total_sets),
-                 static_cast<unsigned long long>(out_capacity));
-    if (total_sets > 0) {
-        RPVG_HIP_CHECK(pinnedAlloc(&result->block, (GS + 2) * total_sets * sizeof(uint32_t)));
-        uint32_t * host = static_cast<uint32_t *>(result->block);
-        uint32_t * host_count = host + GS * total_sets, * host_seq = host + (GS + 1) * total_sets;
-        RPVG_HIP_CHECK(hipMemcpyAsync(host, out_members, GS * total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipMemcpyAsync(host_count, out_count, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (progress->hdr.unsorted) {
-            RPVG_HIP_CHECK(hipMemcpyAsync(host_seq, out_seq, total_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        }
-        RPVG_HIP_CHECK(waitStream(st));
-        if (progress->hdr.unsorted) {  // the problems with more sets than the collect kernel ranks in LDS
-            orderUnsortedSets(result->set_off, host_seq, {{host, GS}, {host_count, 1u}});
-        }
-        result->members = host;
-        result->count = host_count;
+    // a flat posterior asks for a new conditional at nearly every draw: rounds by the hundred, looked at less and less often
+    uint32_t chunk() const { return round == 0 ? 6 : std::min<uint32_t>(32, std::max<uint32_t>(4, round / 4)); }
+
+    uint32_t wordsPerSet() const { return GS + 2; }  // members [sets x GS] | count | sequence
+    SetColumns setColumns(uint32_t * block, const uint64_t sets, uint32_t *& seq) const {
+        seq = block + (GS + 1) * sets;
+        return {{block, GS}, {block + GS * sets, 1u}};
     }
-    const int build_status = groups->buildError(st);  // the matrices were built without a host sync
-    if (build_status != RPVG_HIP_OK) return build_status;
-    ctx->stats.gibbs_calls_completed += 1;
-    *result_out = result.release();
+    void queueCollect(const SetColumns & out, uint32_t * out_seq) {
+        gibbsCollectPolyKernel<<<dim3(P), dim3(256), 0, st>>>(pr, GS, d_tab_key.ptr, d_tab_count.ptr, d_tab_first.ptr, d_set_off.ptr, out[0].first,
+                                                              out[1].first, out_seq, d_hdr.ptr);
+    }
+    void publish(const SetColumns & host) {
+        result->members = host[0].first;
+        result->count = host[1].first;
+    }
+};
+
+// What both entry points are behind their group-size checks.  Invalid arguments come before the variant's refusals, and
+// all of them before the context is locked.
+template <typename V>
+int runGibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec, rpvg_hip_gibbs_sets ** result_out) {
+    const uint32_t P = spec->num_problems, NG = spec->num_generators;
+    RPVG_REQUIRE(P == 0 || (spec->matrix && spec->num_chains && spec->num_burn_its && spec->num_gibbs_its && spec->log_freq &&
+                            spec->generator_problem_off && spec->generator_problem && spec->generator_words),
+                 "%s: NULL array", V::kEntry);
+    RPVG_REQUIRE(P == 0 || NG >= 1, "%s: no generators", V::kEntry);
+    std::unique_ptr<HostScope> scope;  // (in front of the run: a phase's time includes giving back what it used)
+    V run(ctx, groups, spec);
+    run.result = std::make_unique<rpvg_hip_gibbs_sets>();
+    run.result->num_problems = P;
+    run.result->group_size = spec->group_size;
+    run.result->set_off.assign(static_cast<size_t>(P) + 1, 0);
+    run.result->words_consumed.assign(NG, 0);
+    int status = RPVG_HIP_OK;
+    if (P > 0) {
+        scope.reset(new HostScope(V::kScopes[0]));
+        if ((status = run.validateAndSize()) != RPVG_HIP_OK) return status;
+        run.lock = std::unique_lock<std::mutex>(ctx->mutex);
+        RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+        run.st = ctx->stream;
+        scope.reset(new HostScope(V::kScopes[1]));
+        if ((status = run.uploadAndAllocate()) != RPVG_HIP_OK) return status;
+        if ((status = run.startStreams()) != RPVG_HIP_OK) return status;
+        scope.reset(new HostScope(V::kScopes[2]));
+        if ((status = run.runRounds()) != RPVG_HIP_OK) return status;
+        scope.reset(new HostScope(V::kScopes[3]));
+        if ((status = run.collect()) != RPVG_HIP_OK) return status;
+    }
+    *result_out = run.result.release();
     return RPVG_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int rpvg_hip_group_gibbs(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
+                                    rpvg_hip_gibbs_sets ** result_out) {
+    RPVG_REQUIRE(ctx && groups && spec && result_out, "rpvg_hip_group_gibbs: NULL argument");
+    *result_out = nullptr;
+    if (spec->group_size < 1 || spec->group_size > 2) {
+        setError("rpvg_hip_group_gibbs: group size %u (the device sampler takes 1 and 2)", spec->group_size);
+        return RPVG_HIP_ERR_UNSUPPORTED;
+    }
+    return runGibbs<PairVariant>(ctx, groups, spec, result_out);
+}
+
+extern "C" int rpvg_hip_group_gibbs_polyploid(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const rpvg_hip_gibbs_spec * spec,
+                                              rpvg_hip_gibbs_sets ** result_out) {
+    RPVG_REQUIRE(ctx && groups && spec && result_out, "rpvg_hip_group_gibbs_polyploid: NULL argument");
+    *result_out = nullptr;
+    if (spec->group_size < 3 || spec->group_size > kMaxGroupSize) {
+        setError("rpvg_hip_group_gibbs_polyploid: group size %u (this entry point takes 3 .. 8, rpvg_hip_group_gibbs 1 and 2)", spec->group_size);
+        return RPVG_HIP_ERR_UNSUPPORTED;
+    }
+    return runGibbs<PolyVariant>(ctx, groups, spec, result_out);
 }
 
 extern "C" int rpvg_hip_gibbs_sets_get(const rpvg_hip_gibbs_sets * result, rpvg_hip_gibbs_sets_view * view_out) {
