@@ -177,7 +177,15 @@ int rpvg_hip_em_solve(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t
  * Random numbers come from the counter-based Philox4x32-10 generator keyed by seeds[p]: the reference's
  * mt19937 / libstdc++ distribution streams cannot be reproduced on a GPU, parity is statistical.
  * noise_samples: [sum num_samples]; abundance_samples: per problem num_samples[p] x columns, sample-major
- * (the layout of CountSamples::abundance_samples, src/path_cluster_estimates.hpp:35-43). */
+ * (the layout of CountSamples::abundance_samples, src/path_cluster_estimates.hpp:35-43).
+ * There is no limit on the columns of a problem (rows, entries and iterations: below 2^32 each).  Two routes: a problem runs all its iterations on ONE
+ * workgroup (abundances and counts in LDS; its generator is keyed by seeds[p] and streamed by (p, thread), so its samples
+ * depend on its index in the call) unless its columns do not fit that workgroup's LDS (~10 000) or its kept rows + entries
+ * reach the sampler's threshold (2^16; RPVG_HIP_EM_GRID_MIN_WORK, the EM's variable, overrides it; 0: never for its size).
+ * Such a problem takes the whole GPU, one round of launches per iteration (rpvg_amd/csrc/gibbs_grid.hip); its generator is
+ * keyed by seeds[p] and counted by (row or column, iteration, draw), so its samples depend on its seed and its data alone:
+ * not on its index in the call, on what else is in the call, or on the GPU's size.  The dense problems of the EM's dense
+ * route run on their compacted CSR here. */
 int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_em_problems * problems,
                                const double * init_abundances, const double * init_noise_count,
                                const uint32_t * num_samples, const uint64_t * seeds, uint32_t gibbs_thin_its,
@@ -592,6 +600,10 @@ typedef struct rpvg_hip_kernel_stats {
     /* calls of rpvg_hip_group_gibbs and rpvg_hip_group_gibbs_polyploid that returned their sets (RPVG_HIP_OK with at least one
      * problem): a call that gave up on the way (RPVG_HIP_ERR_UNSUPPORTED) has a span in gibbs_ms and no count here */
     uint64_t gibbs_calls_completed;
+    /* rpvg_hip_gibbs_read_counts: problems that took the whole-GPU route (gibbs_grid.hip) and their Gibbs iterations
+     * (num_samples x gibbs_thin_its each) */
+    uint64_t gibbs_count_grid_problems;
+    uint64_t gibbs_count_grid_iterations;
 } rpvg_hip_kernel_stats;
 
 int rpvg_hip_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_kernel_stats * stats_out);

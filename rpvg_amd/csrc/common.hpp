@@ -962,6 +962,8 @@ struct EmGridStorage {
 
 // rows + entries from which a problem leaves the one-workgroup kernels (RPVG_HIP_EM_GRID_MIN_WORK; 0: never)
 uint64_t emGridMinWork();
+// the same for the read-count Gibbs sampler (gibbs_grid.hip): the EM's environment variable, a default of its own
+uint64_t gibbsGridMinWork();
 // whether a problem of the grid bin is solved on a dense row-major copy (em_dense.hip's streaming kernels) rather than
 // on its CSR: the dense matrix is the smaller one (8 B per cell against 12 B per entry) and narrow enough for a
 // register-resident row
@@ -970,6 +972,38 @@ bool emGridDenseRoute(uint32_t columns, uint32_t rows, uint32_t entries);
 // stream).  Caller holds ctx->mutex and has set the device.
 int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * problems, uint32_t count, const EmGridStorage & storage,
                       uint32_t max_em_its, double max_rel_em_conv);
+
+// ---- read-count Gibbs problems too wide or too large for one workgroup (gibbs_grid.hip) -----------------
+// One problem of rpvg_hip_gibbs_read_counts that takes the whole GPU, as the host describes it (em_sparse.hip).
+struct GibbsGridProblem {
+    uint32_t problem, columns;  // index in the call's list; paths + noise
+    uint32_t rows, entries;     // kept rows / entries (its compacted CSR)
+    uint32_t num_samples, pad;
+    uint64_t col_begin;         // of its columns in init_abundances
+    uint64_t sample_off, abund_sample_off;  // of its samples in noise_samples / abundance_samples
+    uint64_t seed;
+};
+// device arrays of the call the problems belong to ([P] arrays are indexed by GibbsGridProblem::problem)
+struct GibbsGridStorage {
+    const uint64_t * row_base;
+    const uint64_t * ent_base;
+    const uint32_t * prow_off;
+    const double * prow_count;
+    const double * prow_noise;
+    const uint32_t * pent_col;
+    const double * pent_val;
+    const double * zero_mass;
+    const double * total_mass;
+    const double * init_abundances;
+    const double * init_noise_count;
+    double * noise_samples;
+    double * abundance_samples;
+};
+// Samples the described problems one after the other on `st`, every launch over the whole GPU; the launches of all
+// iterations are queued without a host wait in between, the stream is waited for behind each problem.  Caller holds
+// ctx->mutex and has set the device.
+int runGibbsGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const GibbsGridProblem * problems, uint32_t count, const GibbsGridStorage & storage,
+                         uint32_t gibbs_thin_its, double gamma);
 
 // The dense streaming EM of em_dense.hip on a resident row-major matrix, up to the stop rule; the abundance vector stays
 // on the device (d_a, C doubles).  zero_mass: read mass of the rows the matrix does not hold because they touch no

@@ -304,6 +304,19 @@ uint64_t emGridMinWork() {
     return env ? std::strtoull(env, nullptr, 10) : (1ull << 18);
 }
 
+uint64_t gibbsGridMinWork() {
+    // (the EM's environment variable, read per call; 0: never)  The sampler's own default: an iteration of
+    // gibbsReadCountKernel costs ~3.7 ns per work unit on its one workgroup (a binomial draw per entry: 16 000 rows x 3
+    // entries 233 us, 60 000 x 3 877 us, 200 000 x 3 3 460 us; 8 000 rows x 40 entries 1 414 us), an iteration over the whole
+    // GPU 11-13 us of launches whatever the size up to 10^5 units, 32 us at 8 x 10^5 (gibbs_grid.hip;
+    // profiles/gibbs_counts_grid/ab.txt): one problem alone breaks even near 4 000 units (1 000 rows x 3 entries: 17 us
+    // against 11).  The threshold follows the EM's rule instead — the grid takes its problems one after the other, the
+    // one-workgroup kernel takes them side by side, so a problem leaves it where it alone would take ~200 us per
+    // iteration there: 2^16 units (235 us against 12).
+    const char * env = std::getenv("RPVG_HIP_EM_GRID_MIN_WORK");
+    return env ? std::strtoull(env, nullptr, 10) : (1ull << 16);
+}
+
 bool emGridDenseRoute(const uint32_t columns, const uint32_t rows, const uint32_t entries) {
     if (RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_GRID_NO_DENSE")) return false;  // A/B knob
     return emDenseRule(columns, rows, entries);

@@ -31,6 +31,7 @@
 // src/path_estimator.cpp:219-259, would merge among those rows).
 
 #include "common.hpp"
+#include "gibbs_random.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -1303,133 +1304,12 @@ bool oneRegisterLaunch() {
 // iteration every row's reads are split multinomially over its columns with probabilities
 // P_ij a_j / s_i (the reference draws the multinomial as a chain of binomials, :149-178), then every
 // component draws a_j ~ Gamma(count_j + gamma, 1) and the vector is renormalised (:182-190); every
-// `thin`-th state is recorded (:192-210).  ONE workgroup per problem runs all iterations.  The
+// `thin`-th state is recorded (:192-210).  ONE workgroup per problem runs all iterations (a problem too
+// wide for its LDS or too large for one workgroup takes the whole GPU instead: gibbs_grid.hip).  The
 // reference's mt19937 / libstdc++ distribution streams cannot be reproduced on a GPU:
-// draws come from the counter-based Philox4x32-10 generator keyed by the problem's seed, so parity with
-// the reference is statistical.  Rows without any selected path put all their reads on the noise
-// component (their posterior there is exactly 1), as in the EM kernel.
-
-struct Philox {
-    uint32_t key[2];
-    uint32_t ctr[4];
-    uint32_t out[4];
-    int have;
-
-    __device__ __forceinline__ void init(const uint64_t seed, const uint32_t stream_hi, const uint32_t stream_lo) {
-        key[0] = static_cast<uint32_t>(seed);
-        key[1] = static_cast<uint32_t>(seed >> 32);
-        ctr[0] = 0;
-        ctr[1] = 0;
-        ctr[2] = stream_lo;
-        ctr[3] = stream_hi;
-        have = 0;
-    }
-
-    __device__ __forceinline__ void round(uint32_t (&c)[4], const uint32_t k0, const uint32_t k1) {
-        const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c[0];
-        const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * c[2];
-        const uint32_t n0 = static_cast<uint32_t>(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n1 = static_cast<uint32_t>(p1);
-        const uint32_t n2 = static_cast<uint32_t>(p0 >> 32) ^ c[3] ^ k1;
-        const uint32_t n3 = static_cast<uint32_t>(p0);
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    }
-
-    __device__ __forceinline__ void refill() {
-        uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]};
-        uint32_t k0 = key[0], k1 = key[1];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-        if (++ctr[0] == 0) ++ctr[1];
-        have = 4;
-    }
-
-    __device__ __forceinline__ uint32_t next() {
-        if (have == 0) refill();
-        return out[--have];
-    }
-
-    // uniform in (0, 1)
-    __device__ __forceinline__ double uniform() {
-        const uint64_t hi = next(), lo = next();
-        return (static_cast<double>(((hi << 32) | lo) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    }
-
-    __device__ __forceinline__ double normal() {
-        const double u1 = uniform(), u2 = uniform();
-        return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
-    }
-};
-
-// Binomial(n, p) by inversion: from 0 when the mean is small, otherwise outwards from the mode (expected
-// O(sqrt(n p q)) steps; exact up to floating point).
-__device__ uint32_t sampleBinomial(Philox & rng, const uint32_t n, double p) {
-    if (n == 0 || !(p > 0.0)) return 0;
-    if (p >= 1.0) return n;
-    const bool flip = p > 0.5;
-    if (flip) p = 1.0 - p;
-    const double q = 1.0 - p, ratio = p / q;
-    uint32_t k;
-    if (n * p < 16.0) {
-        double pmf = exp(n * log(q));
-        double u = rng.uniform();
-        k = 0;
-        while (u > pmf && k < n) {
-            u -= pmf;
-            pmf *= ratio * (static_cast<double>(n - k) / (k + 1.0));
-            ++k;
-        }
-    } else {
-        const uint32_t mode = static_cast<uint32_t>((n + 1.0) * p);
-        const double log_pmf_mode = lgamma(n + 1.0) - lgamma(mode + 1.0) - lgamma(n - mode + 1.0) + mode * log(p) + (n - mode) * log(q);
-        const double pmf_mode = exp(log_pmf_mode);
-        double u = rng.uniform();
-        // walk outwards from the mode, alternating sides, until the accumulated mass passes u
-        double up = pmf_mode, down = pmf_mode;
-        uint32_t ku = mode, kd = mode;
-        k = mode;
-        if (u > pmf_mode) {
-            u -= pmf_mode;
-            while (true) {
-                bool moved = false;
-                if (ku < n) {
-                    up *= ratio * (static_cast<double>(n - ku) / (ku + 1.0));
-                    ++ku;
-                    moved = true;
-                    if (u <= up) { k = ku; break; }
-                    u -= up;
-                }
-                if (kd > 0) {
-                    down *= (static_cast<double>(kd) / (n - kd + 1.0)) / ratio;
-                    --kd;
-                    moved = true;
-                    if (u <= down) { k = kd; break; }
-                    u -= down;
-                }
-                if (!moved) { k = mode; break; }
-            }
-        }
-    }
-    return flip ? n - k : k;
-}
-
-// Gamma(shape >= 1, 1) by Marsaglia and Tsang's squeeze method.
-__device__ double sampleGamma(Philox & rng, const double shape) {
-    const double d = shape - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-    while (true) {
-        const double x = rng.normal();
-        double v = 1.0 + c * x;
-        if (v <= 0.0) continue;
-        v = v * v * v;
-        const double u = rng.uniform();
-        if (log(u) < 0.5 * x * x + d - d * v + d * log(v)) return d * v;
-    }
-}
+// draws come from the counter-based Philox4x32-10 generator keyed by the problem's seed (gibbs_random.hpp),
+// so parity with the reference is statistical.  Rows without any selected path put all their reads on the
+// noise component (their posterior there is exactly 1), as in the EM kernel.
 
 struct GibbsLaunchArgs {
     uint32_t count;
@@ -2313,53 +2193,138 @@ extern "C" int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_bat
     rc = queueEmSolve(ctx, batch, ps.list, 1, 0.0, out, ps.work, true);
     if (rc != RPVG_HIP_OK) return rc;
 
+    // Two routes.  A problem whose columns do not fit gibbsReadCountKernel's LDS-resident vectors, or whose kept rows +
+    // entries reach gibbsGridMinWork() (0: never for its size — a problem too wide still goes), takes the whole GPU per
+    // iteration (gibbs_grid.hip).  The host has to see the counts for that: only a call that sits on a cluster large
+    // enough, or has a problem wide enough, pays for the look (the gate of queueEmSolve's grid_possible).  Every other
+    // problem runs on one workgroup, under its index in the call: the launch covers all problems, the grid ones with no
+    // samples to draw.
+    auto oneWorkgroupLds = [](const uint32_t columns) {
+        return (sizeof(double) * (2 * static_cast<size_t>(columns) + 256 / 64 + 2) + 15) & ~static_cast<size_t>(15);
+    };
+    constexpr size_t kOneWorkgroupLdsLimit = 160 * 1024;
+    const uint64_t grid_min_work = gibbsGridMinWork();
+    const bool grid_possible = oneWorkgroupLds(ps.list.max_cols) > kOneWorkgroupLdsLimit || (grid_min_work != 0 && ps.list.max_cluster_work >= grid_min_work);
+    std::vector<uint32_t> staying_samples;  // num_samples with the grid problems masked out
+    std::vector<GibbsGridProblem> grid_problems;
+    uint32_t staying_max_cols = ps.list.max_cols;
+    bool any_staying = true;
+    if (grid_possible) {
+        std::vector<uint32_t> kept_rows(P), kept_ent(P);
+        RPVG_HIP_CHECK(d_kept_rows.download(kept_rows.data(), st));
+        RPVG_HIP_CHECK(d_kept_ent.download(kept_ent.data(), st));
+        RPVG_HIP_CHECK(waitStream(st));
+        staying_samples.assign(num_samples, num_samples + P);
+        staying_max_cols = 1;
+        any_staying = false;
+        for (uint32_t p = 0; p < P; ++p) {
+            if (num_samples[p] == 0) continue;
+            const uint32_t C = static_cast<uint32_t>(problems->col_off[p + 1] - problems->col_off[p]) + 1;
+            const bool too_wide = oneWorkgroupLds(C) > kOneWorkgroupLdsLimit;
+            const bool too_large = grid_min_work != 0 && static_cast<uint64_t>(kept_rows[p]) + kept_ent[p] >= grid_min_work;
+            if (!too_wide && !too_large) {
+                staying_max_cols = std::max(staying_max_cols, C);
+                any_staying = true;
+                continue;
+            }
+            staying_samples[p] = 0;
+            GibbsGridProblem g;
+            g.problem = p;
+            g.columns = C;
+            g.rows = kept_rows[p];
+            g.entries = kept_ent[p];
+            g.num_samples = num_samples[p];
+            g.pad = 0;
+            g.col_begin = problems->col_off[p];
+            g.sample_off = sample_off[p];
+            g.abund_sample_off = abund_sample_off[p];
+            g.seed = seeds[p];
+            grid_problems.push_back(g);
+        }
+    }
+
     DeviceBuffer<double> d_init_abund, d_init_noise, d_noise_samples, d_abund_samples;
     DeviceBuffer<uint32_t> d_num_samples;
     DeviceBuffer<uint64_t> d_seed, d_sample_off, d_abund_sample_off;
     RPVG_HIP_CHECK(d_init_abund.upload(init_abundances, ps.n_cols_total, st));
     RPVG_HIP_CHECK(d_init_noise.upload(init_noise_count, P, st));
-    RPVG_HIP_CHECK(d_num_samples.upload(num_samples, P, st));
+    RPVG_HIP_CHECK(d_num_samples.upload(grid_problems.empty() ? num_samples : staying_samples.data(), P, st));
     RPVG_HIP_CHECK(d_seed.upload(seeds, P, st));
     RPVG_HIP_CHECK(d_sample_off.upload(sample_off.data(), P + 1, st));
     RPVG_HIP_CHECK(d_abund_sample_off.upload(abund_sample_off.data(), P + 1, st));
     RPVG_HIP_CHECK(d_noise_samples.alloc(sample_off[P]));
     RPVG_HIP_CHECK(d_abund_samples.alloc(abund_sample_off[P]));
 
-    GibbsLaunchArgs args;
-    args.count = P;
-    args.col_off = ps.d_col_off.ptr;
-    args.row_base = ps.d_row_base.ptr;
-    args.ent_base = ps.d_ent_base.ptr;
-    args.kept_rows = d_kept_rows.ptr;
-    args.zero_mass = ps.work.d_zero.ptr;
-    args.total_mass = d_total.ptr;
-    args.prow_off = ps.work.d_prow_off.ptr;
-    args.prow_count = ps.work.d_prow_count.ptr;
-    args.prow_noise = ps.work.d_prow_noise.ptr;
-    args.pent_col = ps.work.d_pent_col.ptr;
-    args.pent_val = ps.work.d_pent_val.ptr;
-    args.init_abundances = d_init_abund.ptr;
-    args.init_noise_count = d_init_noise.ptr;
-    args.num_samples = d_num_samples.ptr;
-    args.seed = d_seed.ptr;
-    args.sample_off = d_sample_off.ptr;
-    args.abund_sample_off = d_abund_sample_off.ptr;
-    args.thin = gibbs_thin_its;
-    args.gamma = gamma;
-    args.noise_samples = d_noise_samples.ptr;
-    args.abundance_samples = d_abund_samples.ptr;
-
-    const size_t lds = (sizeof(double) * (2 * static_cast<size_t>(ps.list.max_cols) + 256 / 64 + 2) + 15) & ~static_cast<size_t>(15);
-    RPVG_REQUIRE(lds <= 160 * 1024, "rpvg_hip_gibbs_read_counts: a problem with %u columns does not fit the sampler's LDS-resident vectors (limit ~10 000 columns)",
-                 ps.list.max_cols);
-    if (lds > 64 * 1024) {
-        RPVG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gibbsReadCountKernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    // the grid problems run next to the one-workgroup kernel: on a stream of their own (the EM's first, em_grid.hip), behind what
+    // `st` holds so far — the compacted CSR and the uploads
+    hipStream_t grid_st = st;
+    if (any_staying && !grid_problems.empty()) {
+        hipError_t e = hipSuccess;
+        if (!ctx->grid_stream[0]) e = hipStreamCreateWithFlags(&ctx->grid_stream[0], hipStreamNonBlocking);
+        if (e == hipSuccess && !ctx->grid_ready) e = hipEventCreateWithFlags(&ctx->grid_ready, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ctx->grid_ready, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->grid_stream[0], ctx->grid_ready, 0);
+        RPVG_HIP_CHECK(e);
+        grid_st = ctx->grid_stream[0];
     }
-    const int span = ctx->spanBegin(FAM_EM_SPARSE);
-    gibbsReadCountKernel<<<dim3(P), dim3(256), lds, st>>>(args);
-    ctx->spanEnd(span);
-    RPVG_HIP_CHECK(hipGetLastError());
+    if (any_staying) {
+        GibbsLaunchArgs args;
+        args.count = P;
+        args.col_off = ps.d_col_off.ptr;
+        args.row_base = ps.d_row_base.ptr;
+        args.ent_base = ps.d_ent_base.ptr;
+        args.kept_rows = d_kept_rows.ptr;
+        args.zero_mass = ps.work.d_zero.ptr;
+        args.total_mass = d_total.ptr;
+        args.prow_off = ps.work.d_prow_off.ptr;
+        args.prow_count = ps.work.d_prow_count.ptr;
+        args.prow_noise = ps.work.d_prow_noise.ptr;
+        args.pent_col = ps.work.d_pent_col.ptr;
+        args.pent_val = ps.work.d_pent_val.ptr;
+        args.init_abundances = d_init_abund.ptr;
+        args.init_noise_count = d_init_noise.ptr;
+        args.num_samples = d_num_samples.ptr;
+        args.seed = d_seed.ptr;
+        args.sample_off = d_sample_off.ptr;
+        args.abund_sample_off = d_abund_sample_off.ptr;
+        args.thin = gibbs_thin_its;
+        args.gamma = gamma;
+        args.noise_samples = d_noise_samples.ptr;
+        args.abundance_samples = d_abund_samples.ptr;
+
+        // (sized by the widest problem that stays)
+        const size_t lds = oneWorkgroupLds(staying_max_cols);
+        if (lds > 64 * 1024) {
+            RPVG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gibbsReadCountKernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        }
+        const int span = ctx->spanBegin(FAM_EM_SPARSE);
+        gibbsReadCountKernel<<<dim3(P), dim3(256), lds, st>>>(args);
+        ctx->spanEnd(span);
+        RPVG_HIP_CHECK(hipGetLastError());
+    }
+    if (!grid_problems.empty()) {
+        GibbsGridStorage storage;
+        storage.row_base = ps.d_row_base.ptr;
+        storage.ent_base = ps.d_ent_base.ptr;
+        storage.prow_off = ps.work.d_prow_off.ptr;
+        storage.prow_count = ps.work.d_prow_count.ptr;
+        storage.prow_noise = ps.work.d_prow_noise.ptr;
+        storage.pent_col = ps.work.d_pent_col.ptr;
+        storage.pent_val = ps.work.d_pent_val.ptr;
+        storage.zero_mass = ps.work.d_zero.ptr;
+        storage.total_mass = d_total.ptr;
+        storage.init_abundances = d_init_abund.ptr;
+        storage.init_noise_count = d_init_noise.ptr;
+        storage.noise_samples = d_noise_samples.ptr;
+        storage.abundance_samples = d_abund_samples.ptr;
+        // (waits for grid_st behind every problem: their samples are in place when the downloads below are queued)
+        rc = runGibbsGridProblems(ctx, grid_st, grid_problems.data(), static_cast<uint32_t>(grid_problems.size()), storage, gibbs_thin_its, gamma);
+        if (rc != RPVG_HIP_OK) {
+            (void) hipDeviceSynchronize();  // (the buffers of this call go back to the pool on return)
+            return rc;
+        }
+    }
     RPVG_HIP_CHECK(d_noise_samples.download(noise_samples, st));
     RPVG_HIP_CHECK(d_abund_samples.download(abundance_samples, st));
     RPVG_HIP_CHECK(waitStream(st));

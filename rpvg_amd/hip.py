@@ -99,6 +99,7 @@ class CKernelStats(C.Structure):
         ("collapse_ms", C.c_double), ("busy_ms", C.c_double), ("gibbs_ms", C.c_double),
         ("search_tile_ms", C.c_double), ("search_tile_launches", C.c_uint64),
         ("gibbs_calls_completed", C.c_uint64),
+        ("gibbs_count_grid_problems", C.c_uint64), ("gibbs_count_grid_iterations", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -568,6 +569,38 @@ class Context:
                                        C.byref(probs), C.byref(res)), "rpvg_hip_em_solve")
         off = col_off.astype(np.int64)
         return [abund[off[p]:off[p + 1]] for p in range(P)], noise, total, iters
+
+    def gibbs_read_counts(self, batch: DeviceBatch, clusters: Sequence[int], columns: Sequence[Sequence[int]], init_abundances,
+                          init_noise_count, num_samples, seeds, thin: int, gamma: float = 1.0):
+        """rpvg_hip_gibbs_read_counts: per problem (noise samples [n], abundance samples [n x columns]), starting from
+        init_abundances[p] (expected read counts per column) and init_noise_count[p]."""
+        P = len(clusters)
+        cl = np.ascontiguousarray(clusters, dtype=np.uint32)
+        col_off = np.zeros(P + 1, dtype=np.uint64)
+        col_off[1:] = np.cumsum([len(c) for c in columns])
+        col_path = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32) for c in columns])
+                                        if P else np.zeros(0), dtype=np.uint32)
+        init = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64) for a in init_abundances])
+                                    if P else np.zeros(0), dtype=np.float64)
+        assert init.size == int(col_off[-1])
+        init_noise = np.ascontiguousarray(init_noise_count, dtype=np.float64)
+        n = np.ascontiguousarray(num_samples, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert init_noise.size == n.size == sd.size == P
+        widths = np.diff(col_off.astype(np.int64))
+        noise = np.zeros(int(n.sum()), dtype=np.float64)
+        abund = np.zeros(int((n.astype(np.int64) * widths).sum()), dtype=np.float64)
+        probs = CEmProblems(P, cl.ctypes.data, col_off.ctypes.data, col_path.ctypes.data, 0.0)
+        _check(lib().rpvg_hip_gibbs_read_counts(self.handle, batch.handle, C.byref(probs), C.c_void_p(init.ctypes.data),
+                                                C.c_void_p(init_noise.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(sd.ctypes.data),
+                                                C.c_uint32(thin), C.c_double(gamma), C.c_void_p(noise.ctypes.data),
+                                                C.c_void_p(abund.ctypes.data)), "rpvg_hip_gibbs_read_counts")
+        out, at_n, at_a = [], 0, 0
+        for p in range(P):
+            k, w = int(n[p]), int(widths[p])
+            out.append((noise[at_n:at_n + k], abund[at_a:at_a + k * w].reshape(k, w)))
+            at_n, at_a = at_n + k, at_a + k * w
+        return out
 
     def min_path_cover(self, batch: DeviceBatch, clusters: Sequence[int]) -> List[List[int]]:
         cl = np.ascontiguousarray(clusters, dtype=np.uint32)

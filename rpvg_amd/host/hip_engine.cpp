@@ -162,6 +162,8 @@ void HipEngine::stats(const std::vector<const HipEngine *> & engines, rpvg_hip_k
         stats_out->search_tile_ms += lane_stats.search_tile_ms;
         stats_out->search_tile_launches += lane_stats.search_tile_launches;
         stats_out->gibbs_calls_completed += lane_stats.gibbs_calls_completed;
+        stats_out->gibbs_count_grid_problems += lane_stats.gibbs_count_grid_problems;
+        stats_out->gibbs_count_grid_iterations += lane_stats.gibbs_count_grid_iterations;
 
         for (int i = 0; i < RPVG_HIP_EM_KERNELS; ++i) {
 
