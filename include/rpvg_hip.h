@@ -507,6 +507,27 @@ int rpvg_hip_read_rows_view(rpvg_hip_ctx * ctx, rpvg_hip_read_rows * rows, rpvg_
                             double * merge_ms);
 void rpvg_hip_read_rows_free(rpvg_hip_ctx * ctx, rpvg_hip_read_rows * rows);
 
+/* ---- fragment-length model (rpvg_frag.h; rpvg_amd/csrc/frag_length.hip) ------------------------------------------
+ *   rpvg_hip_frag_length_fit       FragmentLengthDist(counts, skew_normal) in one kernel launch of one workgroup.
+ *                                  RPVG_HIP_ERR_INVALID for n == 0, counts[0] != 0 or n > 65536; fewer than two samples
+ *                                  are RPVG_HIP_OK with valid = 0 (loc = the sum of the lengths, scale = shape = 0).
+ *   rpvg_hip_frag_length_table     logProb(v), v = 0 .. 65535, computed into a device table that rpvg_row_params can name;
+ *                                  _get copies it to the host ([RPVG_FRAG_LENGTH_TABLE_SIZE]).
+ *   rpvg_hip_effective_lengths     PathsIndex::effectivePathLength for n path lengths (host arrays).
+ *   rpvg_hip_alignments_set_effective_lengths   the same for the paths of a resident alignment batch: replaces its
+ *                                  path_effective_length on the device and returns the values ([P], for PathInfo).
+ *   rpvg_hip_frag_length_eval      for tests and measurements: rows of five doubles -> one double each.
+ *                                  what = 0: skew_normal_cdf(x, m, s, a)   1: truncated mean (m, s, a, c, d)   2: Owen's T(h, a) */
+int rpvg_hip_frag_length_fit(rpvg_hip_ctx * ctx, const uint32_t * counts, uint32_t n, int skew_normal, rpvg_frag_length_fit * out);
+int rpvg_hip_frag_length_table(rpvg_hip_ctx * ctx, double loc, double scale, double shape, rpvg_hip_frag_table ** out);
+int rpvg_hip_frag_length_table_get(rpvg_hip_ctx * ctx, const rpvg_hip_frag_table * table, double * log_prob_out);
+void rpvg_hip_frag_length_table_free(rpvg_hip_ctx * ctx, rpvg_hip_frag_table * table);
+int rpvg_hip_effective_lengths(rpvg_hip_ctx * ctx, double loc, double scale, double shape, const uint32_t * path_length, uint64_t n,
+                               double * out);
+int rpvg_hip_alignments_set_effective_lengths(rpvg_hip_ctx * ctx, rpvg_hip_alignments * alignments, double loc, double scale,
+                                              double shape, const uint32_t * path_length, double * out);
+int rpvg_hip_frag_length_eval(rpvg_hip_ctx * ctx, int what, const double * rows, uint64_t n, double * out);
+
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the
  * only collectives of this engine are the per-iteration all-reduce of rpvg_hip_em_dense_sharded and

@@ -21,6 +21,8 @@
 
 #include <stdint.h>
 
+#include "rpvg_frag.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -61,6 +63,8 @@ typedef struct rpvg_row_params {
     int32_t is_single_end;  /* -e: the fragment length term is skipped  src/read_path_probabilities.cpp:58-61 */
     /* log density of every fragment length 0 .. 65535: FragmentLengthDist::logProb(v).  Ignored if is_single_end. */
     const double * frag_length_log_prob; /* [RPVG_FRAG_LENGTH_TABLE_SIZE] */
+    /* The same table already on the GPU (rpvg_hip_frag_length_table, rpvg_frag.h); read when frag_length_log_prob is NULL. */
+    const rpvg_hip_frag_table * frag_length_table;
 } rpvg_row_params;
 
 #ifdef __cplusplus

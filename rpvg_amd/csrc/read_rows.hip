@@ -29,6 +29,7 @@
 
 #include "../../include/rpvg_rows.h"
 #include "common.hpp"
+#include "frag_length.hpp"
 
 using namespace rpvg_hip_detail;
 
@@ -1324,11 +1325,31 @@ extern "C" void rpvg_hip_alignments_free(rpvg_hip_ctx * ctx, rpvg_hip_alignments
     delete alignments;
 }
 
+// PathInfo::effective_length of every path of the batch from its length (src/main.cpp:880), computed where the rows read it
+extern "C" int rpvg_hip_alignments_set_effective_lengths(rpvg_hip_ctx * ctx, rpvg_hip_alignments * al, double loc, double scale, double shape,
+                                                         const uint32_t * path_length, double * out) {
+    RPVG_REQUIRE(ctx && al, "rpvg_hip_alignments_set_effective_lengths: NULL argument");
+    const uint64_t P = al->num_paths;
+    RPVG_REQUIRE(P == 0 || path_length, "rpvg_hip_alignments_set_effective_lengths: NULL path_length");
+    if (P == 0) return RPVG_HIP_OK;
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DeviceBuffer<uint32_t> d_length;
+    DeviceBuffer<double> d_lower;
+    RPVG_HIP_CHECK(d_length.upload(path_length, P, st));
+    if (const int rc = launchEffectiveLengths(st, loc, scale, shape, d_length.ptr, P, al->eff_len.ptr, d_lower)) return rc;
+    if (out) RPVG_HIP_CHECK(al->eff_len.download(out, st));
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    return RPVG_HIP_OK;
+}
+
 extern "C" int rpvg_hip_read_rows_build(rpvg_hip_ctx * ctx, const rpvg_hip_alignments * al, const rpvg_row_params * prm,
                                         int32_t merge, rpvg_hip_read_rows ** rows_out) {
     RPVG_REQUIRE(ctx && al && prm && rows_out, "rpvg_hip_read_rows_build: NULL argument");
     *rows_out = nullptr;
-    RPVG_REQUIRE(prm->is_single_end || prm->frag_length_log_prob, "rpvg_hip_read_rows_build: paired-end rows need frag_length_log_prob");
+    RPVG_REQUIRE(prm->is_single_end || prm->frag_length_log_prob || prm->frag_length_table,
+                 "rpvg_hip_read_rows_build: paired-end rows need frag_length_log_prob");
     RPVG_REQUIRE(prm->prob_precision > 0 && prm->min_noise_prob >= 0 && prm->min_noise_prob <= 1,
                  "rpvg_hip_read_rows_build: prob_precision / min_noise_prob out of range");
     const uint32_t K = al->num_clusters;
@@ -1361,7 +1382,13 @@ extern "C" int rpvg_hip_read_rows_build(rpvg_hip_ctx * ctx, const rpvg_hip_align
     std::vector<double> phred(256);
     for (int q = 0; q < 256; ++q) phred[q] = std::pow(10, -static_cast<double>(q) / 10);  // Utils::phred_to_prob, src/utils.hpp:131-133
     DeviceBuffer<double> d_frag, d_phred;
-    if (!prm->is_single_end) RPVG_HIP_CHECK(d_frag.upload(prm->frag_length_log_prob, RPVG_FRAG_LENGTH_TABLE_SIZE, st));
+    if (!prm->is_single_end) {
+        if (prm->frag_length_log_prob) {
+            RPVG_HIP_CHECK(d_frag.upload(prm->frag_length_log_prob, RPVG_FRAG_LENGTH_TABLE_SIZE, st));
+        } else {
+            d_frag.borrow(prm->frag_length_table->log_prob.ptr, RPVG_FRAG_LENGTH_TABLE_SIZE);  // computed on the device (frag_length.hip)
+        }
+    }
     RPVG_HIP_CHECK(d_phred.upload(phred.data(), 256, st));
 
     RowsScratchBuffers buffers;

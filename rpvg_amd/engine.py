@@ -9,7 +9,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
+
+import numpy as np
 
 from . import hip
 from .batch import CClusterBatch, CEstimatesView, CParams, ClusterBatch, ClusterEstimates, decode_view
@@ -48,6 +50,13 @@ def lib() -> C.CDLL:
         L.rpvg_amd_batch_prepare_from_alignments.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CClusterBatch), C.c_double, C.c_double,
                                                              C.c_double, C.c_uint32, C.c_int, C.c_double, C.c_double,
                                                              C.POINTER(C.c_double)]
+        L.rpvg_amd_batch_prepare_from_alignments_fit.restype = C.c_void_p
+        L.rpvg_amd_batch_prepare_from_alignments_fit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CClusterBatch), C.c_void_p, C.c_uint32, C.c_int,
+                                                                 C.c_void_p, C.c_double, C.c_double, C.POINTER(hip.CFragLengthFit),
+                                                                 C.c_void_p, C.POINTER(C.c_double)]
+        L.rpvg_amd_batch_prepare_from_alignments_fitted.restype = C.c_void_p
+        L.rpvg_amd_batch_prepare_from_alignments_fitted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CClusterBatch), C.c_double, C.c_double,
+                                                                    C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
         L.rpvg_amd_batch_prepare_synth_dense.restype = C.c_void_p
         L.rpvg_amd_batch_prepare_synth_dense.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]
         L.rpvg_amd_run.restype = C.c_void_p
@@ -86,6 +95,23 @@ def lib() -> C.CDLL:
         L.rpvg_amd_result_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
+
+
+class FragLengthFit(NamedTuple):
+    """What Engine.fit_frag_length returns: the FragmentLengthDist fitted to counts of fragment lengths.  Unlike the
+    parametric (loc, scale, shape, sd_max_multi) it carries its maximum length; handed to prepare_from_alignments as
+    `frag`, its density table is computed on the GPU."""
+    loc: float
+    scale: float
+    shape: float
+    max_length: int
+    valid: bool
+    stats: dict  # sample_size, iterations (outer passes), evaluations (log-likelihood sums)
+
+
+def _fit_tuple(fit) -> FragLengthFit:
+    return FragLengthFit(fit.loc, fit.scale, fit.shape, fit.max_length, bool(fit.valid),
+                         dict(sample_size=fit.sample_size, iterations=fit.iterations, evaluations=fit.evaluations))
 
 
 def _err() -> str:
@@ -134,16 +160,64 @@ class Engine:
     def prepare(self, batch: ClusterBatch, per_cluster: bool = False) -> "PreparedBatch":
         return PreparedBatch(self, batch, per_cluster)
 
-    def prepare_from_alignments(self, alignments, path_info: ClusterBatch, frag=(300.0, 50.0, 0.0, 10), is_single_end: bool = False,
-                                min_noise_prob: float = 1e-4, prob_precision: float = 1e-8) -> "PreparedBatch":
+    def fit_frag_length(self, counts, skew_normal: bool = True) -> FragLengthFit:
+        """FragmentLengthDist(frag_length_counts, skew_normal) fitted on the GPU: counts[v] = read pairs of fragment length v.
+        Returns (loc, scale, shape, max_length, valid, stats); stats = {"sample_size", "iterations", "evaluations"}."""
+        return _fit_tuple(hip.frag_length_fit(self._ctx(), counts, skew_normal))
+
+    def effective_lengths(self, path_lengths, frag) -> np.ndarray:
+        """PathsIndex::effectivePathLength of every path length on the GPU; frag = (loc, scale, shape, ...)."""
+        return hip.effective_lengths(self._ctx(), path_lengths, float(frag[0]), float(frag[1]), float(frag[2]))
+
+    def prepare_from_alignments(self, alignments, path_info: ClusterBatch, frag=None, is_single_end: bool = False,
+                                min_noise_prob: float = 1e-4, prob_precision: float = 1e-8, frag_counts=None, path_lengths=None,
+                                skew_normal: bool = True) -> "PreparedBatch":
         """Batch whose rows are constructed on the GPU from alignment-path lists (rpvg_amd/host/read_rows.hpp):
         alignments = rows.AlignmentBatch, path_info = a ClusterBatch whose path arrays describe the clusters' paths,
-        frag = (loc, scale, shape, sd_max_multi) of the FragmentLengthDist."""
+        frag = (loc, scale, shape, sd_max_multi) of the FragmentLengthDist (default (300, 50, 0, 10)), or a FragLengthFit
+        (from fit_frag_length: the table of its log densities is then computed on the GPU and never leaves it).
+        frag_counts + path_lengths instead of frag: the distribution is fitted to the counts of the observed fragment
+        lengths and the effective lengths are derived from the path lengths, both on the GPU (paired-end only); the
+        result carries .frag_fit (as fit_frag_length returns it) and .path_effective_length."""
+        if frag is not None and frag_counts is not None:
+            raise ValueError("prepare_from_alignments: frag and frag_counts exclude each other")
+        if (frag_counts is None) != (path_lengths is None):
+            raise ValueError("prepare_from_alignments: frag_counts and path_lengths come together")
+        if frag_counts is not None and is_single_end:
+            raise ValueError("prepare_from_alignments: a single-end run has no fragment lengths to fit")
         prep = PreparedBatch.__new__(PreparedBatch)
         prep.engine = self
         prep.batch = path_info
         ca, cb = alignments.as_c(), path_info.as_c()
         secs = C.c_double(0)
+        if frag_counts is not None:
+            counts = np.ascontiguousarray(frag_counts, dtype=np.uint32)
+            lengths = np.ascontiguousarray(path_lengths, dtype=np.uint32)
+            if lengths.size != len(alignments.path_effective_length):
+                raise ValueError("prepare_from_alignments: one path length per path")
+            fit = hip.CFragLengthFit()
+            eff = np.zeros(lengths.size, dtype=np.float64)
+            prep.handle = lib().rpvg_amd_batch_prepare_from_alignments_fit(
+                self.handle, C.byref(ca), C.byref(cb), C.c_void_p(counts.ctypes.data if counts.size else None), counts.size,
+                1 if skew_normal else 0, C.c_void_p(lengths.ctypes.data if lengths.size else None), min_noise_prob, prob_precision,
+                C.byref(fit), C.c_void_p(eff.ctypes.data if eff.size else None), C.byref(secs))
+            if not prep.handle:
+                raise hip.EngineError(f"batch prepare from alignments failed: {_err()}")
+            prep.frag_fit = _fit_tuple(fit)
+            prep.path_effective_length = eff
+            prep.row_construction_seconds = secs.value
+            return prep
+        if isinstance(frag, FragLengthFit):
+            if is_single_end or not frag.valid:
+                raise ValueError("prepare_from_alignments: a fitted distribution must be valid and belongs to a paired-end run")
+            prep.handle = lib().rpvg_amd_batch_prepare_from_alignments_fitted(
+                self.handle, C.byref(ca), C.byref(cb), frag.loc, frag.scale, frag.shape, min_noise_prob, prob_precision, C.byref(secs))
+            if not prep.handle:
+                raise hip.EngineError(f"batch prepare from alignments failed: {_err()}")
+            prep.row_construction_seconds = secs.value
+            return prep
+        if frag is None:
+            frag = (300.0, 50.0, 0.0, 10)
         prep.handle = lib().rpvg_amd_batch_prepare_from_alignments(
             self.handle, C.byref(ca), C.byref(cb), frag[0], frag[1], frag[2], int(frag[3]), 1 if is_single_end else 0,
             min_noise_prob, prob_precision, C.byref(secs))

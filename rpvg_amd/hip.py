@@ -35,6 +35,8 @@ EXPORTS = [
     "rpvg_hip_batch_upload_finish_queue", "rpvg_hip_batch_upload_finish_wait",
     "rpvg_hip_batch_upload_segments", "rpvg_hip_pinned_alloc", "rpvg_hip_pinned_free", "rpvg_hip_thread_wait_spin_us",
     "rpvg_hip_group_full_posteriors", "rpvg_hip_full_set_count",
+    "rpvg_hip_frag_length_fit", "rpvg_hip_frag_length_table", "rpvg_hip_frag_length_table_get", "rpvg_hip_frag_length_table_free",
+    "rpvg_hip_effective_lengths", "rpvg_hip_alignments_set_effective_lengths", "rpvg_hip_frag_length_eval",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -324,9 +326,74 @@ class DeviceAlignments:
                "rpvg_hip_read_rows_build")
         return DeviceRows(self.ctx, h)
 
+    def set_effective_lengths(self, path_lengths, loc: float, scale: float, shape: float) -> np.ndarray:
+        """Replaces the resident path_effective_length by effectivePathLength(path length) and returns the values."""
+        path_lengths = np.ascontiguousarray(path_lengths, dtype=np.uint32)
+        assert path_lengths.size == len(self.host.path_effective_length)
+        out = np.zeros(path_lengths.size, dtype=np.float64)
+        _check(lib().rpvg_hip_alignments_set_effective_lengths(
+            self.ctx.handle, self.handle, C.c_double(loc), C.c_double(scale), C.c_double(shape),
+            C.c_void_p(path_lengths.ctypes.data if path_lengths.size else None), C.c_void_p(out.ctypes.data if out.size else None)),
+            "rpvg_hip_alignments_set_effective_lengths")
+        return out
+
     def free(self):
         if self.handle:
             lib().rpvg_hip_alignments_free(self.ctx.handle, self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+# ---- fragment-length model (include/rpvg_frag.h) ------------------------------------
+class CFragLengthFit(C.Structure):
+    """rpvg_frag_length_fit"""
+    _fields_ = [("loc", C.c_double), ("scale", C.c_double), ("shape", C.c_double), ("max_length", C.c_uint32),
+                ("sample_size", C.c_uint32), ("iterations", C.c_uint32), ("evaluations", C.c_uint32), ("valid", C.c_int32)]
+
+
+def frag_length_fit(ctx_handle, counts, skew_normal: bool = True) -> CFragLengthFit:
+    """FragmentLengthDist(counts, skew_normal) on the GPU (one kernel launch)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    fit = CFragLengthFit()
+    _check(lib().rpvg_hip_frag_length_fit(ctx_handle, C.c_void_p(counts.ctypes.data if counts.size else None), C.c_uint32(counts.size),
+                                          C.c_int(1 if skew_normal else 0), C.byref(fit)), "rpvg_hip_frag_length_fit")
+    return fit
+
+
+def effective_lengths(ctx_handle, path_lengths, loc: float, scale: float, shape: float) -> np.ndarray:
+    """PathsIndex::effectivePathLength for every path length, on the GPU."""
+    path_lengths = np.ascontiguousarray(path_lengths, dtype=np.uint32)
+    out = np.zeros(path_lengths.size, dtype=np.float64)
+    _check(lib().rpvg_hip_effective_lengths(ctx_handle, C.c_double(loc), C.c_double(scale), C.c_double(shape),
+                                            C.c_void_p(path_lengths.ctypes.data if path_lengths.size else None),
+                                            C.c_uint64(path_lengths.size), C.c_void_p(out.ctypes.data if out.size else None)),
+           "rpvg_hip_effective_lengths")
+    return out
+
+
+class DeviceFragTable:
+    """logProb(v), v = 0 .. 65535, computed and resident on the GPU (rpvg_hip_frag_table)."""
+
+    def __init__(self, ctx_handle, loc: float, scale: float, shape: float):
+        self.ctx_handle = ctx_handle
+        self.handle = C.c_void_p()
+        _check(lib().rpvg_hip_frag_length_table(ctx_handle, C.c_double(loc), C.c_double(scale), C.c_double(shape), C.byref(self.handle)),
+               "rpvg_hip_frag_length_table")
+
+    def download(self) -> np.ndarray:
+        out = np.zeros(65536, dtype=np.float64)
+        _check(lib().rpvg_hip_frag_length_table_get(self.ctx_handle, self.handle, C.c_void_p(out.ctypes.data)),
+               "rpvg_hip_frag_length_table_get")
+        return out
+
+    def free(self):
+        if self.handle:
+            lib().rpvg_hip_frag_length_table_free(self.ctx_handle, self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):
@@ -717,6 +784,27 @@ class Context:
         finally:
             if dev is not align_batch:
                 dev.free()
+
+    # ---- fragment-length model (include/rpvg_frag.h) ---------------------------------
+    def frag_length_fit(self, counts, skew_normal: bool = True) -> CFragLengthFit:
+        return frag_length_fit(self.handle, counts, skew_normal)
+
+    def frag_length_table(self, loc: float, scale: float, shape: float) -> DeviceFragTable:
+        return DeviceFragTable(self.handle, loc, scale, shape)
+
+    def effective_lengths(self, path_lengths, loc: float, scale: float, shape: float) -> np.ndarray:
+        return effective_lengths(self.handle, path_lengths, loc, scale, shape)
+
+    def frag_length_eval(self, what: str, rows) -> np.ndarray:
+        """what = "cdf": rows (x, m, s, a); "truncated_mean": (m, s, a, c, d); "owens_t": (h, a) -> one double per row."""
+        kind = {"cdf": 0, "truncated_mean": 1, "owens_t": 2}[what]
+        rows = np.asarray(rows, dtype=np.float64)
+        padded = np.zeros((rows.shape[0], 5), dtype=np.float64)
+        padded[:, :rows.shape[1]] = rows
+        out = np.zeros(rows.shape[0], dtype=np.float64)
+        _check(lib().rpvg_hip_frag_length_eval(self.handle, C.c_int(kind), C.c_void_p(padded.ctypes.data), C.c_uint64(rows.shape[0]),
+                                               C.c_void_p(out.ctypes.data)), "rpvg_hip_frag_length_eval")
+        return out
 
     # ---- path clustering ----------------------------------------------------------
     def path_clusters(self, num_paths: int, sets):

@@ -108,6 +108,37 @@ FragmentLengthDist::FragmentLengthDist(const double loc_in, const double scale_i
     }
 }
 
+// src/fragment_length_dist.cpp:60-285 (the fit: rpvg_hip_frag_length_fit) and :407-427
+FragmentLengthDist::FragmentLengthDist(const std::vector<uint32_t> & frag_length_counts, const bool skew_normal, std::shared_ptr<HipEngine> engine) {
+
+    assert(engine);
+    assert(!frag_length_counts.empty());
+    assert(frag_length_counts.front() == 0);
+
+    rpvg_frag_length_fit fit;
+    HipEngine::check(rpvg_hip_frag_length_fit(engine->ctx(), frag_length_counts.data(), frag_length_counts.size(), skew_normal, &fit), "rpvg_hip_frag_length_fit");
+
+    loc_ = fit.loc;
+    scale_ = fit.scale;
+    shape_ = fit.shape;
+    max_length_ = 0;
+
+    fit_sample_size = fit.sample_size;
+    fit_iterations = fit.iterations;
+    fit_evaluations = fit.evaluations;
+
+    if (fit.valid) {
+
+        max_length_ = fit.max_length;
+        log_prob_buffer.resize(frag_length_counts.size() + 1);
+
+        for (size_t i = 0; i < log_prob_buffer.size(); ++i) {
+
+            log_prob_buffer[i] = logDensity(i, loc_, scale_, shape_);
+        }
+    }
+}
+
 bool FragmentLengthDist::isValid() const {
 
     return (loc_ >= 0 && scale_ > 0);
@@ -134,6 +165,35 @@ std::vector<double> FragmentLengthDist::logProbTable() const {
     }
 
     return table;
+}
+
+DeviceFragmentLengthTable::DeviceFragmentLengthTable(std::shared_ptr<HipEngine> engine_in, const FragmentLengthDist & fragment_length_dist) : hip_engine(engine_in), table(nullptr) {
+
+    assert(hip_engine);
+    HipEngine::check(rpvg_hip_frag_length_table(hip_engine->ctx(), fragment_length_dist.loc(), fragment_length_dist.scale(), fragment_length_dist.shape(), &table), "rpvg_hip_frag_length_table");
+}
+
+DeviceFragmentLengthTable::~DeviceFragmentLengthTable() {
+
+    rpvg_hip_frag_length_table_free(hip_engine->ctx(), table);
+}
+
+std::vector<double> DeviceFragmentLengthTable::download() const {
+
+    std::vector<double> log_prob(RPVG_FRAG_LENGTH_TABLE_SIZE);
+    HipEngine::check(rpvg_hip_frag_length_table_get(hip_engine->ctx(), table, log_prob.data()), "rpvg_hip_frag_length_table_get");
+
+    return log_prob;
+}
+
+std::vector<double> effectivePathLengths(std::shared_ptr<HipEngine> engine, const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist) {
+
+    assert(engine);
+
+    std::vector<double> effective_lengths(path_lengths.size());
+    HipEngine::check(rpvg_hip_effective_lengths(engine->ctx(), fragment_length_dist.loc(), fragment_length_dist.scale(), fragment_length_dist.shape(), path_lengths.data(), path_lengths.size(), effective_lengths.data()), "rpvg_hip_effective_lengths");
+
+    return effective_lengths;
 }
 
 AlignmentBatchBuilder::AlignmentBatchBuilder() : collapse(false), cluster_read_off(1, 0), cluster_path_off(1, 0), cluster_group_off(1, 0), read_align_off(1, 0), align_path_off(1, 0) {}
@@ -232,6 +292,30 @@ rpvg_alignment_batch AlignmentBatchBuilder::view() const {
 
 DeviceAlignmentBatch::DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, const AlignmentBatchBuilder & alignments) : hip_engine(engine_in), device_alignments(nullptr) {
 
+    upload(alignments);
+}
+
+DeviceAlignmentBatch::DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, const AlignmentBatchBuilder & alignments, const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist) : hip_engine(engine_in), device_alignments(nullptr) {
+
+    upload(alignments);
+
+    const auto alignment_batch = alignments.view();
+    assert(path_lengths.size() == alignment_batch.cluster_path_off[alignment_batch.num_clusters]);
+
+    effective_length.resize(path_lengths.size());
+    const int status = rpvg_hip_alignments_set_effective_lengths(hip_engine->ctx(), device_alignments, fragment_length_dist.loc(), fragment_length_dist.scale(), fragment_length_dist.shape(), path_lengths.data(), effective_length.data());
+
+    if (status != 0) {
+
+        rpvg_hip_alignments_free(hip_engine->ctx(), device_alignments);
+        device_alignments = nullptr;
+    }
+
+    HipEngine::check(status, "rpvg_hip_alignments_set_effective_lengths");
+}
+
+void DeviceAlignmentBatch::upload(const AlignmentBatchBuilder & alignments) {
+
     assert(hip_engine);
 
     const auto alignment_batch = alignments.view();
@@ -248,23 +332,11 @@ DeviceAlignmentBatch::~DeviceAlignmentBatch() {
     rpvg_hip_alignments_free(hip_engine->ctx(), device_alignments);
 }
 
-std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision) {
+namespace {
+
+std::unique_ptr<DeviceClusterBatch> buildRows(const DeviceAlignmentBatch & alignments, const rpvg_row_params & params) {
 
     const auto & engine = alignments.engine();
-
-    std::vector<double> frag_length_table;
-
-    rpvg_row_params params;
-    params.prob_precision = prob_precision;
-    params.min_noise_prob = min_noise_prob;
-    params.is_single_end = is_single_end;
-    params.frag_length_log_prob = nullptr;
-
-    if (!is_single_end) {
-
-        frag_length_table = fragment_length_dist.logProbTable();
-        params.frag_length_log_prob = frag_length_table.data();
-    }
 
     rpvg_hip_read_rows * rows = nullptr;
     HipEngine::check(rpvg_hip_read_rows_build(engine->ctx(), alignments.handle(), &params, 1, &rows), "rpvg_hip_read_rows_build");
@@ -288,6 +360,40 @@ std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceA
     HipEngine::check(view_status, "rpvg_hip_read_rows_sizes");
 
     return cluster_batch;
+}
+
+}
+
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision) {
+
+    std::vector<double> frag_length_table;
+
+    rpvg_row_params params;
+    params.prob_precision = prob_precision;
+    params.min_noise_prob = min_noise_prob;
+    params.is_single_end = is_single_end;
+    params.frag_length_log_prob = nullptr;
+    params.frag_length_table = nullptr;
+
+    if (!is_single_end) {
+
+        frag_length_table = fragment_length_dist.logProbTable();
+        params.frag_length_log_prob = frag_length_table.data();
+    }
+
+    return buildRows(alignments, params);
+}
+
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const DeviceFragmentLengthTable & fragment_length_table, const double min_noise_prob, const double prob_precision) {
+
+    rpvg_row_params params;
+    params.prob_precision = prob_precision;
+    params.min_noise_prob = min_noise_prob;
+    params.is_single_end = false;
+    params.frag_length_log_prob = nullptr;
+    params.frag_length_table = fragment_length_table.handle();
+
+    return buildRows(alignments, params);
 }
 
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(std::shared_ptr<HipEngine> engine, const AlignmentBatchBuilder & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision) {

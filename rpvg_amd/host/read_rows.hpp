@@ -28,6 +28,11 @@ class FragmentLengthDist {
         FragmentLengthDist(const double mean_in, const double sd_in, const uint32_t sd_max_multi);
         FragmentLengthDist(const double loc_in, const double scale_in, const double shape_in, const uint32_t sd_max_multi);
 
+        // Fitted to the counts of the observed fragment lengths (frag_length_counts[v] pairs of length v) on the GPU:
+        // sample mean and standard deviation, or the skew-normal maximum-likelihood fit
+        // (src/fragment_length_dist.cpp:60-285).  Fewer than two samples leave an invalid distribution.
+        FragmentLengthDist(const std::vector<uint32_t> & frag_length_counts, const bool skew_normal, std::shared_ptr<HipEngine> engine = HipEngine::processDefault());
+
         double loc() const { return loc_; }
         double scale() const { return scale_; }
         double shape() const { return shape_; }
@@ -39,6 +44,11 @@ class FragmentLengthDist {
         // logProb(v) for every uint16_t fragment length: the table the GPU path reads
         std::vector<double> logProbTable() const;
 
+        // of the fit on the device: samples counted, passes of the outer loop and log-likelihood sums (0 for the other constructors)
+        uint32_t fitSampleSize() const { return fit_sample_size; }
+        uint32_t fitIterations() const { return fit_iterations; }
+        uint32_t fitEvaluations() const { return fit_evaluations; }
+
     private:
 
         double loc_;
@@ -47,7 +57,34 @@ class FragmentLengthDist {
         double max_length_;
 
         std::vector<double> log_prob_buffer;
+
+        uint32_t fit_sample_size = 0;
+        uint32_t fit_iterations = 0;
+        uint32_t fit_evaluations = 0;
 };
+
+// logProb(v) of every uint16_t fragment length computed on the GPU and kept there (rpvg_hip_frag_length_table)
+class DeviceFragmentLengthTable {
+
+    public:
+
+        DeviceFragmentLengthTable(std::shared_ptr<HipEngine> engine_in, const FragmentLengthDist & fragment_length_dist);
+        ~DeviceFragmentLengthTable();
+
+        DeviceFragmentLengthTable(const DeviceFragmentLengthTable &) = delete;
+        DeviceFragmentLengthTable & operator=(const DeviceFragmentLengthTable &) = delete;
+
+        const rpvg_hip_frag_table * handle() const { return table; }
+        std::vector<double> download() const;
+
+    private:
+
+        std::shared_ptr<HipEngine> hip_engine;
+        rpvg_hip_frag_table * table;
+};
+
+// PathsIndex::effectivePathLength for every path length (src/paths_index.cpp:190-219), on the GPU
+std::vector<double> effectivePathLengths(std::shared_ptr<HipEngine> engine, const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist);
 
 // The AlignmentPath fields addPathProbs reads; the gbwt search state is replaced by the cluster-local
 // indices of the paths it locates (align_paths_ids mapped through clustered_path_index).
@@ -104,6 +141,10 @@ class DeviceAlignmentBatch {
     public:
 
         DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, const AlignmentBatchBuilder & alignments);
+
+        // The same from path lengths (one per path, in the order of the builder's clusters): the effective lengths
+        // of the builder's PathInfo are ignored, they are computed on the device from the distribution.
+        DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, const AlignmentBatchBuilder & alignments, const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist);
         ~DeviceAlignmentBatch();
 
         DeviceAlignmentBatch(const DeviceAlignmentBatch &) = delete;
@@ -113,16 +154,25 @@ class DeviceAlignmentBatch {
         const std::shared_ptr<HipEngine> & engine() const { return hip_engine; }
         const std::vector<double> & totalReadCounts() const { return total_read_count; }
 
+        // PathInfo::effective_length of every path as computed on the device (second constructor only)
+        const std::vector<double> & effectiveLengths() const { return effective_length; }
+
     private:
+
+        void upload(const AlignmentBatchBuilder & alignments);
 
         std::shared_ptr<HipEngine> hip_engine;
         rpvg_hip_alignments * device_alignments;
         std::vector<double> total_read_count;
+        std::vector<double> effective_length;
 };
 
 // addPathProbs for every list of the batch + the caller's sort and merge, on the GPU; the rows stay on
 // the device as the batch the estimators take.
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision);
+
+// The same with the density table the device computed itself: no host copy of the table, nothing to upload.
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const DeviceFragmentLengthTable & fragment_length_table, const double min_noise_prob, const double prob_precision);
 
 // The same from host memory (uploads the lists first).
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(std::shared_ptr<HipEngine> engine, const AlignmentBatchBuilder & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision);

@@ -6,7 +6,9 @@
 #include <cassert>
 #include <chrono>
 #include <cstring>
+#include <algorithm>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -36,6 +38,7 @@ struct PreparedBatch {
     // batches that start from alignment-path lists keep the lists resident: rows can be rebuilt on the device
     std::unique_ptr<DeviceAlignmentBatch> alignments;
     std::unique_ptr<FragmentLengthDist> fragment_length_dist;
+    std::unique_ptr<DeviceFragmentLengthTable> fragment_length_table;  // batches whose distribution was fitted on the device
     bool is_single_end = false;
     double min_noise_prob = 0;
     double prob_precision = 1e-8;
@@ -158,6 +161,39 @@ Result * packResult(const std::vector<PathClusterEstimates> & estimates) {
     }
 
     return result;
+}
+
+// The alignment-path lists of a flat batch handed to the builder the way a caller of the classes would
+void fillBuilder(const rpvg_alignment_batch & alignments, const std::vector<std::vector<PathInfo> > & paths, AlignmentBatchBuilder * builder) {
+
+    const bool collapse = alignments.path_group != nullptr;
+
+    for (uint32_t i = 0; i < alignments.num_clusters; ++i) {
+
+        std::vector<uint32_t> group_name_index;
+        uint32_t num_groups = 0;
+
+        if (collapse) {
+
+            group_name_index.assign(alignments.path_group + alignments.cluster_path_off[i], alignments.path_group + alignments.cluster_path_off[i + 1]);
+            num_groups = alignments.cluster_group_off[i + 1] - alignments.cluster_group_off[i];
+        }
+
+        builder->beginCluster(paths.at(i), group_name_index, num_groups);
+
+        for (uint64_t r = alignments.cluster_read_off[i]; r < alignments.cluster_read_off[i + 1]; ++r) {
+
+            std::vector<AlignmentPath> align_paths;
+
+            for (uint64_t a = alignments.read_align_off[r]; a < alignments.read_align_off[r + 1]; ++a) {
+
+                align_paths.emplace_back(alignments.read_min_mapq[r], alignments.align_score_sum[a], alignments.align_length[a], alignments.align_frag_length[a], std::vector<uint32_t>(alignments.align_path_idx + alignments.align_path_off[a], alignments.align_path_idx + alignments.align_path_off[a + 1]));
+            }
+
+            align_paths.emplace_back(alignments.read_min_mapq[r], alignments.read_noise_score[r], 0, 0, std::vector<uint32_t>());
+            builder->addAlignmentPaths(align_paths, alignments.read_count[r]);
+        }
+    }
 }
 
 }
@@ -299,34 +335,7 @@ void * rpvg_amd_batch_prepare_from_alignments(void * engine, const rpvg_alignmen
         assert(prepared->paths.size() == alignments->num_clusters);
 
         AlignmentBatchBuilder builder;
-        const bool collapse = alignments->path_group != nullptr;
-
-        for (uint32_t i = 0; i < alignments->num_clusters; ++i) {
-
-            std::vector<uint32_t> group_name_index;
-            uint32_t num_groups = 0;
-
-            if (collapse) {
-
-                group_name_index.assign(alignments->path_group + alignments->cluster_path_off[i], alignments->path_group + alignments->cluster_path_off[i + 1]);
-                num_groups = alignments->cluster_group_off[i + 1] - alignments->cluster_group_off[i];
-            }
-
-            builder.beginCluster(prepared->paths.at(i), group_name_index, num_groups);
-
-            for (uint64_t r = alignments->cluster_read_off[i]; r < alignments->cluster_read_off[i + 1]; ++r) {
-
-                std::vector<AlignmentPath> align_paths;
-
-                for (uint64_t a = alignments->read_align_off[r]; a < alignments->read_align_off[r + 1]; ++a) {
-
-                    align_paths.emplace_back(alignments->read_min_mapq[r], alignments->align_score_sum[a], alignments->align_length[a], alignments->align_frag_length[a], std::vector<uint32_t>(alignments->align_path_idx + alignments->align_path_off[a], alignments->align_path_idx + alignments->align_path_off[a + 1]));
-                }
-
-                align_paths.emplace_back(alignments->read_min_mapq[r], alignments->read_noise_score[r], 0, 0, std::vector<uint32_t>());
-                builder.addAlignmentPaths(align_paths, alignments->read_count[r]);
-            }
-        }
+        fillBuilder(*alignments, prepared->paths, &builder);
 
         prepared->fragment_length_dist.reset(is_single_end ? new FragmentLengthDist() : new FragmentLengthDist(frag_loc, frag_scale, frag_shape, frag_sd_max_multi));
         prepared->is_single_end = is_single_end != 0;
@@ -336,6 +345,143 @@ void * rpvg_amd_batch_prepare_from_alignments(void * engine, const rpvg_alignmen
         const auto start = std::chrono::steady_clock::now();
         prepared->alignments.reset(new DeviceAlignmentBatch(static_cast<Engine *>(engine)->hip, builder));
         prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, prepared->is_single_end, min_noise_prob, prob_precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return guard.release();
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// The same for a paired-end run that brings neither a fitted distribution nor effective lengths: the counts of the
+// observed fragment lengths (FragmentLengthDist's third constructor, src/main.cpp:235) and the length of every path
+// (path_length[P], in the order of path_info's paths; src/main.cpp:880).  The fit, the density table and the effective
+// lengths are computed on the GPU; path_info's effective lengths are ignored.  fit_out (may be NULL) receives the fit,
+// effective_length_out (may be NULL, [P]) the effective lengths that the PathInfo of the batch now hold.  A fit that is
+// not a valid distribution (fewer than two samples) is an error.
+void * rpvg_amd_batch_prepare_from_alignments_fit(void * engine, const rpvg_alignment_batch * alignments, const rpvg_cluster_batch * path_info, const uint32_t * frag_length_counts, uint32_t num_frag_length_counts, int skew_normal, const uint32_t * path_length, double min_noise_prob, double prob_precision, rpvg_frag_length_fit * fit_out, double * effective_length_out, double * seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = new PreparedBatch();
+        std::unique_ptr<PreparedBatch> guard(prepared);
+
+        prepared->paths = unpackPaths(*path_info);
+        assert(prepared->paths.size() == alignments->num_clusters);
+
+        AlignmentBatchBuilder builder;
+        fillBuilder(*alignments, prepared->paths, &builder);
+
+        auto hip = static_cast<Engine *>(engine)->hip;
+
+        if (num_frag_length_counts == 0 || frag_length_counts[0] != 0 || num_frag_length_counts > RPVG_FRAG_LENGTH_MAX_COUNTS) {
+
+            throw std::runtime_error("fragment length counts: between 1 and 65536 entries, none of length 0");
+        }
+
+        prepared->fragment_length_dist.reset(new FragmentLengthDist(std::vector<uint32_t>(frag_length_counts, frag_length_counts + num_frag_length_counts), skew_normal != 0, hip));
+
+        if (fit_out) {
+
+            fit_out->loc = prepared->fragment_length_dist->loc();
+            fit_out->scale = prepared->fragment_length_dist->scale();
+            fit_out->shape = prepared->fragment_length_dist->shape();
+            fit_out->max_length = prepared->fragment_length_dist->maxLength();
+            fit_out->sample_size = prepared->fragment_length_dist->fitSampleSize();
+            fit_out->iterations = prepared->fragment_length_dist->fitIterations();
+            fit_out->evaluations = prepared->fragment_length_dist->fitEvaluations();
+            fit_out->valid = prepared->fragment_length_dist->isValid();
+        }
+
+        if (!prepared->fragment_length_dist->isValid()) {
+
+            throw std::runtime_error("too few fragment lengths to fit their distribution");
+        }
+
+        prepared->is_single_end = false;
+        prepared->min_noise_prob = min_noise_prob;
+        prepared->prob_precision = prob_precision;
+
+        const uint64_t num_paths = alignments->cluster_path_off[alignments->num_clusters];
+
+        const auto start = std::chrono::steady_clock::now();
+        prepared->fragment_length_table.reset(new DeviceFragmentLengthTable(hip, *prepared->fragment_length_dist));
+        prepared->alignments.reset(new DeviceAlignmentBatch(hip, builder, std::vector<uint32_t>(path_length, path_length + num_paths), *prepared->fragment_length_dist));
+        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_table, min_noise_prob, prob_precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        const auto & effective_lengths = prepared->alignments->effectiveLengths();
+        size_t path = 0;
+
+        for (auto & cluster_paths: prepared->paths) {
+
+            for (auto & info: cluster_paths) {
+
+                info.effective_length = effective_lengths.at(path);
+                info.length = path_length[path];
+                ++path;
+            }
+        }
+
+        assert(path == effective_lengths.size());
+
+        if (effective_length_out) {
+
+            std::copy(effective_lengths.begin(), effective_lengths.end(), effective_length_out);
+        }
+
+        return guard.release();
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// The rows of a distribution that was fitted earlier (rpvg_hip_frag_length_fit: it has a maximum length, not the
+// sd_max_multi of the parametric constructors): its density table is computed on the GPU and stays there, as in
+// rpvg_amd_batch_prepare_from_alignments_fit; the effective lengths are path_info's.
+void * rpvg_amd_batch_prepare_from_alignments_fitted(void * engine, const rpvg_alignment_batch * alignments, const rpvg_cluster_batch * path_info, double frag_loc, double frag_scale, double frag_shape, double min_noise_prob, double prob_precision, double * seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = new PreparedBatch();
+        std::unique_ptr<PreparedBatch> guard(prepared);
+
+        prepared->paths = unpackPaths(*path_info);
+        assert(prepared->paths.size() == alignments->num_clusters);
+
+        AlignmentBatchBuilder builder;
+        fillBuilder(*alignments, prepared->paths, &builder);
+
+        if (!(frag_loc >= 0 && frag_scale > 0)) {
+
+            throw std::runtime_error("not a valid fragment length distribution");
+        }
+
+        auto hip = static_cast<Engine *>(engine)->hip;
+
+        prepared->fragment_length_dist.reset(new FragmentLengthDist(frag_loc, frag_scale, frag_shape, 10));
+        prepared->is_single_end = false;
+        prepared->min_noise_prob = min_noise_prob;
+        prepared->prob_precision = prob_precision;
+
+        const auto start = std::chrono::steady_clock::now();
+        prepared->fragment_length_table.reset(new DeviceFragmentLengthTable(hip, *prepared->fragment_length_dist));
+        prepared->alignments.reset(new DeviceAlignmentBatch(hip, builder));
+        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_table, min_noise_prob, prob_precision);
 
         if (seconds_out) {
 
@@ -651,7 +797,15 @@ int rpvg_amd_run_from_alignments_inplace(void * engine, void * prepared_batch, c
         const auto start = std::chrono::steady_clock::now();
 
         prepared->device.reset();
-        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, prepared->is_single_end, prepared->min_noise_prob, prepared->prob_precision);
+
+        if (prepared->fragment_length_table) {
+
+            prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_table, prepared->min_noise_prob, prepared->prob_precision);
+
+        } else {
+
+            prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, prepared->is_single_end, prepared->min_noise_prob, prepared->prob_precision);
+        }
 
         const auto rows_done = std::chrono::steady_clock::now();
 

@@ -30,7 +30,7 @@ class CAlignmentBatch(C.Structure):
 
 class CRowParams(C.Structure):
     _fields_ = [("prob_precision", C.c_double), ("min_noise_prob", C.c_double), ("is_single_end", C.c_int32),
-                ("frag_length_log_prob", f64p)]
+                ("frag_length_log_prob", f64p), ("frag_length_table", C.c_void_p)]
 
 
 @dataclass
@@ -39,13 +39,15 @@ class RowParams:
     min_noise_prob: float = 1e-4
     is_single_end: bool = False
     frag_length_log_prob: Optional[np.ndarray] = None  # f64 [65536]
+    frag_length_table: Optional[object] = None  # hip.DeviceFragTable: the same table already on the GPU
 
     def as_c(self) -> CRowParams:
-        if not self.is_single_end:
+        if not self.is_single_end and self.frag_length_table is None:
             assert self.frag_length_log_prob is not None and len(self.frag_length_log_prob) == FRAG_LENGTH_TABLE_SIZE
             self.frag_length_log_prob = np.ascontiguousarray(self.frag_length_log_prob, dtype=np.float64)
         ptr = _ptr(self.frag_length_log_prob, f64p) if self.frag_length_log_prob is not None else None
-        return CRowParams(self.prob_precision, self.min_noise_prob, 1 if self.is_single_end else 0, ptr)
+        table = self.frag_length_table.handle if self.frag_length_table is not None else None
+        return CRowParams(self.prob_precision, self.min_noise_prob, 1 if self.is_single_end else 0, ptr, table)
 
 
 @dataclass
