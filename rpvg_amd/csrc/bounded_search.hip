@@ -19,6 +19,7 @@
 // is re-read from L2.
 
 #include "common.hpp"
+#include "search_plan.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -28,6 +29,7 @@
 #include <numeric>
 
 using namespace rpvg_hip_detail;
+using namespace rpvg_search;
 
 // ---- one search at a time per device -------------------------------------------------
 // The host lanes of a batch (two contexts of one device) overlap one lane's host work with the other's kernels.
@@ -102,7 +104,6 @@ struct rpvg_hip_pair_posteriors {
 namespace {
 
 constexpr uint32_t kLdsRows = 2048;   // rows of (base, count) staged in LDS by the search kernel: 32 KB
-constexpr uint32_t kSmallRows = 512;  // ... for matrices with at most this many rows: 8 KB
 constexpr uint32_t kSmallRowLdsCols = 128;  // ... by the kernel for matrices with few rows (24 KB of LDS per workgroup: six per CU)
 constexpr uint32_t kRowLdsCols = 512; // pair log-likelihoods of one first column kept in LDS up to this many columns: 4 KB
 
@@ -150,16 +151,7 @@ __device__ __forceinline__ double blockLogSumExp(const uint32_t n, ValueFn value
 struct SearchArgs {
     const uint32_t * order;          // matrices, expensive first
     uint32_t count;
-    const uint64_t * mat_val_off;
-    const uint64_t * mat_row_off;
-    const uint32_t * mat_fast;       // row classes of the matrix (LogProduct, common.hpp): end of the fast rows,
-    const uint32_t * mat_mid;        // end of the mid rows
-    const uint64_t * mat_rows;
-    const uint32_t * mat_cols;
-    const double * values;
-    const double * rowmax;
-    const double * row_count;        // in matrix row order (rpvg_hip_groups), like row_noise
-    const double * row_noise;
+    GroupMatricesView g;             // (row_count and row_noise in matrix row order, like the rows' classes)
     const uint64_t * col_off;        // [M+1] prefix of columns (scratch + counts)
     const uint32_t * col_count;      // path_counts of every column
     const uint64_t * pair_cap_off;   // [M+1] prefix of G(G+1)/2 (output regions)
@@ -232,13 +224,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     loadLogTable(lt);  // visible after the first barrier below
     const uint32_t m = args.order[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t R = args.mat_rows[m];
-    const uint32_t G = args.mat_cols[m];
-    const double * M = args.values + args.mat_val_off[m];
-    const double * rm = args.rowmax + args.mat_row_off[m];
-    const double * cnt = args.row_count + args.mat_row_off[m];
-    const double * nz = args.row_noise + args.mat_row_off[m];
-    const uint64_t fast_end = args.mat_fast[m], mid_end = args.mat_mid[m];
+    const GroupMatrix mat = args.g.matrix(m);
+    const uint64_t R = mat.R, fast_end = mat.fast_end, mid_end = mat.mid_end;
+    const uint32_t G = mat.G;
+    const double * M = mat.values, * rm = mat.rowmax, * cnt = mat.row_count, * nz = mat.row_noise;
     const uint64_t c0 = args.col_off[m];
     const uint32_t * ccount = args.col_count + c0;
     double * lf = args.log_freq + c0;
@@ -434,29 +423,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 // and one workgroup then applies an exclusive prefix-max scan in the
 // reference's pair order.
 
-constexpr uint32_t kChunkRows = 1024;
-constexpr int kTileA = 4;
-
 struct TableWork {
     const uint32_t * item_matrix;   // [W]
     const uint32_t * item_col;      // [W]
     const uint32_t * item_chunk;    // [W]
     uint32_t count;
-    const uint64_t * mat_val_off;
-    const uint64_t * mat_row_off;
-    const uint32_t * mat_fast;
-    const uint32_t * mat_mid;
-    const uint64_t * mat_rows;
-    const uint32_t * mat_cols;
-    const double * values;
-    const double * rowmax;
-    const double * row_count;
-    const double * row_noise;
-    const uint64_t * big_col_part_off;   // [M] offset of the matrix's [chunk][G] partial column sums (0 for small ones)
-    const uint64_t * big_pair_part_off;  // [M] offset of the matrix's [chunk][G][G] partial pair sums
-    double * part_marginal;
-    double * part_optimistic;
-    double * part_pair;
+    GroupMatricesView g;
+    SearchParts parts;              // (the offsets: 0 for the matrices outside the table part)
     unsigned long long * log_evals;
 };
 
@@ -477,16 +450,15 @@ __global__ __launch_bounds__(256) void pairTableKernel(const TableWork w) {
     loadLogTable(lt);  // visible after the barrier that publishes the staged rows
     const uint32_t m = w.item_matrix[item], a0 = w.item_col[item], chunk = w.item_chunk[item];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t R = w.mat_rows[m];
-    const uint32_t G = w.mat_cols[m];
+    const GroupMatrix mat = w.g.matrix(m);
+    const uint64_t R = mat.R;
+    const uint32_t G = mat.G;
     const uint32_t ta = (G - a0) < kTileA ? (G - a0) : kTileA;
     const uint64_t r_begin = static_cast<uint64_t>(chunk) * kChunkRows;
     const uint32_t n = static_cast<uint32_t>((R - r_begin) < kChunkRows ? (R - r_begin) : kChunkRows);
-    const double * M = w.values + w.mat_val_off[m] + r_begin;
-    const double * cnt = w.row_count + w.mat_row_off[m] + r_begin;
-    const double * nz = w.row_noise + w.mat_row_off[m] + r_begin;
+    const double * M = mat.values + r_begin, * cnt = mat.row_count + r_begin, * nz = mat.row_noise + r_begin;
     auto local = [&](const uint64_t end_row) { return end_row <= r_begin ? 0u : (end_row - r_begin < n ? static_cast<uint32_t>(end_row - r_begin) : n); };
-    const uint32_t nf = local(w.mat_fast[m]), nm = local(w.mat_mid[m]);  // class boundaries within the chunk
+    const uint32_t nf = local(mat.fast_end), nm = local(mat.mid_end);  // class boundaries within the chunk
 
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
         const double noise = nz[i];
@@ -506,7 +478,7 @@ __global__ __launch_bounds__(256) void pairTableKernel(const TableWork w) {
             const uint32_t a = a0 + task;
             const double * col_a = M + static_cast<uint64_t>(a) * R;
             const double acc = waveSum(sumCountLogs<uint32_t>(lt, lds_count, [&](const uint32_t i) { return nz[i] + col_a[i] / 1.0; }, 0u, nf, nm, n, lane));
-            if (lane == 0) w.part_marginal[w.big_col_part_off[m] + static_cast<uint64_t>(chunk) * G + a] = acc;
+            if (lane == 0) w.parts.part_marginal[w.parts.col_part_off[m] + static_cast<uint64_t>(chunk) * G + a] = acc;
         } else {
             const uint32_t b = a0 + (task - ta);
             const double * col_b = M + static_cast<uint64_t>(b) * R;
@@ -527,7 +499,7 @@ __global__ __launch_bounds__(256) void pairTableKernel(const TableWork w) {
             for (int t = 0; t < kTileA; ++t) {
                 const double total = waveSum(acc[t]);
                 if (lane == 0 && t < static_cast<int>(ta) && a0 + t <= b) {
-                    w.part_pair[w.big_pair_part_off[m] + (static_cast<uint64_t>(chunk) * G + (a0 + t)) * G + b] = total;
+                    w.parts.part_pair[w.parts.pair_part_off[m] + (static_cast<uint64_t>(chunk) * G + (a0 + t)) * G + b] = total;
                 }
             }
         }
@@ -557,14 +529,9 @@ __global__ __launch_bounds__(256) void pairTableKernel(const TableWork w) {
 //     slice takes every S-th row): the partial sums of a slice are one more part of the chunk for the resolving
 //     workgroup, which adds parts anyway.
 // Rows with read counts 2 .. kMidMaxCount multiply that many times, the others take the table logarithm, as everywhere.
-constexpr uint32_t kTileBlock = 256;
 constexpr uint32_t kTileLdsDoubles = 6 * 1024;   // staged values + noise + counts: 48 KB (three workgroups per CU)
-constexpr uint32_t kTileMaxColumns = 1024;       // wider matrices keep the sequential search (their pair tables would not fit either)
 
-__host__ __device__ inline uint32_t tileColumns(const uint32_t G) { return (G + 3) / 4; }
-__host__ __device__ inline uint32_t tileCount(const uint32_t G) { return tileColumns(G) * (tileColumns(G) + 1) / 2; }
-// row slices of a chunk: lanes left over by the tiles
-__host__ __device__ inline uint32_t tileSlices(const uint32_t G) { return tileCount(G) <= kTileBlock ? kTileBlock / tileCount(G) : 1u; }
+// (tileColumns, tileCount, tileSlices: search_plan.hpp)
 // ... for the single columns (marginals): a lane per four columns and slice — all lanes of the workgroup, so that the
 // few column sums are not a serial tail behind the pairs (26 lanes walking every second row cost 1.9 of the kernel's 6.5 ms)
 __host__ __device__ inline uint32_t marginalSlices(const uint32_t G) { return kTileBlock / tileColumns(G); }
@@ -572,23 +539,12 @@ __host__ __device__ inline uint32_t marginalSlices(const uint32_t G) { return kT
 struct PairTileWork {
     const uint32_t * item_matrix;   // [W]
     const uint32_t * item_chunk;    // [W]
-    const uint32_t * item_tiles;    // [W] pairTile2Kernel: first tile | (tiles - 1) << 16
-    uint32_t chunk_rows;            // pairTile2Kernel: rows of a chunk (kChunkRows for the others)
+    const uint32_t * item_tiles;    // [W] first tile | (tiles - 1) << 16
     uint32_t count;
-    const uint64_t * mat_val_off;
-    const uint64_t * mat_row_off;
-    const uint32_t * mat_fast;
-    const uint32_t * mat_mid;
-    const uint64_t * mat_rows;
-    const uint32_t * mat_cols;
-    const double * values;
-    const double * row_count;
-    const double * row_noise;
-    const uint64_t * col_part_off;   // [M] offset of the matrix's [chunk][G] partial column sums
-    const uint64_t * pair_part_off;  // [M] offset of the matrix's [chunk][G][G] partial pair sums
-    double * part_marginal;
-    double * part_pair;
+    // (this order of the three below: the one at which the compiler allocates pairTile2Kernel's registers as it did for the loose pointers)
     unsigned long long * log_evals;
+    SearchParts parts;              // (chunk_rows: rows of a chunk)
+    GroupMatricesView g;
 #ifdef RPVG_HIP_EXPERIMENTS
     uint32_t debug_skip;  // timing experiments (RPVG_HIP_PAIR_DEBUG): 1 no count-1 rows, 2 no mid rows, 4 no other rows, 8 no marginals, 16 no loads,
                           // 32 no epilogue, 64 the prologue alone, 128 the dispatch of the grid alone
@@ -604,7 +560,8 @@ struct PairTileWork {
 
 // ---- the same tiles, lanes balanced and the staging asynchronous (round 4) -----------------------------------------
 //
-// What pairTileKernel left on the table (configs[2] bench: 99 % of its evaluations are in matrices of 33 .. 64 columns, most
+// What round 2's tile kernel (one item per chunk, tileSlices(G) slices) left on the table (configs[2] bench: 99 % of its
+// evaluations are in matrices of 33 .. 64 columns, most
 // of them 64): 136 tiles on 256 lanes is one slice — 53 % of the lanes, a wave of 8 lanes walking every row — and its staging
 // (loads to registers, transposed stores to LDS, between two barriers) and its arithmetic added up instead of overlapping
 // (1.40 ms = 0.47 staging and fixed costs + 0.93 arithmetic; without the loads 0.93).  Here
@@ -616,7 +573,7 @@ struct PairTileWork {
 //     lanes work on the current ones, one barrier per staged block;
 //   * the values are staged as they are, not halved: a lane multiplies 2 x = (u + 2 noise) + v — the same roundings as
 //     (u / 2 + noise) + v / 2 scaled by two — and takes one from the product's exponent per factor.
-constexpr uint32_t kTile2BufferDoubles = 3 * 1024;  // two of them: 48 KB (three workgroups per CU)
+// (kTile2BufferDoubles: search_plan.hpp)
 
 __host__ __device__ inline uint32_t tileRowOfTile(const uint32_t t, const uint32_t T) {
     uint32_t lo = 0, hi = T - 1;  // row ta of the triangle starts at tile ta * T - ta (ta - 1) / 2
@@ -661,19 +618,14 @@ __device__ __forceinline__ uint32_t ldsByteAddress(const double * const p) {
     return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p));  // (a generic pointer into LDS: the offset is its low word)
 }
 
-// Rows per staged block: a compile-time constant, so that the eight values of a row sit at immediate offsets from one address
-// per side (a stride in a register cost nine address additions and nine increments per row next to the 36 FP64 instructions);
-// even (a lane loads two).  The largest of the menu whose block fits a buffer.
-__host__ __device__ inline uint32_t tileSubRows(const uint32_t ncols) {
-    const uint32_t fit = (kTile2BufferDoubles - ncols / 2) / (ncols + 2);
-    return fit >= 126 ? 126u : fit >= 94 ? 94u : fit >= 46 ? 46u : fit >= 30 ? 30u : fit >= 14 ? 14u : fit >= 6 ? 6u : 2u;
-}
+// (tileSubRows — rows per staged block, a compile-time constant of pairTile2Item — and planTileRanges: search_plan.hpp)
 
 template <uint32_t kSubRows>
 __device__ __forceinline__ void pairTile2Item(const PairTileWork & w, double * const tile_lds, const LogTableEntry * const lt, const uint32_t m, const uint32_t chunk,
                                               const uint32_t t0, const uint32_t tcount, const uint32_t c_lo, const uint32_t ncols) {
-    const uint64_t R = w.mat_rows[m];
-    const uint32_t G = w.mat_cols[m];
+    const GroupMatrix mat = w.g.matrix(m);
+    const uint64_t R = mat.R;
+    const uint32_t G = mat.G;
     const uint32_t T = tileColumns(G);
     const uint32_t S = kTileBlock / tcount;
     constexpr uint32_t sub_rows = kSubRows;
@@ -682,13 +634,12 @@ __device__ __forceinline__ void pairTile2Item(const PairTileWork & w, double * c
     // 4 (mod 8) words that way — with 8 sub_rows words they would fall on four bank positions)
     const uint32_t lanes_per_column = sub_rows / 2, columns_per_load = lanes_per_column <= 16 ? 4u : lanes_per_column <= 32 ? 2u : 1u;
     auto columnOffset = [&](const uint32_t c) { return static_cast<size_t>(c) * sub_rows + (c / 4) * 2; };
-    const uint64_t r_begin = static_cast<uint64_t>(chunk) * w.chunk_rows;
-    const uint32_t n = static_cast<uint32_t>((R - r_begin) < w.chunk_rows ? (R - r_begin) : w.chunk_rows);
-    const double * M = w.values + w.mat_val_off[m] + r_begin;  // column-major: M[column * R + row]
-    const double * cnt = w.row_count + w.mat_row_off[m] + r_begin;
-    const double * nz = w.row_noise + w.mat_row_off[m] + r_begin;
+    const uint64_t r_begin = static_cast<uint64_t>(chunk) * w.parts.chunk_rows;
+    const uint32_t n = static_cast<uint32_t>((R - r_begin) < w.parts.chunk_rows ? (R - r_begin) : w.parts.chunk_rows);
+    const double * M = mat.values + r_begin;  // column-major: M[column * R + row]
+    const double * cnt = mat.row_count + r_begin, * nz = mat.row_noise + r_begin;
     auto local = [&](const uint64_t end_row) { return end_row <= r_begin ? 0u : (end_row - r_begin < n ? static_cast<uint32_t>(end_row - r_begin) : n); };
-    const uint32_t nf = local(w.mat_fast[m]), nm = local(w.mat_mid[m]);  // class boundaries within the chunk
+    const uint32_t nf = local(mat.fast_end), nm = local(mat.mid_end);  // class boundaries within the chunk
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 
     // a buffer: [ncols][sub_rows] values, [sub_rows] noise, [sub_rows] counts
@@ -849,8 +800,8 @@ __device__ __forceinline__ void pairTile2Item(const PairTileWork & w, double * c
     // The sums of a chunk: one per pair and column.  Slices add theirs up in LDS, in the order of the slices (the staged rows
     // are done with, no load is in flight), so that the resolving workgroup reads one part per chunk.
     if (RPVG_PAIR_DEBUG_SKIP(w) & 32u) return;  // (timing: without the epilogue)
-    double * const out_pairs = w.part_pair + w.pair_part_off[m] + static_cast<uint64_t>(chunk) * G * G;
-    double * const out_columns = w.part_marginal + w.col_part_off[m] + static_cast<uint64_t>(chunk) * G;
+    double * const out_pairs = w.parts.part_pair + w.parts.pair_part_off[m] + static_cast<uint64_t>(chunk) * G * G;
+    double * const out_columns = w.parts.part_marginal + w.parts.col_part_off[m] + static_cast<uint64_t>(chunk) * G;
     double * const sums = tile_lds;         // [S][tcount][16], then
     double * const column_sums = tile_lds;  // [SM][T][4]: one after the other in the same LDS
     if (S > 1) __syncthreads();
@@ -911,7 +862,7 @@ __global__ __launch_bounds__(kTileBlock) __attribute__((amdgpu_waves_per_eu(3)))
     const uint32_t t0 = w.item_tiles[item] & 0xffffu, tcount = (w.item_tiles[item] >> 16) + 1;  // tiles [t0, t0 + tcount)
     if (RPVG_PAIR_DEBUG_SKIP(w) & 128u) return;  // (timing: the dispatch of the grid alone)
     loadLogTable(lt);  // visible after the first barrier of the item
-    const uint32_t T = tileColumns(w.mat_cols[m]);
+    const uint32_t T = tileColumns(w.g.mat_cols[m]);
     const uint32_t c_lo = 4 * tileRowOfTile(t0, T), ncols = 4 * T - c_lo;  // columns the item's tiles touch: [c_lo, 4 T)
     switch (tileSubRows(ncols)) {
         case 126: pairTile2Item<126>(w, tile_lds, lt, m, chunk, t0, tcount, c_lo, ncols); break;
@@ -924,46 +875,14 @@ __global__ __launch_bounds__(kTileBlock) __attribute__((amdgpu_waves_per_eu(3)))
     }
 }
 
-// The tiles of a matrix cut into the ranges of its work items: 256 at a time, and what is left so that tiles x slices fills
-// the workgroup — one more slice for as many tiles as fit then, the rest of the tiles in an item of their own (its lanes walk
-// 1 / slices of the rows each) — whenever that walks at least a tenth fewer rows per lane than one item with the slices that fit.
-inline void planTileRanges(const uint32_t tiles, std::vector<std::pair<uint32_t, uint32_t> > * ranges) {
-    uint32_t t0 = 0, left = tiles;
-    while (left > 0) {
-        if (left >= kTileBlock) {
-            ranges->emplace_back(t0, kTileBlock);
-            t0 += kTileBlock;
-            left -= kTileBlock;
-            continue;
-        }
-        const uint32_t slices = kTileBlock / left;
-        const uint32_t more = kTileBlock / (slices + 1), rest = left - more;
-        const double one = 1.0 / slices, two = 1.0 / (slices + 1) + 1.0 / (kTileBlock / rest);
-        if (two < 0.9 * one) {
-            ranges->emplace_back(t0, more);
-            t0 += more;
-            left = rest;
-        } else {
-            ranges->emplace_back(t0, left);
-            left = 0;
-        }
-    }
-}
-
 struct ResolveArgs {
     const uint32_t * big_matrix;    // [B] matrices on the table path
-    uint32_t chunk_rows;            // rows of a chunk of the partial sums
     uint32_t count;
-    const uint64_t * mat_rows;
-    const uint32_t * mat_cols;
+    GroupMatricesView g;
     const uint64_t * col_off;
     const uint32_t * col_count;
     const uint64_t * pair_cap_off;
-    const uint64_t * big_col_part_off;
-    const uint64_t * big_pair_part_off;
-    const double * part_marginal;
-    const double * part_optimistic;
-    const double * part_pair;
+    SearchParts parts;              // (read only here)
     double min_log_likelihood_diff;
     double * log_freq;
     double * marginal;
@@ -998,16 +917,16 @@ __global__ __launch_bounds__(256) void resolveTableKernel(const ResolveArgs args
     if (blockIdx.x >= args.count) return;
     const uint32_t m = args.big_matrix[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t R = args.mat_rows[m];
-    const uint32_t G = args.mat_cols[m];
-    const uint32_t chunks = static_cast<uint32_t>((R + args.chunk_rows - 1) / args.chunk_rows);
+    const uint64_t R = args.g.mat_rows[m];
+    const uint32_t G = args.g.mat_cols[m];
+    const uint32_t chunks = static_cast<uint32_t>((R + args.parts.chunk_rows - 1) / args.parts.chunk_rows);
     const uint64_t c0 = args.col_off[m];
     const uint32_t * ccount = args.col_count + c0;
     double * lf = args.log_freq + c0;
     double * marg = args.marginal + c0;
     uint32_t * ord = args.col_order + c0;
-    const double * pm = args.part_marginal + args.big_col_part_off[m];
-    const double * pp = args.part_pair + args.big_pair_part_off[m];
+    const double * pm = args.parts.part_marginal + args.parts.col_part_off[m];
+    const double * pp = args.parts.part_pair + args.parts.pair_part_off[m];
     const uint64_t p0 = args.pair_cap_off[m];
     double * seq = args.seq_value + p0;
     uint32_t * out_first = args.out_first + p0;
@@ -1172,6 +1091,206 @@ __global__ void compactPairsBlockKernel(const uint32_t num_matrices, const uint6
     }
 }
 
+// ---- the host side: plan (search_plan.hpp) -> queue -> resolve ---------------------------------------------------------
+
+// what the environment changes of the plan, read per call (the tests switch between the two searches)
+PairSearchKnobs pairSearchKnobs() {
+    PairSearchKnobs knobs;
+    if (const char * env = std::getenv("RPVG_HIP_PAIR_TILES")) knobs.tiles_wanted = std::atoi(env);
+    if (const char * env = std::getenv("RPVG_HIP_TABLE_MIN_WORK")) knobs.table_min_work = std::atof(env);
+    if (const char * env = std::getenv("RPVG_HIP_PAIR_CHUNK_ROWS")) knobs.chunk_rows = std::max(256, std::atoi(env));
+    return knobs;
+}
+
+int searchFailed(const hipError_t e) {
+    setError("rpvg_hip_bounded_pair_posteriors: %s", hipGetErrorString(e));
+    return (e == hipErrorOutOfMemory) ? RPVG_HIP_ERR_ALLOC : RPVG_HIP_ERR_RUNTIME;
+}
+
+// RPVG_HIP_SEARCH_CLASSES (experiments builds): the three parts of the plan's order on stderr
+void showSearchClasses(const rpvg_hip_groups * groups, const PairSearchPlan & plan) {
+    const std::vector<uint32_t> & order = plan.order;
+    const uint32_t M = static_cast<uint32_t>(order.size()), num_big = plan.num_big, num_medium = plan.num_medium;
+    auto show = [&](const char * name, uint32_t first, uint32_t count) {
+        double evals = 0;
+        for (uint32_t i = first; i < first + count; ++i) evals += 0.5 * groups->h_num_rows[order[i]] * groups->h_num_cols[order[i]] * groups->h_num_cols[order[i]];
+        std::fprintf(stderr, "[search classes] %-6s %6u matrices, %.3g pair-row evaluations if nothing is skipped; largest:", name, count, evals);
+        for (uint32_t i = first; i < first + std::min<uint32_t>(count, 6); ++i) std::fprintf(stderr, " %llux%u", static_cast<unsigned long long>(groups->h_num_rows[order[i]]), groups->h_num_cols[order[i]]);
+        std::fprintf(stderr, "\n");
+    };
+    show("table", 0, num_big);
+    if (plan.pair_tiles) {  // the tile kernel's lanes: how many of a workgroup's 256 carry a tile, how many of a tile's 16 slots a pair
+        struct Bucket { uint64_t matrices = 0; double rows = 0, evals = 0, lane_rows = 0, slot_rows = 0; };
+        std::map<uint32_t, Bucket> buckets;
+        for (uint32_t i = 0; i < num_big; ++i) {
+            const double R = static_cast<double>(groups->h_num_rows[order[i]]);
+            const uint32_t G = groups->h_num_cols[order[i]];
+            uint32_t key = 1;
+            while (key < G) key <<= 1;
+            Bucket & b = buckets[key];
+            const uint32_t tiles = tileCount(G);
+            b.matrices += 1;
+            b.rows += R;
+            b.evals += R * (0.5 * G * (G + 1));
+            // rows a lane walks x lanes of the workgroup, summed over the matrix's work items (planTileRanges: an item's lanes walk
+            // 1 / slices of the rows each) — until round 6 this line priced round 2's kernel, one item per chunk with
+            // tileSlices(G) slices: 0.58 for 64 columns, where the ranges of pairTile2Kernel reach 1.00
+            std::vector<std::pair<uint32_t, uint32_t> > ranges;
+            planTileRanges(tiles, &ranges);
+            for (auto & range : ranges) b.lane_rows += R / (kTileBlock / range.second) * kTileBlock;
+            b.slot_rows += R * tiles * 16;
+        }
+        for (auto & kv : buckets) {
+            const Bucket & b = kv.second;
+            std::fprintf(stderr, "[search classes]   columns <= %4u: %6llu matrices, %9.0f rows, %.3g evaluations, pairs / tile slots %.2f, tile slots / lane slots %.2f\n",
+                         kv.first, static_cast<unsigned long long>(b.matrices), b.rows, b.evals, b.evals / b.slot_rows, b.slot_rows / (16.0 * b.lane_rows));
+        }
+    }
+    show("medium", num_big, num_medium);
+    show("small", num_big + num_medium, M - num_big - num_medium);
+}
+
+unsigned long long * searchLogEvals(const PairSearchWork & w) { return reinterpret_cast<unsigned long long *>(w.d_tail.ptr + w.evals_word); }
+
+// The table part of the plan on the context's stream: every pair of its matrices by the tile kernel (or, on the sequential
+// route, pairTableKernel), the held-back stage of the matrices' collapse where the search ran in front of it, and the
+// resolving workgroups.
+hipError_t launchTablePart(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const GroupMatricesView & view, const PairSearchPlan & plan,
+                           PairSearchWork & w, const bool runs_behind_search) {
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+    hipStream_t st = ctx->stream;
+    const SearchParts parts = {w.d_part_pair.ptr, w.d_part_marg.ptr, w.d_part_opt.ptr, w.d_big_pair_part_off.ptr, w.d_big_col_part_off.ptr, plan.chunk_rows};
+    const uint32_t items = static_cast<uint32_t>(plan.item_matrix.size());
+    if (plan.pair_tiles) {
+        PairTileWork pw;
+        pw.item_matrix = w.d_item_matrix.ptr;
+        pw.item_chunk = w.d_item_chunk.ptr;
+        pw.item_tiles = w.d_item_col.ptr;
+        pw.count = items;
+        pw.g = view;
+        pw.parts = parts;
+        pw.log_evals = searchLogEvals(w);
+#ifdef RPVG_HIP_EXPERIMENTS
+        pw.debug_skip = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_DEBUG") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_DEBUG"))) : 0u;
+#endif
+        // A/B knob RPVG_HIP_PAIR_LDS_KB: more dynamic LDS than the kernel uses = fewer workgroups per CU (64: two instead of
+        // three — registers left over for the other lane's kernels while this one runs)
+        static const size_t tile_lds_bytes = []() {
+            const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_LDS_KB");
+            return std::max<size_t>(kTileLdsDoubles * sizeof(double), env ? static_cast<size_t>(std::atoi(env)) * 1024 : 0);
+        }();
+        if (tile_lds_bytes > 64 * 1024) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pairTile2Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes));
+            if (e != hipSuccess) return e;
+        }
+        // (On the device's lowest stream priority — the slots its workgroups free going to the other lane's short kernels first —
+        // the batch took 11.6 against 10.5 ms: the search is itself on its lane's critical path.  Two passes around the replay of
+        // the matrices' collapse — the matrices it leaves alone as soon as its first stages have told them apart, the others when
+        // it is done — 10.4 against 9.9 ms: the second pass's grid of mostly empty workgroups, and the replay's small kernels next
+        // to the lane's own tile kernel.)
+        const int tile_span = ctx->spanBegin(FAM_TILE, st);  // (the kernel alone: rpvg_hip_kernel_stats::search_tile_ms)
+        pairTile2Kernel<<<dim3(pw.count), dim3(kTileBlock), tile_lds_bytes, st>>>(pw);
+        ctx->spanEnd(tile_span);
+#ifdef RPVG_HIP_EXPERIMENTS
+        // (RPVG_HIP_PAIR_REPEAT=n: the same launch n more times — what a batch pays per millisecond of this kernel)
+        for (int k = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_REPEAT") ? std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_REPEAT")) : 0; k > 0; --k) {
+            pairTile2Kernel<<<dim3(pw.count), dim3(kTileBlock), tile_lds_bytes, st>>>(pw);
+        }
+#endif
+    } else {
+        TableWork tw;
+        tw.item_matrix = w.d_item_matrix.ptr;
+        tw.item_col = w.d_item_col.ptr;
+        tw.item_chunk = w.d_item_chunk.ptr;
+        tw.count = items;
+        tw.g = view;
+        tw.parts = parts;
+        tw.log_evals = searchLogEvals(w);
+        pairTableKernel<<<dim3(((tw.count + 7) / 8) * 8), dim3(256), 0, st>>>(tw);
+    }
+    if (runs_behind_search) {
+        if (groups->collapse_done) {
+            HostScope wait_scope("search: wait for the runs of the matrices' collapse");
+            ok(searchLaunchesEarly() ? hipStreamWaitEvent(st, groups->collapse_done, 0) : waitEvent(groups->collapse_done));
+        }
+        ok(groups->held_back_runs(st, &parts));
+        groups->held_back_runs = nullptr;
+    }
+
+    ResolveArgs ra;
+    ra.big_matrix = w.d_order.ptr;
+    ra.count = plan.num_big;
+    ra.g = view;
+    ra.col_off = w.d_col_off.ptr;
+    ra.col_count = w.d_col_count.ptr;
+    ra.pair_cap_off = w.d_pair_cap_off.ptr;
+    ra.parts = parts;
+    ra.min_log_likelihood_diff = w.min_log_likelihood_diff;
+    ra.log_freq = w.d_lf.ptr;
+    ra.marginal = w.d_marg.ptr;
+    ra.col_order = w.d_col_order.ptr;
+    ra.seq_value = w.d_seq.ptr;
+    ra.out_first = w.d_out_first.ptr;
+    ra.out_second = w.d_out_second.ptr;
+    ra.out_value = w.d_out_value.ptr;
+    ra.out_count = w.d_tail.ptr;
+    resolveTableKernel<<<dim3(plan.num_big), dim3(256), 0, st>>>(ra);
+    return e;
+}
+
+// The medium and the small part of the plan: the search inside one workgroup per matrix; matrices with few rows stage less
+// LDS (more workgroups per CU).  Independent of the table part and of each other: a stream each, so that the tail of one does
+// not idle the GPU (RPVG_HIP_SEARCH_STREAMS: A/B knob, 3 = one stream each next to the table part on the context's, 2 = medium
+// and small share one, 1 = everything on the context's).
+void launchSequentialParts(rpvg_hip_ctx * ctx, const GroupMatricesView & view, const PairSearchPlan & plan, PairSearchWork & w) {
+    static const int search_streams = []() {
+        const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_SEARCH_STREAMS");
+        return env ? std::max(1, std::min(3, std::atoi(env))) : 3;
+    }();
+    hipStream_t s_medium = search_streams == 1 ? ctx->stream : ctx->aux[0];
+    hipStream_t s_small = search_streams == 1 ? ctx->stream : (search_streams == 2 ? ctx->aux[0] : ctx->aux[1]);
+    SearchArgs args;
+    args.g = view;
+    args.col_off = w.d_col_off.ptr;
+    args.col_count = w.d_col_count.ptr;
+    args.pair_cap_off = w.d_pair_cap_off.ptr;
+    args.min_log_likelihood_diff = w.min_log_likelihood_diff;
+    args.log_freq = w.d_lf.ptr;
+    args.marginal = w.d_marg.ptr;
+    args.optimistic_raw = w.d_opt_raw.ptr;
+    args.optimistic = w.d_opt.ptr;
+    args.col_order = w.d_col_order.ptr;
+    args.out_first = w.d_out_first.ptr;
+    args.out_second = w.d_out_second.ptr;
+    args.out_value = w.d_out_value.ptr;
+    args.out_count = w.d_tail.ptr;
+    args.log_evals = searchLogEvals(w);
+    auto search_lds_bytes = [](uint32_t stage_rows, uint32_t row_cols) { return static_cast<size_t>((kTileFirst + 1) * stage_rows + kTileFirst * row_cols) * sizeof(double); };
+    {
+        static std::once_flag once;  // 96 KB of dynamic LDS: above the 64 KB a kernel gets without asking
+        std::call_once(once, [&]() {
+            (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&boundedSearchKernel<1024, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(search_lds_bytes(kLdsRows, kRowLdsCols)));
+        });
+    }
+    const uint32_t num_small = w.M - plan.num_big - plan.num_medium;
+    if (plan.num_medium > 0) {
+        args.order = w.d_order.ptr + plan.num_big;
+        args.count = plan.num_medium;
+        args.stage_rows = kLdsRows;
+        args.row_lds_cols = kRowLdsCols;
+        boundedSearchKernel<1024, 64><<<dim3(plan.num_medium), dim3(1024), search_lds_bytes(kLdsRows, kRowLdsCols), s_medium>>>(args);
+    }
+    if (num_small > 0) {
+        args.order = w.d_order.ptr + plan.num_big + plan.num_medium;
+        args.count = num_small;
+        args.stage_rows = kSmallRows;
+        args.row_lds_cols = kSmallRowLdsCols;
+        boundedSearchKernel<256, 16><<<dim3(num_small), dim3(256), search_lds_bytes(kSmallRows, kSmallRowLdsCols), s_small>>>(args);
+    }
+}
+
 }  // namespace
 
 namespace rpvg_hip_detail {
@@ -1186,264 +1305,80 @@ int queuePairSearch(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const ui
     std::unique_ptr<HostScope> scope(new HostScope("bounded search: host order + work items"));
     const uint32_t M = groups->num_matrices;
     w.M = M;
-    std::vector<uint64_t> & col_off = w.col_off, & pair_cap_off = w.pair_cap_off;
-    col_off.assign(M + 1, 0);
-    pair_cap_off.assign(M + 1, 0);
-    for (uint32_t m = 0; m < M; ++m) {
-        const uint64_t G = groups->h_num_cols[m];
-        col_off[m + 1] = col_off[m] + G;
-        pair_cap_off[m + 1] = pair_cap_off[m] + G * (G + 1) / 2;
-    }
+    w.min_log_likelihood_diff = std::log(min_rel_likelihood);
     // (column_counts == NULL: the matrices were built from the batch's own haplotype columns, whose multiplicities — at least one
     // haplotype each — are on the device already)
     if (!column_counts && M > 0 && !groups->d_column_counts) {
         setError("rpvg_hip_bounded_pair_posteriors: column_counts is NULL");
         return RPVG_HIP_ERR_INVALID;
     }
-    for (uint64_t c = 0; column_counts && c < col_off[M]; ++c) {
+    const uint64_t num_columns = std::accumulate(groups->h_num_cols.begin(), groups->h_num_cols.begin() + M, uint64_t(0));
+    for (uint64_t c = 0; column_counts && c < num_columns; ++c) {
         if (column_counts[c] == 0) {
             setError("rpvg_hip_bounded_pair_posteriors: column %llu has a zero count", static_cast<unsigned long long>(c));
             return RPVG_HIP_ERR_INVALID;
         }
     }
-    // expensive matrices first
-    std::vector<uint32_t> & order = w.order;
-    order.assign(M, 0);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        const double wx = static_cast<double>(groups->h_num_rows[x]) * groups->h_num_cols[x] * groups->h_num_cols[x];
-        const double wy = static_cast<double>(groups->h_num_rows[y]) * groups->h_num_cols[y] * groups->h_num_cols[y];
-        return wx != wy ? wx > wy : x < y;
-    });
-
-    // Big matrices (leading part of `order`) take the table path: every pair evaluated in parallel by
-    // (column, row chunk) workgroups, then one resolving workgroup; the rest take the in-workgroup search.
-    const uint64_t table_budget = 1ull << 28;  // doubles of partial pair sums (2 GiB)
-    // rows x columns from which a matrix takes the table path (RPVG_HIP_TABLE_MIN_WORK overrides; tests use 0)
-    double table_min_work = 65536.0;
-    if (const char * env = std::getenv("RPVG_HIP_TABLE_MIN_WORK")) table_min_work = std::atof(env);
-    if (min_rel_likelihood > 1) table_min_work = 1e300;  // positive threshold: the prefix-maximum form of the rule does not hold
-    // every pair of every matrix from LDS-staged rows, a tile of pairs per lane (pairTileKernel): the default for a
-    // threshold that is a ratio <= 1; RPVG_HIP_PAIR_TILES=0 keeps the sequential search with its table path (A/B)
-    const char * tiles_env = std::getenv("RPVG_HIP_PAIR_TILES");  // (read per call: the tests switch between the two searches)
-    const int tiles_wanted = tiles_env ? std::atoi(tiles_env) : 2;
-    const bool pair_tiles = tiles_wanted != 0 && min_rel_likelihood <= 1;
-    const bool tile_ranges = pair_tiles;  // (round 2's tile kernel, one item per chunk, went with round 5: pairTile2Kernel has two rounds of sweeps behind it)
-    // rows of a work item's chunk (RPVG_HIP_PAIR_CHUNK_ROWS: the tests cut small matrices into several chunks with it)
-    const uint32_t chunk_rows = tile_ranges && std::getenv("RPVG_HIP_PAIR_CHUNK_ROWS") ? std::max(256, std::atoi(std::getenv("RPVG_HIP_PAIR_CHUNK_ROWS"))) : kChunkRows;
-    if (pair_tiles) table_min_work = 0.0;
-    const uint32_t tile_step = kTileA;
-    uint32_t & num_big = w.num_big;
-    num_big = 0;
-    std::vector<uint64_t> big_col_part_off(M, 0), big_pair_part_off(M, 0);
-    std::vector<uint32_t> item_matrix, item_col, item_chunk;  // (item_col: with tile ranges, first tile | (tiles - 1) << 16)
-    std::vector<std::pair<uint32_t, uint32_t> > ranges;
-    uint64_t col_part_total = 0, pair_part_total = 0;
-    {
-        std::vector<uint32_t> table_matrices, others;
-        bool table_closed = false;  // (the sequential kernels' table path: a prefix of the order, as before)
-        for (uint32_t i = 0; i < M; ++i) {
-            const uint32_t m = order[i];
-            const uint64_t R = groups->h_num_rows[m], G = groups->h_num_cols[m];
-            const uint64_t chunks = (R + chunk_rows - 1) / chunk_rows;
-            const uint64_t parts = chunks;
-            const bool fits = pair_part_total + parts * G * G <= table_budget;
-            const bool takes_table = pair_tiles ? (G <= kTileMaxColumns && fits)
-                                                : (!table_closed && static_cast<double>(R) * G >= table_min_work && fits);
-            if (!takes_table) {
-                table_closed = true;
-                others.push_back(m);
-                continue;
-            }
-            table_matrices.push_back(m);
-            big_col_part_off[m] = col_part_total;
-            big_pair_part_off[m] = pair_part_total;
-            col_part_total += parts * G;
-            pair_part_total += parts * G * G;
-            if (tile_ranges) {
-                ranges.clear();
-                planTileRanges(tileCount(static_cast<uint32_t>(G)), &ranges);
-                for (uint32_t c = 0; c < chunks; ++c) {
-                    for (auto & range: ranges) {
-                        item_matrix.push_back(m);
-                        item_col.push_back(range.first | ((range.second - 1) << 16));
-                        item_chunk.push_back(c);
-                    }
-                }
-                continue;
-            }
-            for (uint32_t c = 0; c < chunks; ++c) {
-                for (uint32_t a = 0; a < (pair_tiles ? 1u : G); a += tile_step) {
-                    item_matrix.push_back(m);
-                    item_col.push_back(a);
-                    item_chunk.push_back(c);
-                }
-            }
-        }
-        num_big = static_cast<uint32_t>(table_matrices.size());
-        std::copy(table_matrices.begin(), table_matrices.end(), order.begin());
-        std::copy(others.begin(), others.end(), order.begin() + num_big);
-    }
+    w.plan = planPairSearch(groups->h_num_rows.data(), groups->h_num_cols.data(), M, min_rel_likelihood, pairSearchKnobs());
+    const PairSearchPlan & plan = w.plan;
+    if (RPVG_EXPERIMENT_ENV("RPVG_HIP_SEARCH_CLASSES")) showSearchClasses(groups, plan);
 
     scope.reset(new HostScope("bounded search: uploads + launches"));
     hipError_t e = hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
 
-    uint32_t num_medium = 0;
-    {
-        std::vector<uint32_t> medium, small;
-        for (uint32_t i = num_big; i < M; ++i) (groups->h_num_rows[order[i]] > kSmallRows ? medium : small).push_back(order[i]);
-        num_medium = static_cast<uint32_t>(medium.size());
-        std::copy(medium.begin(), medium.end(), order.begin() + num_big);
-        std::copy(small.begin(), small.end(), order.begin() + num_big + num_medium);
-    }
-
-    if (RPVG_EXPERIMENT_ENV("RPVG_HIP_SEARCH_CLASSES")) {
-        auto show = [&](const char * name, uint32_t first, uint32_t count) {
-            double evals = 0;
-            for (uint32_t i = first; i < first + count; ++i) evals += 0.5 * groups->h_num_rows[order[i]] * groups->h_num_cols[order[i]] * groups->h_num_cols[order[i]];
-            std::fprintf(stderr, "[search classes] %-6s %6u matrices, %.3g pair-row evaluations if nothing is skipped; largest:", name, count, evals);
-            for (uint32_t i = first; i < first + std::min<uint32_t>(count, 6); ++i) std::fprintf(stderr, " %llux%u", static_cast<unsigned long long>(groups->h_num_rows[order[i]]), groups->h_num_cols[order[i]]);
-            std::fprintf(stderr, "\n");
-        };
-        show("table", 0, num_big);
-        if (pair_tiles) {  // the tile kernel's lanes: how many of a workgroup's 256 carry a tile, how many of a tile's 16 slots a pair
-            struct Bucket { uint64_t matrices = 0; double rows = 0, evals = 0, lane_rows = 0, slot_rows = 0; };
-            std::map<uint32_t, Bucket> buckets;
-            for (uint32_t i = 0; i < num_big; ++i) {
-                const double R = static_cast<double>(groups->h_num_rows[order[i]]);
-                const uint32_t G = groups->h_num_cols[order[i]];
-                uint32_t key = 1;
-                while (key < G) key <<= 1;
-                Bucket & b = buckets[key];
-                const uint32_t tiles = tileCount(G);
-                b.matrices += 1;
-                b.rows += R;
-                b.evals += R * (0.5 * G * (G + 1));
-                // rows a lane walks x lanes of the workgroup, summed over the matrix's work items (planTileRanges: an item's lanes walk
-                // 1 / slices of the rows each) — until round 6 this line priced round 2's kernel, one item per chunk with
-                // tileSlices(G) slices: 0.58 for 64 columns, where the ranges of pairTile2Kernel reach 1.00
-                std::vector<std::pair<uint32_t, uint32_t> > ranges;
-                planTileRanges(tiles, &ranges);
-                for (auto & range : ranges) b.lane_rows += R / (kTileBlock / range.second) * kTileBlock;
-                b.slot_rows += R * tiles * 16;
-            }
-            for (auto & kv : buckets) {
-                const Bucket & b = kv.second;
-                std::fprintf(stderr, "[search classes]   columns <= %4u: %6llu matrices, %9.0f rows, %.3g evaluations, pairs / tile slots %.2f, tile slots / lane slots %.2f\n",
-                             kv.first, static_cast<unsigned long long>(b.matrices), b.rows, b.evals, b.evals / b.slot_rows, b.slot_rows / (16.0 * b.lane_rows));
-            }
-        }
-        show("medium", num_big, num_medium);
-        show("small", num_big + num_medium, M - num_big - num_medium);
-    }
-
-    auto & d_order = w.d_order; auto & d_col_count = w.d_col_count; auto & d_col_order = w.d_col_order;
-    auto & d_out_first = w.d_out_first; auto & d_out_second = w.d_out_second;
-    auto & d_col_off = w.d_col_off; auto & d_pair_cap_off = w.d_pair_cap_off;
-    auto & d_lf = w.d_lf; auto & d_marg = w.d_marg; auto & d_opt_raw = w.d_opt_raw; auto & d_opt = w.d_opt; auto & d_out_value = w.d_out_value;
-
     // every host array of the search in one block, one copy (UploadPack: a command per array was 1 ms per search)
     UploadPack & pack = w.pack;
-    auto & d_item_matrix = w.d_item_matrix; auto & d_item_col = w.d_item_col; auto & d_item_chunk = w.d_item_chunk;
-    auto & d_big_col_part_off = w.d_big_col_part_off; auto & d_big_pair_part_off = w.d_big_pair_part_off;
-    pack.add(d_order, order.data(), M);
-    pack.add(d_col_off, col_off.data(), M + 1);
-    pack.add(d_pair_cap_off, pair_cap_off.data(), M + 1);
-    if (column_counts) pack.add(d_col_count, column_counts, col_off[M]);
-    if (num_big > 0) {
-        pack.add(d_item_matrix, item_matrix.data(), item_matrix.size());
-        pack.add(d_item_col, item_col.data(), item_col.size());
-        pack.add(d_item_chunk, item_chunk.data(), item_chunk.size());
-        pack.add(d_big_col_part_off, big_col_part_off.data(), M);
-        pack.add(d_big_pair_part_off, big_pair_part_off.data(), M);
+    const uint64_t columns = plan.col_off[M], pair_cap = plan.pair_cap_off[M];
+    pack.add(w.d_order, plan.order.data(), M);
+    pack.add(w.d_col_off, plan.col_off.data(), M + 1);
+    pack.add(w.d_pair_cap_off, plan.pair_cap_off.data(), M + 1);
+    if (column_counts) pack.add(w.d_col_count, column_counts, columns);
+    if (plan.num_big > 0) {
+        pack.add(w.d_item_matrix, plan.item_matrix.data(), plan.item_matrix.size());
+        pack.add(w.d_item_col, plan.item_col.data(), plan.item_col.size());
+        pack.add(w.d_item_chunk, plan.item_chunk.data(), plan.item_chunk.size());
+        pack.add(w.d_big_col_part_off, plan.big_col_part_off.data(), M);
+        pack.add(w.d_big_pair_part_off, plan.big_pair_part_off.data(), M);
     }
     // [kept pairs per matrix: M words | evaluation counter: 2 words | validity flag of the build | -]: what the host reads first
-    const uint32_t evals_word = (M + 1) & ~1u, tail_words = evals_word + 4;
-    w.evals_word = evals_word;
-    w.tail_words = tail_words;
-    auto & d_tail = w.d_tail;
-    pack.addZero(d_tail, tail_words);
+    w.evals_word = (M + 1) & ~1u;
+    w.tail_words = w.evals_word + 4;
+    pack.addZero(w.d_tail, w.tail_words);
     if (w.extra_u64_count) pack.add(w.d_extra_u64, w.extra_u64, w.extra_u64_count);
     if (w.extra_zero_bytes) pack.addZero(w.d_extra_zero, w.extra_zero_bytes);
     int span = ctx->spanBegin(FAM_H2D);
     ok(pack.commit(st));
-    if (!column_counts) d_col_count.borrow(const_cast<uint32_t *>(groups->d_column_counts), col_off[M]);
+    if (!column_counts) w.d_col_count.borrow(const_cast<uint32_t *>(groups->d_column_counts), columns);
     ctx->spanEnd(span);
-    ctx->stats.h2d_bytes += static_cast<double>(M * 20 + col_off[M] * 4);
-    ok(d_lf.alloc(col_off[M]));
-    ok(d_marg.alloc(col_off[M]));
-    ok(d_opt_raw.alloc(col_off[M]));
-    ok(d_opt.alloc(col_off[M]));
-    ok(d_col_order.alloc(col_off[M]));
-    ok(d_out_first.alloc(pair_cap_off[M]));
-    ok(d_out_second.alloc(pair_cap_off[M]));
-    ok(d_out_value.alloc(pair_cap_off[M]));
-    if (e != hipSuccess) {
-        setError("rpvg_hip_bounded_pair_posteriors: %s", hipGetErrorString(e));
-        return (e == hipErrorOutOfMemory) ? RPVG_HIP_ERR_ALLOC : RPVG_HIP_ERR_RUNTIME;
+    ctx->stats.h2d_bytes += static_cast<double>(M * 20 + columns * 4);
+    ok(w.d_lf.alloc(columns));
+    ok(w.d_marg.alloc(columns));
+    ok(w.d_opt_raw.alloc(columns));
+    ok(w.d_opt.alloc(columns));
+    ok(w.d_col_order.alloc(columns));
+    ok(w.d_out_first.alloc(pair_cap));
+    ok(w.d_out_second.alloc(pair_cap));
+    ok(w.d_out_value.alloc(pair_cap));
+    if (e != hipSuccess) return searchFailed(e);
+    if (plan.num_big > 0) {
+        ok(w.d_part_marg.alloc(plan.col_part_total));
+        ok(w.d_part_opt.alloc(plan.col_part_total));
+        ok(w.d_part_pair.alloc(plan.pair_part_total));
+        ok(w.d_seq.alloc(pair_cap));
     }
+    if (e != hipSuccess) return searchFailed(e);
 
-    SearchArgs args;
-    args.order = d_order.ptr;
-    args.count = M;
-    args.mat_val_off = groups->mat_val_off.ptr;
-    args.mat_row_off = groups->mat_row_off.ptr;
-    args.mat_fast = groups->mat_fast.ptr;
-    args.mat_mid = groups->mat_mid.ptr;
-    args.mat_rows = groups->mat_rows.ptr;
-    args.mat_cols = groups->mat_cols.ptr;
-    args.values = groups->values.ptr;
-    args.rowmax = groups->rowmax.ptr;
-    args.row_count = groups->row_count.ptr;
-    args.row_noise = groups->row_noise.ptr;
-    args.col_off = d_col_off.ptr;
-    args.col_count = d_col_count.ptr;
-    args.pair_cap_off = d_pair_cap_off.ptr;
-    args.min_log_likelihood_diff = std::log(min_rel_likelihood);
-    args.log_freq = d_lf.ptr;
-    args.marginal = d_marg.ptr;
-    args.optimistic_raw = d_opt_raw.ptr;
-    args.optimistic = d_opt.ptr;
-    args.col_order = d_col_order.ptr;
-    args.out_first = d_out_first.ptr;
-    args.out_second = d_out_second.ptr;
-    args.out_value = d_out_value.ptr;
-    args.out_count = d_tail.ptr;
-
-    args.log_evals = reinterpret_cast<unsigned long long *>(d_tail.ptr + evals_word);
-    auto & d_part_marg = w.d_part_marg; auto & d_part_opt = w.d_part_opt; auto & d_part_pair = w.d_part_pair; auto & d_seq = w.d_seq;
-    if (num_big > 0) {
-        ok(d_part_marg.alloc(col_part_total));
-        ok(d_part_opt.alloc(col_part_total));
-        ok(d_part_pair.alloc(pair_part_total));
-        ok(d_seq.alloc(pair_cap_off[M]));
-    }
-    if (e != hipSuccess) {
-        setError("rpvg_hip_bounded_pair_posteriors: %s", hipGetErrorString(e));
-        return (e == hipErrorOutOfMemory) ? RPVG_HIP_ERR_ALLOC : RPVG_HIP_ERR_RUNTIME;
-    }
-
-    // the table path, the medium and the small matrices are independent: three streams, so that the
-    // tail of one does not idle the GPU
-    // streams of the medium / small kernels next to the table path on `st` (RPVG_HIP_SEARCH_STREAMS: A/B knob, 3 = one
-    // stream each, 2 = medium and small share one, 1 = everything on st)
-    static const int search_streams = []() {
-        const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_SEARCH_STREAMS");
-        return env ? std::max(1, std::min(3, std::atoi(env))) : 3;
-    }();
-    hipStream_t s_medium = search_streams == 1 ? st : ctx->aux[0];
-    hipStream_t s_small = search_streams == 1 ? st : (search_streams == 2 ? ctx->aux[0] : ctx->aux[1]);
     // The row collapse of the matrices runs on a stream of its own behind their build (rpvg_hip_groups_build): the uploads
     // above did not wait for it, the kernels do.  (Searching the matrices as built and once more the few the collapse
     // replayed was tried: its small kernels then wait for slots next to the search's large one, no gain.)
-    const bool side_kernels = M > num_big;  // the sequential kernels on the aux streams
+    const bool side_kernels = M > plan.num_big;  // the sequential kernels on the aux streams
     // Matrices whose collapse holds its last stage back (rpvg_hip_groups::held_back_runs), all of them on the table path: the tile
     // kernel reads them as built, at once — the twenty launches that find the collapse's runs (2 ms of a batch's chain of
     // kernels, for some hundred rows of three million) run beside it —, and the stage that rewrites rows comes behind both and
     // adjusts the tile kernel's sums for them.  3.8 against 4.6 ms per configs[2] batch in the pipeline.
-    const bool runs_behind_search = static_cast<bool>(groups->held_back_runs) && pair_tiles && num_big == M;
+    const bool runs_behind_search = static_cast<bool>(groups->held_back_runs) && plan.pair_tiles && plan.num_big == M;
     if (!runs_behind_search) {
         ok(groups->waitCollapse(st));
         if (groups->collapse_done && !searchLaunchesEarly()) {  // (see searchGateEnter: the thread waits, not the stream's queue)
@@ -1454,149 +1389,16 @@ int queuePairSearch(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const ui
     span = ctx->spanBegin(FAM_LOGLIK);
     searchGateEnter(ctx, st, std::accumulate(groups->h_num_rows.begin(), groups->h_num_rows.end(), uint64_t(0)));
     if (side_kernels) ok(ctx->forkAux());
-    if (num_big > 0) {
-        TableWork tw;
-        tw.item_matrix = d_item_matrix.ptr;
-        tw.item_col = d_item_col.ptr;
-        tw.item_chunk = d_item_chunk.ptr;
-        tw.count = static_cast<uint32_t>(item_matrix.size());
-        tw.mat_val_off = groups->mat_val_off.ptr;
-        tw.mat_row_off = groups->mat_row_off.ptr;
-        tw.mat_fast = groups->mat_fast.ptr;
-        tw.mat_mid = groups->mat_mid.ptr;
-        tw.mat_rows = groups->mat_rows.ptr;
-        tw.mat_cols = groups->mat_cols.ptr;
-        tw.values = groups->values.ptr;
-        tw.rowmax = groups->rowmax.ptr;
-        tw.row_count = groups->row_count.ptr;
-        tw.row_noise = groups->row_noise.ptr;
-        tw.big_col_part_off = d_big_col_part_off.ptr;
-        tw.big_pair_part_off = d_big_pair_part_off.ptr;
-        tw.part_marginal = d_part_marg.ptr;
-        tw.part_optimistic = d_part_opt.ptr;
-        tw.part_pair = d_part_pair.ptr;
-        tw.log_evals = args.log_evals;
-        if (pair_tiles) {
-            PairTileWork pw;
-            pw.item_matrix = d_item_matrix.ptr;
-            pw.item_chunk = d_item_chunk.ptr;
-            pw.item_tiles = d_item_col.ptr;
-            pw.chunk_rows = chunk_rows;
-            pw.count = tw.count;
-            pw.mat_val_off = groups->mat_val_off.ptr;
-            pw.mat_row_off = groups->mat_row_off.ptr;
-            pw.mat_fast = groups->mat_fast.ptr;
-            pw.mat_mid = groups->mat_mid.ptr;
-            pw.mat_rows = groups->mat_rows.ptr;
-            pw.mat_cols = groups->mat_cols.ptr;
-            pw.values = groups->values.ptr;
-            pw.row_count = groups->row_count.ptr;
-            pw.row_noise = groups->row_noise.ptr;
-            pw.col_part_off = d_big_col_part_off.ptr;
-            pw.pair_part_off = d_big_pair_part_off.ptr;
-            pw.part_marginal = d_part_marg.ptr;
-            pw.part_pair = d_part_pair.ptr;
-            pw.log_evals = args.log_evals;
-#ifdef RPVG_HIP_EXPERIMENTS
-            pw.debug_skip = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_DEBUG") ? static_cast<uint32_t>(std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_DEBUG"))) : 0u;
-#endif
-            // A/B knob RPVG_HIP_PAIR_LDS_KB: more dynamic LDS than the kernel uses = fewer workgroups per CU (64: two instead of
-            // three — registers left over for the other lane's kernels while this one runs)
-            static const size_t tile_lds_bytes = []() {
-                const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_LDS_KB");
-                return std::max<size_t>(kTileLdsDoubles * sizeof(double), env ? static_cast<size_t>(std::atoi(env)) * 1024 : 0);
-            }();
-            if (tile_lds_bytes > 64 * 1024) {
-                RPVG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&pairTile2Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes)));
-            }
-            // (On the device's lowest stream priority — the slots its workgroups free going to the other lane's short kernels first —
-            // the batch took 11.6 against 10.5 ms: the search is itself on its lane's critical path.  Two passes around the replay of
-            // the matrices' collapse — the matrices it leaves alone as soon as its first stages have told them apart, the others when
-            // it is done — 10.4 against 9.9 ms: the second pass's grid of mostly empty workgroups, and the replay's small kernels next
-            // to the lane's own tile kernel.)
-            const int tile_span = ctx->spanBegin(FAM_TILE, st);  // (the kernel alone: rpvg_hip_kernel_stats::search_tile_ms)
-            pairTile2Kernel<<<dim3(pw.count), dim3(kTileBlock), tile_lds_bytes, st>>>(pw);
-            ctx->spanEnd(tile_span);
-#ifdef RPVG_HIP_EXPERIMENTS
-            // (RPVG_HIP_PAIR_REPEAT=n: the same launch n more times — what a batch pays per millisecond of this kernel)
-            for (int k = RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_REPEAT") ? std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_PAIR_REPEAT")) : 0; k > 0; --k) {
-                pairTile2Kernel<<<dim3(pw.count), dim3(kTileBlock), tile_lds_bytes, st>>>(pw);
-            }
-#endif
-        } else {
-            pairTableKernel<<<dim3(((tw.count + 7) / 8) * 8), dim3(256), 0, st>>>(tw);
-        }
-        if (runs_behind_search && e == hipSuccess) {
-            if (groups->collapse_done) {
-                HostScope wait_scope("search: wait for the runs of the matrices' collapse");
-                ok(searchLaunchesEarly() ? hipStreamWaitEvent(st, groups->collapse_done, 0) : waitEvent(groups->collapse_done));
-            }
-            rpvg_hip_groups::SearchSums sums;
-            sums.part_pair = d_part_pair.ptr;
-            sums.part_marginal = d_part_marg.ptr;
-            sums.pair_part_off = d_big_pair_part_off.ptr;
-            sums.col_part_off = d_big_col_part_off.ptr;
-            sums.chunk_rows = chunk_rows;
-            ok(groups->held_back_runs(st, &sums));
-            groups->held_back_runs = nullptr;
-        }
-
-        ResolveArgs ra;
-        ra.big_matrix = d_order.ptr;
-        ra.count = num_big;
-        ra.mat_rows = groups->mat_rows.ptr;
-        ra.mat_cols = groups->mat_cols.ptr;
-        ra.chunk_rows = chunk_rows;
-        ra.col_off = d_col_off.ptr;
-        ra.col_count = d_col_count.ptr;
-        ra.pair_cap_off = d_pair_cap_off.ptr;
-        ra.big_col_part_off = d_big_col_part_off.ptr;
-        ra.big_pair_part_off = d_big_pair_part_off.ptr;
-        ra.part_marginal = d_part_marg.ptr;
-        ra.part_optimistic = d_part_opt.ptr;
-        ra.part_pair = d_part_pair.ptr;
-        ra.min_log_likelihood_diff = args.min_log_likelihood_diff;
-        ra.log_freq = d_lf.ptr;
-        ra.marginal = d_marg.ptr;
-        ra.col_order = d_col_order.ptr;
-        ra.seq_value = d_seq.ptr;
-        ra.out_first = d_out_first.ptr;
-        ra.out_second = d_out_second.ptr;
-        ra.out_value = d_out_value.ptr;
-        ra.out_count = d_tail.ptr;
-        resolveTableKernel<<<dim3(num_big), dim3(256), 0, st>>>(ra);
-    }
-    // the rest walk the search inside one workgroup; matrices with few rows stage less LDS (more
-    // workgroups per CU).  `order` is [big | medium | small], each part expensive first.
-    args.row_lds_cols = kRowLdsCols;
-    auto search_lds_bytes = [](uint32_t stage_rows, uint32_t row_cols) { return static_cast<size_t>((kTileFirst + 1) * stage_rows + kTileFirst * row_cols) * sizeof(double); };
-    {
-        static std::once_flag once;  // 96 KB of dynamic LDS: above the 64 KB a kernel gets without asking
-        std::call_once(once, [&]() {
-            (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&boundedSearchKernel<1024, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(search_lds_bytes(kLdsRows, kRowLdsCols)));
-        });
-    }
-    if (num_medium > 0) {
-        args.order = d_order.ptr + num_big;
-        args.count = num_medium;
-        args.stage_rows = kLdsRows;
-        boundedSearchKernel<1024, 64><<<dim3(num_medium), dim3(1024), search_lds_bytes(kLdsRows, kRowLdsCols), s_medium>>>(args);
-    }
-    if (M > num_big + num_medium) {
-        args.order = d_order.ptr + num_big + num_medium;
-        args.count = M - num_big - num_medium;
-        args.stage_rows = kSmallRows;
-        args.row_lds_cols = kSmallRowLdsCols;
-        boundedSearchKernel<256, 16><<<dim3(args.count), dim3(256), search_lds_bytes(kSmallRows, kSmallRowLdsCols), s_small>>>(args);
-    }
+    const GroupMatricesView view = groups->view();
+    if (plan.num_big > 0) ok(launchTablePart(ctx, groups, view, plan, w, runs_behind_search && e == hipSuccess));
+    launchSequentialParts(ctx, view, plan, w);
     if (side_kernels) ok(ctx->joinAux());
     ctx->spanEnd(span);
-    ctx->stats.loglik_launches += (num_big > 0 ? 2 : 0) + (num_medium > 0) + (M > num_big + num_medium);
+    ctx->stats.loglik_launches += (plan.num_big > 0 ? 2 : 0) + (plan.num_medium > 0) + (M > plan.num_big + plan.num_medium);
     ok(hipGetLastError());
     if (e != hipSuccess) {
-        setError("rpvg_hip_bounded_pair_posteriors: %s", hipGetErrorString(e));
         (void) hipStreamSynchronize(st);
+        searchFailed(e);
         return RPVG_HIP_ERR_RUNTIME;
     }
     return RPVG_HIP_OK;
@@ -1608,9 +1410,9 @@ void accountPairSearch(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const
                        const uint64_t kept_pairs) {
     ctx->stats.loglik_evals += static_cast<double>(log_evals);  // counted by the kernels
     for (uint32_t i = 0; i < w.M; ++i) {
-        const double G = groups->h_num_cols[w.order[i]];
+        const double G = groups->h_num_cols[w.plan.order[i]];
         ctx->stats.search_pairs_possible += G * (G + 1) / 2;
-        if (i < w.num_big) ctx->stats.search_pairs_table += G * (G + 1) / 2;
+        if (i < w.plan.num_big) ctx->stats.search_pairs_table += G * (G + 1) / 2;
     }
     ctx->stats.search_pairs_kept += static_cast<double>(kept_pairs);
 }
@@ -1653,7 +1455,7 @@ extern "C" int rpvg_hip_bounded_pair_posteriors(rpvg_hip_ctx * ctx, const rpvg_h
     hipStream_t st = ctx->stream;
     auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
     std::unique_ptr<HostScope> scope;
-    const std::vector<uint64_t> & pair_cap_off = w.pair_cap_off;
+    const std::vector<uint64_t> & pair_cap_off = w.plan.pair_cap_off;
     const uint32_t evals_word = w.evals_word, tail_words = w.tail_words;
     auto & d_tail = w.d_tail; auto & d_pair_cap_off = w.d_pair_cap_off; auto & d_out_first = w.d_out_first;
     auto & d_out_second = w.d_out_second; auto & d_out_value = w.d_out_value;
@@ -1730,8 +1532,7 @@ extern "C" int rpvg_hip_bounded_pair_posteriors(rpvg_hip_ctx * ctx, const rpvg_h
     if (host_result) pinnedFree(host_result);
     if (e != hipSuccess) {
         delete res;
-        setError("rpvg_hip_bounded_pair_posteriors: %s", hipGetErrorString(e));
-        return (e == hipErrorOutOfMemory) ? RPVG_HIP_ERR_ALLOC : RPVG_HIP_ERR_RUNTIME;
+        return searchFailed(e);
     }
     *result_out = res;
     return RPVG_HIP_OK;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rpvg_hip.h"
+#include "search_plan.hpp"
 
 namespace rpvg_hip_detail {
 
@@ -768,6 +769,41 @@ struct rpvg_hip_batch {
 // bounded_search.hip: the searches of different contexts of one device run one after the other on the device
 void searchGateForget(const rpvg_hip_ctx * ctx);
 
+// The matrices of a built rpvg_hip_groups as the kernels that read them see them: the one device-side description of their layout
+// (row_collapse.hip's MatrixArrays is the writers').  rpvg_hip_groups::view() fills it.
+struct GroupMatrix {  // matrix m: column-major values, R rows (fast rows [0, fast_end), mid rows up to mid_end: LogProduct), G columns
+    const double * values, * rowmax, * row_count, * row_noise;
+    uint64_t R, fast_end, mid_end;
+    uint32_t G;
+};
+struct GroupMatricesView {
+    const uint64_t * mat_val_off;
+    const uint64_t * mat_row_off;
+    const uint32_t * mat_fast;
+    const uint32_t * mat_mid;
+    const uint64_t * mat_rows;
+    const uint32_t * mat_cols;
+    const double * values;
+    const double * rowmax;
+    const double * row_count;
+    const double * row_noise;
+    __device__ __forceinline__ GroupMatrix matrix(const uint32_t m) const {
+        const uint64_t row_off = mat_row_off[m];
+        return {values + mat_val_off[m], rowmax + row_off, row_count + row_off, row_noise + row_off, mat_rows[m], mat_fast[m], mat_mid[m], mat_cols[m]};
+    }
+};
+
+// The per-chunk partial sums of the search's table path (pairTile2Kernel, pairTableKernel), which resolveTableKernel adds up and the
+// held-back stage of the row collapse adjusts (rpvg_hip_groups::held_back_runs)
+struct SearchParts {
+    double * part_pair = nullptr;         // [pair_part_off[m] + chunk * G * G + a * G + b], a <= b
+    double * part_marginal = nullptr;     // [col_part_off[m] + chunk * G + a]
+    double * part_optimistic = nullptr;
+    const uint64_t * pair_part_off = nullptr;
+    const uint64_t * col_part_off = nullptr;
+    uint32_t chunk_rows = 0;
+};
+
 struct rpvg_hip_groups {
     const rpvg_hip_batch * batch = nullptr;
     uint32_t num_matrices = 0;
@@ -819,14 +855,10 @@ struct rpvg_hip_groups {
     // reads the matrices as built WHILE the stages in front find the runs, and the stage that is left adjusts the search's sums
     // for the rows it rewrites (bounded_search.hip).  Every other reader gets it queued in front of its own kernels by
     // waitCollapse().  collapse_done: the stages that were queued.
-    struct SearchSums {               // the per-chunk sums of the table path (pairTile2Kernel)
-        double * part_pair = nullptr;         // [pair_part_off[m] + chunk * G * G + a * G + b], a <= b
-        double * part_marginal = nullptr;     // [col_part_off[m] + chunk * G + a]
-        const uint64_t * pair_part_off = nullptr;
-        const uint64_t * col_part_off = nullptr;
-        uint32_t chunk_rows = 0;
-    };
-    mutable std::function<hipError_t(hipStream_t, const SearchSums *)> held_back_runs;  // empty: nothing held back (any more)
+    mutable std::function<hipError_t(hipStream_t, const SearchParts *)> held_back_runs;  // empty: nothing held back (any more)
+    GroupMatricesView view() const {  // the only place that hands the buffers above to a reader
+        return {mat_val_off.ptr, mat_row_off.ptr, mat_fast.ptr, mat_mid.ptr, mat_rows.ptr, mat_cols.ptr, values.ptr, rowmax.ptr, row_count.ptr, row_noise.ptr};
+    }
     hipError_t waitCollapse(hipStream_t stream) const {
         hipError_t e = collapse_done ? hipStreamWaitEvent(stream, collapse_done, 0) : hipSuccess;
         if (e == hipSuccess && held_back_runs) {
@@ -1031,9 +1063,9 @@ void accountEmSolve(rpvg_hip_ctx * ctx, uint32_t P, const uint64_t * col_off, co
 
 // ---- the diploid search, queued (bounded_search.hip) -----------------------------------------------
 struct PairSearchWork {  // what one search leaves on the device (and the host arrays its statistics need)
-    uint32_t M = 0, num_big = 0, evals_word = 0, tail_words = 0;
-    std::vector<uint32_t> order;
-    std::vector<uint64_t> col_off, pair_cap_off;
+    uint32_t M = 0, evals_word = 0, tail_words = 0;
+    double min_log_likelihood_diff = 0;
+    rpvg_search::PairSearchPlan plan;  // order, num_big: accountPairSearch
     DeviceBuffer<uint32_t> d_order, d_col_count, d_col_order, d_out_first, d_out_second, d_item_matrix, d_item_col, d_item_chunk;
     DeviceBuffer<uint32_t> d_tail;  // [kept pairs per matrix: M words | evaluation counter: 2 words | validity flag of the build | -]
     DeviceBuffer<uint64_t> d_col_off, d_pair_cap_off, d_big_col_part_off, d_big_pair_part_off;

@@ -1222,11 +1222,7 @@ template <int GS>
 __global__ __launch_bounds__(256) void gibbsConditionalPolyKernel(const GibbsProblems pr, const GibbsHeader * __restrict__ hdr,
                                                                   const ActiveEntry * __restrict__ entries, const uint32_t * __restrict__ req_slot,
                                                                   const unsigned long long * __restrict__ memo_key,
-                                                                  const uint64_t * __restrict__ mat_val_off, const uint64_t * __restrict__ mat_row_off,
-                                                                  const uint32_t * __restrict__ mat_fast, const uint32_t * __restrict__ mat_mid,
-                                                                  const uint64_t * __restrict__ mat_rows, const uint32_t * __restrict__ mat_cols,
-                                                                  const double * __restrict__ values, const double * __restrict__ row_count,
-                                                                  const double * __restrict__ row_noise, double * __restrict__ dist) {
+                                                                  const GroupMatricesView matrices, double * __restrict__ dist) {
     constexpr int kCand = 4;
     constexpr uint32_t kBits = 64 / GS;
     constexpr unsigned long long kMask = (1ull << kBits) - 1;
@@ -1247,15 +1243,13 @@ __global__ __launch_bounds__(256) void gibbsConditionalPolyKernel(const GibbsPro
         }
         const ActiveEntry e = entries[lo];
         const uint32_t p = e.problem;
-        const uint32_t m = pr.matrix[p];
-        const uint64_t R = mat_rows[m];
-        const uint32_t G = mat_cols[m];
-        const double * M = values + mat_val_off[m];
-        const double * cnt = row_count + mat_row_off[m];
-        const double * nz = row_noise + mat_row_off[m];
+        const GroupMatrix mat = matrices.matrix(pr.matrix[p]);
+        const uint64_t R = mat.R;
+        const uint32_t G = mat.G;
+        const double * M = mat.values, * cnt = mat.row_count, * nz = mat.row_noise;
         const double * lf = pr.log_freq + pr.col_off[p];
         const uint64_t memo = pr.rec_off[p];
-        const uint64_t fast_end = mat_fast[m], mid_end = mat_mid[m];
+        const uint64_t fast_end = mat.fast_end, mid_end = mat.mid_end;
         const uint32_t other_groups = (e.count + 3) / 4;
         const uint32_t work_items = other_groups * ((G + 3) / 4);
         const uint32_t per_turn = itemsPerTurn(R);
@@ -1749,9 +1743,10 @@ struct PairVariant : GibbsRun<PairVariant> {
     }
     void queueConditionals(decltype(&gibbsConditionalKernel<2>) kernel) {  // (the tile kernel takes the same arguments)
         const int span = ctx->spanBegin(FAM_LOGLIK);
-        kernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,
-                                                       groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr,
-                                                       groups->values.ptr, groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);
+        // (these two keep their pointer lists: with the view as one parameter the compiler allocates the tile kernel's registers differently)
+        const GroupMatricesView v = groups->view();
+        kernel<<<dim3(work_blocks), dim3(256), 0, st>>>(pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, v.mat_val_off, v.mat_row_off, v.mat_fast, v.mat_mid, v.mat_rows,
+                                                       v.mat_cols, v.values, v.row_count, v.row_noise, d_dist.ptr);
         ctx->spanEnd(span);
     }
 
@@ -1865,9 +1860,7 @@ struct PolyVariant : GibbsRun<PolyVariant> {
         queueRequestOffsets(0u);
         const int span = ctx->spanBegin(FAM_LOGLIK);
         gibbsConditionalPolyKernel<W><<<dim3(work_blocks), dim3(256), 0, st>>>(
-            pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, d_memo_key.ptr, groups->mat_val_off.ptr, groups->mat_row_off.ptr,
-            groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr, groups->values.ptr,
-            groups->row_count.ptr, groups->row_noise.ptr, d_dist.ptr);
+            pr, d_hdr.ptr, d_entries.ptr, d_req.ptr, d_memo_key.ptr, groups->view(), d_dist.ptr);
         ctx->spanEnd(span);
         queueDistributions(2.0);  // (ask-ahead share 2: never — it numbers requests by the other COLUMN, which is group size 2's memo)
     }

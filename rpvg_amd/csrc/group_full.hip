@@ -48,10 +48,7 @@ template <int GS>
 __global__ __launch_bounds__(256) void groupFullKernel(
     const uint32_t num_problems, const uint64_t num_items, const uint64_t * __restrict__ prefix_off,
     const uint64_t * __restrict__ set_off, const uint64_t * __restrict__ lf_off, const uint32_t * __restrict__ req_matrix,
-    const double * __restrict__ log_freq, const FullLogPerm log_perm, const uint64_t * __restrict__ mat_val_off,
-    const uint64_t * __restrict__ mat_row_off, const uint32_t * __restrict__ mat_fast, const uint32_t * __restrict__ mat_mid,
-    const uint64_t * __restrict__ mat_rows, const uint32_t * __restrict__ mat_cols, const double * __restrict__ values,
-    const double * __restrict__ row_count, const double * __restrict__ row_noise, double * __restrict__ out) {
+    const double * __restrict__ log_freq, const FullLogPerm log_perm, const GroupMatricesView matrices, double * __restrict__ out) {
     constexpr int kPre = GS - 1;
     __shared__ LogTableEntry lt[kLogTableSize];
     loadLogTable(lt);
@@ -65,9 +62,9 @@ __global__ __launch_bounds__(256) void groupFullKernel(
         if (prefix_off[mid] <= item) lo = mid; else hi = mid - 1;
     }
     const uint32_t q = lo;
-    const uint32_t m = req_matrix[q];
-    const uint64_t R = mat_rows[m];
-    const uint32_t G = mat_cols[m];
+    const GroupMatrix mat = matrices.matrix(req_matrix[q]);
+    const uint64_t R = mat.R;
+    const uint32_t G = mat.G;
     const double divisor = static_cast<double>(GS);
 
     // the prefix: combination of kPre out of G + kPre - 1 with rank `p` (lexicographic), members = element - position
@@ -105,14 +102,12 @@ __global__ __launch_bounds__(256) void groupFullKernel(
 #pragma unroll
     for (int i = 1; i < kPre; ++i) distinct += (pre[i] != pre[i - 1]);
 
-    const double * M = values + mat_val_off[m];
-    const double * cnt = row_count + mat_row_off[m];
-    const double * nz = row_noise + mat_row_off[m];
+    const double * M = mat.values, * cnt = mat.row_count, * nz = mat.row_noise;
     const double * lf = log_freq + lf_off[q];
     const double * prefix_col[kPre > 0 ? kPre : 1];
 #pragma unroll
     for (int w = 0; w < kPre; ++w) prefix_col[w] = M + static_cast<uint64_t>(pre[w]) * R;
-    const uint64_t fast_end = mat_fast[m], mid_end = mat_mid[m];
+    const uint64_t fast_end = mat.fast_end, mid_end = mat.mid_end;
     double * dst = out + set_off[q] + rank;
 
     for (uint32_t k0 = last; k0 < G; k0 += kFullCand) {
@@ -269,9 +264,7 @@ extern "C" int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip
             span = ctx->spanBegin(FAM_LOGLIK);
 #define RPVG_LAUNCH_FULL(W)                                                                                                     \
     groupFullKernel<W><<<dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st>>>(                                              \
-        P, num_items, d_prefix_off.ptr, d_set_off.ptr, d_lf_off.ptr, d_matrix.ptr, d_lf.ptr, log_perm, groups->mat_val_off.ptr, \
-        groups->mat_row_off.ptr, groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr,         \
-        groups->values.ptr, groups->row_count.ptr, groups->row_noise.ptr, d_out.ptr)
+        P, num_items, d_prefix_off.ptr, d_set_off.ptr, d_lf_off.ptr, d_matrix.ptr, d_lf.ptr, log_perm, groups->view(), d_out.ptr)
             switch (group_size) {
                 case 1: RPVG_LAUNCH_FULL(1); break;
                 case 2: RPVG_LAUNCH_FULL(2); break;

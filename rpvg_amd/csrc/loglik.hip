@@ -760,22 +760,17 @@ __global__ __launch_bounds__(256) void zeroWideMatricesKernel(const uint32_t * _
 template <int WIDTH>
 __global__ __launch_bounds__(256) void groupLoglikKernel(
     const uint32_t num_requests, const uint32_t * __restrict__ req_matrix, const uint32_t * __restrict__ req_members,
-    const uint8_t * __restrict__ req_rowmax, const double divisor, const uint64_t * __restrict__ mat_val_off,
-    const uint64_t * __restrict__ mat_row_off, const uint32_t * __restrict__ mat_fast, const uint32_t * __restrict__ mat_mid,
-    const uint64_t * __restrict__ mat_rows, const double * __restrict__ values, const double * __restrict__ rowmax,
-    const double * __restrict__ row_count, const double * __restrict__ row_noise, double * __restrict__ out) {
+    const uint8_t * __restrict__ req_rowmax, const double divisor, const GroupMatricesView matrices, double * __restrict__ out) {
     __shared__ LogTableEntry lt[kLogTableSize];
     loadLogTable(lt);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const uint32_t q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (q >= num_requests) return;
-    const uint32_t m = req_matrix[q];
-    const uint64_t R = mat_rows[m];
-    const double * M = values + mat_val_off[m];
-    const double * cnt = row_count + mat_row_off[m];
-    const double * nz = row_noise + mat_row_off[m];
-    const double * rm = req_rowmax && req_rowmax[q] ? rowmax + mat_row_off[m] : nullptr;
+    const GroupMatrix mat = matrices.matrix(req_matrix[q]);
+    const uint64_t R = mat.R;
+    const double * M = mat.values, * cnt = mat.row_count, * nz = mat.row_noise;
+    const double * rm = req_rowmax && req_rowmax[q] ? mat.rowmax : nullptr;
     const double * col[WIDTH];
 #pragma unroll
     for (int w = 0; w < WIDTH; ++w) {
@@ -790,7 +785,7 @@ __global__ __launch_bounds__(256) void groupLoglikKernel(
         if (rm) v += rm[i] / divisor;
         return v;
     };
-    const double acc = waveSumF64(sumCountLogs<uint64_t>(lt, cnt, x, 0, mat_fast[m], mat_mid[m], R, lane));
+    const double acc = waveSumF64(sumCountLogs<uint64_t>(lt, cnt, x, 0, mat.fast_end, mat.mid_end, R, lane));
     if (lane == 0) out[q] = acc;
 }
 
@@ -802,10 +797,7 @@ template <int WIDTH>
 __global__ __launch_bounds__(256) void groupConditionalKernel(
     const uint32_t num_requests, const uint64_t num_items, const uint64_t * __restrict__ item_off,
     const uint64_t * __restrict__ out_off, const uint32_t * __restrict__ req_matrix,
-    const uint32_t * __restrict__ req_others, const double divisor, const uint64_t * __restrict__ mat_val_off,
-    const uint64_t * __restrict__ mat_row_off, const uint32_t * __restrict__ mat_fast, const uint32_t * __restrict__ mat_mid,
-    const uint64_t * __restrict__ mat_rows, const uint32_t * __restrict__ mat_cols, const double * __restrict__ values, const double * __restrict__ row_count,
-    const double * __restrict__ row_noise, double * __restrict__ out) {
+    const uint32_t * __restrict__ req_others, const double divisor, const GroupMatricesView matrices, double * __restrict__ out) {
     constexpr int kCand = 4;
     __shared__ LogTableEntry lt[kLogTableSize];
     loadLogTable(lt);
@@ -819,13 +811,11 @@ __global__ __launch_bounds__(256) void groupConditionalKernel(
         if (item_off[mid] <= item) lo = mid; else hi = mid - 1;
     }
     const uint32_t q = lo;
-    const uint32_t m = req_matrix[q];
-    const uint64_t R = mat_rows[m];
-    const uint32_t G = mat_cols[m];
+    const GroupMatrix mat = matrices.matrix(req_matrix[q]);
+    const uint64_t R = mat.R;
+    const uint32_t G = mat.G;
     const uint32_t k0 = static_cast<uint32_t>(item - item_off[q]) * kCand;
-    const double * M = values + mat_val_off[m];
-    const double * cnt = row_count + mat_row_off[m];
-    const double * nz = row_noise + mat_row_off[m];
+    const double * M = mat.values, * cnt = mat.row_count, * nz = mat.row_noise;
     const double * other[WIDTH > 1 ? WIDTH - 1 : 1];
 #pragma unroll
     for (int w = 0; w + 1 < WIDTH; ++w) other[w] = M + static_cast<uint64_t>(req_others[static_cast<uint64_t>(q) * (WIDTH - 1) + w]) * R;
@@ -834,7 +824,7 @@ __global__ __launch_bounds__(256) void groupConditionalKernel(
     for (int c = 0; c < kCand; ++c) cand[c] = M + static_cast<uint64_t>(min(k0 + c, G - 1)) * R;
     double acc[kCand] = {0.0, 0.0, 0.0, 0.0};
     LogProduct pr[kCand];
-    const uint64_t fast_end = mat_fast[m], mid_end = mat_mid[m];
+    const uint64_t fast_end = mat.fast_end, mid_end = mat.mid_end;
     auto x = [&](const uint64_t i, double (&xs)[kCand]) {
         double base = nz[i];
 #pragma unroll
@@ -1436,10 +1426,7 @@ extern "C" int rpvg_hip_group_loglik(rpvg_hip_ctx * ctx, const rpvg_hip_groups *
     const uint32_t blocks = (num_requests + 3) / 4;
     span = ctx->spanBegin(FAM_LOGLIK);
 #define RPVG_LAUNCH_LOGLIK(W)                                                                                              \
-    groupLoglikKernel<W><<<dim3(blocks), dim3(256), 0, st>>>(num_requests, d_matrix.ptr, d_members.ptr, d_flag.ptr, divisor, \
-                                                            groups->mat_val_off.ptr, groups->mat_row_off.ptr,               \
-                                                            groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->values.ptr, \
-                                                            groups->rowmax.ptr, groups->row_count.ptr, groups->row_noise.ptr, d_out.ptr)
+    groupLoglikKernel<W><<<dim3(blocks), dim3(256), 0, st>>>(num_requests, d_matrix.ptr, d_members.ptr, d_flag.ptr, divisor, groups->view(), d_out.ptr)
     switch (width) {
         case 1: RPVG_LAUNCH_LOGLIK(1); break;
         case 2: RPVG_LAUNCH_LOGLIK(2); break;
@@ -1507,10 +1494,7 @@ extern "C" int rpvg_hip_group_conditionals(rpvg_hip_ctx * ctx, const rpvg_hip_gr
     span = ctx->spanBegin(FAM_LOGLIK);
 #define RPVG_LAUNCH_COND(W)                                                                                                  \
     groupConditionalKernel<W><<<dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st>>>(                                    \
-        num_requests, num_items, d_item_off.ptr, d_out_off.ptr, d_matrix.ptr, d_others.ptr, divisor, groups->mat_val_off.ptr, \
-        groups->mat_row_off.ptr, groups->mat_fast.ptr, groups->mat_mid.ptr, groups->mat_rows.ptr, groups->mat_cols.ptr,      \
-        groups->values.ptr,                                                                                                  \
-        groups->row_count.ptr, groups->row_noise.ptr, d_out.ptr)
+        num_requests, num_items, d_item_off.ptr, d_out_off.ptr, d_matrix.ptr, d_others.ptr, divisor, groups->view(), d_out.ptr)
     switch (width) {
         case 1: RPVG_LAUNCH_COND(1); break;
         case 2: RPVG_LAUNCH_COND(2); break;

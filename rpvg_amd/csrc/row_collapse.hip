@@ -593,11 +593,7 @@ struct ReplayArgs {
     bool no_lds_tables;          // RPVG_HIP_COLLAPSE_NO_LDS_TABLES (A/B): pair tables read from global memory as in round 3
     // group matrices whose diploid search ran on the values as built (rpvg_hip_groups::held_back_runs): its sums, to be adjusted
     // for every row the runs rewrite; part_pair == NULL: nobody has read the matrices yet
-    double * part_pair;
-    double * part_marginal;
-    const uint64_t * pair_part_off;
-    const uint64_t * col_part_off;
-    uint32_t chunk_rows;
+    SearchParts sums;
     uint32_t * rewritten_count;  // [M] rows of the matrix's list that take the values of a head (listRewrittenRows)
     bool walk_only;              // collapseRunsKernel stops behind the runs (collapseAdjustSumsKernel and collapseRewriteKernel follow)
 };
@@ -927,8 +923,8 @@ __device__ void adjustSearchSums(const ReplayArgs<MatrixArrays> & a, const uint3
     __shared__ double stage_noise[2 * kStageRows], stage_count[kStageRows];
     __shared__ uint32_t stage_chunk[kStageRows];
     const uint32_t rows_per_stage = G <= kStageDoubles / 2 ? min(kStageRows, kStageDoubles / (2 * G)) : 0u;
-    double * pairs = a.part_pair + a.pair_part_off[m];
-    double * singles = a.part_marginal + a.col_part_off[m];
+    double * pairs = a.sums.part_pair + a.sums.pair_part_off[m];
+    double * singles = a.sums.part_marginal + a.sums.col_part_off[m];
     const double * cnt = a.g.row_count + r0;
     // count * log(after / before): after / before - 1 is tiny for rows within prob_precision of each other unless the values
     // themselves are — the series then, the logarithm otherwise
@@ -948,7 +944,7 @@ __device__ void adjustSearchSums(const ReplayArgs<MatrixArrays> & a, const uint3
         if (threadIdx.x < rows) {
             const uint64_t q = rewritten[i0 + threadIdx.x];
             const uint32_t dst = order[q], src = order[head_of[q]];
-            stage_chunk[threadIdx.x] = dst / a.chunk_rows;
+            stage_chunk[threadIdx.x] = dst / a.sums.chunk_rows;
             stage_noise[2 * threadIdx.x] = nz[dst];
             stage_noise[2 * threadIdx.x + 1] = nz[src];
             stage_count[threadIdx.x] = cnt[dst];
@@ -1710,7 +1706,7 @@ template <typename Arrays>
 hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const uint64_t total_rows, const double precision, const uint64_t * key,
                                const uint32_t * row, const uint32_t * segment_begin, const uint32_t * segment_end, const bool segmented, DeviceBuffer<uint32_t> & info, double * rowmax, uint32_t * mat_fast,
                                uint32_t * mat_mid, CollapseTemporaries * tmp, hipStream_t st, const SegmentSortPlan * plan = nullptr, hipEvent_t sorted = nullptr,
-                               std::function<hipError_t(hipStream_t, const rpvg_hip_groups::SearchSums *)> * held_back_runs = nullptr) {
+                               std::function<hipError_t(hipStream_t, const SearchParts *)> * held_back_runs = nullptr) {
     hipError_t e = hipSuccess;
     auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
     // zeroed words: the pair table's byte counter (8 bytes, first: aligned), matrix flags [M], replay list [M] + its
@@ -1900,11 +1896,7 @@ hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const ui
     collapseRankKernel<Arrays><<<dim3(staged_grid), dim3(256), 0, st>>>(r);
     collapseSortKernel<Arrays><<<dim3(std::min<uint32_t>(M, 32)), dim3(kSortThreads), 0, st>>>(r);
     collapseBetweenKernel<Arrays><<<dim3(2 * staged_grid), dim3(kBetweenThreads), 0, st>>>(r);
-    r.part_pair = nullptr;
-    r.part_marginal = nullptr;
-    r.pair_part_off = nullptr;
-    r.col_part_off = nullptr;
-    r.chunk_rows = 0;
+    r.sums = SearchParts();
     r.rewritten_count = nullptr;
     r.walk_only = false;
     if (held_back_runs) {
@@ -1916,14 +1908,10 @@ hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const ui
         r.rewritten_count = tmp->rewritten_count.ptr;
         r.walk_only = true;
         collapseRunsKernel<Arrays><<<dim3(staged_grid), dim3(256), 0, st>>>(r);
-        *held_back_runs = [=](hipStream_t on, const rpvg_hip_groups::SearchSums * sums) {
+        *held_back_runs = [=](hipStream_t on, const SearchParts * sums) {
             ReplayArgs<Arrays> mine = r;
             if (sums) {  // the search has read the matrices as built: its sums, then the rows
-                mine.part_pair = sums->part_pair;
-                mine.part_marginal = sums->part_marginal;
-                mine.pair_part_off = sums->pair_part_off;
-                mine.col_part_off = sums->col_part_off;
-                mine.chunk_rows = sums->chunk_rows;
+                mine.sums = *sums;
                 launchAdjustAndRewrite(mine, staged_grid, on);
             } else {
                 launchRewrite(mine, staged_grid, on);

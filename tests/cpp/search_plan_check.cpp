@@ -1,0 +1,213 @@
+// The host plan of the diploid search (rpvg_amd/csrc/search_plan.hpp) on the CPU: every decision of planPairSearch checked
+// against its specification, restated here, at the smallest sizes where one flips.  Prints "ok".
+//   g++ -std=c++17 -I rpvg_amd/csrc tests/cpp/search_plan_check.cpp
+#include "search_plan.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+
+using namespace rpvg_search;
+
+#define REQUIRE(cond)                                                                            \
+    do {                                                                                         \
+        if (!(cond)) {                                                                           \
+            std::fprintf(stderr, "%s:%d: case '%s': %s\n", __FILE__, __LINE__, g_case, #cond);   \
+            std::exit(1);                                                                        \
+        }                                                                                        \
+    } while (0)
+
+static const char * g_case = "";
+
+struct Batch {
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> cols;
+    void add(const uint64_t R, const uint32_t G) { rows.push_back(R); cols.push_back(G); }
+};
+
+static double cost(const Batch & b, const uint32_t m) { return static_cast<double>(b.rows[m]) * b.cols[m] * b.cols[m]; }
+
+static void checkPlan(const char * name, const Batch & b, const double min_rel_likelihood, const PairSearchKnobs & knobs) {
+    g_case = name;
+    const uint32_t M = static_cast<uint32_t>(b.rows.size());
+    const PairSearchPlan p = planPairSearch(b.rows.data(), b.cols.data(), M, min_rel_likelihood, knobs);
+    const bool tiles = knobs.tiles_wanted != 0 && min_rel_likelihood <= 1;
+    const uint32_t chunk_rows = tiles ? knobs.chunk_rows : 1024u;
+    REQUIRE(p.pair_tiles == tiles);
+    REQUIRE(p.chunk_rows == chunk_rows);
+    auto chunksOf = [&](const uint32_t m) { return (b.rows[m] + chunk_rows - 1) / chunk_rows; };
+
+    // a permutation in three parts, each expensive first and ties by index
+    REQUIRE(p.order.size() == M);
+    REQUIRE(p.num_big <= M && p.num_medium <= M - p.num_big);
+    std::vector<int> seen(M, 0);
+    for (const uint32_t m : p.order) {
+        REQUIRE(m < M);
+        REQUIRE(seen[m]++ == 0);
+    }
+    const uint32_t part_begin[4] = {0, p.num_big, p.num_big + p.num_medium, M};
+    for (int part = 0; part < 3; ++part) {
+        for (uint32_t i = part_begin[part]; i + 1 < part_begin[part + 1]; ++i) {
+            const uint32_t x = p.order[i], y = p.order[i + 1];
+            REQUIRE(cost(b, x) > cost(b, y) || (cost(b, x) == cost(b, y) && x < y));
+        }
+    }
+    for (uint32_t i = p.num_big; i < M; ++i) REQUIRE((b.rows[p.order[i]] > 512) == (i < p.num_big + p.num_medium));
+
+    // prefix sums of G and of G (G + 1) / 2
+    REQUIRE(p.col_off.size() == M + 1 && p.pair_cap_off.size() == M + 1);
+    REQUIRE(p.col_off[0] == 0 && p.pair_cap_off[0] == 0);
+    for (uint32_t m = 0; m < M; ++m) {
+        const uint64_t G = b.cols[m];
+        REQUIRE(p.col_off[m + 1] - p.col_off[m] == G);
+        REQUIRE(p.pair_cap_off[m + 1] - p.pair_cap_off[m] == G * (G + 1) / 2);
+    }
+
+    // the cost order of the whole batch, and which of its matrices the table part must hold
+    std::vector<uint32_t> by_cost(M);
+    for (uint32_t m = 0; m < M; ++m) by_cost[m] = m;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t x, uint32_t y) { return cost(b, x) > cost(b, y); });
+    std::vector<uint32_t> expected_table;
+    {
+        uint64_t used = 0;
+        const double min_work = min_rel_likelihood > 1 ? 1e300 : knobs.table_min_work;
+        for (const uint32_t m : by_cost) {
+            const uint64_t need = chunksOf(m) * b.cols[m] * b.cols[m];
+            const bool fits = used + need <= (1ull << 28);
+            if (tiles) {
+                if (!(b.cols[m] <= 1024 && fits)) continue;  // every matrix that fits: a later, smaller one too
+            } else {
+                if (!(static_cast<double>(b.rows[m]) * b.cols[m] >= min_work && fits)) break;  // a prefix of the cost order
+            }
+            expected_table.push_back(m);
+            used += need;
+        }
+    }
+    REQUIRE(p.num_big == expected_table.size());
+    for (uint32_t i = 0; i < p.num_big; ++i) REQUIRE(p.order[i] == expected_table[i]);
+    if (min_rel_likelihood > 1) REQUIRE(p.num_big == 0 && p.item_matrix.empty());
+
+    // offsets of the partial sums: running sums of chunks G and chunks G^2 in the table part's order, inside the budget
+    REQUIRE(p.big_col_part_off.size() == M && p.big_pair_part_off.size() == M);
+    uint64_t col_run = 0, pair_run = 0;
+    for (uint32_t i = 0; i < p.num_big; ++i) {
+        const uint32_t m = p.order[i];
+        REQUIRE(p.big_col_part_off[m] == col_run && p.big_pair_part_off[m] == pair_run);
+        col_run += chunksOf(m) * b.cols[m];
+        pair_run += chunksOf(m) * b.cols[m] * b.cols[m];
+    }
+    for (uint32_t i = p.num_big; i < M; ++i) REQUIRE(p.big_col_part_off[p.order[i]] == 0 && p.big_pair_part_off[p.order[i]] == 0);
+    REQUIRE(p.col_part_total == col_run && p.pair_part_total == pair_run);
+    REQUIRE(p.pair_part_total <= (1ull << 28));
+
+    // the work items: every (chunk, tile) or (chunk, step of kTileA columns) of a table matrix exactly once, nothing else
+    REQUIRE(p.item_col.size() == p.item_matrix.size() && p.item_chunk.size() == p.item_matrix.size());
+    std::map<std::pair<uint32_t, uint32_t>, std::vector<int> > covered;  // (matrix, chunk) -> units
+    std::vector<int> in_table(M, 0);
+    for (uint32_t i = 0; i < p.num_big; ++i) in_table[p.order[i]] = 1;
+    uint64_t units_expected = 0;
+    for (uint32_t i = 0; i < p.num_big; ++i) {
+        const uint32_t m = p.order[i], G = b.cols[m];
+        const uint32_t units = tiles ? ((G + 3) / 4) * ((G + 3) / 4 + 1) / 2 : (G + 3) / 4;
+        units_expected += units * chunksOf(m);
+    }
+    uint64_t units_seen = 0;
+    for (size_t i = 0; i < p.item_matrix.size(); ++i) {
+        const uint32_t m = p.item_matrix[i], c = p.item_chunk[i], G = b.cols[m];
+        REQUIRE(m < M && in_table[m]);
+        REQUIRE(c < chunksOf(m));
+        const uint32_t units = tiles ? ((G + 3) / 4) * ((G + 3) / 4 + 1) / 2 : (G + 3) / 4;
+        std::vector<int> & u = covered[std::make_pair(m, c)];
+        u.resize(units, 0);
+        if (tiles) {
+            const uint32_t t0 = p.item_col[i] & 0xffffu, count = (p.item_col[i] >> 16) + 1;
+            REQUIRE(count <= 256 && t0 + count <= units);
+            for (uint32_t t = t0; t < t0 + count; ++t) REQUIRE(u[t]++ == 0);
+            units_seen += count;
+        } else {
+            const uint32_t a = p.item_col[i];
+            REQUIRE(a % 4 == 0 && a < G);
+            REQUIRE(u[a / 4]++ == 0);
+            units_seen += 1;
+        }
+    }
+    REQUIRE(units_seen == units_expected);  // (no unit twice and as many as there are: every unit once)
+}
+
+static void checkRanges(const uint32_t tiles, const std::vector<std::pair<uint32_t, uint32_t> > & expected) {
+    std::vector<std::pair<uint32_t, uint32_t> > ranges;
+    planTileRanges(tiles, &ranges);
+    REQUIRE(ranges == expected);
+}
+
+int main() {
+    // the ranges of a matrix's tiles, worked out by hand
+    g_case = "ranges";
+    REQUIRE(tileCount(64) == 136 && tileCount(100) == 325 && tileColumns(1) == 1 && tileColumns(5) == 2);
+    checkRanges(136, {{0, 128}, {128, 8}});
+    checkRanges(325, {{0, 256}, {256, 64}, {320, 5}});
+
+    // every width against every height, and equal costs (rows x columns^2) twice: the sizes of an earlier matrix, and other sizes
+    Batch grid;
+    for (const uint32_t G : {1u, 4u, 5u, 64u, 100u, 1024u, 1025u})
+        for (const uint64_t R : {1ull, 512ull, 513ull, 1024ull, 1025ull}) grid.add(R, G);
+    grid.add(513, 64);   // the same sizes as an earlier matrix
+    grid.add(2052, 32);  // 2052 x 32^2 = 513 x 64^2: equal cost, other sizes
+    // a set whose partial pair sums cross the budget in the middle: 2^26 doubles each, the fifth does not fit
+    Batch full;
+    for (int i = 0; i < 5; ++i) full.add(65536, 1024);
+    full.add(2000, 64);
+    full.add(300, 12);
+    // ... and one where a smaller matrix fits behind one that did not
+    Batch crossing;
+    for (int i = 0; i < 3; ++i) crossing.add(65536, 1024);
+    crossing.add(60000, 1024);
+    crossing.add(50000, 1024);
+    crossing.add(2000, 64);
+    crossing.add(300, 1100);
+    Batch empty;
+
+    for (const Batch * b : {&grid, &full, &crossing, &empty}) {
+        for (const uint32_t chunk_rows : {256u, 1024u}) {
+            PairSearchKnobs knobs;
+            knobs.chunk_rows = chunk_rows;
+            checkPlan("tiles", *b, 1.0, knobs);
+            checkPlan("tiles, small ratio", *b, 1e-3, knobs);
+            checkPlan("ratio 1.5", *b, 1.5, knobs);
+            knobs.tiles_wanted = 0;
+            for (const double min_work : {0.0, 65536.0, 1e300}) {
+                knobs.table_min_work = min_work;
+                checkPlan("sequential", *b, 1.0, knobs);
+                checkPlan("sequential, ratio 1.5", *b, 1.5, knobs);
+            }
+        }
+    }
+
+    // the shapes themselves, spelled out once
+    {
+        g_case = "crossing, spelled out";
+        const PairSearchPlan p = planPairSearch(crossing.rows.data(), crossing.cols.data(), 7, 1.0, PairSearchKnobs());
+        REQUIRE(p.num_big == 5 && p.num_medium == 1);
+        REQUIRE((p.order == std::vector<uint32_t>{0, 1, 2, 3, 5, 4, 6}));
+        PairSearchKnobs sequential;
+        sequential.tiles_wanted = 0;
+        sequential.table_min_work = 0;
+        const PairSearchPlan q = planPairSearch(crossing.rows.data(), crossing.cols.data(), 7, 1.0, sequential);
+        REQUIRE(q.num_big == 4 && q.num_medium == 2);
+        REQUIRE((q.order == std::vector<uint32_t>{0, 1, 2, 3, 4, 5, 6}));
+        g_case = "full, spelled out";
+        const PairSearchPlan f = planPairSearch(full.rows.data(), full.cols.data(), 7, 1.0, PairSearchKnobs());
+        REQUIRE(f.num_big == 4 && f.pair_part_total == (1ull << 28) && f.num_medium == 2);
+        g_case = "items of 64 and 100 columns";
+        Batch two;
+        two.add(1500, 64);
+        two.add(700, 100);
+        const PairSearchPlan t = planPairSearch(two.rows.data(), two.cols.data(), 2, 1.0, PairSearchKnobs());
+        // 100 columns first (700 x 100^2 > 1500 x 64^2): one chunk of three ranges, then two chunks of two ranges
+        REQUIRE((t.item_matrix == std::vector<uint32_t>{1, 1, 1, 0, 0, 0, 0}));
+        REQUIRE((t.item_chunk == std::vector<uint32_t>{0, 0, 0, 0, 0, 1, 1}));
+        REQUIRE((t.item_col == std::vector<uint32_t>{0u | 255u << 16, 256u | 63u << 16, 320u | 4u << 16, 0u | 127u << 16, 128u | 7u << 16, 0u | 127u << 16, 128u | 7u << 16}));
+    }
+    std::printf("ok\n");
+    return 0;
+}

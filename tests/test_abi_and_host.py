@@ -185,6 +185,20 @@ def test_restated_random_streams_equal_libstdcxx():
     assert subprocess.run([binary], capture_output=True, text=True, check=True).stdout.strip() == "ok"
 
 
+def test_search_plan_decisions_at_their_edges():
+    """rpvg_amd/csrc/search_plan.hpp, the host plan of the diploid search — cost order, table / medium / small split, tile ranges per
+    chunk, offsets of the partial sums under their budget — against its specification at the sizes where a decision flips
+    (tests/cpp/search_plan_check.cpp): plain C++, no GPU."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = os.path.join(root, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    binary = os.path.join(out_dir, "search_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(root, "rpvg_amd", "csrc"),
+                           os.path.join(root, "tests", "cpp", "search_plan_check.cpp"), "-o", binary])
+    assert subprocess.run([binary], capture_output=True, text=True, check=True).stdout.strip() == "ok"
+
+
 def test_generator_states_read_and_written_in_place_equal_the_standard_interface():
     """The host side of the device sampler takes a generator's next 624 outputs from its state array and sets the state it goes
     on from (path_estimator.cpp, GeneratorLayout) instead of copying the generator, calling it 624 times and seeding it: the same

@@ -690,6 +690,35 @@ def test_bounded_search_with_more_columns_than_the_lds_rows_hold(hip_ctx, n_path
     assert small_cases.rel_close(got[0][1], post, rel=1e-9, floor=1e-300)
 
 
+def test_bounded_search_with_table_and_side_kernels_in_one_batch(hip_ctx):
+    """One default search whose plan has both parts (0 < table matrices < all): 1 100 columns are too wide for the tiles and take the
+    small sequential kernel on a side stream, while 12 columns x three chunks of rows and the [9, 7, 8] cluster take the tile
+    kernel and the resolving workgroups."""
+    rng = np.random.default_rng(961)
+    clusters = [small_cases.make_cluster(rng, 1, [1100], n_haps=1100, n_reads=600),
+                small_cases.make_cluster(rng, 1, [12], n_haps=12, n_reads=9000),
+                small_cases.make_cluster(rng, 3, [9, 7, 8], n_haps=40, n_reads=600)]
+    dev = hip_ctx.upload(ClusterBatch.from_clusters(clusters))
+    groups, mult = [], []
+    for cl in clusters:
+        g, m = np_oracle.source_groups(cl["paths"])
+        groups.append(g)
+        mult.append(m)
+    dg = hip_ctx.groups(dev, [0, 1, 2], groups, True)
+    got = dg.bounded_pair_posteriors(np.concatenate(mult), 1e-3)
+    shapes = []
+    for m, cl in enumerate(clusters):
+        M, noise, counts = np_oracle.grouped_matrix(cl["rows"], groups[m])
+        M = np_oracle.add_noise_and_normalize(M, noise)[:, :-1]
+        shapes.append(M.shape)
+        sets, post = pyoracle.group_posteriors(M, noise, counts, mult[m], 2, bounded=True, min_rel_lik=1e-3)
+        assert got[m][0] == sets
+        assert small_cases.rel_close(got[m][1], post, rel=1e-9, floor=1e-300)
+    assert shapes[0][1] == 1100 and shapes[0][0] <= 512
+    assert shapes[1][1] == 12 and 2048 < shapes[1][0] <= 3072
+    assert shapes[2][1] <= 1024
+
+
 def test_groups_with_a_path_outside_the_cluster_are_reported_by_the_first_consumer(hip_ctx):
     """rpvg_hip_groups_build returns with its kernels queued; the validity flag they set surfaces at the first use."""
     from rpvg_amd import hip
