@@ -469,7 +469,13 @@ void rpvg_hip_subset_em_free(rpvg_hip_subset_em * result);
 /* For every listed cluster: the read-path cover and path weights of MinimumPathAbundanceEstimator::estimate
  * (src/path_abundance_estimator.cpp:233-257) and the greedy weightedMinimumPathCover (:297-340) on the GPU.
  * cover[cover_off[i] .. cover_off[i] + cover_size[i]) receives the ascending cover of clusters[i];
- * the range cover_off[i+1] - cover_off[i] must hold the cluster's number of paths. */
+ * the range cover_off[i+1] - cover_off[i] must hold the cluster's number of paths (it may be larger: the cells behind
+ * cover_size[i] are left as they are).  A cluster may be listed more than once: every entry of `clusters` is a problem
+ * of its own.  The weight of a path is the sum of its terms in ascending row order, as the reference adds them: paths
+ * with the same rows and probabilities tie exactly and the lower index is taken; two calls give the same covers.
+ * A cluster may have at most 9600 paths (two vectors of doubles per path in LDS); a call that lists a larger one fails
+ * with RPVG_HIP_ERR_INVALID before anything is launched.  A cluster of one path has the cover {0}; a cluster none of
+ * whose rows count (noise probability 1) has the empty cover. */
 int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters,
                             const uint32_t * clusters, const uint64_t * cover_off, uint32_t * cover, uint32_t * cover_size);
 

@@ -669,11 +669,12 @@ class Context:
             at_n, at_a = at_n + k, at_a + k * w
         return out
 
-    def min_path_cover(self, batch: DeviceBatch, clusters: Sequence[int]) -> List[List[int]]:
+    def min_path_cover(self, batch: DeviceBatch, clusters: Sequence[int], extra: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """The ascending cover of every listed cluster; extra[i]: cells of listing i's output range beyond the cluster's paths."""
         cl = np.ascontiguousarray(clusters, dtype=np.uint32)
         n_paths = [int(batch.host.cluster_path_off[k + 1] - batch.host.cluster_path_off[k]) for k in clusters]
         off = np.zeros(len(cl) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum(n_paths)
+        off[1:] = np.cumsum(n_paths if extra is None else [n + int(x) for n, x in zip(n_paths, extra)])
         cover = np.zeros(int(off[-1]), dtype=np.uint32)
         size = np.zeros(len(cl), dtype=np.uint32)
         _check(lib().rpvg_hip_min_path_cover(self.handle, batch.handle, C.c_uint32(len(cl)), C.c_void_p(cl.ctypes.data),
