@@ -146,6 +146,29 @@ int main() {
     REQUIRE(tileCount(64) == 136 && tileCount(100) == 325 && tileColumns(1) == 1 && tileColumns(5) == 2);
     checkRanges(136, {{0, 128}, {128, 8}});
     checkRanges(325, {{0, 256}, {256, 64}, {320, 5}});
+    // the column counts of tests/pair_search_cases.py: 65 columns are 153 tiles = 128 + 25, 85 and 88 one item of 253 tiles in one slice
+    // (three idle lanes), 89 and 92 the first matrices with an item of 256 tiles, 1 024 the widest: 128 items of 256 and one of 128
+    REQUIRE(tileCount(61) == 136 && tileCount(65) == 153 && tileCount(85) == 253 && tileCount(88) == 253 && tileCount(89) == 276 && tileCount(92) == 276);
+    checkRanges(1, {{0, 1}});
+    checkRanges(6, {{0, 6}});
+    checkRanges(153, {{0, 128}, {128, 25}});
+    checkRanges(253, {{0, 253}});
+    checkRanges(276, {{0, 256}, {256, 20}});
+    {
+        std::vector<std::pair<uint32_t, uint32_t> > widest;
+        planTileRanges(tileCount(kTileMaxColumns), &widest);
+        REQUIRE(tileCount(kTileMaxColumns) == 32896 && widest.size() == 129 && widest.back() == std::make_pair(32768u, 128u));
+        for (const auto & range : widest) REQUIRE(range.first <= 0xffffu && range.second - 1 <= 0xffffu);  // 16 bits each in an item's word
+    }
+    // rows of a staged block: every switch of the menu, at the numbers of columns (multiples of four) on both sides of it
+    g_case = "rows of a staged block";
+    REQUIRE(tileSubRows(4) == 126 && tileSubRows(20) == 126 && tileSubRows(24) == 94 && tileSubRows(28) == 94 && tileSubRows(32) == 46);
+    REQUIRE(tileSubRows(64) == 46 && tileSubRows(68) == 30 && tileSubRows(96) == 30 && tileSubRows(100) == 14);
+    REQUIRE(tileSubRows(208) == 14 && tileSubRows(212) == 6 && tileSubRows(468) == 6 && tileSubRows(472) == 2 && tileSubRows(1024) == 2);
+    for (uint32_t ncols = 4; ncols <= kTileMaxColumns; ncols += 4) {  // even, and the block with its noise and counts fits a buffer
+        const uint32_t rows = tileSubRows(ncols);
+        REQUIRE(rows % 2 == 0 && (ncols + 2) * rows + ncols / 2 <= kTile2BufferDoubles);
+    }
 
     // every width against every height, and equal costs (rows x columns^2) twice: the sizes of an earlier matrix, and other sizes
     Batch grid;
