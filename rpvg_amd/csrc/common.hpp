@@ -20,6 +20,7 @@
 
 #include "../../include/rpvg_hip.h"
 #include "search_plan.hpp"
+#include "em_plan.hpp"
 
 namespace rpvg_hip_detail {
 
@@ -881,6 +882,7 @@ struct rpvg_hip_groups {
 };
 
 namespace rpvg_hip_detail {
+using namespace rpvg_em;  // the size rule and the plan of a solve (em_plan.hpp)
 // ---- EM solves on problem lists in device memory (em_sparse.hip) -------------------------------------
 // The problems may come from the host (rpvg_hip_em_solve) or be written by kernels (subset_em.hip: the path subsets the
 // diploid search retains): everything behind the list — compaction of the problems' rows, size bins, work queues, the EM
@@ -923,14 +925,58 @@ struct EmFusedDense {
     double * matrix;
     uint64_t ld;
 };
-constexpr int kEmMaxFusedDense = 4;
-constexpr uint32_t kEmDenseMaxCols = 2048;   // em_dense.hip: a row in the registers of one workgroup
-// the dense matrix is the smaller representation (8 B per cell against 12 B per entry + 20 B per row) and a row is narrow enough
-__host__ __device__ inline bool emDenseRule(const uint32_t columns, const uint32_t rows, const uint32_t entries) {
-    if (columns > kEmDenseMaxCols || columns < 2) return false;
-    const uint64_t ld = (static_cast<uint64_t>(columns) + 1) & ~1ull;
-    return 8ull * rows * ld <= 12ull * entries + 20ull * rows;
-}
+// (kEmMaxFusedDense, emDenseRule: em_plan.hpp)
+
+// The compacted per-problem CSR of a solve as every reader sees it: the one description of its layout.  EmSolveWork::view()
+// fills it; the fill kernels of em_sparse.hip write the arrays (problem p at slots(p)), everybody else reads a
+// problem through rows(p).  Every problem owns one slot more than its rows in prow_off, so its offsets start at
+// prow_off + row_base[p] + p, and they are relative to ent_base[p] — a rule that lives in at() and nowhere else.
+template <typename U32, typename F64>
+struct EmProblemRowsT {
+    U32 * off;        // [rows + 1] offsets of the rows' entries in col / val
+    F64 * count;      // [rows] read counts
+    F64 * noise;      // [rows]
+    U32 * col;        // column of every entry
+    F64 * val;        // P / rowsum * (1 - noise)
+    uint32_t rows;    // kept rows
+};
+typedef EmProblemRowsT<const uint32_t, const double> EmProblemRows;
+struct EmProblemsView {
+    const uint64_t * col_off = nullptr;      // [P+1] columns (paths) of the problems
+    const uint64_t * row_base = nullptr;     // [P] first compacted row of the problem
+    const uint64_t * ent_base = nullptr;     // [P] first compacted entry of the problem
+    uint32_t * kept_rows = nullptr;          // [P]
+    double * zero_mass = nullptr;            // [P] read mass of the rows without a selected path
+    double * total_mass = nullptr;           // [P] read count of the problem's cluster
+    uint32_t * prow_off = nullptr;           // [rows_total + P]; null: a counting pass, no storage
+    double * prow_count = nullptr;
+    const double * merged_count = nullptr;      // read counts after the row collapse (row_collapse.hip), for the problems with ...
+    const uint32_t * problem_merged = nullptr;  // ... this flag; both null: no collapse
+    double * prow_noise = nullptr;
+    uint32_t * pent_col = nullptr;
+    double * pent_val = nullptr;
+
+    // problem p of a solve whose bases and kept rows the caller holds (the host: em_grid.hip); merged: the collapse merged rows of
+    // it, so its read counts are the merged ones (a row whose count moved to its run head has none left and takes no part)
+    __host__ __device__ __forceinline__ EmProblemRows at(const uint32_t p, const uint64_t rb, const uint64_t eb, const uint32_t rows, const bool merged) const {
+        // (the order of the test, and the test of merged_count itself, are what keeps the EM kernels' registers: profiles/em_problems_view)
+        return {prow_off + rb + p, (merged_count && merged ? merged_count : prow_count) + rb, prow_noise + rb, pent_col + eb, pent_val + eb, rows};
+    }
+    __device__ __forceinline__ EmProblemRows rows(const uint32_t p) const { return at(p, row_base[p], ent_base[p], kept_rows[p], false); }
+    __device__ __forceinline__ EmProblemRows mergedRows(const uint32_t p) const {
+        return at(p, row_base[p], ent_base[p], kept_rows[p], problem_merged != nullptr && problem_merged[p] != 0);
+    }
+    // for the kernels that write problem p: where its offsets, rows and entries start in prow_off, prow_count / prow_noise and
+    // pent_col / pent_val (indices, not pointers: the fill kernels have no registers to spare for five more addresses)
+    struct Slots {
+        uint64_t off, row, ent;
+    };
+    __device__ __forceinline__ Slots slots(const uint32_t p) const {
+        const uint64_t rb = row_base[p];
+        return {rb + p, rb, ent_base[p]};
+    }
+    __device__ __forceinline__ uint32_t paths(const uint32_t p) const { return static_cast<uint32_t>(col_off[p + 1] - col_off[p]); }
+};
 
 struct EmSolveWork {  // scratch of one solve: lives until its kernels are done
     DeviceBuffer<uint32_t> d_prow_off, d_pent_col, d_bucket, d_order, d_seg_rows, d_seg_entries;
@@ -938,14 +984,29 @@ struct EmSolveWork {  // scratch of one solve: lives until its kernels are done
     DeviceBuffer<unsigned long long> d_wide_off;
     DeviceBuffer<unsigned char> d_queues;
     unsigned char * zeroed_queues = nullptr;  // set by a caller that provides the (zeroed) work queues itself: emQueuesBytes()
-    // row collapse of the problems (row_collapse.hip) and the second EM pass over the problems it merged rows in
+    // row collapse of the problems (row_collapse.hip)
     std::shared_ptr<void> collapse;
-    DeviceBuffer<unsigned char> d_queues_merged;
     // dense matrices the compaction wrote itself (queueEmSolve)
     DeviceBuffer<double> fused_matrix[kEmMaxFusedDense];
     EmFusedDense fused[kEmMaxFusedDense];
     uint32_t num_fused = 0;
     hipEvent_t filled = nullptr, collapsed = nullptr, collapse_sorted = nullptr;
+    // the only place that hands the buffers above to a reader (the collapse adds its merged counts: queueEmCollapse)
+    EmProblemsView view(const EmProblemList & list, const EmOutputs & out) const {
+        EmProblemsView v;
+        v.col_off = list.d_col_off;
+        v.row_base = list.d_row_base;
+        v.ent_base = list.d_ent_base;
+        v.kept_rows = out.d_kept_rows;
+        v.zero_mass = d_zero.ptr;
+        v.total_mass = out.d_total;
+        v.prow_off = d_prow_off.ptr;
+        v.prow_count = d_prow_count.ptr;
+        v.prow_noise = d_prow_noise.ptr;
+        v.pent_col = d_pent_col.ptr;
+        v.pent_val = d_pent_val.ptr;
+        return v;
+    }
     ~EmSolveWork() {
         if (filled) (void) hipEventDestroy(filled);
         if (collapsed) (void) hipEventDestroy(collapsed);
@@ -979,12 +1040,7 @@ struct EmGridProblem {
 
 // device arrays of the solve the problems belong to
 struct EmGridStorage {
-    const uint32_t * prow_off;
-    const double * prow_count;
-    const double * merged_count;  // NULL: no collapse
-    const double * prow_noise;
-    const uint32_t * pent_col;
-    const double * pent_val;
+    EmProblemsView problems;
     double * abundances;
     double * noise_count;
     uint32_t * iterations;
@@ -1017,15 +1073,7 @@ struct GibbsGridProblem {
 };
 // device arrays of the call the problems belong to ([P] arrays are indexed by GibbsGridProblem::problem)
 struct GibbsGridStorage {
-    const uint64_t * row_base;
-    const uint64_t * ent_base;
-    const uint32_t * prow_off;
-    const double * prow_count;
-    const double * prow_noise;
-    const uint32_t * pent_col;
-    const double * pent_val;
-    const double * zero_mass;
-    const double * total_mass;
+    EmProblemsView problems;
     const double * init_abundances;
     const double * init_noise_count;
     double * noise_samples;
@@ -1055,9 +1103,35 @@ struct DenseEmRun {
 };
 int emDenseIterate(rpvg_hip_ctx * ctx, const char * who, DenseEmRun & run);
 
+// Everything between a problem list in device memory and its EM results, queued on the context's streams.
 // collapse_precision > 0: readCollapseProbabilityMatrix on the rows of every problem (prob_precision of the reference)
 int queueEmSolve(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const EmProblemList & list, uint32_t max_em_its,
-                 double max_rel_em_conv, const EmOutputs & out, EmSolveWork & work, bool fill_only, double collapse_precision = 0.0);
+                 double max_rel_em_conv, const EmOutputs & out, EmSolveWork & work, double collapse_precision = 0.0);
+// The first stage of a solve alone: the compacted CSR of the problems in `work` (and their size bins counted in its work queues),
+// queued on the context's stream — what the read-count sampler needs of a solve (gibbs_counts.hip).  fused_look: the host looks
+// for problems of the grid bin whose dense matrix the compaction writes itself (a solve's plan says when).  build_span: the
+// FAM_BUILD span of the launches, which the caller closes.
+EmSolveKnobs emSolveKnobs();  // the environment of a solve, read in this one function
+int queueEmFill(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const EmProblemList & list, const EmOutputs & out, EmSolveWork & work,
+                const EmSolveKnobs & knobs, const EmFillPlan & plan, bool fused_look, int & build_span);
+EmSolveShape emSolveShape(const rpvg_hip_ctx * ctx, const EmProblemList & list, bool collapse_wanted);
+
+// The problems of an rpvg_hip_em_solve / rpvg_hip_gibbs_read_counts call: validated, uploaded, and laid out.
+struct HostProblemSet {
+    EmProblemList list;
+    EmSolveWork work;
+    DeviceBuffer<uint32_t> d_cluster, d_col_path, d_item_problem;
+    DeviceBuffer<uint64_t> d_col_off, d_row_base, d_ent_base, d_seg_first;
+    UploadPack uploads;
+    uint64_t n_cols_total = 0;
+};
+// Caller holds ctx->mutex and has set the device.  Validates the problems and uploads their description; the storage of a
+// problem starts where that of the problems before it ends at the most (a problem keeps at most the rows and entries of
+// its cluster) — offsets the host knows, so one kernel counts and fills.  When that bound does not fit the memory the
+// call may use (RPVG_HIP_EM_BOUND_BYTES, at most two fifths of the free device memory), a counting pass comes first and the
+// storage is exact.
+int prepareHostProblems(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_em_problems * problems,
+                        HostProblemSet & ps, const EmOutputs & out, const char * who);
 void accountEmSolve(rpvg_hip_ctx * ctx, uint32_t P, const uint64_t * col_off, const uint32_t * kept_rows, const uint32_t * kept_entries,
                     const uint32_t * iterations);
 
@@ -1087,15 +1161,7 @@ struct CsrCollapseInput {  // the compacted CSR of a solve's problems (em_sparse
     uint32_t num_problems_bound = 0;
     const uint32_t * num_problems_dev = nullptr;
     uint64_t rows_capacity = 0;
-    const uint64_t * row_base = nullptr;
-    const uint64_t * ent_base = nullptr;
-    const uint32_t * kept_rows = nullptr;
-    const uint64_t * col_off = nullptr;
-    const uint32_t * prow_off = nullptr;
-    const double * prow_count = nullptr;
-    const double * prow_noise = nullptr;
-    const uint32_t * pent_col = nullptr;
-    const double * pent_val = nullptr;
+    EmProblemsView problems;
     // the work items of the fill (EmProblemList): problem p has items seg_first[p] .. seg_first[p + 1], of segment_rows row slots each
     uint32_t num_items_bound = 0;
     const uint32_t * num_items_dev = nullptr;

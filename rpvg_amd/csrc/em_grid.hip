@@ -329,11 +329,7 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
     for (uint32_t i = 0; i < count; ++i) {
         const EmGridProblem & d = problems[i];
         const uint32_t p = d.problem, C = d.columns, rows = d.rows;
-        const uint32_t * off = storage.prow_off + d.row_base + p;
-        const double * cnt = ((d.merged && storage.merged_count) ? storage.merged_count : storage.prow_count) + d.row_base;
-        const double * nz = storage.prow_noise + d.row_base;
-        const uint32_t * col = storage.pent_col + d.ent_base;
-        const double * val = storage.pent_val + d.ent_base;
+        const EmProblemRows csr = storage.problems.at(p, d.row_base, d.ent_base, rows, d.merged != 0);
         double * out_abundances = storage.abundances + d.col_begin;
 
         const uint64_t dense_ld = (static_cast<uint64_t>(C) + 1) & ~1ull;
@@ -350,7 +346,7 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
                 hipError_t build_error = hipMemsetAsync(d_matrix.ptr, 0, sizeof(double) * rows * ld, st);
                 const uint32_t build_grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(rows) + 3) / 4, static_cast<uint64_t>(cus) * 16));
                 if (build_error == hipSuccess) {
-                    emGridDenseBuildKernel<<<dim3(std::max(1u, build_grid)), dim3(kGridBlock), 0, st>>>(rows, C, ld, off, nz, col, val, d_matrix.ptr);
+                    emGridDenseBuildKernel<<<dim3(std::max(1u, build_grid)), dim3(kGridBlock), 0, st>>>(rows, C, ld, csr.off, csr.noise, csr.col, csr.val, d_matrix.ptr);
                     build_error = hipGetLastError();
                 }
                 ctx->spanEnd(span);  // (closed on the error path too)
@@ -362,7 +358,7 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
             run.num_rows = rows;
             run.num_cols = C;
             run.ld = ld;
-            run.counts = cnt;
+            run.counts = csr.count;
             run.total_count = d.total_mass;
             run.zero_mass = d.zero_mass;
             run.max_em_its = max_em_its;
@@ -449,11 +445,12 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
         if (err != hipSuccess) return err;
         // src/path_abundance_estimator.cpp:54 — 1 / float(C), widened
         gridFillKernel<<<dim3((C + 255) / 256), dim3(256), 0, r.stream>>>(r.d_a.ptr, C, static_cast<double>(1.0f / static_cast<float>(C)));
-        r.aa.off = storage.prow_off + d.row_base + p;
-        r.aa.cnt = ((d.merged && storage.merged_count) ? storage.merged_count : storage.prow_count) + d.row_base;
-        r.aa.nz = storage.prow_noise + d.row_base;
-        r.aa.col = storage.pent_col + d.ent_base;
-        r.aa.val = storage.pent_val + d.ent_base;
+        const EmProblemRows csr = storage.problems.at(p, d.row_base, d.ent_base, rows, d.merged != 0);
+        r.aa.off = csr.off;
+        r.aa.cnt = csr.count;
+        r.aa.nz = csr.noise;
+        r.aa.col = csr.col;
+        r.aa.val = csr.val;
         r.aa.rows = rows;
         r.aa.C = C;
         r.aa.rows_per_block = rows_per_block;

@@ -1,6 +1,6 @@
 // Read-count Gibbs problems too wide or too large for one workgroup: every iteration runs over the whole GPU (gfx950).
 //
-// rpvg_hip_gibbs_read_counts puts every problem on ONE workgroup (em_sparse.hip, gibbsReadCountKernel): right for the
+// rpvg_hip_gibbs_read_counts puts every problem on ONE workgroup (gibbs_counts.hip, gibbsReadCountKernel): right for the
 // thousands of small problems of a batch; a problem whose columns do not fit that kernel's LDS, or whose kept rows + entries
 // reach gibbsGridMinWork() (em_grid.hip), comes here — the sampler's counterpart of em_grid.hip.  gibbsReadCountSampler
 // (src/path_abundance_estimator.cpp:116-212) per Gibbs iteration: every row's reads are split multinomially over its columns
@@ -82,6 +82,8 @@ __device__ __forceinline__ double gridTotal(const double * partials, const uint3
 struct GibbsSplitArgs {
     uint32_t problem, C, rows, rows_per_block, iteration;
     uint64_t seed;
+    // (the arrays of the EmProblemsView this kernel reads, member by member: with the view as one member the kernel's SGPR spills
+    // moved; csrOf() below puts them back into a view)
     const uint64_t * row_base;
     const uint64_t * ent_base;
     const uint32_t * prow_off;
@@ -114,19 +116,25 @@ __global__ __launch_bounds__(kGibbsBlock) void gibbsGridSplitKernel(const GibbsS
     unsigned long long * noise_word = LDS_COLS ? c_lds + noise_col : c_lds;
 
     const uint32_t p = args.problem;
-    const uint64_t rb = args.row_base[p], eb = args.ent_base[p];
-    const uint32_t * off = args.prow_off + rb + p;
-    const double * cnt = args.prow_count + rb;
-    const double * nzv = args.prow_noise + rb;
-    const uint32_t * col = args.pent_col + eb;
-    const double * val = args.pent_val + eb;
+    EmProblemsView view;
+    view.prow_off = const_cast<uint32_t *>(args.prow_off);
+    view.prow_count = const_cast<double *>(args.prow_count);
+    view.prow_noise = const_cast<double *>(args.prow_noise);
+    view.pent_col = const_cast<uint32_t *>(args.pent_col);
+    view.pent_val = const_cast<double *>(args.pent_val);
+    const EmProblemRows csr = view.at(p, args.row_base[p], args.ent_base[p], args.rows, false);
+    const uint32_t * off = csr.off;
+    const double * cnt = csr.count;
+    const double * nzv = csr.noise;
+    const uint32_t * col = csr.col;
+    const double * val = csr.val;
     const uint32_t r0 = blockIdx.x * args.rows_per_block;
     const uint32_t r1 = min(args.rows, r0 + args.rows_per_block);
     const double a_noise = a[noise_col];
     unsigned long long to_noise = 0;
 
     if (LANES == 1) {
-        // a thread per row: the loop of gibbsReadCountKernel (em_sparse.hip)
+        // a thread per row: the loop of gibbsReadCountKernel (gibbs_counts.hip)
         for (uint32_t r = r0 + threadIdx.x; r < r1; r += kGibbsBlock) {
             const uint32_t e0 = off[r], e1 = off[r + 1];
             double s = nzv[r] * a_noise;
@@ -370,13 +378,13 @@ int runGibbsGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const GibbsGridProb
         sa.rows_per_block = rows_per_block;
         sa.iteration = 0;
         sa.seed = d.seed;
-        sa.row_base = storage.row_base;
-        sa.ent_base = storage.ent_base;
-        sa.prow_off = storage.prow_off;
-        sa.prow_count = storage.prow_count;
-        sa.prow_noise = storage.prow_noise;
-        sa.pent_col = storage.pent_col;
-        sa.pent_val = storage.pent_val;
+        sa.row_base = storage.problems.row_base;
+        sa.ent_base = storage.problems.ent_base;
+        sa.prow_off = storage.problems.prow_off;
+        sa.prow_count = storage.problems.prow_count;
+        sa.prow_noise = storage.problems.prow_noise;
+        sa.pent_col = storage.problems.pent_col;
+        sa.pent_val = storage.problems.pent_val;
         sa.g = d_g.ptr;
         sa.counts = d_counts.ptr;
         GibbsUpdateArgs ua;
@@ -385,7 +393,7 @@ int runGibbsGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const GibbsGridProb
         ua.iteration = 0;
         ua.seed = d.seed;
         ua.gamma = gamma;
-        ua.zero_mass = storage.zero_mass;
+        ua.zero_mass = storage.problems.zero_mass;
         ua.counts = d_counts.ptr;
         ua.g = d_g.ptr;
         ua.partials = d_partials.ptr;
@@ -394,7 +402,7 @@ int runGibbsGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const GibbsGridProb
         ra.C = C;
         ra.num_partials = num_partials;
         ra.recorded = 0;
-        ra.total_mass = storage.total_mass;
+        ra.total_mass = storage.problems.total_mass;
         ra.g = d_g.ptr;
         ra.partials = d_partials.ptr;
         ra.abundance_out = storage.abundance_samples + d.abund_sample_off;
@@ -403,7 +411,7 @@ int runGibbsGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const GibbsGridProb
 
         const int span = ctx->spanBegin(FAM_EM_SPARSE, st);
         gibbsGridInitKernel<<<dim3(num_partials), dim3(kGibbsBlock), 0, st>>>(d.problem, C, num_partials, storage.init_abundances + d.col_begin, storage.init_noise_count,
-                                                                             storage.total_mass, storage.zero_mass, d_g.ptr, d_counts.ptr, d_partials.ptr);
+                                                                             storage.problems.total_mass, storage.problems.zero_mass, d_g.ptr, d_counts.ptr, d_partials.ptr);
         for (uint32_t it = 1; it <= num_its; ++it) {
             sa.iteration = ua.iteration = it;
             if (row_lanes == 1) {

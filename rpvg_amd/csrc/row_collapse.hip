@@ -257,34 +257,26 @@ struct MatrixArrays {
 // the EM problems of a solve as "matrices": problem p's rows sit at row_base[p] (the layout by the bound: there are unused
 // row slots between the problems, whose sort keys carry a matrix index no problem has)
 struct CsrArrays {
-    const uint64_t * row_base;     // [P]
-    const uint64_t * ent_base;     // [P]
-    const uint32_t * kept_rows;    // [P]
-    const uint64_t * col_off;      // [P+1]
-    const uint32_t * prow_off;     // [rows + P]
-    const double * prow_count;
-    const double * prow_noise;
-    const uint32_t * pent_col;
-    const double * pent_val;
+    EmProblemsView problems;       // (as filled: without the merged counts, which this collapse writes)
     const uint64_t * zero_pattern; // [rows]
     double * merged_count;         // [rows] read counts after the merges (written for the problems with a replay)
     uint32_t * problem_merged;     // [P] 1: rows of the problem were merged
     uint32_t * merged_problems;    // [0]: their number
     typedef CsrView View;
     static constexpr int kHashBits = kCsrCellHashBits;  // stretches: rows of equal cells (rowsSameCells), kept together by a hash of them in the key
-    __device__ __forceinline__ uint64_t rowOffset(const uint32_t p) const { return row_base[p]; }
-    __device__ __forceinline__ uint64_t numRows(const uint32_t p) const { return kept_rows[p]; }
-    __device__ __forceinline__ uint32_t numCols(const uint32_t p) const { return static_cast<uint32_t>(col_off[p + 1] - col_off[p]); }
+    __device__ __forceinline__ uint64_t rowOffset(const uint32_t p) const { return problems.row_base[p]; }
+    __device__ __forceinline__ uint64_t numRows(const uint32_t p) const { return problems.kept_rows[p]; }
+    __device__ __forceinline__ uint32_t numCols(const uint32_t p) const { return problems.paths(p); }
     __device__ __forceinline__ CsrView view(const uint32_t p) const {
         CsrView mv;
-        const uint64_t rb = row_base[p], eb = ent_base[p];
-        mv.off = prow_off + rb + p;
-        mv.col = pent_col + eb;
-        mv.val = pent_val + eb;
-        mv.noise = prow_noise + rb;
-        mv.count = prow_count + rb;
-        mv.pattern = zero_pattern + rb;
-        mv.R = kept_rows[p];
+        const EmProblemRows csr = problems.rows(p);
+        mv.off = csr.off;
+        mv.col = csr.col;
+        mv.val = csr.val;
+        mv.noise = csr.noise;
+        mv.count = csr.count;
+        mv.pattern = zero_pattern + problems.row_base[p];
+        mv.R = csr.rows;
         mv.G = numCols(p);
         return mv;
     }
@@ -1075,7 +1067,7 @@ __device__ __forceinline__ void finishRuns(const ReplayArgs<CsrArrays> & a, cons
     const uint64_t r0 = a.g.rowOffset(p);
     const uint64_t R = a.g.numRows(p);
     double * merged = a.g.merged_count + r0;
-    const double * count = a.g.prow_count + r0;
+    const double * count = a.g.problems.rows(p).count;
     uint8_t * joined = a.barrier + r0;  // (free again: the runs are known) by list position: 1 = a head that rows joined
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, num_waves = blockDim.x >> 6;
     if (threadIdx.x == 0) any_merge = 0, members_total = 0;
@@ -1948,8 +1940,8 @@ __global__ __launch_bounds__(256) void csrCollapseKeysKernel(const CsrArrays g, 
         const uint64_t s = item - seg_first[p];
         const bool last = item + 1 == seg_first[p + 1];
         const CsrView mv = g.view(p);
-        const uint64_t r0 = g.row_base[p];
-        const uint64_t slots = (p + 1 < P ? g.row_base[p + 1] : r0 + mv.R) - r0;
+        const uint64_t r0 = g.rowOffset(p);
+        const uint64_t slots = (p + 1 < P ? g.rowOffset(p + 1) : r0 + mv.R) - r0;
         if (s == 0 && threadIdx.x == 0 && segment_begin) {
             segment_begin[p] = static_cast<uint32_t>(r0);
             segment_end[p] = static_cast<uint32_t>(r0 + mv.R);
@@ -1988,7 +1980,7 @@ __global__ __launch_bounds__(256) void csrCollapseKeysKernel(const CsrArrays g, 
         for (uint64_t p = P + thread; p < num_problems_bound; p += threads) segment_begin[p] = segment_end[p] = 0;
     }
     // the tail behind the last problem (everything, if there is no problem)
-    const uint64_t from = P == 0 ? 0 : g.row_base[P - 1] + g.kept_rows[P - 1];
+    const uint64_t from = P == 0 ? 0 : g.rowOffset(P - 1) + g.numRows(P - 1);
     for (uint64_t r = from + thread; r < total_rows; r += threads) {
         key[r] = unused;
         row[r] = static_cast<uint32_t>(r);
@@ -2065,15 +2057,7 @@ hipError_t rpvg_hip_detail::queueCsrCollapse(rpvg_hip_ctx * ctx, const CsrCollap
     if (e != hipSuccess) return e;
     ok(zeroAsync(work.problem_merged.ptr, (P + 1) * sizeof(uint32_t), st));
     CsrArrays arrays;
-    arrays.row_base = in.row_base;
-    arrays.ent_base = in.ent_base;
-    arrays.kept_rows = in.kept_rows;
-    arrays.col_off = in.col_off;
-    arrays.prow_off = in.prow_off;
-    arrays.prow_count = in.prow_count;
-    arrays.prow_noise = in.prow_noise;
-    arrays.pent_col = in.pent_col;
-    arrays.pent_val = in.pent_val;
+    arrays.problems = in.problems;
     arrays.zero_pattern = tmp->csr_pattern.ptr;
     arrays.merged_count = work.merged_count.ptr;
     arrays.problem_merged = work.problem_merged.ptr;

@@ -1052,7 +1052,7 @@ static int nestedSubsetEmAttempt(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batc
     EmSolveWork work;
     work.zeroed_queues = search.d_extra_zero.ptr + header_room;
     if (e == hipSuccess) {
-        rc = queueEmSolve(ctx, batch, list, max_em_its, max_rel_em_conv, out, work, false, collapse_precision);
+        rc = queueEmSolve(ctx, batch, list, max_em_its, max_rel_em_conv, out, work, collapse_precision);
         if (rc != RPVG_HIP_OK) {
             (void) hipStreamSynchronize(st);
             (void) hipEventDestroy(header_here);

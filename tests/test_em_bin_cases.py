@@ -1,6 +1,10 @@
 """The table of EM size-bin edges (tests/em_bin_cases.py) checked without a GPU: every case lands in the bin it names by
 the Python restatement of emBinOf, every named boundary has a case on each side, one unit apart, and the kept rows of
-every case are pairwise farther apart than prob_precision."""
+every case are pairwise farther apart than prob_precision.  The C++ rule itself (rpvg_amd/csrc/em_plan.hpp) is compiled with g++
+and held to the same restatement, shape by shape, and its plan of a solve to expectations at the sizes where a decision flips."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -97,3 +101,51 @@ def test_fill_workgroups_switch_maps_between_subsets_of_one_cluster(cus):
     assert len(lanes) == 4 and all(len({problems[p][0] for p in seq}) == 1 for seq in lanes)
     # the grid-stride restated on a small list: problem 0 has five segments, the others one; G = min(10, 8)
     assert ebc.fill_sequences([5000, 1, 1, 1, 1, 1], 1) == [[0, 4], [0, 5], [0], [0], [0], [1], [2], [3]]
+
+
+def _em_plan_check():
+    """tests/cpp/em_plan_check.cpp compiled against rpvg_amd/csrc/em_plan.hpp alone: plain C++17, no GPU."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = os.path.join(root, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    binary = os.path.join(out_dir, "em_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(root, "rpvg_amd", "csrc"),
+                           os.path.join(root, "tests", "cpp", "em_plan_check.cpp"), "-o", binary])
+    return binary
+
+
+def test_em_plan_decisions_at_their_edges():
+    """The plan of a solve — grid gate, mid-size move, fused look, grids per CU, LDS per variant, the launch tables with their
+    streams for one and five register launches —, the sampler's route and the storage layout, at the sizes where each flips."""
+    assert subprocess.run([_em_plan_check()], capture_output=True, text=True, check=True).stdout.strip() == "ok"
+
+
+def test_cpp_rule_equals_the_python_restatement():
+    """emBinOf, the mid-size predicate, emDenseRule, the route inside a call and the statistics slots of em_plan.hpp — the code
+    the device and the host run — against em_bin, is_mid, dense_rule, routes and expected_stats, for the shape of every case,
+    the fillers of every bin, the eight and the nine mid-size problems in one call, and the byte limits of the LDS formulas."""
+    calls = [[c.shape()] for c in ebc.CASES]
+    calls += [[f.shape() for f in ebc.fillers(b)] for b in (0, 1, 7) + ebc.REGISTER_BINS]
+    mids = [ebc.BY_NAME[n].shape() for n in ebc.MID_COUNT_CASES]
+    calls += [mids[:8], mids]
+    calls += [[(C, 10, 10)] for C in (1173, 1174, 3992, 3993, 3994)]
+    calls += [[(C, 4096, ebc.GRID_MIN_WORK - 4096)] for C in (3993, 3994)]
+    calls.append([s for call in calls for s in call])   # and everything in one call (more than eight mid-size problems: none moves)
+    text = "".join("".join(f"{C} {rows} {entries}\n" for C, rows, entries in call) + "-\n" for call in calls)
+    out = subprocess.run([_em_plan_check(), "shapes"], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+    at = 0
+    for call in calls:
+        got = [tuple(int(x) for x in out[at + i].split()) for i in range(len(call))]
+        assert out[at + len(call)] == "-"
+        at += len(call) + 1
+        want_routes = ebc.routes(call)
+        for s, g, route in zip(call, got, want_routes):
+            assert g[:4] == (ebc.em_bin(*s), int(ebc.is_mid(*s)), int(ebc.dense_rule(*s)), route), (s, g)
+        for launches, column in ((1, 4), (5, 5)):
+            slots = {}
+            for g in got:
+                slots[g[column]] = slots.get(g[column], 0) + 1
+            want_slots, want_dense = ebc.expected_stats(call, launches)
+            assert slots == want_slots, (call[:3], launches)
+            assert sum(1 for g in got if g[3] == ebc.GRID_BIN and g[2]) == want_dense
+    assert at == len(out) - 1 and out[-1] == ""

@@ -906,6 +906,22 @@ def test_em_problem_sets_in_two_passes_when_the_storage_bound_is_over_budget(hip
     assert small_cases.rel_close(one_pass[1], two_pass[1], rel=1e-12, floor=1e-12)
     for a, b in zip(one_pass[0], two_pass[0]):
         assert small_cases.rel_close(a, b, rel=1e-12, floor=1e-12)  # (LDS atomics: the last bits are run-dependent)
+    # the read-count sampler compacts the problems through the same first stage of a solve, counting pass included: from the
+    # one-pass EM result it draws the same samples on the layout by the bound and on the exact one
+    def draw():
+        return hip_ctx.gibbs_read_counts(dev, owners, columns, one_pass[0], one_pass[1], [24] * len(problems),
+                                         [7001 + p for p in range(len(problems))], 2)
+    by_bound = draw()
+    os.environ["RPVG_HIP_EM_BOUND_BYTES"] = "1"
+    try:
+        exact = draw()
+    finally:
+        os.environ.pop("RPVG_HIP_EM_BOUND_BYTES", None)
+    assert len(by_bound) == len(exact) == len(problems)
+    for (noise_a, abund_a), (noise_b, abund_b) in zip(by_bound, exact):
+        assert noise_a.shape == noise_b.shape == (24,) and abund_a.shape == abund_b.shape
+        assert small_cases.rel_close(noise_a, noise_b, rel=1e-12, floor=1e-12)
+        assert small_cases.rel_close(abund_a.ravel(), abund_b.ravel(), rel=1e-12, floor=1e-12)
 
 
 # ---- the Gibbs sampler of the group posteriors on the device (rpvg_hip_group_gibbs) ---------------------------------
