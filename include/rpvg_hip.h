@@ -26,6 +26,7 @@
 
 #include "rpvg_batch.h"
 #include "rpvg_rows.h"
+#include "rpvg_index.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -533,6 +534,37 @@ int rpvg_hip_effective_lengths(rpvg_hip_ctx * ctx, double loc, double scale, dou
 int rpvg_hip_alignments_set_effective_lengths(rpvg_hip_ctx * ctx, rpvg_hip_alignments * alignments, double loc, double scale,
                                               double shape, const uint32_t * path_length, double * out);
 int rpvg_hip_frag_length_eval(rpvg_hip_ctx * ctx, int what, const double * rows, uint64_t n, double * out);
+
+/* ---- alignment-path index (rpvg_index.h; rpvg_amd/csrc/align_index.hip) ---------------------------------------------
+ * A stream of per-fragment alignment-path lists in, a resident rpvg_hip_alignments in the reference's cluster order out
+ * (addAlignmentPathsBufferToIndexes, src/main.cpp:200-237; PathClusters; the caller's loop, :731-754,811-827,846-857).
+ *   rpvg_hip_align_index_create     RPVG_HIP_ERR_INVALID for max_frag_length >= 65536.
+ *   rpvg_hip_align_index_add        copies one chunk to the device (pinned staging), validates it there and appends it;
+ *                                   any number of times: the stream is the chunks in the order they were added.  A chunk
+ *                                   that fails (RPVG_HIP_ERR_INVALID: the first offending list is named in last_error — a
+ *                                   list without alignments, an alignment without paths, ids not ascending or >= num_paths,
+ *                                   a noise score > 0, non-monotone offsets, a counted fragment length of 0 or above
+ *                                   max_frag_length) leaves the index as it was.
+ *   rpvg_hip_align_index_finish     histogram, normalisation, dedupe, clustering, ordering.  The optional extra id sets
+ *                                   (set s = extra_set_path[extra_set_off[s] .. extra_set_off[s+1]), non-empty, ids <
+ *                                   num_paths: the node-sharing sets of addNodeClusters) join the union-find of
+ *                                   rpvg_hip_path_clusters.  Once; no chunk can be added afterwards.  info may be NULL.
+ *   rpvg_hip_align_index_frag_counts   host copy of the histogram ([max_frag_length + 1]) for rpvg_hip_frag_length_fit.
+ *   rpvg_hip_align_index_view       host copies of the result (rpvg_index_view).
+ *   rpvg_hip_align_index_alignments the resident rpvg_hip_alignments that rpvg_hip_alignments_upload would have made from
+ *                                   the view, without the lists leaving the device.  path_effective_length (and the
+ *                                   optional path_source_count) are per GLOBAL path ([num_paths]);
+ *                                   rpvg_hip_alignments_set_effective_lengths takes path lengths in the order of the view's
+ *                                   cluster_paths.  Freed with rpvg_hip_alignments_free; independent of the index. */
+int rpvg_hip_align_index_create(rpvg_hip_ctx * ctx, const rpvg_index_params * params, rpvg_hip_align_index ** index_out);
+void rpvg_hip_align_index_free(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index);
+int rpvg_hip_align_index_add(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index, const rpvg_fragment_lists * chunk);
+int rpvg_hip_align_index_finish(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index, const uint64_t * extra_set_off,
+                                const uint32_t * extra_set_path, uint64_t num_extra_sets, rpvg_index_info * info);
+int rpvg_hip_align_index_frag_counts(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, uint32_t * counts_out);
+int rpvg_hip_align_index_view(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index, rpvg_index_view * view_out);
+int rpvg_hip_align_index_alignments(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, const double * path_effective_length,
+                                    const uint32_t * path_source_count, rpvg_hip_alignments ** alignments_out);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the

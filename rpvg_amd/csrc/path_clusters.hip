@@ -11,6 +11,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "path_clusters.hpp"
 
 using namespace rpvg_hip_detail;
 
@@ -79,6 +80,73 @@ __global__ void labelKernel(const uint32_t n, const uint32_t * __restrict__ root
 
 }  // namespace
 
+int rpvg_hip_detail::PathClustersDevice::begin(rpvg_hip_ctx *, hipStream_t st, const uint32_t n) {
+    num_paths = n;
+    num_clusters = 0;
+    RPVG_HIP_CHECK(parent.alloc(n));
+    RPVG_HIP_CHECK(is_root.alloc(n));
+    RPVG_HIP_CHECK(root_rank.alloc(n));
+    RPVG_HIP_CHECK(label.alloc(n));
+    RPVG_HIP_CHECK(path_id.alloc(n));
+    RPVG_HIP_CHECK(label_sorted.alloc(n));
+    RPVG_HIP_CHECK(path_sorted.alloc(n));
+    RPVG_HIP_CHECK(cluster_size.alloc(static_cast<size_t>(n) + 1));
+    RPVG_HIP_CHECK(cluster_off.alloc(static_cast<size_t>(n) + 1));
+    initParentKernel<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(n, parent.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    return RPVG_HIP_OK;
+}
+
+int rpvg_hip_detail::PathClustersDevice::unite(hipStream_t st, const uint64_t num_sets, const uint64_t * d_set_off, const uint32_t * d_set_path) {
+    if (num_sets == 0) return RPVG_HIP_OK;
+    unionSetsKernel<<<dim3(static_cast<uint32_t>((num_sets + 255) / 256)), dim3(256), 0, st>>>(num_sets, d_set_off, d_set_path, parent.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    return RPVG_HIP_OK;
+}
+
+int rpvg_hip_detail::PathClustersDevice::finish(hipStream_t st) {
+    const uint32_t n = num_paths;
+    const dim3 block(256), grid_n((n + 255) / 256);
+    flattenKernel<<<grid_n, block, 0, st>>>(n, parent.ptr, is_root.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    {
+        size_t bytes = 0;
+        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, is_root.ptr, root_rank.ptr, static_cast<int>(n), st));
+        DeviceBuffer<uint8_t> tmp;
+        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
+        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, is_root.ptr, root_rank.ptr, static_cast<int>(n), st));
+        RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    RPVG_HIP_CHECK(hipMemsetAsync(cluster_size.ptr, 0, sizeof(uint64_t) * (static_cast<size_t>(n) + 1), st));
+    labelKernel<<<grid_n, block, 0, st>>>(n, parent.ptr, root_rank.ptr, label.ptr, path_id.ptr, cluster_size.ptr);
+    RPVG_HIP_CHECK(hipGetLastError());
+    {
+        size_t bytes = 0;
+        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cluster_size.ptr, cluster_off.ptr, static_cast<int>(n + 1), st));
+        DeviceBuffer<uint8_t> tmp;
+        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
+        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, cluster_size.ptr, cluster_off.ptr, static_cast<int>(n + 1), st));
+        RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    {
+        // stable sort by cluster: members stay in ascending path id (:203)
+        size_t bytes = 0;
+        RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, label.ptr, label_sorted.ptr, path_id.ptr, path_sorted.ptr,
+                                                          static_cast<int>(n), 0, 32, st));
+        DeviceBuffer<uint8_t> tmp;
+        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
+        RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.ptr, bytes, label.ptr, label_sorted.ptr, path_id.ptr, path_sorted.ptr,
+                                                          static_cast<int>(n), 0, 32, st));
+        RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    uint32_t last_rank = 0, last_is_root = 0;
+    RPVG_HIP_CHECK(hipMemcpyAsync(&last_rank, root_rank.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(&last_is_root, is_root.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    num_clusters = last_rank + last_is_root;
+    return RPVG_HIP_OK;
+}
+
 extern "C" int rpvg_hip_path_clusters(rpvg_hip_ctx * ctx, uint32_t num_paths, uint64_t num_sets, const uint64_t * set_off,
                                       const uint32_t * set_path, uint32_t * path_to_cluster, uint32_t * num_clusters_out,
                                       uint64_t * cluster_off, uint32_t * cluster_paths) {
@@ -99,75 +167,30 @@ extern "C" int rpvg_hip_path_clusters(rpvg_hip_ctx * ctx, uint32_t num_paths, ui
     RPVG_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint32_t n = num_paths;
-    const dim3 block(256), grid_n((n + 255) / 256);
 
-    DeviceBuffer<uint64_t> d_set_off, d_cluster_size, d_cluster_off;
-    DeviceBuffer<uint32_t> d_set_path, d_parent, d_is_root, d_root_rank, d_label, d_path_id, d_label_sorted, d_path_sorted;
+    DeviceBuffer<uint64_t> d_set_off;
+    DeviceBuffer<uint32_t> d_set_path;
+    PathClustersDevice pc;
     int span = ctx->spanBegin(FAM_H2D);
     if (num_sets) {
         RPVG_HIP_CHECK(d_set_off.upload(set_off, num_sets + 1, st));
         RPVG_HIP_CHECK(d_set_path.upload(set_path, num_members, st));
     }
     ctx->spanEnd(span);
-    RPVG_HIP_CHECK(d_parent.alloc(n));
-    RPVG_HIP_CHECK(d_is_root.alloc(n));
-    RPVG_HIP_CHECK(d_root_rank.alloc(n));
-    RPVG_HIP_CHECK(d_label.alloc(n));
-    RPVG_HIP_CHECK(d_path_id.alloc(n));
-    RPVG_HIP_CHECK(d_label_sorted.alloc(n));
-    RPVG_HIP_CHECK(d_path_sorted.alloc(n));
-    RPVG_HIP_CHECK(d_cluster_size.alloc(static_cast<size_t>(n) + 1));
-    RPVG_HIP_CHECK(d_cluster_off.alloc(static_cast<size_t>(n) + 1));
-
     span = ctx->spanBegin(FAM_BUILD);
-    initParentKernel<<<grid_n, block, 0, st>>>(n, d_parent.ptr);
-    if (num_members) {
-        unionSetsKernel<<<dim3(static_cast<uint32_t>((num_sets + 255) / 256)), block, 0, st>>>(num_sets, d_set_off.ptr, d_set_path.ptr,
-                                                                                            d_parent.ptr);
-    }
-    flattenKernel<<<grid_n, block, 0, st>>>(n, d_parent.ptr, d_is_root.ptr);
+    int rc = pc.begin(ctx, st, n);
+    if (rc == RPVG_HIP_OK && num_members) rc = pc.unite(st, num_sets, d_set_off.ptr, d_set_path.ptr);
     ctx->spanEnd(span);
+    if (rc != RPVG_HIP_OK) {
+        (void) hipDeviceSynchronize();
+        return rc;
+    }
     ctx->stats.build_launches += 3;
-    RPVG_HIP_CHECK(hipGetLastError());
-    {
-        size_t bytes = 0;
-        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_is_root.ptr, d_root_rank.ptr, static_cast<int>(n), st));
-        DeviceBuffer<uint8_t> tmp;
-        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, d_is_root.ptr, d_root_rank.ptr, static_cast<int>(n), st));
-        RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    RPVG_HIP_CHECK(hipMemsetAsync(d_cluster_size.ptr, 0, sizeof(uint64_t) * (static_cast<size_t>(n) + 1), st));
-    labelKernel<<<grid_n, block, 0, st>>>(n, d_parent.ptr, d_root_rank.ptr, d_label.ptr, d_path_id.ptr, d_cluster_size.ptr);
-    RPVG_HIP_CHECK(hipGetLastError());
-    {
-        size_t bytes = 0;
-        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cluster_size.ptr, d_cluster_off.ptr, static_cast<int>(n + 1), st));
-        DeviceBuffer<uint8_t> tmp;
-        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-        RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, d_cluster_size.ptr, d_cluster_off.ptr, static_cast<int>(n + 1), st));
-        RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    {
-        // stable sort by cluster: members stay in ascending path id (:203)
-        size_t bytes = 0;
-        RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_label.ptr, d_label_sorted.ptr, d_path_id.ptr, d_path_sorted.ptr,
-                                                          static_cast<int>(n), 0, 32, st));
-        DeviceBuffer<uint8_t> tmp;
-        RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-        RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.ptr, bytes, d_label.ptr, d_label_sorted.ptr, d_path_id.ptr, d_path_sorted.ptr,
-                                                          static_cast<int>(n), 0, 32, st));
-        RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    uint32_t last_rank = 0, last_is_root = 0;
-    RPVG_HIP_CHECK(hipMemcpyAsync(&last_rank, d_root_rank.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(&last_is_root, d_is_root.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(path_to_cluster, d_label.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(cluster_paths, d_path_sorted.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    if (const int rc2 = pc.finish(st)) return rc2;
+    RPVG_HIP_CHECK(hipMemcpyAsync(path_to_cluster, pc.label.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(cluster_paths, pc.path_sorted.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(cluster_off, pc.cluster_off.ptr, sizeof(uint64_t) * (static_cast<size_t>(pc.num_clusters) + 1), hipMemcpyDeviceToHost, st));
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    const uint32_t num_clusters = last_rank + last_is_root;
-    RPVG_HIP_CHECK(hipMemcpyAsync(cluster_off, d_cluster_off.ptr, sizeof(uint64_t) * (static_cast<size_t>(num_clusters) + 1), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    *num_clusters_out = num_clusters;
+    *num_clusters_out = pc.num_clusters;
     return RPVG_HIP_OK;
 }

@@ -29,26 +29,10 @@
 
 #include "../../include/rpvg_rows.h"
 #include "common.hpp"
+#include "alignments.hpp"
 #include "frag_length.hpp"
 
 using namespace rpvg_hip_detail;
-
-// Device-resident alignment batch (validated copy of a rpvg_alignment_batch).
-struct rpvg_hip_alignments {
-    uint32_t num_clusters = 0;
-    uint64_t num_reads = 0, num_aligns = 0, num_entries = 0, num_paths = 0;
-    bool collapse = false;
-    std::vector<uint64_t> h_cluster_read_off;  // [K+1]
-    std::vector<uint64_t> h_out_path_off;      // [K+1] output columns of each cluster (paths, or name groups)
-    rpvg_hip_detail::DeviceBuffer<uint32_t> read_cluster, read_count, source_count, path_group, path_idx;
-    rpvg_hip_detail::DeviceBuffer<uint32_t> small_reads, large_reads;  // at most / more than 16 (alignment, path) entries
-    uint64_t num_small = 0, num_large = 0;
-    rpvg_hip_detail::DeviceBuffer<uint64_t> cluster_path_off, cluster_read_off, read_align_off, align_path_off;
-    rpvg_hip_detail::DeviceBuffer<double> eff_len;
-    rpvg_hip_detail::DeviceBuffer<uint8_t> mapq;
-    rpvg_hip_detail::DeviceBuffer<int32_t> noise_score, score;
-    rpvg_hip_detail::DeviceBuffer<uint16_t> align_length, frag_length;
-};
 
 // Device-resident rows in the grouped layout of rpvg_cluster_batch; host copies are made on demand (view).
 struct rpvg_hip_read_rows {
@@ -435,7 +419,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void readRowKernel(const RowsI
 // is handled by a 16-lane group — four reads per wavefront — entirely in registers: lane = entry, then lane = unit,
 // then lane = bucket; the phases talk through width-16 shuffles and ballots.  Same arithmetic, same order of the
 // sequential bucketing, same output slices as readRowKernel (which keeps the larger reads and the collapsing mode).
-constexpr int kGroupLanes = 16;
 
 __device__ __forceinline__ uint32_t groupBallot(const bool pred, const int group_shift) {
     return static_cast<uint32_t>((__ballot(pred) >> group_shift) & 0xffffull);

@@ -57,6 +57,11 @@ def lib() -> C.CDLL:
         L.rpvg_amd_batch_prepare_from_alignments_fitted.restype = C.c_void_p
         L.rpvg_amd_batch_prepare_from_alignments_fitted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CClusterBatch), C.c_double, C.c_double,
                                                                     C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+        L.rpvg_amd_batch_prepare_from_fragments.restype = C.c_void_p
+        L.rpvg_amd_batch_prepare_from_fragments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                            C.POINTER(CClusterBatch), C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_double)]
         L.rpvg_amd_batch_prepare_synth_dense.restype = C.c_void_p
         L.rpvg_amd_batch_prepare_synth_dense.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]
         L.rpvg_amd_run.restype = C.c_void_p
@@ -223,6 +228,46 @@ class Engine:
             min_noise_prob, prob_precision, C.byref(secs))
         if not prep.handle:
             raise hip.EngineError(f"batch prepare from alignments failed: {_err()}")
+        prep.row_construction_seconds = secs.value
+        return prep
+
+    def prepare_from_fragments(self, chunks, index_params, path_info: ClusterBatch, extra_sets=None, frag=None,
+                               min_noise_prob: float = 1e-4, prob_precision: float = 1e-8) -> "PreparedBatch":
+        """Batch that starts from the stream of per-fragment alignment-path lists (rpvg_amd/host/align_index.hpp): chunks = a sequence of
+        index.FragmentLists with GLOBAL path ids, index_params = index.IndexParams, path_info = a ClusterBatch whose paths, clusters
+        back to back, are the global paths 0 .. P-1.  The index (histogram, equal lists, clusters, their order) and the rows are made
+        on the GPU; the prepared batch holds the clusters in the index's order.  The result carries .index_info, .frag_counts,
+        .cluster_path_off and .cluster_paths (the global paths of every cluster)."""
+        from . import index as index_mod
+        chunks = list(chunks)
+        cchunks = (index_mod.CFragmentLists * max(len(chunks), 1))(*[c.as_c() for c in chunks])
+        cparams = index_params.as_c()
+        sets = list(extra_sets or [])
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64) if sets else []
+        flat = np.ascontiguousarray([p for x in sets for p in x], dtype=np.uint32)
+        if frag is None:
+            frag = (300.0, 50.0, 0.0, 10)
+        P = index_params.num_paths
+        info = index_mod.CIndexInfo()
+        counts = np.zeros(index_params.max_frag_length + 1, dtype=np.uint32)
+        cpo, cpaths = np.zeros(P + 1, dtype=np.uint64), np.zeros(max(P, 1), dtype=np.uint32)
+        prep = PreparedBatch.__new__(PreparedBatch)
+        prep.engine = self
+        prep.batch = path_info
+        cb = path_info.as_c()
+        secs = C.c_double(0)
+        prep.handle = lib().rpvg_amd_batch_prepare_from_fragments(
+            self.handle, C.addressof(cchunks), len(chunks), C.addressof(cparams), C.c_void_p(off.ctypes.data if sets else None),
+            C.c_void_p(flat.ctypes.data if flat.size else None), len(sets), C.byref(cb), frag[0], frag[1], frag[2], int(frag[3]),
+            min_noise_prob, prob_precision, C.addressof(info), C.c_void_p(counts.ctypes.data), C.c_void_p(cpo.ctypes.data),
+            C.c_void_p(cpaths.ctypes.data), C.byref(secs))
+        if not prep.handle:
+            raise hip.EngineError(f"batch prepare from fragments failed: {_err()}")
+        prep.index_info = info
+        prep.frag_counts = counts
+        prep.cluster_path_off = cpo[:info.num_clusters + 1].copy()
+        prep.cluster_paths = cpaths[:P].copy()
         prep.row_construction_seconds = secs.value
         return prep
 

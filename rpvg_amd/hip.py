@@ -37,6 +37,8 @@ EXPORTS = [
     "rpvg_hip_group_full_posteriors", "rpvg_hip_full_set_count",
     "rpvg_hip_frag_length_fit", "rpvg_hip_frag_length_table", "rpvg_hip_frag_length_table_get", "rpvg_hip_frag_length_table_free",
     "rpvg_hip_effective_lengths", "rpvg_hip_alignments_set_effective_lengths", "rpvg_hip_frag_length_eval",
+    "rpvg_hip_align_index_create", "rpvg_hip_align_index_free", "rpvg_hip_align_index_add", "rpvg_hip_align_index_finish",
+    "rpvg_hip_align_index_frag_counts", "rpvg_hip_align_index_view", "rpvg_hip_align_index_alignments",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -318,6 +320,14 @@ class DeviceAlignments:
         self.handle = C.c_void_p()
         cb = host.as_c()
         _check(lib().rpvg_hip_alignments_upload(ctx.handle, C.byref(cb), C.byref(self.handle)), "rpvg_hip_alignments_upload")
+        self.num_paths = len(host.path_effective_length)
+
+    @classmethod
+    def from_handle(cls, ctx: "Context", handle, num_paths: int) -> "DeviceAlignments":
+        """A batch made on the device (rpvg_hip_align_index_alignments, rpvg_amd/index.py): there is no host copy."""
+        self = cls.__new__(cls)
+        self.ctx, self.host, self.handle, self.num_paths = ctx, None, handle, num_paths
+        return self
 
     def build_rows(self, row_params, merge: bool = True) -> DeviceRows:
         cp = row_params.as_c()
@@ -329,7 +339,7 @@ class DeviceAlignments:
     def set_effective_lengths(self, path_lengths, loc: float, scale: float, shape: float) -> np.ndarray:
         """Replaces the resident path_effective_length by effectivePathLength(path length) and returns the values."""
         path_lengths = np.ascontiguousarray(path_lengths, dtype=np.uint32)
-        assert path_lengths.size == len(self.host.path_effective_length)
+        assert path_lengths.size == self.num_paths
         out = np.zeros(path_lengths.size, dtype=np.float64)
         _check(lib().rpvg_hip_alignments_set_effective_lengths(
             self.ctx.handle, self.handle, C.c_double(loc), C.c_double(scale), C.c_double(shape),

@@ -314,6 +314,18 @@ DeviceAlignmentBatch::DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in,
     HipEngine::check(status, "rpvg_hip_alignments_set_effective_lengths");
 }
 
+DeviceAlignmentBatch::DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, rpvg_hip_alignments * device_alignments_in, const std::vector<double> & total_read_count_in) : hip_engine(engine_in), device_alignments(device_alignments_in), total_read_count(total_read_count_in) {
+
+    assert(hip_engine);
+    assert(device_alignments);
+}
+
+void DeviceAlignmentBatch::setEffectiveLengths(const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist) {
+
+    effective_length.resize(path_lengths.size());
+    HipEngine::check(rpvg_hip_alignments_set_effective_lengths(hip_engine->ctx(), device_alignments, fragment_length_dist.loc(), fragment_length_dist.scale(), fragment_length_dist.shape(), path_lengths.data(), effective_length.data()), "rpvg_hip_alignments_set_effective_lengths");
+}
+
 void DeviceAlignmentBatch::upload(const AlignmentBatchBuilder & alignments) {
 
     assert(hip_engine);

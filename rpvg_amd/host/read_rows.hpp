@@ -145,7 +145,14 @@ class DeviceAlignmentBatch {
         // The same from path lengths (one per path, in the order of the builder's clusters): the effective lengths
         // of the builder's PathInfo are ignored, they are computed on the device from the distribution.
         DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, const AlignmentBatchBuilder & alignments, const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist);
+
+        // Adopts a batch that was made on the device (AlignmentPathsIndex::deviceAlignments, align_index.hpp) with the read count of
+        // every cluster.
+        DeviceAlignmentBatch(std::shared_ptr<HipEngine> engine_in, rpvg_hip_alignments * device_alignments_in, const std::vector<double> & total_read_count_in);
         ~DeviceAlignmentBatch();
+
+        // Replaces the effective lengths of the resident paths by those of the path lengths (one per path, in the batch's order).
+        void setEffectiveLengths(const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist);
 
         DeviceAlignmentBatch(const DeviceAlignmentBatch &) = delete;
         DeviceAlignmentBatch & operator=(const DeviceAlignmentBatch &) = delete;
@@ -154,7 +161,7 @@ class DeviceAlignmentBatch {
         const std::shared_ptr<HipEngine> & engine() const { return hip_engine; }
         const std::vector<double> & totalReadCounts() const { return total_read_count; }
 
-        // PathInfo::effective_length of every path as computed on the device (second constructor only)
+        // PathInfo::effective_length of every path as computed on the device (second constructor, setEffectiveLengths)
         const std::vector<double> & effectiveLengths() const { return effective_length; }
 
     private:

@@ -10,12 +10,15 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/rpvg_batch.h"
 #include "batch_pipeline.hpp"
 #include "device_group.hpp"
 #include "estimator_factory.hpp"
+#include "align_index.hpp"
 #include "read_rows.hpp"
 #include "trace.hpp"
 
@@ -494,6 +497,246 @@ void * rpvg_amd_batch_prepare_from_alignments_fitted(void * engine, const rpvg_a
 
         last_error = e.what();
         return nullptr;
+    }
+}
+
+// The same, starting two steps earlier: the reads arrive as the stream of per-fragment alignment-path lists (include/rpvg_index.h),
+// `num_chunks` chunks in order, with GLOBAL path ids.  The index (align_index.hpp) counts the fragment lengths, merges equal lists,
+// clusters the paths (extra sets: addNodeClusters) and orders the clusters on the GPU; the rows are constructed from its resident
+// result.  `path_info` supplies the PathInfo of the global paths: its clusters back to back are paths 0 .. P-1 (its row arrays are
+// ignored).  The prepared batch holds the clusters in the index's rank order.  Outputs (any may be NULL): info_out; frag_counts_out
+// [max_frag_length + 1]; cluster_path_off_out [P + 1 cells, K + 1 used] and cluster_paths_out [P]: the global paths of every cluster.
+// The distribution is the caller's (frag_loc ...), as in rpvg_amd_batch_prepare_from_alignments; seconds_out = wall time from the
+// first chunk to the rows.
+void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * index_params, const uint64_t * extra_set_off, const uint32_t * extra_set_path, uint64_t num_extra_sets, const rpvg_cluster_batch * path_info, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, double min_noise_prob, double prob_precision, rpvg_index_info * info_out, uint32_t * frag_counts_out, uint64_t * cluster_path_off_out, uint32_t * cluster_paths_out, double * seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = new PreparedBatch();
+        std::unique_ptr<PreparedBatch> guard(prepared);
+
+        std::vector<PathInfo> global_paths;
+
+        for (auto & cluster_paths: unpackPaths(*path_info)) {
+
+            for (auto & info: cluster_paths) {
+
+                global_paths.emplace_back(std::move(info));
+            }
+        }
+
+        if (global_paths.size() != index_params->num_paths) {
+
+            throw std::runtime_error("one PathInfo per path of the index");
+        }
+
+        std::vector<std::vector<uint32_t> > extra_sets;
+
+        for (uint64_t i = 0; i < num_extra_sets; ++i) {
+
+            extra_sets.emplace_back(extra_set_path + extra_set_off[i], extra_set_path + extra_set_off[i + 1]);
+        }
+
+        const bool is_single_end = index_params->is_single_end != 0;
+
+        prepared->fragment_length_dist.reset(is_single_end ? new FragmentLengthDist() : new FragmentLengthDist(frag_loc, frag_scale, frag_shape, frag_sd_max_multi));
+        prepared->is_single_end = is_single_end;
+        prepared->min_noise_prob = min_noise_prob;
+        prepared->prob_precision = prob_precision;
+
+        const auto start = std::chrono::steady_clock::now();
+
+        AlignmentPathsIndex index(static_cast<Engine *>(engine)->hip, *index_params);
+
+        for (uint32_t i = 0; i < num_chunks; ++i) {
+
+            index.add(chunks[i]);
+        }
+
+        index.finish(extra_sets);
+
+        const auto cluster_paths = index.clusterPaths();
+        std::vector<double> effective_lengths;
+        effective_lengths.reserve(global_paths.size());
+
+        for (auto & info: global_paths) {
+
+            effective_lengths.emplace_back(info.effective_length);
+        }
+
+        prepared->alignments = index.deviceAlignments(effective_lengths);
+        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, is_single_end, min_noise_prob, prob_precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        uint64_t num_cluster_paths = 0;
+
+        for (size_t i = 0; i < cluster_paths.size(); ++i) {
+
+            prepared->paths.emplace_back();
+
+            if (cluster_path_off_out) {
+
+                cluster_path_off_out[i] = num_cluster_paths;
+            }
+
+            for (auto & path_id: cluster_paths[i]) {
+
+                prepared->paths.back().emplace_back(global_paths.at(path_id));
+
+                if (cluster_paths_out) {
+
+                    cluster_paths_out[num_cluster_paths] = path_id;
+                }
+
+                ++num_cluster_paths;
+            }
+        }
+
+        if (cluster_path_off_out) {
+
+            cluster_path_off_out[cluster_paths.size()] = num_cluster_paths;
+        }
+
+        if (info_out) {
+
+            *info_out = index.info();
+        }
+
+        if (frag_counts_out) {
+
+            const auto counts = index.fragLengthCounts();
+            std::copy(counts.begin(), counts.end(), frag_counts_out);
+        }
+
+        return guard.release();
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// A measurement line for the index, not product: the structure of addAlignmentPathsBufferToIndexes (src/main.cpp:200-237) on ONE
+// host thread — the histogram gate, the normalisation of one-alignment lists, a std::unordered_map keyed by the list's contents
+// (the reference's spp::sparse_hash_map and its gbwt search states cannot be built here) — over the same flat chunks.  Outputs
+// (any may be NULL): frag_counts_out [max_frag_length + 1]; the distinct lists in order of first occurrence: first_occurrence_out
+// and multiplicity_out (capacity: the number of lists of the stream); their number.  seconds_out: wall time of the loop.
+namespace {
+
+struct HostLineKey {
+
+    uint8_t is_simple, min_mapq;
+    int32_t noise_score;
+    std::vector<uint32_t> words;  // per alignment: score, lengths, number of paths, the path ids
+
+    bool operator==(const HostLineKey & other) const { return is_simple == other.is_simple && min_mapq == other.min_mapq && noise_score == other.noise_score && words == other.words; }
+};
+
+struct HostLineKeyHash {
+
+    size_t operator()(const HostLineKey & key) const {
+
+        uint64_t h = 1469598103934665603ull ^ key.is_simple ^ (static_cast<uint64_t>(key.min_mapq) << 8) ^ (static_cast<uint64_t>(static_cast<uint32_t>(key.noise_score)) << 16);
+
+        for (auto word: key.words) {
+
+            h = (h ^ word) * 1099511628211ull;
+        }
+
+        return h;
+    }
+};
+
+}
+
+int rpvg_amd_align_index_host_line(const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * params, uint32_t * frag_counts_out, uint64_t * num_distinct_out, uint64_t * first_occurrence_out, uint32_t * multiplicity_out, double * seconds_out) {
+
+    try {
+
+        std::vector<uint32_t> frag_length_counts(static_cast<size_t>(params->max_frag_length) + 1, 0);
+        std::unordered_map<HostLineKey, std::pair<uint64_t, uint32_t>, HostLineKeyHash> index;  // contents -> (first occurrence, multiplicity)
+        uint64_t num_lists = 0;
+
+        const auto start = std::chrono::steady_clock::now();
+
+        for (uint32_t c = 0; c < num_chunks; ++c) {
+
+            const auto & chunk = chunks[c];
+
+            for (uint64_t i = 0; i < chunk.num_lists; ++i) {
+
+                const uint64_t a0 = chunk.list_align_off[i], a1 = chunk.list_align_off[i + 1];
+
+                if (!params->is_single_end && chunk.list_is_simple[i] && chunk.list_min_mapq[i] >= params->frag_length_min_mapq) {
+
+                    frag_length_counts.at(chunk.align_frag_length[a0])++;
+                }
+
+                HostLineKey key;
+                key.is_simple = chunk.list_is_simple[i] != 0;
+                key.min_mapq = chunk.list_min_mapq[i];
+                key.noise_score = chunk.list_noise_score[i];
+
+                for (uint64_t a = a0; a < a1; ++a) {
+
+                    const bool single = (a1 - a0 == 1);
+                    key.words.emplace_back(single ? 1 : static_cast<uint32_t>(chunk.align_score_sum[a]));
+                    key.words.emplace_back(single ? (1u | (static_cast<uint32_t>(params->pre_frag_loc) << 16)) : (chunk.align_length[a] | (static_cast<uint32_t>(chunk.align_frag_length[a]) << 16)));
+                    key.words.emplace_back(chunk.align_path_off[a + 1] - chunk.align_path_off[a]);
+                    key.words.insert(key.words.end(), chunk.align_path_id + chunk.align_path_off[a], chunk.align_path_id + chunk.align_path_off[a + 1]);
+                }
+
+                auto it = index.emplace(std::move(key), std::make_pair(num_lists, 0u));
+                it.first->second.second++;
+                ++num_lists;
+            }
+        }
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        if (frag_counts_out) {
+
+            std::copy(frag_length_counts.begin(), frag_length_counts.end(), frag_counts_out);
+        }
+
+        if (num_distinct_out) {
+
+            *num_distinct_out = index.size();
+        }
+
+        if (first_occurrence_out && multiplicity_out) {
+
+            std::vector<std::pair<uint64_t, uint32_t> > ordered;
+            ordered.reserve(index.size());
+
+            for (auto & entry: index) {
+
+                ordered.emplace_back(entry.second);
+            }
+
+            std::sort(ordered.begin(), ordered.end());
+
+            for (size_t i = 0; i < ordered.size(); ++i) {
+
+                first_occurrence_out[i] = ordered[i].first;
+                multiplicity_out[i] = ordered[i].second;
+            }
+        }
+
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
     }
 }
 
