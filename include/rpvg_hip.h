@@ -566,6 +566,37 @@ int rpvg_hip_align_index_view(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index, 
 int rpvg_hip_align_index_alignments(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, const double * path_effective_length,
                                     const uint32_t * path_source_count, rpvg_hip_alignments ** alignments_out);
 
+/* ---- path table (rpvg_index.h; rpvg_amd/csrc/path_table.hip) ----------------------------------------------------------
+ *   rpvg_hip_path_table_upload      copies the table to the device and validates it there: source_off non-decreasing and
+ *                                   ending at num_sources (RPVG_HIP_ERR_INVALID, the first offending path named in last_error).
+ *   rpvg_hip_read_rows_to_batch_with_paths   the batch of rpvg_hip_read_rows_to_batch plus its path side: path_group_id and the
+ *                                   source-id lists gathered into the index's cluster order, the haplotype columns formed from
+ *                                   them as rpvg_hip_batch_upload forms them, and the read total of every cluster.  The rows
+ *                                   must be those of the index's clusters (not collapsed).  A table without source ids, or with
+ *                                   more than 2^32 - 16 of them (the limit of rpvg_hip_batch_upload's columns), gives a batch
+ *                                   without columns (rpvg_hip_batch_has_source_columns is 0: the caller groups on the host);
+ *                                   its group ids and totals are filled all the same.  To the host come the 3K + 4 size words
+ *                                   of the columns, the K + 1 slot offsets of the clusters and the K totals; no list.
+ *   rpvg_hip_batch_path_group_ids   host copy of path_group_id ([paths of the batch]) of a batch that has a path side.
+ *   rpvg_hip_align_index_name_groups   the name groups of every cluster and the collapsed PathInfo of every group (the table
+ *                                   needs name_id).  RPVG_HIP_ERR_INVALID for a source count of 0 and for a group whose summed
+ *                                   source count or length exceeds 32 bits (cluster and group named in last_error).
+ *   rpvg_hip_align_index_alignments_collapsed   the resident rpvg_hip_alignments that rpvg_hip_alignments_upload would have
+ *                                   made from the view with the groups' path_group / cluster_group_off and the table's source
+ *                                   counts and effective lengths: every read on the list of the wavefront-per-read kernel. */
+int rpvg_hip_path_table_upload(rpvg_hip_ctx * ctx, const rpvg_path_table * table, rpvg_hip_path_table ** table_out);
+void rpvg_hip_path_table_free(rpvg_hip_ctx * ctx, rpvg_hip_path_table * table);
+int rpvg_hip_read_rows_to_batch_with_paths(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, const rpvg_hip_align_index * index,
+                                           const rpvg_hip_path_table * table, rpvg_hip_batch ** batch_out);
+int rpvg_hip_batch_path_group_ids(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t * group_ids_out);
+void rpvg_hip_name_groups_limits(rpvg_name_groups_limits * limits_out);
+int rpvg_hip_align_index_name_groups(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, const rpvg_hip_path_table * table,
+                                     rpvg_hip_name_groups ** groups_out);
+int rpvg_hip_name_groups_view(rpvg_hip_ctx * ctx, rpvg_hip_name_groups * groups, rpvg_name_groups_view * view_out);
+void rpvg_hip_name_groups_free(rpvg_hip_ctx * ctx, rpvg_hip_name_groups * groups);
+int rpvg_hip_align_index_alignments_collapsed(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, const rpvg_hip_path_table * table,
+                                              const rpvg_hip_name_groups * groups, rpvg_hip_alignments ** alignments_out);
+
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the
  * only collectives of this engine are the per-iteration all-reduce of rpvg_hip_em_dense_sharded and

@@ -11,8 +11,13 @@
  * The functions that take a rpvg_hip_ctx are declared in rpvg_hip.h.
  *
  * Not taken over: the consecutive-duplicate rule of addAlignmentPathsToBuffer (src/main.cpp:72-89) stays with the producer
- * of the lists; the name-group collapsing of `-i transcripts --path-info` stays with the caller, who can build path_group
- * from the view; an index holds at most 2^32 - 2 lists, alignments and (alignment, path) entries.
+ * of the lists; an index holds at most 2^31 - 1 lists, alignments and (alignment, path) entries.
+ *
+ * The path table (rpvg_path_table, rpvg_amd/csrc/path_table.hip) is the PathInfo of every global path, resident once per run
+ * and read by kernels in the index's cluster order.  With it the device also forms
+ *   - the path side of a batch made from rows (group ids, haplotype columns, read totals):  rpvg_hip_read_rows_to_batch_with_paths
+ *   - the name groups of `-i transcripts --path-info` (group_name_index)                   src/main.cpp:853-887
+ *     and the collapsed PathInfo of every group                                             src/main.cpp:909-951
  */
 #ifndef RPVG_INDEX_H
 #define RPVG_INDEX_H
@@ -72,6 +77,47 @@ typedef struct rpvg_index_view {
 } rpvg_index_view;
 
 typedef struct rpvg_hip_align_index rpvg_hip_align_index;
+
+/* The PathInfo of every path of a run by GLOBAL path id (P = rpvg_index_params::num_paths).  Caller-owned host memory,
+ * read-only for the callee and free again when rpvg_hip_path_table_upload returns. */
+typedef struct rpvg_path_table {
+    uint32_t num_paths;               /* P */
+    uint64_t num_sources;             /* S: length of source_id (0 without haplotype ids) */
+    const uint32_t * group_id;        /* [P] PathInfo::group_id */
+    const uint32_t * source_count;    /* [P] PathInfo::source_count */
+    const uint64_t * source_off;      /* [P+1] non-decreasing, source_off[P] = S; NULL together with source_id: no haplotype ids */
+    const uint32_t * source_id;       /* [S] PathInfo::source_ids, the lists of the paths back to back */
+    const uint32_t * name_id;         /* [P] or NULL; equal ids = equal PathInfo::name.  Neither dense nor ordered. */
+    const uint32_t * length;          /* [P] PathInfo::length */
+    const double * effective_length;  /* [P] PathInfo::effective_length */
+} rpvg_path_table;
+
+typedef struct rpvg_hip_path_table rpvg_hip_path_table;
+
+/* The routes of rpvg_hip_align_index_name_groups by the number of paths of a cluster: at most wave_paths one wavefront, at
+ * most lds_paths one workgroup with a sort in LDS, beyond that global memory. */
+typedef struct rpvg_name_groups_limits {
+    uint32_t wave_paths;
+    uint32_t lds_paths;
+} rpvg_name_groups_limits;
+
+/* Host copies of the name groups of a finished index (valid until the groups are freed).  Groups of a cluster are numbered by
+ * the first appearance of their name along the cluster's paths (group_name_index.emplace(name, size), src/main.cpp:885); the
+ * group arrays hold the collapsed PathInfo of src/main.cpp:909-951, clusters back to back in rank order. */
+typedef struct rpvg_name_groups_view {
+    uint32_t num_clusters;                 /* K */
+    uint32_t num_paths;                    /* P */
+    const uint32_t * path_group;           /* [P] cluster order: cluster-local group of every path */
+    const uint64_t * cluster_group_off;    /* [K+1] */
+    const uint32_t * group_first_path;     /* [G] GLOBAL id of the group's first member: its name and group_id come from it */
+    const uint32_t * group_name_id;        /* [G] */
+    const uint32_t * group_group_id;       /* [G] */
+    const uint32_t * group_source_count;   /* [G] sum of the members' source counts */
+    const uint32_t * group_length;         /* [G] round(sum(length * source_count) / double(sum(source_count))), half away from zero */
+    const double * group_effective_length; /* [G] (sum in member order of effective_length * double(source_count)) / double(sum) */
+} rpvg_name_groups_view;
+
+typedef struct rpvg_hip_name_groups rpvg_hip_name_groups;
 
 #ifdef __cplusplus
 }

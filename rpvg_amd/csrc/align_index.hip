@@ -21,11 +21,11 @@
 //   gather      the cluster-ordered, cluster-local arrays of rpvg_alignment_batch.
 // No kernel allocates; every array is sized by F, A, E (lists, alignments, entries of the stream) or P (paths).
 
-#include <hipcub/hipcub.hpp>
-
 #include "alignments.hpp"
 #include "common.hpp"
+#include "device_algos.hpp"
 #include "path_clusters.hpp"
+#include "path_table.hpp"
 
 using namespace rpvg_hip_detail;
 
@@ -424,43 +424,6 @@ __global__ void gatherByPathKernel(const uint32_t num_paths, const uint32_t * __
     if (i < num_paths) out[i] = by_global_path[cluster_paths[i]];
 }
 
-struct MaxU32 {
-    __host__ __device__ __forceinline__ uint32_t operator()(const uint32_t a, const uint32_t b) const { return a > b ? a : b; }
-};
-
-inline dim3 gridFor(const uint64_t n, const uint32_t per_block = 256) { return dim3(static_cast<uint32_t>((n + per_block - 1) / per_block)); }
-
-template <typename In, typename Out>
-int exclusiveSum(hipStream_t st, const In * in, Out * out, const uint64_t n) {
-    if (n == 0) return RPVG_HIP_OK;
-    size_t bytes = 0;
-    RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, static_cast<int>(n), st));
-    DeviceBuffer<uint8_t> tmp;
-    RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-    RPVG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, in, out, static_cast<int>(n), st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));  // tmp goes back to the pool
-    return RPVG_HIP_OK;
-}
-
-template <typename Key, typename Value>
-int sortPairs(hipStream_t st, const Key * key_in, Key * key_out, const Value * value_in, Value * value_out, const uint64_t n, const int end_bit) {
-    if (n == 0) return RPVG_HIP_OK;
-    size_t bytes = 0;
-    RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, value_in, value_out, static_cast<int>(n), 0, end_bit, st));
-    DeviceBuffer<uint8_t> tmp;
-    RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-    RPVG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.ptr, bytes, key_in, key_out, value_in, value_out, static_cast<int>(n), 0, end_bit, st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    return RPVG_HIP_OK;
-}
-
-template <typename T>
-int fetchOne(hipStream_t st, const T * device, T * host) {
-    RPVG_HIP_CHECK(hipMemcpyAsync(host, device, sizeof(T), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    return RPVG_HIP_OK;
-}
-
 // one array of a chunk behind the stream's: from the caller's own pinned memory directly, else through a pinned block of the
 // library's (kept in `staging` until the copies are done), as DeviceBuffer::upload does
 template <typename T>
@@ -481,13 +444,6 @@ struct StagingBlocks {
     std::vector<void *> blocks;
     ~StagingBlocks() { for (void * b : blocks) pinnedFree(b); }
 };
-
-template <typename T>
-int downloadVector(hipStream_t st, const T * device, const size_t n, std::vector<T> & host) {
-    host.assign(n, T());
-    if (n) RPVG_HIP_CHECK(hipMemcpyAsync(host.data(), device, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    return RPVG_HIP_OK;
-}
 
 template <typename T>
 int copyBuffer(hipStream_t st, DeviceBuffer<T> & to, const DeviceBuffer<T> & from, const size_t n) {
@@ -934,45 +890,46 @@ extern "C" int rpvg_hip_align_index_view(rpvg_hip_ctx * ctx, rpvg_hip_align_inde
     return RPVG_HIP_OK;
 }
 
-extern "C" int rpvg_hip_align_index_alignments(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * ix, const double * path_effective_length,
-                                               const uint32_t * path_source_count, rpvg_hip_alignments ** out_handle) {
-    RPVG_REQUIRE(ctx && ix && out_handle, "rpvg_hip_align_index_alignments: NULL argument");
-    *out_handle = nullptr;
-    RPVG_REQUIRE(ix->finished, "rpvg_hip_align_index_alignments: the index is not finished");
+namespace rpvg_hip_detail {
+bool alignIndexParts(const rpvg_hip_align_index * ix, AlignIndexParts & parts) {
+    if (!ix || !ix->finished) return false;
+    parts.num_clusters = ix->K;
+    parts.num_paths = ix->params.num_paths;
+    parts.cluster_paths = ix->cluster_paths.ptr;
+    parts.cluster_path_off = ix->cluster_path_off.ptr;
+    parts.h_cluster_path_off = &ix->h_cluster_path_off;
+    return true;
+}
+}  // namespace rpvg_hip_detail
+
+namespace {
+
+__global__ void iotaKernel(const uint64_t n, uint32_t * __restrict__ out) {
+    const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    if (i < n) out[i] = static_cast<uint32_t>(i);
+}
+
+// The lists of a finished index as a resident alignment batch; the path arrays are gathered from device arrays by GLOBAL path
+// (by_path_count may be NULL).  all_large: every read on the list of readRowKernel (collapsing).  The caller holds ctx->mutex.
+int fillAlignments(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * ix, const double * by_path_length, const uint32_t * by_path_count,
+                   const bool all_large, rpvg_hip_alignments * al) {
     const uint32_t P = ix->params.num_paths, K = ix->K;
-    RPVG_REQUIRE(P == 0 || path_effective_length, "rpvg_hip_align_index_alignments: NULL path_effective_length");
-    std::unique_ptr<rpvg_hip_alignments> al(new (std::nothrow) rpvg_hip_alignments());
-    if (!al) {
-        setError("rpvg_hip_align_index_alignments: out of host memory");
-        return RPVG_HIP_ERR_ALLOC;
-    }
+    hipStream_t st = ctx->stream;
     al->num_clusters = K;
     al->num_reads = ix->D;
     al->num_aligns = ix->DA;
     al->num_entries = ix->DE;
     al->num_paths = P;
-    al->collapse = false;
     al->h_cluster_read_off = ix->h_cluster_read_off;
-    al->h_out_path_off = ix->h_cluster_path_off;
-    al->num_small = ix->num_small;
-    al->num_large = ix->D - ix->num_small;
-
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DeviceBuffer<double> by_path_length;
-    DeviceBuffer<uint32_t> by_path_count;
-    int span = ctx->spanBegin(FAM_H2D);
-    RPVG_HIP_CHECK(by_path_length.upload(path_effective_length, P, st));
-    if (path_source_count) RPVG_HIP_CHECK(by_path_count.upload(path_source_count, P, st));
-    ctx->spanEnd(span);
-    span = ctx->spanBegin(FAM_BUILD);
+    al->num_small = all_large ? 0 : ix->num_small;
+    al->num_large = ix->D - al->num_small;
+    SpanScope span(ctx, FAM_BUILD);
     RPVG_HIP_CHECK(al->eff_len.alloc(P));
     if (P) {
-        gatherByPathKernel<double><<<gridFor(P), dim3(256), 0, st>>>(P, ix->cluster_paths.ptr, by_path_length.ptr, al->eff_len.ptr);
-        if (path_source_count) {
+        gatherByPathKernel<double><<<gridFor(P), dim3(256), 0, st>>>(P, ix->cluster_paths.ptr, by_path_length, al->eff_len.ptr);
+        if (by_path_count) {
             RPVG_HIP_CHECK(al->source_count.alloc(P));
-            gatherByPathKernel<uint32_t><<<gridFor(P), dim3(256), 0, st>>>(P, ix->cluster_paths.ptr, by_path_count.ptr, al->source_count.ptr);
+            gatherByPathKernel<uint32_t><<<gridFor(P), dim3(256), 0, st>>>(P, ix->cluster_paths.ptr, by_path_count, al->source_count.ptr);
         }
         RPVG_HIP_CHECK(hipGetLastError());
     }
@@ -989,14 +946,74 @@ extern "C" int rpvg_hip_align_index_alignments(rpvg_hip_ctx * ctx, const rpvg_hi
         if (!rc) rc = copyBuffer(st, al->frag_length, ix->out_frag_length, ix->DA);
         if (!rc) rc = copyBuffer(st, al->align_path_off, ix->out_align_path_off, ix->DA + 1);
         if (!rc) rc = copyBuffer(st, al->path_idx, ix->align_path_idx, ix->DE);
-        if (!rc && al->num_small) rc = copyBuffer(st, al->small_reads, ix->small_reads, al->num_small);
-        if (!rc && al->num_large) rc = copyBuffer(st, al->large_reads, ix->large_reads, al->num_large);
+        if (!rc && all_large) {
+            RPVG_HIP_CHECK(al->large_reads.alloc(ix->D));
+            iotaKernel<<<gridFor(ix->D), dim3(256), 0, st>>>(ix->D, al->large_reads.ptr);
+            RPVG_HIP_CHECK(hipGetLastError());
+        } else {
+            if (!rc && al->num_small) rc = copyBuffer(st, al->small_reads, ix->small_reads, al->num_small);
+            if (!rc && al->num_large) rc = copyBuffer(st, al->large_reads, ix->large_reads, al->num_large);
+        }
     }
+    span.end();
+    if (rc) (void) hipDeviceSynchronize();
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int rpvg_hip_align_index_alignments(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * ix, const double * path_effective_length,
+                                               const uint32_t * path_source_count, rpvg_hip_alignments ** out_handle) {
+    RPVG_REQUIRE(ctx && ix && out_handle, "rpvg_hip_align_index_alignments: NULL argument");
+    *out_handle = nullptr;
+    RPVG_REQUIRE(ix->finished, "rpvg_hip_align_index_alignments: the index is not finished");
+    const uint32_t P = ix->params.num_paths;
+    RPVG_REQUIRE(P == 0 || path_effective_length, "rpvg_hip_align_index_alignments: NULL path_effective_length");
+    std::unique_ptr<rpvg_hip_alignments> al(new (std::nothrow) rpvg_hip_alignments());
+    if (!al) {
+        setError("rpvg_hip_align_index_alignments: out of host memory");
+        return RPVG_HIP_ERR_ALLOC;
+    }
+    al->collapse = false;
+    al->h_out_path_off = ix->h_cluster_path_off;
+
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DeviceBuffer<double> by_path_length;
+    DeviceBuffer<uint32_t> by_path_count;
+    const int span = ctx->spanBegin(FAM_H2D);
+    RPVG_HIP_CHECK(by_path_length.upload(path_effective_length, P, st));
+    if (path_source_count) RPVG_HIP_CHECK(by_path_count.upload(path_source_count, P, st));
     ctx->spanEnd(span);
-    if (rc) {
-        (void) hipDeviceSynchronize();
-        return rc;
+    if (const int rc = fillAlignments(ctx, ix, by_path_length.ptr, path_source_count ? by_path_count.ptr : nullptr, false, al.get())) return rc;
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    *out_handle = al.release();
+    return RPVG_HIP_OK;
+}
+
+extern "C" int rpvg_hip_align_index_alignments_collapsed(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * ix, const rpvg_hip_path_table * table,
+                                                         const rpvg_hip_name_groups * groups, rpvg_hip_alignments ** out_handle) {
+    RPVG_REQUIRE(ctx && ix && table && groups && out_handle, "rpvg_hip_align_index_alignments_collapsed: NULL argument");
+    *out_handle = nullptr;
+    RPVG_REQUIRE(ix->finished, "rpvg_hip_align_index_alignments_collapsed: the index is not finished");
+    const uint32_t P = ix->params.num_paths;
+    RPVG_REQUIRE(table->num_paths == P && groups->num_paths == P && groups->num_clusters == ix->K,
+                 "rpvg_hip_align_index_alignments_collapsed: the table and the groups are not those of the index");
+    std::unique_ptr<rpvg_hip_alignments> al(new (std::nothrow) rpvg_hip_alignments());
+    if (!al) {
+        setError("rpvg_hip_align_index_alignments_collapsed: out of host memory");
+        return RPVG_HIP_ERR_ALLOC;
     }
+    al->collapse = true;
+    al->h_out_path_off = groups->h_cluster_group_off;
+
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (const int rc = fillAlignments(ctx, ix, table->effective_length.ptr, table->source_count.ptr, true, al.get())) return rc;
+    if (!al->source_count.ptr) RPVG_HIP_CHECK(al->source_count.alloc(P));
+    if (const int rc = copyBuffer(st, al->path_group, groups->path_group, P)) return rc;
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
     *out_handle = al.release();
     return RPVG_HIP_OK;

@@ -30,6 +30,7 @@
 #include "../../include/rpvg_rows.h"
 #include "common.hpp"
 #include "alignments.hpp"
+#include "path_table.hpp"
 #include "frag_length.hpp"
 
 using namespace rpvg_hip_detail;
@@ -1504,15 +1505,12 @@ extern "C" int rpvg_hip_read_rows_sizes(rpvg_hip_ctx * ctx, const rpvg_hip_read_
 }
 
 // rows -> the device-resident batch the estimators take, without leaving the GPU
-extern "C" int rpvg_hip_read_rows_to_batch(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, rpvg_hip_batch ** batch_out) {
-    RPVG_REQUIRE(ctx && rows && batch_out, "rpvg_hip_read_rows_to_batch: NULL argument");
-    *batch_out = nullptr;
+// (the caller holds ctx->mutex and has set the device)
+static int rowsToBatch(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, std::unique_ptr<rpvg_hip_batch> & b) {
     const uint32_t K = rows->num_clusters;
     const uint64_t R = rows->num_rows, G = rows->num_groups, M = rows->num_members;
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::unique_ptr<rpvg_hip_batch> b(new (std::nothrow) rpvg_hip_batch());
+    b.reset(new (std::nothrow) rpvg_hip_batch());
     if (!b) {
         setError("rpvg_hip_read_rows_to_batch: out of host memory");
         return RPVG_HIP_ERR_ALLOC;
@@ -1545,6 +1543,30 @@ extern "C" int rpvg_hip_read_rows_to_batch(rpvg_hip_ctx * ctx, const rpvg_hip_re
     RPVG_HIP_CHECK(hipGetLastError());
     RPVG_HIP_CHECK(hipMemcpyAsync(b->h_cluster_ent_off.data(), d_cluster_ent_off.ptr, sizeof(uint64_t) * (K + 1), hipMemcpyDeviceToHost, st));
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    return RPVG_HIP_OK;
+}
+
+extern "C" int rpvg_hip_read_rows_to_batch(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, rpvg_hip_batch ** batch_out) {
+    RPVG_REQUIRE(ctx && rows && batch_out, "rpvg_hip_read_rows_to_batch: NULL argument");
+    *batch_out = nullptr;
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<rpvg_hip_batch> b;
+    if (const int rc = rowsToBatch(ctx, rows, b)) return rc;
+    *batch_out = b.release();
+    return RPVG_HIP_OK;
+}
+
+// the same with the path side of the batch from the resident path table (path_table.hip)
+extern "C" int rpvg_hip_read_rows_to_batch_with_paths(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, const rpvg_hip_align_index * index,
+                                                      const rpvg_hip_path_table * table, rpvg_hip_batch ** batch_out) {
+    RPVG_REQUIRE(ctx && rows && index && table && batch_out, "rpvg_hip_read_rows_to_batch_with_paths: NULL argument");
+    *batch_out = nullptr;
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<rpvg_hip_batch> b;
+    if (const int rc = rowsToBatch(ctx, rows, b)) return rc;
+    if (const int rc = attachPathSide(ctx, b.get(), rows->row_count.ptr, index, table)) return rc;
     *batch_out = b.release();
     return RPVG_HIP_OK;
 }

@@ -62,6 +62,13 @@ def lib() -> C.CDLL:
                                                             C.POINTER(CClusterBatch), C.c_double, C.c_double, C.c_double, C.c_uint32,
                                                             C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                             C.POINTER(C.c_double)]
+        L.rpvg_amd_batch_prepare_from_fragments_table.restype = C.c_void_p
+        L.rpvg_amd_batch_prepare_from_fragments_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                                  C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                                                  C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                  C.POINTER(C.c_double)]
+        L.rpvg_amd_batch_has_source_columns.restype = C.c_int
+        L.rpvg_amd_batch_has_source_columns.argtypes = [C.c_void_p]
         L.rpvg_amd_batch_prepare_synth_dense.restype = C.c_void_p
         L.rpvg_amd_batch_prepare_synth_dense.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]
         L.rpvg_amd_run.restype = C.c_void_p
@@ -231,14 +238,23 @@ class Engine:
         prep.row_construction_seconds = secs.value
         return prep
 
-    def prepare_from_fragments(self, chunks, index_params, path_info: ClusterBatch, extra_sets=None, frag=None,
-                               min_noise_prob: float = 1e-4, prob_precision: float = 1e-8) -> "PreparedBatch":
+    def prepare_from_fragments(self, chunks, index_params, path_info: Optional[ClusterBatch] = None, extra_sets=None, frag=None,
+                               min_noise_prob: float = 1e-4, prob_precision: float = 1e-8, path_table=None,
+                               collapse_names: bool = False) -> "PreparedBatch":
         """Batch that starts from the stream of per-fragment alignment-path lists (rpvg_amd/host/align_index.hpp): chunks = a sequence of
         index.FragmentLists with GLOBAL path ids, index_params = index.IndexParams, path_info = a ClusterBatch whose paths, clusters
         back to back, are the global paths 0 .. P-1.  The index (histogram, equal lists, clusters, their order) and the rows are made
         on the GPU; the prepared batch holds the clusters in the index's order.  The result carries .index_info, .frag_counts,
-        .cluster_path_off and .cluster_paths (the global paths of every cluster)."""
+        .cluster_path_off and .cluster_paths (the global paths of every cluster).
+        path_table (an index.PathTable, instead of path_info): the PathInfo of the global paths goes to the GPU as a table and the
+        path side of the batch — group ids, haplotype columns — is formed there: the result reports .has_source_columns when the
+        table has source ids.  collapse_names (the table needs name_id): the batch's columns are the name groups of every cluster
+        and its paths the collapsed ones (`-i transcripts --path-info`)."""
         from . import index as index_mod
+        if (path_table is None) == (path_info is None):
+            raise ValueError("prepare_from_fragments: either path_info or path_table")
+        if collapse_names and (path_table is None or path_table.name_id is None):
+            raise ValueError("prepare_from_fragments: collapse_names needs a path_table with name_id")
         chunks = list(chunks)
         cchunks = (index_mod.CFragmentLists * max(len(chunks), 1))(*[c.as_c() for c in chunks])
         cparams = index_params.as_c()
@@ -255,13 +271,23 @@ class Engine:
         prep = PreparedBatch.__new__(PreparedBatch)
         prep.engine = self
         prep.batch = path_info
-        cb = path_info.as_c()
         secs = C.c_double(0)
-        prep.handle = lib().rpvg_amd_batch_prepare_from_fragments(
-            self.handle, C.addressof(cchunks), len(chunks), C.addressof(cparams), C.c_void_p(off.ctypes.data if sets else None),
-            C.c_void_p(flat.ctypes.data if flat.size else None), len(sets), C.byref(cb), frag[0], frag[1], frag[2], int(frag[3]),
-            min_noise_prob, prob_precision, C.addressof(info), C.c_void_p(counts.ctypes.data), C.c_void_p(cpo.ctypes.data),
-            C.c_void_p(cpaths.ctypes.data), C.byref(secs))
+        if path_table is not None:
+            if path_table.num_paths != P:
+                raise ValueError("prepare_from_fragments: one table entry per path of the index")
+            ct = path_table.as_c()
+            prep.handle = lib().rpvg_amd_batch_prepare_from_fragments_table(
+                self.handle, C.addressof(cchunks), len(chunks), C.addressof(cparams), C.c_void_p(off.ctypes.data if sets else None),
+                C.c_void_p(flat.ctypes.data if flat.size else None), len(sets), C.addressof(ct), 1 if collapse_names else 0,
+                frag[0], frag[1], frag[2], int(frag[3]), min_noise_prob, prob_precision, C.addressof(info),
+                C.c_void_p(counts.ctypes.data), C.c_void_p(cpo.ctypes.data), C.c_void_p(cpaths.ctypes.data), C.byref(secs))
+        else:
+            cb = path_info.as_c()
+            prep.handle = lib().rpvg_amd_batch_prepare_from_fragments(
+                self.handle, C.addressof(cchunks), len(chunks), C.addressof(cparams), C.c_void_p(off.ctypes.data if sets else None),
+                C.c_void_p(flat.ctypes.data if flat.size else None), len(sets), C.byref(cb), frag[0], frag[1], frag[2], int(frag[3]),
+                min_noise_prob, prob_precision, C.addressof(info), C.c_void_p(counts.ctypes.data), C.c_void_p(cpo.ctypes.data),
+                C.c_void_p(cpaths.ctypes.data), C.byref(secs))
         if not prep.handle:
             raise hip.EngineError(f"batch prepare from fragments failed: {_err()}")
         prep.index_info = info
@@ -487,11 +513,18 @@ class PreparedBatch:
     def reupload(self, engine: "Engine", batch: Optional[ClusterBatch] = None, compact: bool = False) -> float:
         """Replaces the resident rows by a fresh upload of `batch` (default: the batch this was prepared from) through
         `engine` (an uploader engine on the same GPU keeps the copy off the estimating engine's streams); seconds."""
+        if batch is None and self.batch is None:
+            raise ValueError("reupload: this batch was prepared without a host batch (path_table=...): pass the batch to upload")
         cb = (batch or self.batch).as_c(compact)
         secs = C.c_double(0)
         if lib().rpvg_amd_batch_reupload(engine.handle, self.handle, C.byref(cb), C.byref(secs)) != 0:
             raise hip.EngineError(f"batch reupload failed: {_err()}")
         return secs.value
+
+    @property
+    def has_source_columns(self) -> bool:
+        """Whether the resident batch holds the haplotype columns of its clusters (formed on the device)."""
+        return bool(lib().rpvg_amd_batch_has_source_columns(self.handle))
 
     def free(self):
         if self.handle:

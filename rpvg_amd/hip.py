@@ -39,6 +39,9 @@ EXPORTS = [
     "rpvg_hip_effective_lengths", "rpvg_hip_alignments_set_effective_lengths", "rpvg_hip_frag_length_eval",
     "rpvg_hip_align_index_create", "rpvg_hip_align_index_free", "rpvg_hip_align_index_add", "rpvg_hip_align_index_finish",
     "rpvg_hip_align_index_frag_counts", "rpvg_hip_align_index_view", "rpvg_hip_align_index_alignments",
+    "rpvg_hip_path_table_upload", "rpvg_hip_path_table_free", "rpvg_hip_read_rows_to_batch_with_paths", "rpvg_hip_batch_path_group_ids",
+    "rpvg_hip_name_groups_limits", "rpvg_hip_align_index_name_groups", "rpvg_hip_name_groups_view", "rpvg_hip_name_groups_free",
+    "rpvg_hip_align_index_alignments_collapsed",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -241,13 +244,34 @@ class DeviceBatch:
         cb = host.as_c(compact or narrow, narrow) if narrow else host.as_c(compact)
         _check(lib().rpvg_hip_batch_upload(ctx.handle, C.byref(cb), C.byref(self.handle)), "rpvg_hip_batch_upload")
 
+    @classmethod
+    def from_handle(cls, ctx: "Context", handle, num_clusters: int, num_paths: int) -> "DeviceBatch":
+        """A batch made on the device (DeviceRows.to_batch): there is no host copy."""
+        self = cls.__new__(cls)
+        self.ctx, self.host, self.handle, self._shape = ctx, None, handle, (num_clusters, num_paths)
+        return self
+
+    @property
+    def num_clusters(self) -> int:
+        return self.host.num_clusters if self.host is not None else self._shape[0]
+
+    @property
+    def num_paths(self) -> int:
+        return int(self.host.cluster_path_off[-1]) if self.host is not None else self._shape[1]
+
     def has_source_columns(self) -> bool:
         """Whether the upload formed the haplotype columns of the clusters on the device (path_sources.hip)."""
         return bool(lib().rpvg_hip_batch_has_source_columns(self.handle))
 
     def cluster_totals(self) -> np.ndarray:
-        out = np.zeros(self.host.num_clusters, dtype=np.float64)
-        _check(lib().rpvg_hip_batch_cluster_totals(self.handle, C.c_void_p(out.ctypes.data), self.host.num_clusters), "rpvg_hip_batch_cluster_totals")
+        out = np.zeros(self.num_clusters, dtype=np.float64)
+        _check(lib().rpvg_hip_batch_cluster_totals(self.handle, C.c_void_p(out.ctypes.data), self.num_clusters), "rpvg_hip_batch_cluster_totals")
+        return out
+
+    def path_group_ids(self) -> np.ndarray:
+        """PathInfo::group_id of every path of a batch that has a path side (rpvg_hip_batch_path_group_ids)."""
+        out = np.zeros(self.num_paths, dtype=np.uint32)
+        _check(lib().rpvg_hip_batch_path_group_ids(self.ctx.handle, self.handle, C.c_void_p(out.ctypes.data)), "rpvg_hip_batch_path_group_ids")
         return out
 
     def source_columns(self, cluster: int):
@@ -298,6 +322,21 @@ class DeviceRows:
         h = C.c_void_p()
         _check(lib().rpvg_hip_read_rows_to_batch(self.ctx.handle, self.handle, C.byref(h)), "rpvg_hip_read_rows_to_batch")
         return h
+
+    def to_batch(self, index=None, table=None) -> "DeviceBatch":
+        """The resident batch of the rows; with an index (rpvg_amd.index.AlignmentIndex) and its DevicePathTable the batch has its
+        path side too (rpvg_hip_read_rows_to_batch_with_paths)."""
+        assert (index is None) == (table is None)
+        view = CClusterBatch()
+        _check(lib().rpvg_hip_read_rows_sizes(self.ctx.handle, self.handle, C.byref(view)), "rpvg_hip_read_rows_sizes")
+        K = view.num_clusters
+        P = int(view.cluster_path_off[K])
+        if index is None:
+            return DeviceBatch.from_handle(self.ctx, self.to_batch_handle(), K, P)
+        h = C.c_void_p()
+        _check(lib().rpvg_hip_read_rows_to_batch_with_paths(self.ctx.handle, self.handle, index.handle, table.handle, C.byref(h)),
+               "rpvg_hip_read_rows_to_batch_with_paths")
+        return DeviceBatch.from_handle(self.ctx, h, K, P)
 
     def free(self):
         if self.handle:

@@ -7,7 +7,7 @@
 
 namespace rpvg_amd {
 
-AlignmentPathsIndex::AlignmentPathsIndex(std::shared_ptr<HipEngine> engine_in, const rpvg_index_params & params_in) : hip_engine(engine_in), params(params_in), index(nullptr), index_info() {
+AlignmentPathsIndex::AlignmentPathsIndex(std::shared_ptr<HipEngine> engine_in, const rpvg_index_params & params_in) : hip_engine(engine_in), params(params_in), index(nullptr), index_info(), resident_table_id(0), resident_table(nullptr), resident_groups(nullptr) {
 
     assert(hip_engine);
     HipEngine::check(rpvg_hip_align_index_create(hip_engine->ctx(), &params, &index), "rpvg_hip_align_index_create");
@@ -15,6 +15,8 @@ AlignmentPathsIndex::AlignmentPathsIndex(std::shared_ptr<HipEngine> engine_in, c
 
 AlignmentPathsIndex::~AlignmentPathsIndex() {
 
+    rpvg_hip_name_groups_free(hip_engine->ctx(), resident_groups);
+    rpvg_hip_path_table_free(hip_engine->ctx(), resident_table);
     rpvg_hip_align_index_free(hip_engine->ctx(), index);
 }
 
@@ -51,7 +53,7 @@ std::vector<uint32_t> AlignmentPathsIndex::fragLengthCounts() const {
     return counts;
 }
 
-rpvg_index_view AlignmentPathsIndex::view() {
+rpvg_index_view AlignmentPathsIndex::view() const {
 
     rpvg_index_view index_view = {};
     HipEngine::check(rpvg_hip_align_index_view(hip_engine->ctx(), index, &index_view), "rpvg_hip_align_index_view");
@@ -87,7 +89,15 @@ std::unique_ptr<DeviceAlignmentBatch> AlignmentPathsIndex::deviceAlignments(cons
         throw std::invalid_argument("one effective length per path of the index");
     }
 
-    // the lists stay on the device; the read count of every cluster (a sum over its lists) is formed from the view's counts
+    rpvg_hip_alignments * alignments = nullptr;
+    HipEngine::check(rpvg_hip_align_index_alignments(hip_engine->ctx(), index, effective_lengths.data(), nullptr, &alignments), "rpvg_hip_align_index_alignments");
+
+    return std::unique_ptr<DeviceAlignmentBatch>(new DeviceAlignmentBatch(hip_engine, alignments, totalReadCounts()));
+}
+
+// the lists stay on the device; the read count of every cluster (a sum over its lists) is formed from the view's counts
+std::vector<double> AlignmentPathsIndex::totalReadCounts() const {
+
     const auto index_view = view();
     std::vector<double> total_read_counts(index_view.batch.num_clusters, 0);
 
@@ -103,10 +113,60 @@ std::unique_ptr<DeviceAlignmentBatch> AlignmentPathsIndex::deviceAlignments(cons
         total_read_counts[i] = total;
     }
 
-    rpvg_hip_alignments * alignments = nullptr;
-    HipEngine::check(rpvg_hip_align_index_alignments(hip_engine->ctx(), index, effective_lengths.data(), nullptr, &alignments), "rpvg_hip_align_index_alignments");
+    return total_read_counts;
+}
 
-    return std::unique_ptr<DeviceAlignmentBatch>(new DeviceAlignmentBatch(hip_engine, alignments, total_read_counts));
+const rpvg_hip_path_table * AlignmentPathsIndex::deviceTable(const PathTable & table) const {
+
+    if (resident_table_id != table.id() || !resident_table) {
+
+        if (table.numPaths() != params.num_paths) {
+
+            throw std::invalid_argument("one table entry per path of the index");
+        }
+
+        rpvg_hip_name_groups_free(hip_engine->ctx(), resident_groups);
+        resident_groups = nullptr;
+        rpvg_hip_path_table_free(hip_engine->ctx(), resident_table);
+        resident_table = nullptr;
+        resident_table_id = 0;
+
+        const auto table_view = table.view();
+        HipEngine::check(rpvg_hip_path_table_upload(hip_engine->ctx(), &table_view, &resident_table), "rpvg_hip_path_table_upload");
+        resident_table_id = table.id();
+    }
+
+    return resident_table;
+}
+
+void AlignmentPathsIndex::formGroups(const PathTable & table) const {
+
+    const auto device_table = deviceTable(table);
+
+    if (!resident_groups) {
+
+        HipEngine::check(rpvg_hip_align_index_name_groups(hip_engine->ctx(), index, device_table, &resident_groups), "rpvg_hip_align_index_name_groups");
+    }
+}
+
+std::vector<std::vector<PathInfo> > AlignmentPathsIndex::nameGroups(const PathTable & table) const {
+
+    formGroups(table);
+
+    rpvg_name_groups_view groups_view = {};
+    HipEngine::check(rpvg_hip_name_groups_view(hip_engine->ctx(), resident_groups, &groups_view), "rpvg_hip_name_groups_view");
+
+    return table.collapsedPaths(groups_view);
+}
+
+std::unique_ptr<DeviceAlignmentBatch> AlignmentPathsIndex::deviceAlignmentsCollapsed(const PathTable & table) const {
+
+    formGroups(table);
+
+    rpvg_hip_alignments * alignments = nullptr;
+    HipEngine::check(rpvg_hip_align_index_alignments_collapsed(hip_engine->ctx(), index, resident_table, resident_groups, &alignments), "rpvg_hip_align_index_alignments_collapsed");
+
+    return std::unique_ptr<DeviceAlignmentBatch>(new DeviceAlignmentBatch(hip_engine, alignments, totalReadCounts()));
 }
 
 std::unique_ptr<DeviceAlignmentBatch> AlignmentPathsIndex::deviceAlignments(const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist) {
@@ -130,6 +190,11 @@ std::unique_ptr<DeviceAlignmentBatch> AlignmentPathsIndex::deviceAlignments(cons
     alignments->setEffectiveLengths(ordered_lengths, fragment_length_dist);
 
     return alignments;
+}
+
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision, const AlignmentPathsIndex & index, const PathTable & table) {
+
+    return constructReadPathProbabilities(alignments, fragment_length_dist, is_single_end, min_noise_prob, prob_precision, index.handle(), index.deviceTable(table));
 }
 
 }

@@ -13,6 +13,7 @@
 #include "../../include/rpvg_index.h"
 #include "fragment_lists.hpp"
 #include "hip_engine.hpp"
+#include "path_table.hpp"
 #include "read_rows.hpp"
 
 namespace rpvg_amd {
@@ -49,16 +50,40 @@ class AlignmentPathsIndex {
         std::unique_ptr<DeviceAlignmentBatch> deviceAlignments(const std::vector<double> & effective_lengths);
         std::unique_ptr<DeviceAlignmentBatch> deviceAlignments(const std::vector<uint32_t> & path_lengths, const FragmentLengthDist & fragment_length_dist);
 
+        // `-i transcripts --path-info` (collapse_haps): the name groups of every cluster and their collapsed paths, formed on
+        // the GPU (group_name_index, src/main.cpp:853-887, and :909-951); every name is that of its group's first member.  The
+        // table stays resident in the index until one with other contents (PathTable::id) is handed in.
+        std::vector<std::vector<PathInfo> > nameGroups(const PathTable & table) const;
+
+        // The distinct lists as the resident batch of row construction with the groups of nameGroups(table) as its output
+        // columns (source counts and effective lengths from the table).
+        std::unique_ptr<DeviceAlignmentBatch> deviceAlignmentsCollapsed(const PathTable & table) const;
+
+        // what constructReadPathProbabilities (below) hands to rpvg_hip_read_rows_to_batch_with_paths
+        const rpvg_hip_align_index * handle() const { return index; }
+        const rpvg_hip_path_table * deviceTable(const PathTable & table) const;
+
     private:
 
-        rpvg_index_view view();
+        rpvg_index_view view() const;
+        std::vector<double> totalReadCounts() const;
+        void formGroups(const PathTable & table) const;
 
         std::shared_ptr<HipEngine> hip_engine;
         rpvg_index_params params;
         rpvg_hip_align_index * index;
         rpvg_index_info index_info;
         FlatFragmentLists flat;
+
+        // the table last handed in, resident, and its groups: a cache that does not change what the index is
+        mutable uint64_t resident_table_id;
+        mutable rpvg_hip_path_table * resident_table;
+        mutable rpvg_hip_name_groups * resident_groups;
 };
+
+// The rows of `alignments` (made by index.deviceAlignments) as the batch the estimators take, with its path side — group ids,
+// haplotype columns (DeviceClusterBatch::hasSourceColumns), read totals — formed on the GPU from the table.
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision, const AlignmentPathsIndex & index, const PathTable & table);
 
 }
 

@@ -4,6 +4,7 @@
 #include <cassert>
 #include <cmath>
 #include <limits>
+#include <stdexcept>
 
 #include "numeric_utils.hpp"
 
@@ -346,7 +347,7 @@ DeviceAlignmentBatch::~DeviceAlignmentBatch() {
 
 namespace {
 
-std::unique_ptr<DeviceClusterBatch> buildRows(const DeviceAlignmentBatch & alignments, const rpvg_row_params & params) {
+std::unique_ptr<DeviceClusterBatch> buildRows(const DeviceAlignmentBatch & alignments, const rpvg_row_params & params, const rpvg_hip_align_index * index = nullptr, const rpvg_hip_path_table * table = nullptr) {
 
     const auto & engine = alignments.engine();
 
@@ -354,7 +355,7 @@ std::unique_ptr<DeviceClusterBatch> buildRows(const DeviceAlignmentBatch & align
     HipEngine::check(rpvg_hip_read_rows_build(engine->ctx(), alignments.handle(), &params, 1, &rows), "rpvg_hip_read_rows_build");
 
     rpvg_hip_batch * batch = nullptr;
-    const int status = rpvg_hip_read_rows_to_batch(engine->ctx(), rows, &batch);
+    const int status = table ? rpvg_hip_read_rows_to_batch_with_paths(engine->ctx(), rows, index, table, &batch) : rpvg_hip_read_rows_to_batch(engine->ctx(), rows, &batch);
 
     rpvg_cluster_batch rows_view = {};
     const int view_status = (status == 0) ? rpvg_hip_read_rows_sizes(engine->ctx(), rows, &rows_view) : 0;
@@ -376,7 +377,12 @@ std::unique_ptr<DeviceClusterBatch> buildRows(const DeviceAlignmentBatch & align
 
 }
 
-std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision) {
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision, const rpvg_hip_align_index * index, const rpvg_hip_path_table * table) {
+
+    if ((index == nullptr) != (table == nullptr)) {
+
+        throw std::invalid_argument("an index and its path table come together");
+    }
 
     std::vector<double> frag_length_table;
 
@@ -393,7 +399,12 @@ std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceA
         params.frag_length_log_prob = frag_length_table.data();
     }
 
-    return buildRows(alignments, params);
+    return buildRows(alignments, params, index, table);
+}
+
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision) {
+
+    return constructReadPathProbabilities(alignments, fragment_length_dist, is_single_end, min_noise_prob, prob_precision, nullptr, nullptr);
 }
 
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const DeviceFragmentLengthTable & fragment_length_table, const double min_noise_prob, const double prob_precision) {

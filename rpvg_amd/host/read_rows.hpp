@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/rpvg_index.h"
 #include "../../include/rpvg_rows.h"
 #include "hip_engine.hpp"
 #include "path_cluster_estimates.hpp"
@@ -177,6 +178,10 @@ class DeviceAlignmentBatch {
 // addPathProbs for every list of the batch + the caller's sort and merge, on the GPU; the rows stay on
 // the device as the batch the estimators take.
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision);
+
+// The same with the path side of the batch (group ids, haplotype columns) formed on the GPU from the resident path table of the
+// index the alignments came from (rpvg_hip_read_rows_to_batch_with_paths; align_index.hpp has the form that takes the classes).
+std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const FragmentLengthDist & fragment_length_dist, const bool is_single_end, const double min_noise_prob, const double prob_precision, const rpvg_hip_align_index * index, const rpvg_hip_path_table * table);
 
 // The same with the density table the device computed itself: no host copy of the table, nothing to upload.
 std::unique_ptr<DeviceClusterBatch> constructReadPathProbabilities(const DeviceAlignmentBatch & alignments, const DeviceFragmentLengthTable & fragment_length_table, const double min_noise_prob, const double prob_precision);

@@ -5,6 +5,7 @@
 
 #include <cassert>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <algorithm>
 #include <memory>
@@ -197,6 +198,133 @@ void fillBuilder(const rpvg_alignment_batch & alignments, const std::vector<std:
             builder->addAlignmentPaths(align_paths, alignments.read_count[r]);
         }
     }
+}
+
+// What the two rpvg_amd_batch_prepare_from_fragments entry points share.  with_table: the caller's flat table goes to the device as it is and the path side of the batch is formed there; collapse_names: the batch's columns are the name groups.
+void * prepareFromFragments(void * engine, const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * index_params, const uint64_t * extra_set_off, const uint32_t * extra_set_path, uint64_t num_extra_sets, const std::vector<PathInfo> & global_paths, const rpvg_path_table * flat_table, const bool collapse_names, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, double min_noise_prob, double prob_precision, rpvg_index_info * info_out, uint32_t * frag_counts_out, uint64_t * cluster_path_off_out, uint32_t * cluster_paths_out, double * seconds_out) {
+
+    PreparedBatch * prepared = new PreparedBatch();
+    std::unique_ptr<PreparedBatch> guard(prepared);
+
+    if (global_paths.size() != index_params->num_paths) {
+
+        throw std::runtime_error("one PathInfo per path of the index");
+    }
+
+    std::vector<std::vector<uint32_t> > extra_sets;
+
+    for (uint64_t i = 0; i < num_extra_sets; ++i) {
+
+        extra_sets.emplace_back(extra_set_path + extra_set_off[i], extra_set_path + extra_set_off[i + 1]);
+    }
+
+    const bool is_single_end = index_params->is_single_end != 0;
+
+    prepared->fragment_length_dist.reset(is_single_end ? new FragmentLengthDist() : new FragmentLengthDist(frag_loc, frag_scale, frag_shape, frag_sd_max_multi));
+    prepared->is_single_end = is_single_end;
+    prepared->min_noise_prob = min_noise_prob;
+    prepared->prob_precision = prob_precision;
+
+    const bool with_table = flat_table != nullptr;
+    const auto start = std::chrono::steady_clock::now();
+
+    // the caller's arrays as they are (inside the timed region: it is part of what a run that starts from fragments pays)
+    const PathTable table = with_table ? PathTable::fromArrays(*flat_table) : PathTable();
+
+    AlignmentPathsIndex index(static_cast<Engine *>(engine)->hip, *index_params);
+
+    for (uint32_t i = 0; i < num_chunks; ++i) {
+
+        index.add(chunks[i]);
+    }
+
+    index.finish(extra_sets);
+
+    const auto cluster_paths = index.clusterPaths();
+    std::vector<std::vector<PathInfo> > collapsed_paths;
+
+    if (collapse_names) {
+
+        collapsed_paths = index.nameGroups(table);
+        prepared->alignments = index.deviceAlignmentsCollapsed(table);
+        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, is_single_end, min_noise_prob, prob_precision);
+
+    } else {
+
+        std::vector<double> effective_lengths;
+        effective_lengths.reserve(global_paths.size());
+
+        for (auto & info: global_paths) {
+
+            effective_lengths.emplace_back(info.effective_length);
+        }
+
+        prepared->alignments = index.deviceAlignments(effective_lengths);
+
+        if (with_table) {
+
+            prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, is_single_end, min_noise_prob, prob_precision, index, table);
+
+        } else {
+
+            prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, is_single_end, min_noise_prob, prob_precision);
+        }
+    }
+
+    if (seconds_out) {
+
+        *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    }
+
+    uint64_t num_cluster_paths = 0;
+
+    for (size_t i = 0; i < cluster_paths.size(); ++i) {
+
+        prepared->paths.emplace_back();
+
+        if (cluster_path_off_out) {
+
+            cluster_path_off_out[i] = num_cluster_paths;
+        }
+
+        for (auto & path_id: cluster_paths[i]) {
+
+            if (!collapse_names) {
+
+                prepared->paths.back().emplace_back(global_paths.at(path_id));
+            }
+
+            if (cluster_paths_out) {
+
+                cluster_paths_out[num_cluster_paths] = path_id;
+            }
+
+            ++num_cluster_paths;
+        }
+
+        if (collapse_names) {
+
+            prepared->paths.back() = std::move(collapsed_paths.at(i));
+        }
+    }
+
+    if (cluster_path_off_out) {
+
+        cluster_path_off_out[cluster_paths.size()] = num_cluster_paths;
+    }
+
+    if (info_out) {
+
+        *info_out = index.info();
+    }
+
+    if (frag_counts_out) {
+
+        const auto counts = index.fragLengthCounts();
+        std::copy(counts.begin(), counts.end(), frag_counts_out);
+    }
+
+    return guard.release();
 }
 
 }
@@ -512,9 +640,6 @@ void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_
 
     try {
 
-        PreparedBatch * prepared = new PreparedBatch();
-        std::unique_ptr<PreparedBatch> guard(prepared);
-
         std::vector<PathInfo> global_paths;
 
         for (auto & cluster_paths: unpackPaths(*path_info)) {
@@ -525,99 +650,139 @@ void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_
             }
         }
 
-        if (global_paths.size() != index_params->num_paths) {
+        return prepareFromFragments(engine, chunks, num_chunks, index_params, extra_set_off, extra_set_path, num_extra_sets, global_paths, nullptr, false, frag_loc, frag_scale, frag_shape, frag_sd_max_multi, min_noise_prob, prob_precision, info_out, frag_counts_out, cluster_path_off_out, cluster_paths_out, seconds_out);
 
-            throw std::runtime_error("one PathInfo per path of the index");
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// The same with the PathInfo of the global paths as a path table (include/rpvg_index.h) that is made resident once: the path side
+// of the prepared batch — group ids, haplotype columns, read totals — is formed on the GPU (the batch reports has_source_columns
+// when the table has source ids), nothing of it is permuted on the host but the PathInfo the estimators label their output with.
+// collapse_names (the table needs name_id): `-i transcripts --path-info` — the name groups of every cluster are the columns of
+// the batch and its paths are the collapsed ones (src/main.cpp:853-887,909-951); a path named by name_id n is called "n<n>".
+void * rpvg_amd_batch_prepare_from_fragments_table(void * engine, const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * index_params, const uint64_t * extra_set_off, const uint32_t * extra_set_path, uint64_t num_extra_sets, const rpvg_path_table * table, int collapse_names, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, double min_noise_prob, double prob_precision, rpvg_index_info * info_out, uint32_t * frag_counts_out, uint64_t * cluster_path_off_out, uint32_t * cluster_paths_out, double * seconds_out) {
+
+    try {
+
+        if (collapse_names && !table->name_id) {
+
+            throw std::runtime_error("collapsing names needs name_id");
         }
 
-        std::vector<std::vector<uint32_t> > extra_sets;
+        std::vector<PathInfo> global_paths(table->num_paths);
 
-        for (uint64_t i = 0; i < num_extra_sets; ++i) {
+        for (uint32_t i = 0; i < table->num_paths; ++i) {
 
-            extra_sets.emplace_back(extra_set_path + extra_set_off[i], extra_set_path + extra_set_off[i + 1]);
+            auto & info = global_paths[i];
+            info.name = table->name_id ? "n" + std::to_string(table->name_id[i]) : std::string();
+            info.group_id = table->group_id[i];
+            info.source_count = table->source_count[i];
+            info.length = table->length[i];
+            info.effective_length = table->effective_length[i];
+
+            if (table->source_off && !collapse_names) {
+
+                info.source_ids.insert(table->source_id + table->source_off[i], table->source_id + table->source_off[i + 1]);
+            }
         }
 
-        const bool is_single_end = index_params->is_single_end != 0;
+        return prepareFromFragments(engine, chunks, num_chunks, index_params, extra_set_off, extra_set_path, num_extra_sets, global_paths, table, collapse_names != 0, frag_loc, frag_scale, frag_shape, frag_sd_max_multi, min_noise_prob, prob_precision, info_out, frag_counts_out, cluster_path_off_out, cluster_paths_out, seconds_out);
 
-        prepared->fragment_length_dist.reset(is_single_end ? new FragmentLengthDist() : new FragmentLengthDist(frag_loc, frag_scale, frag_shape, frag_sd_max_multi));
-        prepared->is_single_end = is_single_end;
-        prepared->min_noise_prob = min_noise_prob;
-        prepared->prob_precision = prob_precision;
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// 1 when the resident batch holds the haplotype columns of its clusters (DeviceClusterBatch::hasSourceColumns)
+int rpvg_amd_batch_has_source_columns(void * prepared) {
+
+    auto * batch = static_cast<PreparedBatch *>(prepared);
+    return (batch && batch->device && batch->device->hasSourceColumns()) ? 1 : 0;
+}
+
+// A measurement line for the path table, not product: the two loops of the reference's cluster loop on ONE host thread with
+// std::unordered_map<std::string, uint32_t> (the reference's spp::sparse_hash_map cannot be built here) — group_name_index
+// (src/main.cpp:853-887) and the collapsed paths (:909-951) — over the clusters of an index (cluster_path_off [K+1],
+// cluster_paths [P], global ids) and a flat table with name ids; a path's name is "n<name_id>", made before the clock starts.
+// Unlike the reference the sums are 64-bit (the device's rule).  Outputs: path_group_out [P], cluster_group_off_out [K+1], and per
+// group (capacity P) source_count, length, effective_length; seconds_out: wall time of the two loops.
+int rpvg_amd_path_table_host_line(const rpvg_path_table * table, uint32_t num_clusters, const uint64_t * cluster_path_off, const uint32_t * cluster_paths, uint32_t * path_group_out, uint64_t * cluster_group_off_out, uint32_t * group_source_count_out, uint32_t * group_length_out, double * group_effective_length_out, double * seconds_out) {
+
+    try {
+
+        if (!table->name_id) {
+
+            throw std::runtime_error("the host line needs name_id");
+        }
+
+        std::vector<std::string> names(table->num_paths);
+
+        for (uint32_t i = 0; i < table->num_paths; ++i) {
+
+            names[i] = "n" + std::to_string(table->name_id[i]);
+        }
+
+        struct Collapsed { bool seen = false; uint64_t source_count = 0; uint64_t length = 0; double effective_length = 0; };
 
         const auto start = std::chrono::steady_clock::now();
 
-        AlignmentPathsIndex index(static_cast<Engine *>(engine)->hip, *index_params);
+        uint64_t num_groups = 0;
+        cluster_group_off_out[0] = 0;
 
-        for (uint32_t i = 0; i < num_chunks; ++i) {
+        for (uint32_t i = 0; i < num_clusters; ++i) {
 
-            index.add(chunks[i]);
+            std::unordered_map<std::string, uint32_t> group_name_index;
+
+            for (uint64_t j = cluster_path_off[i]; j < cluster_path_off[i + 1]; ++j) {
+
+                group_name_index.emplace(names[cluster_paths[j]], group_name_index.size());
+            }
+
+            std::vector<Collapsed> collapsed_paths(group_name_index.size());
+
+            for (uint64_t j = cluster_path_off[i]; j < cluster_path_off[i + 1]; ++j) {
+
+                const uint32_t path_id = cluster_paths[j];
+                const uint32_t group = group_name_index.find(names[path_id])->second;
+                path_group_out[j] = group;
+
+                auto & collapsed_path = collapsed_paths[group];
+                const double weighted = table->effective_length[path_id] * table->source_count[path_id];
+
+                collapsed_path.source_count += table->source_count[path_id];
+                collapsed_path.length += static_cast<uint64_t>(table->length[path_id]) * table->source_count[path_id];
+                collapsed_path.effective_length = collapsed_path.seen ? collapsed_path.effective_length + weighted : weighted;
+                collapsed_path.seen = true;
+            }
+
+            for (auto & collapsed_path: collapsed_paths) {
+
+                group_source_count_out[num_groups] = collapsed_path.source_count;
+                group_length_out[num_groups] = std::round(collapsed_path.length / static_cast<double>(collapsed_path.source_count));
+                group_effective_length_out[num_groups] = collapsed_path.effective_length / static_cast<double>(collapsed_path.source_count);
+                ++num_groups;
+            }
+
+            cluster_group_off_out[i + 1] = num_groups;
         }
-
-        index.finish(extra_sets);
-
-        const auto cluster_paths = index.clusterPaths();
-        std::vector<double> effective_lengths;
-        effective_lengths.reserve(global_paths.size());
-
-        for (auto & info: global_paths) {
-
-            effective_lengths.emplace_back(info.effective_length);
-        }
-
-        prepared->alignments = index.deviceAlignments(effective_lengths);
-        prepared->device = constructReadPathProbabilities(*prepared->alignments, *prepared->fragment_length_dist, is_single_end, min_noise_prob, prob_precision);
 
         if (seconds_out) {
 
             *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         }
 
-        uint64_t num_cluster_paths = 0;
-
-        for (size_t i = 0; i < cluster_paths.size(); ++i) {
-
-            prepared->paths.emplace_back();
-
-            if (cluster_path_off_out) {
-
-                cluster_path_off_out[i] = num_cluster_paths;
-            }
-
-            for (auto & path_id: cluster_paths[i]) {
-
-                prepared->paths.back().emplace_back(global_paths.at(path_id));
-
-                if (cluster_paths_out) {
-
-                    cluster_paths_out[num_cluster_paths] = path_id;
-                }
-
-                ++num_cluster_paths;
-            }
-        }
-
-        if (cluster_path_off_out) {
-
-            cluster_path_off_out[cluster_paths.size()] = num_cluster_paths;
-        }
-
-        if (info_out) {
-
-            *info_out = index.info();
-        }
-
-        if (frag_counts_out) {
-
-            const auto counts = index.fragLengthCounts();
-            std::copy(counts.begin(), counts.end(), frag_counts_out);
-        }
-
-        return guard.release();
+        return 0;
 
     } catch (const std::exception & e) {
 
         last_error = e.what();
-        return nullptr;
+        return -1;
     }
 }
 

@@ -11,8 +11,14 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import hip
-from .batch import u32p, u64p, _ptr
+from .batch import f64p, u32p, u64p, _ptr
 from .rows import AlignmentBatch, CAlignmentBatch, i32p, u8p, u16p
+
+
+def _arr(ptr, n, dt):
+    if n == 0:
+        return np.zeros(0, dtype=dt)
+    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
 
 
 class CFragmentLists(C.Structure):
@@ -38,6 +44,131 @@ class CIndexView(C.Structure):
     """rpvg_index_view"""
     _fields_ = [("batch", CAlignmentBatch), ("rank_cluster", u32p), ("path_to_cluster", u32p), ("cluster_paths", u32p),
                 ("first_occurrence", u64p)]
+
+
+class CPathTable(C.Structure):
+    """rpvg_path_table"""
+    _fields_ = [("num_paths", C.c_uint32), ("num_sources", C.c_uint64), ("group_id", u32p), ("source_count", u32p), ("source_off", u64p),
+                ("source_id", u32p), ("name_id", u32p), ("length", u32p), ("effective_length", f64p)]
+
+
+class CNameGroupsLimits(C.Structure):
+    """rpvg_name_groups_limits"""
+    _fields_ = [("wave_paths", C.c_uint32), ("lds_paths", C.c_uint32)]
+
+
+class CNameGroupsView(C.Structure):
+    """rpvg_name_groups_view"""
+    _fields_ = [("num_clusters", C.c_uint32), ("num_paths", C.c_uint32), ("path_group", u32p), ("cluster_group_off", u64p),
+                ("group_first_path", u32p), ("group_name_id", u32p), ("group_group_id", u32p), ("group_source_count", u32p),
+                ("group_length", u32p), ("group_effective_length", f64p)]
+
+
+@dataclass
+class PathTable:
+    """The PathInfo of every path of a run by global path id (rpvg_path_table).  source_off / source_id None: no haplotype ids;
+    name_id None: no names (equal ids = equal names)."""
+    group_id: np.ndarray
+    source_count: np.ndarray
+    length: np.ndarray
+    effective_length: np.ndarray
+    source_off: Optional[np.ndarray] = None
+    source_id: Optional[np.ndarray] = None
+    name_id: Optional[np.ndarray] = None
+
+    _DTYPES = dict(group_id=np.uint32, source_count=np.uint32, length=np.uint32, effective_length=np.float64, source_off=np.uint64,
+                   source_id=np.uint32, name_id=np.uint32)
+
+    def __post_init__(self):
+        for name, dt in self._DTYPES.items():
+            v = getattr(self, name)
+            if v is not None:
+                setattr(self, name, np.ascontiguousarray(v, dtype=dt))
+
+    @property
+    def num_paths(self) -> int:
+        return len(self.group_id)
+
+    @staticmethod
+    def from_paths(paths: Sequence[dict]) -> "PathTable":
+        """paths: [{"group_id", "source_count", "length", "effective_length", "source_ids"?: [...], "name"?: hashable}...];
+        names become ids in order of first appearance; source ids are kept in the order given."""
+        names, name_id, off, ids = {}, [], [0], []
+        with_names = any("name" in p for p in paths)
+        with_sources = any("source_ids" in p for p in paths)
+        for p in paths:
+            if with_names:
+                name_id.append(names.setdefault(p["name"], len(names)))
+            if with_sources:
+                ids.extend(p.get("source_ids", ()))
+                off.append(len(ids))
+        return PathTable([p["group_id"] for p in paths], [p["source_count"] for p in paths], [p["length"] for p in paths],
+                         [p["effective_length"] for p in paths], off if with_sources else None, ids if with_sources else None,
+                         name_id if with_names else None)
+
+    def as_c(self) -> CPathTable:
+        def opt(a, ty):
+            return _ptr(a, ty) if a is not None else None
+        S = len(self.source_id) if self.source_id is not None else 0
+        return CPathTable(self.num_paths, S, _ptr(self.group_id, u32p), _ptr(self.source_count, u32p), opt(self.source_off, u64p),
+                          opt(self.source_id, u32p), opt(self.name_id, u32p), _ptr(self.length, u32p), _ptr(self.effective_length, f64p))
+
+
+class DevicePathTable:
+    """A PathTable resident on the GPU (rpvg_hip_path_table)."""
+
+    def __init__(self, ctx: "hip.Context", host: PathTable):
+        self.ctx, self.host = ctx, host
+        self.handle = C.c_void_p()
+        ct = host.as_c()
+        hip._check(hip.lib().rpvg_hip_path_table_upload(ctx.handle, C.byref(ct), C.byref(self.handle)), "rpvg_hip_path_table_upload")
+
+    def free(self):
+        if self.handle:
+            hip.lib().rpvg_hip_path_table_free(self.ctx.handle, self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def name_groups_limits() -> CNameGroupsLimits:
+    """The largest cluster of the one-wavefront route and of the LDS route of AlignmentIndex.name_groups."""
+    limits = CNameGroupsLimits()
+    hip.lib().rpvg_hip_name_groups_limits(C.byref(limits))
+    return limits
+
+
+class NameGroups:
+    """The name groups of an index and their collapsed paths, resident (rpvg_hip_name_groups)."""
+
+    def __init__(self, ctx: "hip.Context", handle):
+        self.ctx, self.handle = ctx, handle
+
+    def view(self) -> dict:
+        """Host copies by name: path_group [P], cluster_group_off [K+1] and the group_* arrays [G]."""
+        v = CNameGroupsView()
+        hip._check(hip.lib().rpvg_hip_name_groups_view(self.ctx.handle, self.handle, C.byref(v)), "rpvg_hip_name_groups_view")
+        cgo = _arr(v.cluster_group_off, v.num_clusters + 1, np.uint64)
+        G = int(cgo[-1])
+        return dict(path_group=_arr(v.path_group, v.num_paths, np.uint32), cluster_group_off=cgo,
+                    group_first_path=_arr(v.group_first_path, G, np.uint32), group_name_id=_arr(v.group_name_id, G, np.uint32),
+                    group_group_id=_arr(v.group_group_id, G, np.uint32), group_source_count=_arr(v.group_source_count, G, np.uint32),
+                    group_length=_arr(v.group_length, G, np.uint32), group_effective_length=_arr(v.group_effective_length, G, np.float64))
+
+    def free(self):
+        if self.handle:
+            hip.lib().rpvg_hip_name_groups_free(self.ctx.handle, self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 @dataclass
@@ -132,12 +263,6 @@ class IndexView:
         return out
 
 
-def _arr(ptr, n, dt):
-    if n == 0:
-        return np.zeros(0, dtype=dt)
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
-
-
 class AlignmentIndex:
     """rpvg_hip_align_index on a hip.Context: add() chunks, finish(), then frag_counts() / view() / alignments()."""
 
@@ -197,6 +322,20 @@ class AlignmentIndex:
         hip._check(hip.lib().rpvg_hip_align_index_alignments(
             self.ctx.handle, self.handle, C.c_void_p(eff.ctypes.data if eff.size else None),
             C.c_void_p(src.ctypes.data if src is not None and src.size else None), C.byref(h)), "rpvg_hip_align_index_alignments")
+        return hip.DeviceAlignments.from_handle(self.ctx, h, self.params.num_paths)
+
+    def name_groups(self, table: DevicePathTable) -> NameGroups:
+        """group_name_index of every cluster and the collapsed path of every group (rpvg_hip_align_index_name_groups)."""
+        h = C.c_void_p()
+        hip._check(hip.lib().rpvg_hip_align_index_name_groups(self.ctx.handle, self.handle, table.handle, C.byref(h)),
+                   "rpvg_hip_align_index_name_groups")
+        return NameGroups(self.ctx, h)
+
+    def alignments_collapsed(self, table: DevicePathTable, groups: NameGroups) -> "hip.DeviceAlignments":
+        """The resident alignment batch with the groups as its output columns (rpvg_hip_align_index_alignments_collapsed)."""
+        h = C.c_void_p()
+        hip._check(hip.lib().rpvg_hip_align_index_alignments_collapsed(self.ctx.handle, self.handle, table.handle, groups.handle, C.byref(h)),
+                   "rpvg_hip_align_index_alignments_collapsed")
         return hip.DeviceAlignments.from_handle(self.ctx, h, self.params.num_paths)
 
     def free(self):
