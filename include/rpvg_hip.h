@@ -130,6 +130,12 @@ int rpvg_hip_batch_source_columns_sizes(const rpvg_hip_batch * batch, uint32_t c
                                         uint32_t * num_column_paths_out);
 int rpvg_hip_batch_source_columns_get(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t cluster,
                                       uint32_t * column_counts_out, uint32_t * column_path_end_out, uint32_t * column_paths_out);
+/* Inspection (tests and tools): the row side of a complete batch, however it was made, as the estimators read it — sizes first
+ * (rows R, entries NNZ), then host copies of row_ent_off [R + 1], row_count [R] (read counts as doubles), row_noise [R],
+ * ent_path [NNZ] (cluster-local path of every entry) and ent_prob [NNZ] (the probability of the entry's group). */
+int rpvg_hip_batch_rows_sizes(const rpvg_hip_batch * batch, uint64_t * num_rows_out, uint64_t * num_entries_out);
+int rpvg_hip_batch_rows_get(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint64_t * row_ent_off_out, double * row_count_out,
+                            double * row_noise_out, uint32_t * ent_path_out, double * ent_prob_out);
 
 /* ---- EM abundance solves ------------------------------------------------ */
 /* One EM problem = one cluster restricted to a strictly ascending list of its

@@ -21,6 +21,7 @@
 #include "../../include/rpvg_hip.h"
 #include "search_plan.hpp"
 #include "em_plan.hpp"
+#include "batch_forms.hpp"
 
 namespace rpvg_hip_detail {
 
@@ -719,7 +720,10 @@ struct rpvg_hip_batch {
     rpvg_hip_detail::DeviceBuffer<uint64_t> row_ent_off;       // [R+1] entry range of each row
     rpvg_hip_detail::DeviceBuffer<uint32_t> ent_path;          // [NNZ] cluster-local path
     rpvg_hip_detail::DeviceBuffer<double> ent_prob;            // [NNZ]
-    // read count of every cluster (exact: integers), summed on the device behind the copy of the rows
+    // read count of every cluster (exact: integers), summed on the device behind the copy of the rows — or by the callers of the
+    // segments, or behind the path side from the resident table (path_table.hip).  Empty in one state only: a batch made from rows
+    // on the device without a table (rpvg_hip_read_rows_to_batch) has no path side and no totals; rpvg_hip_batch_cluster_totals
+    // refuses it.
     std::vector<double> h_cluster_total;
     // ---- the path side of the batch (path_sources.hip), present when the host batch carried PathInfo::group_id and
     // PathInfo::source_ids: the haplotype columns of every cluster — findPathSourceGroups, src/path_abundance_estimator.cpp:493-546,
@@ -736,6 +740,7 @@ struct rpvg_hip_batch {
     std::vector<uint32_t> h_src_num_cols, h_src_col_paths, h_src_max_col_paths;  // [K] columns, sum and maximum of their list lengths
     // An upload in two halves (rpvg_hip_batch_upload_begin / _finish): what the kernels of the second half read and free.
     struct UploadInProgress {
+        rpvg_batch_forms::BatchForms forms;  // the plan of the upload of a host batch: sizes and the form of every array (both halves read it)
         rpvg_hip_detail::DeviceBuffer<uint32_t> d_row_count_u32, d_row_grp_off32, d_grp_idx_off32;
         rpvg_hip_detail::DeviceBuffer<uint64_t> d_row_grp_off, d_grp_idx_off;
         rpvg_hip_detail::DeviceBuffer<double> d_grp_prob;
@@ -745,7 +750,6 @@ struct rpvg_hip_batch {
         rpvg_hip_detail::DeviceBuffer<double> d_row_noise_table;
         rpvg_hip_detail::DeviceBuffer<uint8_t> d_row_count8;
         rpvg_hip_detail::DeviceBuffer<uint32_t> d_escape_row, d_escape_count;
-        uint64_t num_groups = 0;
         rpvg_hip_detail::PathSourcesPending path_sources;
         // the second half queued (uploadFinishQueue): what its kernels write and what comes back, until the wait
         rpvg_hip_detail::DeviceBuffer<unsigned long long> d_first_bad_row;
@@ -754,7 +758,6 @@ struct rpvg_hip_batch {
         rpvg_hip_detail::DeviceBuffer<unsigned char> scan_scratch_rows, scan_scratch_groups;
         void * h_results = nullptr;   // page-locked
         hipEvent_t finished = nullptr;
-        bool counts = false;
         ~UploadInProgress() {
             if (finished) {
                 (void) hipEventSynchronize(finished);  // (a batch freed between the two steps: its kernels use the buffers above)
@@ -1179,6 +1182,25 @@ struct CsrCollapseWork {
 // sorted: recorded behind the sort of the problems' rows (the first stages of the collapse: most of its time), if not null
 hipError_t queueCsrCollapse(rpvg_hip_ctx * ctx, const CsrCollapseInput & in, double precision, CsrCollapseWork & work, hipStream_t stream,
                             hipEvent_t sorted = nullptr);
+
+// ---- the makers of a device batch (batch_upload.hip) --------------------------------------------------
+// The shell every maker starts from (the upload, the segments, rows built on the device): sizes, the host offset vectors (K + 1
+// zeros each: the maker fills them) and the arrays no maker copies into — row_count, row_ent_off, ent_prob (e: their allocation).
+// The maker brings the cluster offsets, noise and path indices, the path side and h_cluster_total.  null: out of host memory.
+std::unique_ptr<rpvg_hip_batch> newBatchShell(uint32_t num_clusters, uint64_t num_rows, uint64_t num_entries, uint64_t num_paths, hipError_t & e);
+// Grouped rows on the device — a row's (probability, path list) groups by two offset arrays of 32 or 64 bits each — to row_ent_off,
+// row_count and ent_prob of `b` (expandGroupsKernel, rowMetaKernel; offsets out of range are clamped, not followed).
+// d_first_bad_row not null: validateRowsKernel over them and b's noise, path indices and cluster offsets lowers it to the first
+// row that breaks an invariant.  d_cluster_ent_off not null: [K + 1] the entry offset of every cluster's first row.
+struct GroupedRows {
+    uint64_t num_groups = 0;
+    const void * row_grp_off = nullptr;  // [R + 1]
+    const void * grp_idx_off = nullptr;  // [G + 1]
+    bool row_off32 = false, grp_off32 = false;
+    const double * grp_prob = nullptr;          // [G]
+    const uint32_t * row_count_u32 = nullptr;   // [R]
+};
+hipError_t queueGroupedRows(hipStream_t stream, const GroupedRows & rows, rpvg_hip_batch * b, unsigned long long * d_first_bad_row, uint64_t * d_cluster_ent_off);
 
 // The copies of PathInfo::group_id / source_ids of `hb` on the context's stream; then, on the stream of any context of the
 // device, the kernel that forms the haplotype columns of every cluster and the copy of their sizes back to the host;

@@ -924,30 +924,6 @@ __global__ void gatherSizesKernel(const uint64_t n, const uint32_t * __restrict_
     out_nmembers[i] = nmembers[r];
 }
 
-// rows -> the expanded entries of rpvg_hip_batch (as rpvg_hip_batch_upload does for host rows)
-__global__ void rowsExpandGroupsKernel(const uint64_t num_groups, const uint64_t * __restrict__ grp_idx_off,
-                                       const double * __restrict__ grp_prob, double * __restrict__ ent_prob) {
-    const uint64_t g = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
-    if (g >= num_groups) return;
-    const double p = grp_prob[g];
-    for (uint64_t e = grp_idx_off[g]; e < grp_idx_off[g + 1]; ++e) ent_prob[e] = p;
-}
-
-__global__ void rowsMetaKernel(const uint64_t num_rows, const uint64_t * __restrict__ row_grp_off,
-                               const uint64_t * __restrict__ grp_idx_off, const uint32_t * __restrict__ row_count_u32,
-                               uint64_t * __restrict__ row_ent_off, double * __restrict__ row_count) {
-    const uint64_t r = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
-    if (r > num_rows) return;
-    row_ent_off[r] = grp_idx_off[row_grp_off[r]];
-    if (r < num_rows) row_count[r] = static_cast<double>(row_count_u32[r]);
-}
-
-__global__ void clusterEntryOffKernel(const uint32_t num_clusters, const uint64_t * __restrict__ cluster_row_off,
-                                      const uint64_t * __restrict__ row_ent_off, uint64_t * __restrict__ out) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k <= num_clusters) out[k] = row_ent_off[cluster_row_off[k]];
-}
-
 struct MaxOp {
     __device__ uint32_t operator()(const uint32_t a, const uint32_t b) const { return a > b ? a : b; }
 };
@@ -1504,43 +1480,42 @@ extern "C" int rpvg_hip_read_rows_sizes(rpvg_hip_ctx * ctx, const rpvg_hip_read_
     return RPVG_HIP_OK;
 }
 
-// rows -> the device-resident batch the estimators take, without leaving the GPU
+// rows -> the device-resident batch the estimators take, without leaving the GPU: the shell and the routine of the upload
+// (batch_upload.hip), over the rows' own 64-bit offsets; no validation (the rows were built here) and no path side: the batch has
+// no read totals either, until attachPathSide brings both
 // (the caller holds ctx->mutex and has set the device)
 static int rowsToBatch(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, std::unique_ptr<rpvg_hip_batch> & b) {
     const uint32_t K = rows->num_clusters;
-    const uint64_t R = rows->num_rows, G = rows->num_groups, M = rows->num_members;
+    const uint64_t R = rows->num_rows, M = rows->num_members;
     hipStream_t st = ctx->stream;
-    b.reset(new (std::nothrow) rpvg_hip_batch());
+    hipError_t shell = hipSuccess;
+    b = newBatchShell(K, R, M, rows->h_cluster_path_off[K], shell);
     if (!b) {
         setError("rpvg_hip_read_rows_to_batch: out of host memory");
         return RPVG_HIP_ERR_ALLOC;
     }
-    b->num_clusters = K;
-    b->num_rows = R;
-    b->num_entries = M;
-    b->num_paths = rows->h_cluster_path_off[K];
+    RPVG_HIP_CHECK(shell);
     b->h_cluster_row_off = rows->h_cluster_row_off;
     b->h_cluster_path_off = rows->h_cluster_path_off;
-    b->h_cluster_ent_off.assign(K + 1, 0);
     RPVG_HIP_CHECK(b->cluster_row_off.upload(rows->h_cluster_row_off.data(), K + 1, st));
     RPVG_HIP_CHECK(b->cluster_path_off.upload(rows->h_cluster_path_off.data(), K + 1, st));
     RPVG_HIP_CHECK(b->row_noise.alloc(R));
-    RPVG_HIP_CHECK(b->row_count.alloc(R));
-    RPVG_HIP_CHECK(b->row_ent_off.alloc(R + 1));
     RPVG_HIP_CHECK(b->ent_path.alloc(M));
-    RPVG_HIP_CHECK(b->ent_prob.alloc(M));
     DeviceBuffer<uint64_t> d_cluster_ent_off;
     RPVG_HIP_CHECK(d_cluster_ent_off.alloc(K + 1));
     const int span = ctx->spanBegin(FAM_BUILD);
     if (R) RPVG_HIP_CHECK(hipMemcpyAsync(b->row_noise.ptr, rows->row_noise.ptr, sizeof(double) * R, hipMemcpyDeviceToDevice, st));
     if (M) RPVG_HIP_CHECK(hipMemcpyAsync(b->ent_path.ptr, rows->path_idx.ptr, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, st));
-    if (G) rowsExpandGroupsKernel<<<gridFor(G, 256), dim3(256), 0, st>>>(G, rows->grp_idx_off.ptr, rows->grp_prob.ptr, b->ent_prob.ptr);
-    rowsMetaKernel<<<gridFor(R + 1, 256), dim3(256), 0, st>>>(R, rows->row_grp_off.ptr, rows->grp_idx_off.ptr, rows->row_count.ptr,
-                                                            b->row_ent_off.ptr, b->row_count.ptr);
-    clusterEntryOffKernel<<<gridFor(K + 1, 256), dim3(256), 0, st>>>(K, b->cluster_row_off.ptr, b->row_ent_off.ptr, d_cluster_ent_off.ptr);
+    GroupedRows grouped;
+    grouped.num_groups = rows->num_groups;
+    grouped.row_grp_off = rows->row_grp_off.ptr;
+    grouped.grp_idx_off = rows->grp_idx_off.ptr;
+    grouped.grp_prob = rows->grp_prob.ptr;
+    grouped.row_count_u32 = rows->row_count.ptr;
+    const hipError_t queued = queueGroupedRows(st, grouped, b.get(), nullptr, d_cluster_ent_off.ptr);
     ctx->spanEnd(span);
     ctx->stats.build_launches += 3;
-    RPVG_HIP_CHECK(hipGetLastError());
+    RPVG_HIP_CHECK(queued);
     RPVG_HIP_CHECK(hipMemcpyAsync(b->h_cluster_ent_off.data(), d_cluster_ent_off.ptr, sizeof(uint64_t) * (K + 1), hipMemcpyDeviceToHost, st));
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
     return RPVG_HIP_OK;

@@ -42,6 +42,7 @@ EXPORTS = [
     "rpvg_hip_path_table_upload", "rpvg_hip_path_table_free", "rpvg_hip_read_rows_to_batch_with_paths", "rpvg_hip_batch_path_group_ids",
     "rpvg_hip_name_groups_limits", "rpvg_hip_align_index_name_groups", "rpvg_hip_name_groups_view", "rpvg_hip_name_groups_free",
     "rpvg_hip_align_index_alignments_collapsed",
+    "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -272,6 +273,18 @@ class DeviceBatch:
         """PathInfo::group_id of every path of a batch that has a path side (rpvg_hip_batch_path_group_ids)."""
         out = np.zeros(self.num_paths, dtype=np.uint32)
         _check(lib().rpvg_hip_batch_path_group_ids(self.ctx.handle, self.handle, C.c_void_p(out.ctypes.data)), "rpvg_hip_batch_path_group_ids")
+        return out
+
+    def rows(self):
+        """The row side of the device batch (rpvg_hip_batch_rows_get; tests and tools): a dict of row_ent_off [R + 1], row_count
+        [R] (doubles), row_noise [R], ent_path [NNZ] and ent_prob [NNZ]."""
+        R, NNZ = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rpvg_hip_batch_rows_sizes(self.handle, C.byref(R), C.byref(NNZ)), "rpvg_hip_batch_rows_sizes")
+        out = dict(row_ent_off=np.zeros(R.value + 1, dtype=np.uint64), row_count=np.zeros(R.value, dtype=np.float64),
+                   row_noise=np.zeros(R.value, dtype=np.float64), ent_path=np.zeros(NNZ.value, dtype=np.uint32),
+                   ent_prob=np.zeros(NNZ.value, dtype=np.float64))
+        _check(lib().rpvg_hip_batch_rows_get(self.ctx.handle, self.handle, *(C.c_void_p(out[name].ctypes.data) for name in
+                                             ("row_ent_off", "row_count", "row_noise", "ent_path", "ent_prob"))), "rpvg_hip_batch_rows_get")
         return out
 
     def source_columns(self, cluster: int):

@@ -136,6 +136,12 @@ def make_batch_clusters(seed: int, n_clusters: int = 6, max_reads: int = 400, wi
     return out
 
 
+def same_device_rows(a, b) -> bool:
+    """The row sides of two device batches (DeviceBatch.rows(), or a dict of the same arrays) are equal, array by array."""
+    a, b = (x if isinstance(x, dict) else x.rows() for x in (a, b))
+    return sorted(a) == sorted(b) and all(a[name].dtype == b[name].dtype and np.array_equal(a[name], b[name]) for name in a)
+
+
 def rel_close(a, b, rel: float = 1e-4, floor: float = 1e-8) -> bool:
     """|a-b| <= rel*max(|a|,|b|) with an absolute floor (= prob_precision): the parity bar of BASELINE.json."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)

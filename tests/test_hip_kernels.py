@@ -849,10 +849,85 @@ def test_upload_from_counts_of_one_byte_equals_the_upload_from_offsets(hip_ctx):
     hip.lib().rpvg_hip_batch_free(hip_ctx.handle, handle)
 
 
+def _upload_in_form(ctx, batch, offsets, narrow):
+    """The device batch of `batch` handed over with its two long offset arrays as `offsets` says ("64/64", "32/32", "32/64", "64/32":
+    row / group width; "counts": one byte each, where the batch has them) and every other array in its narrow form, or none."""
+    import ctypes as C
+    from rpvg_amd import hip
+    u64p = C.POINTER(C.c_uint64)
+    cb = batch.as_c(True, narrow)
+    if offsets == "counts":
+        if bool(cb.row_grp_count8):  # (nothing but the counts and their totals)
+            cb.row_grp_off32 = None
+            cb.grp_idx_off32 = None
+    else:
+        cb.row_grp_count8 = None
+        cb.grp_idx_count8 = None
+        cb.num_groups = cb.num_entries = 0
+        row_width, group_width = offsets.split("/")
+        if row_width == "64":
+            cb.row_grp_off32 = None
+            cb.row_grp_off = batch.row_grp_off.ctypes.data_as(u64p)
+        if group_width == "64":
+            cb.grp_idx_off32 = None
+            cb.grp_idx_off = batch.grp_idx_off.ctypes.data_as(u64p)
+    handle = C.c_void_p()
+    hip._check(hip.lib().rpvg_hip_batch_upload(ctx.handle, C.byref(cb), C.byref(handle)), "rpvg_hip_batch_upload")
+    dev = hip.DeviceBatch.__new__(hip.DeviceBatch)
+    dev.ctx, dev.host, dev.handle = ctx, batch, handle
+    return dev, cb
+
+
+def _expanded_rows(batch):
+    """What rpvg_hip_batch_upload makes of a host batch's rows, in numpy: the row side of the device batch."""
+    group_entries = np.diff(batch.grp_idx_off.astype(np.int64))
+    return dict(row_ent_off=batch.grp_idx_off[batch.row_grp_off.astype(np.int64)], row_count=batch.row_count.astype(np.float64),
+                row_noise=batch.row_noise, ent_path=batch.path_idx, ent_prob=np.repeat(batch.grp_prob, group_entries))
+
+
+@pytest.mark.parametrize("num_rows,num_groups", [(255, 257), (256, 256), (257, 255), (0, 0), (-1, 0)],
+                         ids=["R255-G257", "R256-G256", "R257-G255", "no-clusters", "one-empty-cluster"])
+def test_every_form_of_a_host_batch_makes_the_same_device_batch(hip_ctx, num_rows, num_groups):
+    """The forms a host batch may arrive in (include/rpvg_batch.h; decided once in batch_forms.hpp): the two long offset arrays in
+    64 or 32 bits each, on their own, or as counts of one byte, times the narrow forms of noise, read counts and path indices on
+    and off.  Every one of the ten makes the device batch that a numpy expansion of the host batch gives, array by array, to the
+    bit.  Rows and groups end one short of, on, and one past a block of 256 threads (rowMetaKernel has R + 1 threads,
+    expandGroupsKernel G); clusters with and without rows, a row without groups, groups of several paths, a read count that does
+    not fit a byte."""
+    if num_rows > 0:
+        clusters = small_cases.make_batch_clusters(9871, n_clusters=4, max_reads=60, with_empty=True)
+        clusters.append(dict(paths=[dict(group_id=p // 3, source_count=1, source_ids=[p % 4], effective_length=100.0) for p in range(6)],
+                             rows=[(300, 0.05, [(0.125, [0, 4, 5]), (0.5, [1, 2])]), (255, 0.01, [(0.25, [3])]), (2, 0.5, [(0.0625, [0, 1, 2, 3, 4, 5])])]))
+        rows = sum(len(cl["rows"]) for cl in clusters)
+        groups = sum(len(row[2]) for cl in clusters for row in cl["rows"])
+        pad, with_group = num_rows - rows, num_groups - groups
+        assert 0 <= with_group <= pad
+        # the last cluster brings the batch to its sizes: rows of one group, then rows of none
+        clusters.append(dict(paths=[dict(group_id=0, source_count=1, source_ids=[p], effective_length=100.0) for p in range(2)],
+                             rows=[(1 + i % 3, 0.125, [(0.5, [i % 2])]) for i in range(with_group)] + [(1, 1.0, [])] * (pad - with_group)))
+    else:
+        clusters = [] if num_rows == 0 else [dict(paths=[dict(group_id=0, source_count=1, source_ids=[0], effective_length=100.0)], rows=[])]
+    batch = ClusterBatch.from_clusters(clusters)
+    assert batch.num_rows == max(num_rows, 0) and len(batch.grp_prob) == num_groups
+    want = _expanded_rows(batch)
+    for narrow in (False, True):
+        for offsets in ("64/64", "32/32", "32/64", "64/32", "counts"):
+            dev, cb = _upload_in_form(hip_ctx, batch, offsets, narrow)
+            try:
+                if num_rows > 0:  # the forms asked for are the forms that travel
+                    assert bool(cb.row_grp_count8) == bool(cb.grp_idx_count8) == (offsets == "counts")
+                    assert bool(cb.path_idx16) == bool(cb.row_count8) == bool(cb.row_noise16) == narrow and (not narrow or cb.num_row_count_escapes == 2)
+                    assert bool(cb.row_grp_off32) == (offsets in ("32/32", "32/64")) and bool(cb.grp_idx_off32) == (offsets in ("32/32", "64/32"))
+                assert small_cases.same_device_rows(dev, want), (offsets, narrow)
+            finally:
+                dev.free()
+
+
 @pytest.mark.parametrize("compact", [False, True], ids=["offsets", "counts"])
 def test_upload_reports_the_first_row_that_breaks_an_invariant(hip_ctx, compact):
     """The rows of a batch are checked on the device, behind their copy (validateRowsKernel: over the offsets the caller wrote, or
     over the running sums of its counts of one byte); the host words the message."""
+    import ctypes as C
     from rpvg_amd import hip
     clusters = small_cases.make_batch_clusters(977, n_clusters=4, with_empty=False)
     good = ClusterBatch.from_clusters(clusters)
@@ -879,6 +954,17 @@ def test_upload_reports_the_first_row_that_breaks_an_invariant(hip_ctx, compact)
         bad.grp_idx_off[1] = bad.grp_idx_off[-1] + 7
         with pytest.raises(hip.EngineError, match="inconsistent group or entry offsets"):
             hip_ctx.upload(bad)
+        # a group offset past the last group at the first row of the second cluster: where the host looks up the cluster's entry
+        # offset before anything has been validated (batch_forms.hpp clamps it; the device refuses the batch)
+        for form in (False, True):
+            bad = ClusterBatch.from_clusters(clusters)
+            bad.row_grp_off[int(bad.cluster_row_off[1])] = len(bad.grp_prob) + 1000
+            cb = bad.as_c(form)
+            cb.row_grp_count8 = None
+            cb.grp_idx_count8 = None
+            handle = C.c_void_p()
+            assert hip.lib().rpvg_hip_batch_upload(hip_ctx.handle, C.byref(cb), C.byref(handle)) != 0
+            assert "inconsistent group or entry offsets" in hip.lib().rpvg_hip_last_error().decode()
     hip_ctx.upload(good, compact=compact)  # the context is still usable
 
 

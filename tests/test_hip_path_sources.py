@@ -215,6 +215,7 @@ def test_an_upload_in_steps_equals_the_upload_in_one_call(hip_ctx, steps):
         stepped.ctx, stepped.host, stepped.handle = hip_ctx, batch, handle
         try:
             assert stepped.has_source_columns() and np.array_equal(stepped.cluster_totals(), whole.cluster_totals())
+            assert small_cases.same_device_rows(stepped, whole)
             for k in range(batch.num_clusters):
                 assert stepped.source_columns(k) == whole.source_columns(k), k
             mats = [k for k, cl in enumerate(clusters) if cl["rows"]]

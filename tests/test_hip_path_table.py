@@ -354,8 +354,9 @@ def test_path_side_equals_the_upload_of_the_permuted_table(hip_ctx, which):
             assert sum(multiplicities) == sum(len({s for p in c for s in table["source_ids"][p]}) for c in clusters)
             assert 300 in multiplicities                                       # the 300 haplotypes of path 30 alone
             assert which != "shared" or any(7 <= m < 300 for m in multiplicities)  # haplotypes 3 and 50 .. 55 carry one list
+        assert small_cases.same_device_rows(batch, baseline)
         plain = rows.to_batch()   # without a table: as before, no path side
-        assert not plain.has_source_columns()
+        assert not plain.has_source_columns() and small_cases.same_device_rows(plain, baseline)
         with pytest.raises(hip.EngineError):
             plain.cluster_totals()
         for b in (plain, batch, baseline):

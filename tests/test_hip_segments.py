@@ -30,6 +30,7 @@ def test_segments_equal_the_joined_upload(hip_ctx, with_paths):
     try:
         assert pulled.has_source_columns() == with_paths
         assert np.array_equal(pulled.cluster_totals(), joined.cluster_totals())
+        assert small_cases.same_device_rows(pulled, joined)
         if with_paths:
             for k in range(batch.num_clusters):
                 assert pulled.source_columns(k) == joined.source_columns(k), k
@@ -58,6 +59,7 @@ def test_segments_with_the_callers_columns_equal_the_device_columns(hip_ctx):
     try:
         assert pulled.has_source_columns()
         assert np.array_equal(pulled.cluster_totals(), joined.cluster_totals())
+        assert small_cases.same_device_rows(pulled, joined)
         for k in range(batch.num_clusters):
             assert pulled.source_columns(k) == joined.source_columns(k) == columns[k], k
         a, b = solve_all(hip_ctx, pulled, batch), solve_all(hip_ctx, joined, batch)
@@ -91,6 +93,7 @@ def test_a_large_cluster_takes_several_slices(hip_ctx):
     try:
         assert int(np.diff(batch.cluster_row_off).max()) > 4096
         assert np.array_equal(pulled.cluster_totals(), joined.cluster_totals())
+        assert small_cases.same_device_rows(pulled, joined)
         for k in range(batch.num_clusters):
             assert pulled.source_columns(k) == joined.source_columns(k), k
         a, b = solve_all(hip_ctx, pulled, batch), solve_all(hip_ctx, joined, batch)
