@@ -27,6 +27,7 @@
 #include "rpvg_batch.h"
 #include "rpvg_rows.h"
 #include "rpvg_index.h"
+#include "rpvg_table.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -602,6 +603,29 @@ int rpvg_hip_name_groups_view(rpvg_hip_ctx * ctx, rpvg_hip_name_groups * groups,
 void rpvg_hip_name_groups_free(rpvg_hip_ctx * ctx, rpvg_hip_name_groups * groups);
 int rpvg_hip_align_index_alignments_collapsed(rpvg_hip_ctx * ctx, const rpvg_hip_align_index * index, const rpvg_hip_path_table * table,
                                               const rpvg_hip_name_groups * groups, rpvg_hip_alignments ** alignments_out);
+
+/* ---- estimates table (rpvg_table.h; rpvg_amd/csrc/estimates_table.hip) ---------------------------------------------------
+ *   rpvg_hip_estimates_table_build   the table of a batch's estimates, every sum in the order rpvg_table.h states: per path the
+ *                                   haplotype probability and read count of HaplotypeAbundanceEstimatesWriter::addEstimates
+ *                                   (src/threaded_output_writer.cpp:346-432), per member the transcript count of the joint writer
+ *                                   (:434-546), per cluster its part of totalTranscriptCount (src/main.cpp:1029-1057) and their sum
+ *                                   in cluster order, the noise totals of the `Unknown` rows (:283-343; evenly over `ploidy`
+ *                                   columns :434-546).  Host arrays are copied as one block; device arrays (on_device = 1) are read
+ *                                   where they lie.  One kernel validates behind the copy: RPVG_HIP_ERR_INVALID for offsets that
+ *                                   are not non-decreasing from 0 to the array sizes, a member at or beyond its cluster's number
+ *                                   of paths, or a cluster whose abundances are neither none nor one per member (the first such
+ *                                   cluster is named in last_error).  To the host come one word for the first offender and three
+ *                                   for the routes' numbers of clusters.
+ *   rpvg_hip_estimates_table_tpm     transcript count / denominator * 1e6 for every path and member (the last step of the three
+ *                                   writers' rows, :324, :413, :519): a second step because the denominator of a run spans batches
+ *                                   and ranks; the table's own total_transcript_count when the batch is the run.
+ *   rpvg_hip_estimates_table_view    host copies of the table, fetched as one packed copy when the table has changed.
+ *   rpvg_hip_estimates_table_limits  the sizes at which a cluster changes its route (rpvg_amd/csrc/estimates_plan.hpp). */
+int rpvg_hip_estimates_table_build(rpvg_hip_ctx * ctx, const rpvg_estimates_flat * estimates, uint32_t ploidy, rpvg_hip_estimates_table ** table_out);
+int rpvg_hip_estimates_table_tpm(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table, double denominator);
+int rpvg_hip_estimates_table_view(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table, rpvg_estimates_table_view * view_out);
+void rpvg_hip_estimates_table_limits(rpvg_estimates_table_limits * limits_out);
+void rpvg_hip_estimates_table_free(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the

@@ -41,6 +41,8 @@ EXPORTS = [
     "rpvg_hip_align_index_frag_counts", "rpvg_hip_align_index_view", "rpvg_hip_align_index_alignments",
     "rpvg_hip_path_table_upload", "rpvg_hip_path_table_free", "rpvg_hip_read_rows_to_batch_with_paths", "rpvg_hip_batch_path_group_ids",
     "rpvg_hip_name_groups_limits", "rpvg_hip_align_index_name_groups", "rpvg_hip_name_groups_view", "rpvg_hip_name_groups_free",
+    "rpvg_hip_estimates_table_build", "rpvg_hip_estimates_table_tpm", "rpvg_hip_estimates_table_view", "rpvg_hip_estimates_table_limits",
+    "rpvg_hip_estimates_table_free",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
 ]

@@ -5,6 +5,7 @@
 #include <iomanip>
 #include <limits>
 
+#include "../hip_engine.hpp"
 #include "cluster_io.hpp"
 
 namespace rpvg_amd {
@@ -240,6 +241,191 @@ void JointHaplotypeAbundanceEstimatesWriter::addNoiseTranscript(const uint32_t u
     }
 
     out << std::endl;
+}
+
+// ---- the same rows from the estimates table of the GPU (include/rpvg_table.h) ------------------------------------------------
+
+// what every addTable() requires of its arguments; `what` names the writer
+static void requireTable(const char * what, const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) {
+
+    const std::string writer(what);
+
+    if (estimates.on_device) {
+
+        throw EngineError(writer + "::addTable: the estimates are device memory");
+    }
+
+    if (estimates.num_clusters != table.num_clusters || estimates.num_paths != table.num_paths || estimates.num_members != table.num_members) {
+
+        throw EngineError(writer + "::addTable: the table is not that of the estimates");
+    }
+
+    if (!table.has_tpm) {
+
+        throw EngineError(writer + "::addTable: the table has no TPMs yet (EstimatesTable::tpm)");
+    }
+
+    if (labels.names.size() != table.num_paths || labels.lengths.size() != table.num_paths || labels.cluster_ids.size() != table.num_clusters) {
+
+        throw EngineError(writer + "::addTable: one name and length per path and one ClusterID per cluster");
+    }
+}
+
+// the first member and the first abundance of cluster k; throws for a cluster with sets and no abundances (the `haplotypes` model
+// has a writer of its own)
+static void clusterRanges(const char * what, const rpvg_estimates_flat & estimates, const uint32_t k, uint64_t * first_member, uint64_t * first_abundance) {
+
+    *first_member = estimates.member_off[estimates.set_off[k]];
+    *first_abundance = estimates.abund_off[k];
+
+    const uint64_t num_members = estimates.member_off[estimates.set_off[k + 1]] - *first_member;
+
+    if (estimates.abund_off[k + 1] - *first_abundance != num_members) {
+
+        throw EngineError(std::string(what) + "::addTable: cluster " + std::to_string(k) + " does not have one abundance per set member");
+    }
+}
+
+void AbundanceEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) {
+
+    requireTable("AbundanceEstimatesWriter", estimates, table, labels);
+
+    // every cluster is checked before a row is written
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        uint64_t first_member = 0, first_abundance = 0;
+        clusterRanges("AbundanceEstimatesWriter", estimates, k, &first_member, &first_abundance);
+
+        const uint64_t num_paths = estimates.cluster_path_off[k + 1] - estimates.cluster_path_off[k];
+        const uint64_t first_set = estimates.set_off[k];
+        bool one_set_per_path = estimates.set_off[k + 1] - first_set == num_paths;
+
+        for (uint64_t i = 0; one_set_per_path && i < num_paths; ++i) {
+
+            one_set_per_path = estimates.member_off[first_set + i + 1] - estimates.member_off[first_set + i] == 1 && estimates.members[estimates.member_off[first_set + i]] == i;
+        }
+
+        if (!one_set_per_path) {
+
+            throw EngineError("AbundanceEstimatesWriter::addTable: cluster " + std::to_string(k) + ": set i is not {i} for every path i");
+        }
+    }
+
+    out << std::setprecision(out_precision_digits);
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        const uint64_t first_path = estimates.cluster_path_off[k];
+        const uint64_t num_paths = estimates.cluster_path_off[k + 1] - first_path;
+        const uint64_t first_member = estimates.member_off[estimates.set_off[k]];
+        const uint64_t first_abundance = estimates.abund_off[k];
+
+        for (uint64_t i = 0; i < num_paths; ++i) {
+
+            out << labels.names[first_path + i] << "\t" << labels.cluster_ids[k] << "\t" << labels.lengths[first_path + i] << "\t" << estimates.path_effective_length[first_path + i];
+            out << "\t" << estimates.abundances[first_abundance + i] << "\t" << table.member_tpm[first_member + i] << std::endl;
+        }
+    }
+
+    noise_count += table.noise_count_total;
+}
+
+void HaplotypeAbundanceEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) {
+
+    requireTable("HaplotypeAbundanceEstimatesWriter", estimates, table, labels);
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        uint64_t first_member = 0, first_abundance = 0;
+        clusterRanges("HaplotypeAbundanceEstimatesWriter", estimates, k, &first_member, &first_abundance);
+    }
+
+    out << std::setprecision(out_precision_digits);
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        for (uint64_t g = estimates.cluster_path_off[k]; g < estimates.cluster_path_off[k + 1]; ++g) {
+
+            out << labels.names[g] << "\t" << labels.cluster_ids[k] << "\t" << labels.lengths[g] << "\t" << estimates.path_effective_length[g];
+            out << "\t" << table.haplotype_prob[g] << "\t" << table.read_count[g] << "\t" << table.tpm[g] << std::endl;
+        }
+    }
+
+    noise_count += table.noise_count_total;
+}
+
+void JointHaplotypeAbundanceEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) {
+
+    requireTable("JointHaplotypeAbundanceEstimatesWriter", estimates, table, labels);
+
+    if (table.ploidy != ploidy) {
+
+        throw EngineError("JointHaplotypeAbundanceEstimatesWriter::addTable: the table was built for ploidy " + std::to_string(table.ploidy) + ", the writer for " + std::to_string(ploidy));
+    }
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        uint64_t first_member = 0, first_abundance = 0;
+        clusterRanges("JointHaplotypeAbundanceEstimatesWriter", estimates, k, &first_member, &first_abundance);
+
+        for (uint64_t s = estimates.set_off[k]; s < estimates.set_off[k + 1]; ++s) {
+
+            const uint64_t set_size = estimates.member_off[s + 1] - estimates.member_off[s];
+
+            if (set_size == 0 || set_size > ploidy) {
+
+                throw EngineError("JointHaplotypeAbundanceEstimatesWriter::addTable: cluster " + std::to_string(k) + " has a set of " + std::to_string(set_size) + " paths");
+            }
+        }
+    }
+
+    out << std::setprecision(out_precision_digits);
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        const uint64_t first_path = estimates.cluster_path_off[k];
+        const uint64_t first_member = estimates.member_off[estimates.set_off[k]];
+        const uint64_t first_abundance = estimates.abund_off[k];
+
+        for (uint64_t s = estimates.set_off[k]; s < estimates.set_off[k + 1]; ++s) {
+
+            if (estimates.posteriors[s] < min_posterior) {
+
+                continue;
+            }
+
+            const uint64_t set_begin = estimates.member_off[s], set_end = estimates.member_off[s + 1];
+
+            for (uint64_t m = set_begin; m < set_end; ++m) {
+
+                out << labels.names[first_path + estimates.members[m]] << "\t";
+            }
+
+            for (uint64_t j = set_end - set_begin; j < ploidy; ++j) {
+
+                out << ".\t";
+            }
+
+            out << labels.cluster_ids[k] << "\t" << estimates.posteriors[s];
+
+            for (uint64_t m = set_begin; m < set_end; ++m) {
+
+                out << "\t" << estimates.abundances[first_abundance + (m - first_member)] << "\t" << table.member_tpm[m];
+            }
+
+            for (uint64_t j = set_end - set_begin; j < ploidy; ++j) {
+
+                out << "\t0\t0";
+            }
+
+            out << std::endl;
+        }
+    }
+
+    for (auto & noise_count: noise_counts) {
+
+        noise_count += table.noise_count_share_total;
+    }
 }
 
 JointHaplotypeEstimatesWriter::JointHaplotypeEstimatesWriter(const std::string filename_prefix, const uint32_t ploidy_in, const double min_posterior_in) : EstimatesWriter(filename_prefix + ".txt"), ploidy(ploidy_in), min_posterior(min_posterior_in) {

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../../include/rpvg_table.h"
 #include "../path_cluster_estimates.hpp"
 
 namespace rpvg_amd {
@@ -28,6 +29,15 @@ typedef std::vector<std::pair<uint32_t, PathClusterEstimates> > ClusterEstimates
 // Sum of abundance / effective length over every group-set member of every cluster
 // (src/main.cpp:1029-1057): the TPM denominator.
 double totalTranscriptCount(const ClusterEstimatesList & path_cluster_estimates);
+
+// What the rows of an estimates table (include/rpvg_table.h) are called: name and length of every path of the batch in cluster
+// order (the batch-wide slots of the table), and the ClusterID of every cluster.
+struct TableLabels {
+
+    std::vector<std::string> names;
+    std::vector<uint32_t> lengths;
+    std::vector<uint32_t> cluster_ids;
+};
 
 class EstimatesWriter {
 
@@ -56,6 +66,14 @@ class AbundanceEstimatesWriter : public EstimatesWriter {
         void addEstimates(const ClusterEstimatesList & path_cluster_estimates);
         void addNoiseTranscript(const uint32_t unaligned_read_count);
 
+        // The same rows from the table the GPU built of the estimates (rpvg_amd/host/estimates_table.hpp) and the flat estimates
+        // it was built from, after EstimatesTable::tpm(): for a denominator > 0 the text is what addEstimates() writes from the
+        // containers, byte for byte — the rows always, the `Unknown` row for ONE table per writer: the table's noise total joins the
+        // writer's in one addition, where addEstimates() adds cluster by cluster onto the running value, so with several batches
+        // into one writer the noise of the `Unknown` row can differ in its last digit.  Throws EngineError for a table without TPMs or labels of another size, and for a cluster
+        // whose set i is not {i} (what addEstimates() asserts).
+        void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
+
     private:
 
         const double total_transcript_count;
@@ -70,6 +88,13 @@ class HaplotypeAbundanceEstimatesWriter : public EstimatesWriter {
 
         void addEstimates(const ClusterEstimatesList & path_cluster_estimates);
         void addNoiseTranscript(const uint32_t unaligned_read_count);
+
+        // The same rows from the table the GPU built of the estimates (rpvg_amd/host/estimates_table.hpp) and the flat estimates
+        // it was built from, after EstimatesTable::tpm(): for a denominator > 0 the text is what addEstimates() writes from the
+        // containers, byte for byte — the rows always, the `Unknown` row for ONE table per writer: the table's noise total joins the
+        // writer's in one addition, where addEstimates() adds cluster by cluster onto the running value, so with several batches
+        // into one writer the noise of the `Unknown` row can differ in its last digit.  Throws EngineError for a table without TPMs or labels of another size.
+        void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
 
     private:
 
@@ -86,6 +111,14 @@ class JointHaplotypeAbundanceEstimatesWriter : public EstimatesWriter {
 
         void addEstimates(const ClusterEstimatesList & path_cluster_estimates);
         void addNoiseTranscript(const uint32_t unaligned_read_count);
+
+        // The same rows from the table the GPU built of the estimates (rpvg_amd/host/estimates_table.hpp) and the flat estimates
+        // it was built from, after EstimatesTable::tpm(): for a denominator > 0 the text is what addEstimates() writes from the
+        // containers, byte for byte — the rows always, the `Unknown` row for ONE table per writer: the table's noise total joins the
+        // writer's in one addition, where addEstimates() adds cluster by cluster onto the running value, so with several batches
+        // into one writer the noise of the `Unknown` row can differ in its last digit.  Throws EngineError for a table without TPMs or labels of another size, and for a table of
+        // another ploidy (its noise share is noise_count / ploidy).
+        void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
 
     private:
 

@@ -18,7 +18,9 @@
 #include "../../include/rpvg_batch.h"
 #include "batch_pipeline.hpp"
 #include "device_group.hpp"
+#include "estimates_table.hpp"
 #include "estimator_factory.hpp"
+#include "io/estimates_writers.hpp"
 #include "align_index.hpp"
 #include "read_rows.hpp"
 #include "trace.hpp"
@@ -1532,6 +1534,261 @@ int rpvg_amd_pipeline_stats_reset(void * pipeline_handle) {
     try {
 
         static_cast<Pipeline *>(pipeline_handle)->pipeline->resetStats();
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+}
+
+// ---- estimates table (estimates_table.hpp; include/rpvg_table.h) ------------------------------------------------------------------
+
+namespace {
+
+struct TableHandle {
+
+    std::unique_ptr<EstimatesTable> table;
+    TableLabels labels;
+    uint32_t ploidy = 0;
+};
+
+// rows are called as the existing writers would call them from the prepared batch: the PathInfo's name ("c<k>_p<j>" for a batch
+// that came without names) and length, ClusterID k + 1
+TableLabels labelsOf(const std::vector<std::vector<PathInfo> > & paths) {
+
+    TableLabels labels;
+
+    for (size_t k = 0; k < paths.size(); ++k) {
+
+        for (size_t j = 0; j < paths[k].size(); ++j) {
+
+            labels.names.emplace_back(paths[k][j].name.empty() ? "c" + std::to_string(k) + "_p" + std::to_string(j) : paths[k][j].name);
+            labels.lengths.emplace_back(paths[k][j].length);
+        }
+
+        labels.cluster_ids.emplace_back(k + 1);
+    }
+
+    return labels;
+}
+
+// "abundance": <prefix>.txt of AbundanceEstimatesWriter; "haplotype": <prefix>.txt of HaplotypeAbundanceEstimatesWriter; "joint":
+// <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter.  add(writer) adds the rows.
+template <typename AddRows>
+void writeWith(const std::string & writer, const uint32_t ploidy, const double min_posterior, const double denominator, const std::string & prefix, const uint32_t unaligned_read_count, AddRows add) {
+
+    if (writer == "abundance") {
+
+        AbundanceEstimatesWriter out(prefix, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else if (writer == "haplotype") {
+
+        HaplotypeAbundanceEstimatesWriter out(prefix, ploidy, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else if (writer == "joint") {
+
+        JointHaplotypeAbundanceEstimatesWriter out(prefix + "_joint", ploidy, min_posterior, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else {
+
+        throw std::runtime_error("no such writer: " + writer);
+    }
+}
+
+}
+
+extern "C" {
+
+// The table of the estimates of a prepared batch, built on the engine's GPU: from a result handle (rpvg_amd_run and the like)
+// when there is one, else from the containers the last run on the prepared batch left in it.
+void * rpvg_amd_estimates_table_build(void * engine, void * result_handle, void * prepared_batch, uint32_t ploidy) {
+
+    try {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+        std::unique_ptr<TableHandle> handle(new TableHandle());
+        handle->labels = labelsOf(prepared->paths);
+        handle->ploidy = ploidy;
+
+        if (result_handle) {
+
+            const Result * result = static_cast<const Result *>(result_handle);
+
+            if (result->noise_count.size() != prepared->paths.size()) {
+
+                throw std::runtime_error("the result is not that of the prepared batch");
+            }
+
+            std::vector<uint64_t> cluster_path_off(1, 0);
+            std::vector<double> effective_length;
+
+            for (auto & paths: prepared->paths) {
+
+                for (auto & path: paths) {
+
+                    effective_length.emplace_back(path.effective_length);
+                }
+
+                cluster_path_off.emplace_back(effective_length.size());
+            }
+
+            rpvg_estimates_flat flat = {};
+            flat.num_clusters = result->noise_count.size();
+            flat.num_sets = result->posteriors.size();
+            flat.num_members = result->members.size();
+            flat.num_abundances = result->abundances.size();
+            flat.num_paths = effective_length.size();
+            flat.set_off = result->set_off.data();
+            flat.member_off = result->member_off.data();
+            flat.members = result->members.data();
+            flat.posteriors = result->posteriors.data();
+            flat.abund_off = result->abund_off.data();
+            flat.abundances = result->abundances.data();
+            flat.noise_count = result->noise_count.data();
+            flat.cluster_path_off = cluster_path_off.data();
+            flat.path_effective_length = effective_length.data();
+
+            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, flat, ploidy));
+
+        } else {
+
+            if (prepared->estimates.size() != prepared->paths.size()) {
+
+                throw std::runtime_error("the prepared batch has no estimates yet");
+            }
+
+            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, prepared->estimates, ploidy));
+        }
+
+        return handle.release();
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+int rpvg_amd_estimates_table_tpm(void * table_handle, double denominator) {
+
+    try {
+
+        static_cast<TableHandle *>(table_handle)->table->tpm(denominator);
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+// valid until the next rpvg_amd_estimates_table_tpm or the table's end
+int rpvg_amd_estimates_table_view(void * table_handle, rpvg_estimates_table_view * view_out) {
+
+    try {
+
+        *view_out = static_cast<TableHandle *>(table_handle)->table->view();
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+// One of the three files from the table (after rpvg_amd_estimates_table_tpm): writer = "abundance", "haplotype" or "joint".
+int rpvg_amd_estimates_table_write(void * table_handle, const char * writer, double min_posterior, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    try {
+
+        TableHandle * handle = static_cast<TableHandle *>(table_handle);
+        const rpvg_estimates_flat estimates = handle->table->estimates();
+        const rpvg_estimates_table_view & view = handle->table->view();
+
+        writeWith(writer, handle->ploidy, min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addTable(estimates, view, handle->labels); });
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+void rpvg_amd_estimates_table_free(void * table_handle) {
+
+    delete static_cast<TableHandle *>(table_handle);
+}
+
+// The same file from the containers of the prepared batch by the writer's addEstimates(), the rows called as the table's are;
+// total_transcript_count_out: totalTranscriptCount() of the containers (one running sum over all members) and seconds_out the
+// time of that sum; write_seconds_out: the writer from its constructor to close().  A denominator of 0 stands for that sum.
+int rpvg_amd_estimates_write_from_containers(void * prepared_batch, const char * writer, uint32_t ploidy, double min_posterior, double denominator, const char * output_prefix, uint32_t unaligned_read_count, double * total_transcript_count_out, double * seconds_out, double * write_seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const TableLabels labels = labelsOf(prepared->paths);
+        ClusterEstimatesList list;
+        size_t g = 0;
+
+        for (size_t k = 0; k < prepared->estimates.size(); ++k) {
+
+            list.emplace_back(labels.cluster_ids[k], prepared->estimates[k]);
+
+            for (auto & path: list.back().second.paths) {
+
+                path.name = labels.names[g];
+                ++g;
+            }
+        }
+
+        const auto start = std::chrono::steady_clock::now();
+        const double total = totalTranscriptCount(list);
+        const auto stop = std::chrono::steady_clock::now();
+
+        if (total_transcript_count_out) {
+
+            *total_transcript_count_out = total;
+        }
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(stop - start).count();
+        }
+
+        if (writer && writer[0]) {
+
+            const auto write_start = std::chrono::steady_clock::now();
+            writeWith(writer, ploidy, min_posterior, denominator == 0 ? total : denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addEstimates(list); });
+
+            if (write_seconds_out) {
+
+                *write_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - write_start).count();
+            }
+        }
+
         return 0;
 
     } catch (const std::exception & e) {
