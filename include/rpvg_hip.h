@@ -486,6 +486,35 @@ void rpvg_hip_subset_em_free(rpvg_hip_subset_em * result);
  * whose rows count (noise probability 1) has the empty cover. */
 int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters,
                             const uint32_t * clusters, const uint64_t * cover_off, uint32_t * cover, uint32_t * cover_size);
+/* The same for clusters of any size: every listed cluster takes one of two routes (rpvg_amd/csrc/cover_plan.hpp) — the workgroup
+ * route of rpvg_hip_min_path_cover (all such clusters of the call side by side in one launch), or the whole GPU, one cluster after
+ * the other (rpvg_amd/csrc/path_cover_grid.hip): a cluster of more than rpvg_cover_limits::workgroup_max_paths paths, or of at
+ * least grid_min_work rows + entries.  grid_min_work: 0 the library default (rpvg_cover_limits::default_grid_min_work), 1 every
+ * cluster of at least two paths on the whole-GPU route, UINT64_MAX every cluster that fits on the workgroup route.  A cluster of
+ * one path never takes the whole-GPU route.  Both routes add a path's weight up in the same order and give the same covers.
+ * The first seven arguments are those of rpvg_hip_min_path_cover (the cells behind cover_size[i] are left as they are).
+ * choice_order may be NULL; it has the ranges of `cover` and receives, for a cluster of the whole-GPU route, the paths of the
+ * cover in the order the greedy rounds chose them; a cluster of the workgroup route gets UINT32_MAX in its first cell.
+ * A cluster of the whole-GPU route with 2^31 rows or entries or more is refused with RPVG_HIP_ERR_INVALID (named in last_error)
+ * before anything is launched. */
+int rpvg_hip_min_path_cover_any(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters,
+                                const uint32_t * clusters, const uint64_t * cover_off, uint32_t * cover, uint32_t * cover_size,
+                                uint64_t grid_min_work, uint32_t * choice_order);
+/* the numbers of rpvg_amd/csrc/cover_plan.hpp */
+typedef struct rpvg_cover_limits {
+    uint32_t workgroup_max_paths;     /* the widest cluster of the workgroup route */
+    uint32_t chunk_rounds;            /* greedy rounds queued between two looks at the control record */
+    uint64_t default_grid_min_work;   /* rows + entries; UINT64_MAX: width only */
+    uint64_t grid_max_rows;           /* the largest cluster of the whole-GPU route */
+    uint64_t grid_max_entries;
+    uint32_t pick_block;              /* threads of a workgroup of the pick kernel */
+    uint32_t pick_per_thread;         /* paths of a thread within its workgroup's tile (pick_block apart) */
+    uint32_t pick_max_blocks;
+    uint32_t strike_block;
+    uint32_t strike_max_blocks;
+    uint32_t hist_max_paths;          /* the widest cluster whose struck gains go through an LDS histogram */
+} rpvg_cover_limits;
+void rpvg_hip_cover_limits(rpvg_cover_limits * limits_out);
 
 /* ---- path clustering ------------------------------------------------------- */
 /* PathClusters (src/path_clusters.cpp:12-86 constructor, :163-207 createPathClusters, :88-262 addNodeClusters +
@@ -724,6 +753,9 @@ typedef struct rpvg_hip_kernel_stats {
      * (num_samples x gibbs_thin_its each) */
     uint64_t gibbs_count_grid_problems;
     uint64_t gibbs_count_grid_iterations;
+    /* rpvg_hip_min_path_cover_any: clusters that took the whole-GPU route (path_cover_grid.hip) and the paths their greedy rounds chose */
+    uint64_t cover_grid_problems;
+    uint64_t cover_grid_rounds;
 } rpvg_hip_kernel_stats;
 
 int rpvg_hip_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_kernel_stats * stats_out);

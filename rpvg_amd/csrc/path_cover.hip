@@ -18,6 +18,8 @@
 // The chosen paths are kept as a bit per path and written out in ascending order by a prefix sum (:337).
 
 #include "common.hpp"
+#include "cover_plan.hpp"
+#include "cover_terms.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -27,13 +29,7 @@ using namespace rpvg_hip_detail;
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kMaxPaths = 9600;  // two vectors of doubles per path in 150 KiB of LDS
-
-// Utils::doubleCompare(x, 1) (src/utils.hpp:87-93)
-__device__ __forceinline__ bool isOne(const double x) {
-    const double precision = 2.220446049250313e-16 * 100;
-    return (x == 1.0) || (fabs(x - 1.0) < fabs(fmin(x, 1.0)) * precision);
-}
+constexpr uint32_t kMaxPaths = rpvg_cover::kWorkgroupMaxPaths;  // two vectors of doubles per path in 150 KiB of LDS
 
 // covered: one byte per row of every LISTED problem (problem p's rows from covered_off[p]): a cluster listed twice is two
 // independent problems.
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void minPathCoverKernel(
         __syncthreads();  // (the previous batch is done with batch_off / batch_count; first batch: weights are zero)
         if (threadIdx.x < batch_rows) {
             const uint64_t r = rb + threadIdx.x;
-            const double c = isOne(row_noise[r]) ? 0.0 : row_count[r];
+            const double c = coverRowCount(row_count[r], row_noise[r]);
             covered[r - r0] = (c > 0.0) ? 0 : 1;
             batch_count[threadIdx.x] = c;
             batch_off[threadIdx.x + 1] = static_cast<uint32_t>(row_ent_off[r + 1] - e_first);
@@ -104,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void minPathCoverKernel(
                 }
                 win_row[threadIdx.x] = static_cast<uint8_t>(lo);
                 win_path[threadIdx.x] = ent_path[e_first + t];
-                win_term[threadIdx.x] = mulRounded(log(ent_prob[e_first + t]), batch_count[lo]);
+                win_term[threadIdx.x] = coverTerm(ent_prob[e_first + t], batch_count[lo]);
             }
             __syncthreads();
             if (wave == 0) {
@@ -207,11 +203,10 @@ __global__ __launch_bounds__(kBlock) void minPathCoverKernel(
 
 }  // namespace
 
-extern "C" int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters,
-                                       const uint32_t * clusters, const uint64_t * cover_off, uint32_t * cover,
-                                       uint32_t * cover_size) {
-    RPVG_REQUIRE(ctx && batch, "rpvg_hip_min_path_cover: NULL argument");
-    if (num_clusters == 0) return RPVG_HIP_OK;
+// The workgroup route of the listed clusters: validation, one launch, the covers on the host.  The caller holds the context's mutex
+// (rpvg_hip_min_path_cover, and rpvg_hip_min_path_cover_any for the clusters it leaves on this route: path_cover_grid.hip).
+int rpvg_hip_detail::minPathCoverWorkgroups(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters, const uint32_t * clusters,
+                                            const uint64_t * cover_off, uint32_t * cover, uint32_t * cover_size) {
     RPVG_REQUIRE(clusters && cover_off && cover && cover_size, "rpvg_hip_min_path_cover: NULL argument");
     uint32_t max_paths = 0;
     std::vector<uint64_t> covered_off(num_clusters + 1, 0);  // the rows of the listed problems, one after the other
@@ -229,7 +224,6 @@ extern "C" int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch 
                  max_paths, kMaxPaths);
     const size_t lds = (static_cast<size_t>(max_paths) * 16 + 15) & ~static_cast<size_t>(15);
 
-    std::lock_guard<std::mutex> lock(ctx->mutex);
     RPVG_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DeviceBuffer<uint32_t> d_clusters, d_cover, d_size;
@@ -259,4 +253,13 @@ extern "C" int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch 
     RPVG_HIP_CHECK(d_size.download(cover_size, st));
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
     return RPVG_HIP_OK;
+}
+
+extern "C" int rpvg_hip_min_path_cover(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, uint32_t num_clusters,
+                                       const uint32_t * clusters, const uint64_t * cover_off, uint32_t * cover,
+                                       uint32_t * cover_size) {
+    RPVG_REQUIRE(ctx && batch, "rpvg_hip_min_path_cover: NULL argument");
+    if (num_clusters == 0) return RPVG_HIP_OK;
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    return minPathCoverWorkgroups(ctx, batch, num_clusters, clusters, cover_off, cover, cover_size);
 }

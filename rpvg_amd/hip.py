@@ -23,7 +23,7 @@ EXPORTS = [
     "rpvg_hip_batch_upload", "rpvg_hip_batch_free", "rpvg_hip_em_solve", "rpvg_hip_em_dense",
     "rpvg_hip_dense_from_cluster", "rpvg_hip_groups_build", "rpvg_hip_groups_free", "rpvg_hip_groups_collapse_info", "rpvg_hip_group_loglik",
     "rpvg_hip_synth_dense_cluster", "rpvg_hip_stats_get", "rpvg_hip_stats_reset", "rpvg_hip_stats_intervals", "rpvg_hip_em_kernel_name",
-    "rpvg_hip_gibbs_read_counts", "rpvg_hip_min_path_cover", "rpvg_hip_bounded_pair_posteriors", "rpvg_hip_pair_posteriors_get", "rpvg_hip_pair_posteriors_free",
+    "rpvg_hip_gibbs_read_counts", "rpvg_hip_min_path_cover", "rpvg_hip_min_path_cover_any", "rpvg_hip_cover_limits", "rpvg_hip_bounded_pair_posteriors", "rpvg_hip_pair_posteriors_get", "rpvg_hip_pair_posteriors_free",
     "rpvg_hip_em_dense_sharded", "rpvg_hip_synth_dense_rows", "rpvg_hip_synth_dense_cluster_batch", "rpvg_hip_comm_unique_id", "rpvg_hip_comm_init",
     "rpvg_hip_comm_destroy", "rpvg_hip_comm_allreduce_sum_f64", "rpvg_hip_comm_init_all", "rpvg_hip_gather", "rpvg_hip_host_register", "rpvg_hip_host_unregister", "rpvg_hip_group_conditionals",
     "rpvg_hip_group_gibbs", "rpvg_hip_group_gibbs_polyploid", "rpvg_hip_gibbs_sets_get", "rpvg_hip_gibbs_sets_free",
@@ -110,12 +110,30 @@ class CKernelStats(C.Structure):
         ("search_tile_ms", C.c_double), ("search_tile_launches", C.c_uint64),
         ("gibbs_calls_completed", C.c_uint64),
         ("gibbs_count_grid_problems", C.c_uint64), ("gibbs_count_grid_iterations", C.c_uint64),
+        ("cover_grid_problems", C.c_uint64), ("cover_grid_rounds", C.c_uint64),
     ]
 
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "em_kernel"}
         d["em_kernel"] = {em_kernel_name(i): {n: getattr(self.em_kernel[i], n) for n, _ in CEmKernelStats._fields_} for i in range(EM_KERNELS)}
         return d
+
+
+GRID_NEVER = 2 ** 64 - 1  # grid_min_work of Context.min_path_cover_any: every cluster that fits stays on the workgroup route
+
+
+class CCoverLimits(C.Structure):
+    """rpvg_cover_limits"""
+    _fields_ = [("workgroup_max_paths", C.c_uint32), ("chunk_rounds", C.c_uint32), ("default_grid_min_work", C.c_uint64),
+                ("grid_max_rows", C.c_uint64), ("grid_max_entries", C.c_uint64), ("pick_block", C.c_uint32), ("pick_per_thread", C.c_uint32),
+                ("pick_max_blocks", C.c_uint32), ("strike_block", C.c_uint32), ("strike_max_blocks", C.c_uint32), ("hist_max_paths", C.c_uint32)]
+
+
+def cover_limits() -> CCoverLimits:
+    """The numbers of the minimum path cover's plan (rpvg_amd/csrc/cover_plan.hpp); needs no GPU."""
+    out = CCoverLimits()
+    lib().rpvg_hip_cover_limits(C.byref(out))
+    return out
 
 
 def em_kernel_name(index: int) -> str:
@@ -137,6 +155,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(LIB_PATH)
         L.rpvg_hip_last_error.restype = C.c_char_p
         L.rpvg_hip_full_set_count.restype = C.c_uint64
+        L.rpvg_hip_cover_limits.restype = None
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -745,6 +764,29 @@ class Context:
                                              C.c_void_p(off.ctypes.data), C.c_void_p(cover.ctypes.data),
                                              C.c_void_p(size.ctypes.data)), "rpvg_hip_min_path_cover")
         return [[int(x) for x in cover[int(off[i]):int(off[i]) + int(size[i])]] for i in range(len(cl))]
+
+    def min_path_cover_any(self, batch: DeviceBatch, clusters: Sequence[int], extra: Optional[Sequence[int]] = None, grid_min_work: int = 0,
+                           order: bool = False):
+        """rpvg_hip_min_path_cover_any: the covers of clusters of any size, each on the route cover_limits() and grid_min_work give it
+        (0: the library default, 1: every cluster of two paths and more over the whole GPU, GRID_NEVER: width only).  With order=True
+        also, per listing, the paths in the order the rounds chose them — None for a cluster of the workgroup route."""
+        cl = np.ascontiguousarray(clusters, dtype=np.uint32)
+        n_paths = [int(batch.host.cluster_path_off[k + 1] - batch.host.cluster_path_off[k]) for k in clusters]
+        off = np.zeros(len(cl) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(n_paths if extra is None else [n + int(x) for n, x in zip(n_paths, extra)])
+        cover = np.zeros(int(off[-1]), dtype=np.uint32)
+        chosen = np.zeros(int(off[-1]), dtype=np.uint32)
+        size = np.zeros(len(cl), dtype=np.uint32)
+        _check(lib().rpvg_hip_min_path_cover_any(self.handle, batch.handle, C.c_uint32(len(cl)), C.c_void_p(cl.ctypes.data),
+                                                 C.c_void_p(off.ctypes.data), C.c_void_p(cover.ctypes.data), C.c_void_p(size.ctypes.data),
+                                                 C.c_uint64(grid_min_work), C.c_void_p(chosen.ctypes.data if order else None)),
+               "rpvg_hip_min_path_cover_any")
+        covers = [[int(x) for x in cover[int(off[i]):int(off[i]) + int(size[i])]] for i in range(len(cl))]
+        if not order:
+            return covers
+        orders = [None if n_paths[i] and int(chosen[int(off[i])]) == 0xFFFFFFFF else [int(x) for x in chosen[int(off[i]):int(off[i]) + int(size[i])]]
+                  for i in range(len(cl))]
+        return covers, orders
 
     # ---- dense ----------------------------------------------------------------
     def malloc(self, nbytes: int) -> int:

@@ -164,6 +164,8 @@ void HipEngine::stats(const std::vector<const HipEngine *> & engines, rpvg_hip_k
         stats_out->gibbs_calls_completed += lane_stats.gibbs_calls_completed;
         stats_out->gibbs_count_grid_problems += lane_stats.gibbs_count_grid_problems;
         stats_out->gibbs_count_grid_iterations += lane_stats.gibbs_count_grid_iterations;
+        stats_out->cover_grid_problems += lane_stats.cover_grid_problems;
+        stats_out->cover_grid_rounds += lane_stats.cover_grid_rounds;
 
         for (int i = 0; i < RPVG_HIP_EM_KERNELS; ++i) {
 
