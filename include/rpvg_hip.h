@@ -280,6 +280,16 @@ void rpvg_hip_groups_free(rpvg_hip_ctx * ctx, rpvg_hip_groups * groups);
  * (otherwise only the rows close to such a pair are); rows that took part in a replay. */
 int rpvg_hip_groups_collapse_info(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t * matrices_replayed,
                                   uint32_t * rows_replaced, uint32_t * matrices_sorted_whole, uint32_t * active_rows);
+/* A test entry, not part of the estimators' path: the segment sort at the head of the row collapse on caller-supplied words, so
+ * that its network is testable without a whole collapse.  Segment s is words[segment_off[s] .. segment_off[s + 1])
+ * (segment_off[0] = 0, ascending, num_segments + 1 entries, fewer than 2^31 words in all); out receives every segment's words
+ * in ascending order, at the segment's place.  The words of a segment must be distinct and below UINT64_MAX (the collapse's
+ * words carry their row; UINT64_MAX pads).  It runs the device routines and launches of the collapse — the small kernel for
+ * segments of up to 1 024 words, the chunk kernel, the merge rounds the longest segment needs, the read-back of every
+ * chunked segment from the buffer its own last round left it in — without the computation of the rows' keys and without
+ * the positions, "equal to its predecessor" and stretch starts the collapse writes. */
+int rpvg_hip_segment_sort_words(rpvg_hip_ctx * ctx, const uint64_t * words, const uint64_t * segment_off, uint32_t num_segments,
+                                uint64_t * out);
 
 /* Evaluates, for every request q,
  *   out[q] = sum_i count_i * log( noise_i + ( sum_{m < width, members[q*width+m] != UINT32_MAX}

@@ -33,6 +33,7 @@
 // whatever std::sort makes of it.
 
 #include "common.hpp"
+#include "segment_sort_plan.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1355,20 +1356,26 @@ namespace {
 // matrix in one go — writes the sorted keys and rows, every row's sorted position, "equal to its predecessor" and the
 // stretch starts itself.  A larger matrix lists its chunks of 2 048 rows; they are sorted the same way into a buffer and
 // merged pairwise, round by round (merge path: every thread finds its eight output words by a binary search on its
-// diagonal), ceil(log2(chunks)) rounds for the largest matrix there can be; a last kernel writes what the one-chunk matrices
-// wrote in the sort.  (Rounds 2-3: hipcub::DeviceRadixSort over all rows of all matrices — five passes of three launches
+// diagonal) — the host launches ceil(log2(chunks)) rounds for the largest matrix there can be, a matrix takes part in
+// the rounds it needs itself; a last kernel writes what the one-chunk matrices wrote in the sort.  (Rounds 2-3:
+// hipcub::DeviceRadixSort over all rows of all matrices — five passes of three launches
 // each, 0.31 ms of a lane's 1.2 ms of collapse standing alone — and DeviceSegmentedRadixSort for the EM problems, 0.5 ms in
 // one kernel behind a host wait for its partition sizes, plus a kernel for the keys and one for "equal to its predecessor"
 // that walked every row slot.  A first version of this one sorted chunks of 8 192 rows on 512 threads whatever the matrix —
 // 0.28 ms for the 5 000 matrices of a configs[2] batch, two workgroups per CU — and ranked every element of a large matrix in
 // every other chunk of it: chunks squared, 0.17-0.64 ms.)
-constexpr uint32_t kSmallSortRows = 1024;
-constexpr uint32_t kSmallSortThreads = 128;
-constexpr uint32_t kSortChunkRows = 2048;
-constexpr uint32_t kSortChunkThreads = 256;
+// (The network itself: segment_sort_plan.hpp has the schedule — size classes, kind, partner and direction of every stage, the
+// rounds a segment needs — and sortWordsInRegisters below runs it with the words in registers: a lane holds up to eight
+// consecutive elements, stages inside a lane are register compare-exchanges, stages inside a wavefront lane exchanges, and only
+// the stages across wavefronts go through LDS behind a barrier.  docs/design/kernels-collapse.md, "Segment sort in registers".)
+constexpr uint32_t kSmallSortRows = rpvg_sort::kSmallSortRows;
+constexpr uint32_t kOneWaveSortRows = rpvg_sort::kOneWaveRows;
+constexpr uint32_t kSmallSortThreads = rpvg_sort::kSmallSortWaves * rpvg_sort::kWaveLanes;
+constexpr uint32_t kSortChunkRows = rpvg_sort::kChunkRows;
+constexpr uint32_t kSortChunkThreads = rpvg_sort::kChunkWaves * rpvg_sort::kWaveLanes;
 constexpr uint32_t kMergeTile = 1024;                       // output words of a merge round per work item
 constexpr uint32_t kMergeThreads = 128;
-constexpr uint32_t kSortRowBits = 20;                       // rows of a matrix the packed word can tell apart
+constexpr uint32_t kSortRowBits = rpvg_sort::kRowBits;      // rows of a matrix the packed word can tell apart
 constexpr uint64_t kSortMaxSegmentRows = (1ull << kSortRowBits) - 1;
 
 template <int HASH>
@@ -1428,6 +1435,15 @@ __device__ __forceinline__ uint64_t sortKeyOfRow(const CsrArrays & g, const uint
     return k;
 }
 
+// caller-supplied words instead of rows (rpvg_hip_segment_sort_words: the sort alone, for its test)
+struct WordArrays {
+    const uint64_t * words;
+    const uint64_t * segment_off;
+    uint64_t * out;
+    __device__ __forceinline__ uint64_t rowOffset(const uint32_t s) const { return segment_off[s]; }
+    __device__ __forceinline__ uint64_t numRows(const uint32_t s) const { return segment_off[s + 1] - segment_off[s]; }
+};
+
 template <typename Arrays>
 struct SegmentSortArgs {
     Arrays g;
@@ -1447,13 +1463,19 @@ struct SegmentSortArgs {
     uint32_t * position_of;              // by row: its sorted position
     uint8_t * same_prev;
     uint32_t * stretch_start;
-    uint64_t * words_a, * words_b;       // [total rows] each: the sorted runs of the larger matrices, source and target of a merge round in turn
+    uint64_t * words_a, * words_b;       // [total rows] each: buffers 0 and 1 of the merge rounds (segment_sort_plan.hpp); the chunk sort writes words_a
     uint32_t * chunks;                   // [2 x capacity] (matrix, chunk of kSortChunkRows rows) of the matrices beyond kSmallSortRows rows
     uint32_t * chunk_count;
     uint32_t chunk_capacity;
     uint32_t round;                      // of the merge
-    uint32_t rounds;
 };
+
+// the word row i of matrix m is sorted as
+template <typename Arrays>
+__device__ __forceinline__ uint64_t sortWordOfRow(const SegmentSortArgs<Arrays> & a, const uint32_t m, const uint64_t r0, const uint32_t i) {
+    return packSortWord<Arrays::kHashBits>(sortKeyOfRow(a.g, m, r0, i, a.key_in, a.pattern_out), i);
+}
+__device__ __forceinline__ uint64_t sortWordOfRow(const SegmentSortArgs<WordArrays> & a, const uint32_t, const uint64_t r0, const uint32_t i) { return a.g.words[r0 + i]; }
 
 template <typename Arrays>
 __device__ __forceinline__ void writeSortedPosition(const SegmentSortArgs<Arrays> & a, const uint32_t m, const uint64_t r0, const uint64_t position, const uint64_t word,
@@ -1472,63 +1494,232 @@ __device__ __forceinline__ void writeSortedPosition(const SegmentSortArgs<Arrays
     a.same_prev[position] = same;
     a.stretch_start[position] = same ? 0u : static_cast<uint32_t>(position);
 }
+__device__ __forceinline__ void writeSortedPosition(const SegmentSortArgs<WordArrays> & a, const uint32_t, const uint64_t, const uint64_t position, const uint64_t word,
+                                                    const uint64_t, const bool) {
+    a.g.out[position] = word;
+}
 
-// the rows [c0, c0 + n) of matrix m, sorted in `words` (LDS, `padded` >= n a power of two) by the calling workgroup
-template <typename Arrays>
-__device__ __forceinline__ void sortChunkInLds(const SegmentSortArgs<Arrays> & a, const uint32_t m, const uint64_t r0, const uint64_t c0, const uint32_t n,
-                                               const uint32_t padded, uint64_t * words) {
-    constexpr int HASH = Arrays::kHashBits;
-    for (uint32_t i = threadIdx.x; i < padded; i += blockDim.x) {
-        words[i] = i < n ? packSortWord<HASH>(sortKeyOfRow(a.g, m, r0, static_cast<uint32_t>(c0 + i), a.key_in, a.pattern_out), static_cast<uint32_t>(c0 + i)) : ~0ull;
+// ---- the network in registers --------------------------------------------------------------------------------------------------
+// The word of lane ^ D.  D = 1, 2: DPP quad_perm (a modifier of a VALU move, nothing leaves the SIMD); D = 4, 8: ds_swizzle in
+// bit mode (the LDS crossbar without an address register or memory: the instruction set has no DPP pattern that is an XOR by 4
+// or 8).  D = 16, 32 take v_permlane16_swap / v_permlane32_swap in exchangeStage below.
+template <uint32_t D>
+__device__ __forceinline__ uint64_t wordOfLaneXor(const uint64_t x) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8, "lane distance");
+    const int lo = static_cast<int>(static_cast<uint32_t>(x)), hi = static_cast<int>(static_cast<uint32_t>(x >> 32));
+    int other_lo, other_hi;
+    if constexpr (D == 1) {
+        other_lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
+        other_hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
+    } else if constexpr (D == 2) {
+        other_lo = __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);  // quad_perm [2,3,0,1]
+        other_hi = __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);
+    } else {
+        constexpr int pattern = static_cast<int>((D << 10) | 0x1F);            // bit mode: and 0x1f, or 0, xor D
+        other_lo = __builtin_amdgcn_ds_swizzle(lo, pattern);
+        other_hi = __builtin_amdgcn_ds_swizzle(hi, pattern);
+    }
+    return (static_cast<uint64_t>(static_cast<uint32_t>(other_hi)) << 32) | static_cast<uint32_t>(other_lo);
+}
+
+// a stage between the lanes l and l ^ D of a wavefront: every word of the lane meets the same word of the other lane
+template <int E, uint32_t D>
+__device__ __forceinline__ void exchangeStage(uint64_t (&v)[E], const bool keep_smaller) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if constexpr (D == 16 || D == 32) {
+            // Both operands are the lane's word: the swap (odd rows of 16 of the first <-> even rows of the second; upper half of
+            // the first <-> lower half of the second) leaves, in BOTH lanes of a pair, the lower lane's word in the first and
+            // the upper lane's in the second result.
+            const uint32_t lo = static_cast<uint32_t>(v[e]), hi = static_cast<uint32_t>(v[e] >> 32);
+            const auto l = D == 16 ? __builtin_amdgcn_permlane16_swap(lo, lo, false, false) : __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+            const auto h = D == 16 ? __builtin_amdgcn_permlane16_swap(hi, hi, false, false) : __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+            const uint64_t lower = (static_cast<uint64_t>(h[0]) << 32) | l[0], upper = (static_cast<uint64_t>(h[1]) << 32) | l[1];
+            v[e] = ((lower < upper) == keep_smaller) ? lower : upper;
+        } else {
+            const uint64_t other = wordOfLaneXor<D>(v[e]);
+            v[e] = ((other < v[e]) == keep_smaller) ? other : v[e];
+        }
+    }
+}
+
+// a stage across the wavefronts of the workgroup: thread t meets thread t ^ distance through LDS (word e of everybody side by
+// side: no bank conflicts), two barriers
+template <int E, int WAVES>
+__device__ __forceinline__ void exchangeThroughLds(uint64_t (&v)[E], uint64_t * lds, const uint32_t t, const uint32_t distance, const bool keep_smaller) {
+    constexpr uint32_t T = rpvg_sort::kWaveLanes * WAVES;
+#pragma unroll
+    for (int e = 0; e < E; ++e) lds[e * T + t] = v[e];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint64_t other = lds[e * T + (t ^ distance)];
+        v[e] = ((other < v[e]) == keep_smaller) ? other : v[e];
     }
     __syncthreads();
-    for (uint32_t k = 2; k <= padded; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < (padded >> 1); t += blockDim.x) {
-                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // bit j of i is clear
-                const uint32_t l = i | j;
-                const uint64_t x = words[i], y = words[l];
-                if (((i & k) == 0) == (x > y)) {
-                    words[i] = y;
-                    words[l] = x;
+}
+
+// a stage inside the lane: words e and e | j
+template <int E>
+__device__ __forceinline__ void inLaneStage(uint64_t (&v)[E], const uint32_t t, const uint32_t k, const uint32_t j) {
+#pragma unroll
+    for (uint32_t e = 0; e < static_cast<uint32_t>(E); ++e) {
+        if (e & j) continue;
+        const bool ascending = rpvg_sort::ascendingAt(t * E + e, k);
+        const uint64_t x = v[e], y = v[e | j];
+        const bool swap = (x > y) == ascending;
+        v[e] = swap ? y : x;
+        v[e | j] = swap ? x : y;
+    }
+}
+
+// ... all of them in one direction (k beyond the lane's words)
+template <int E>
+__device__ __forceinline__ void inLaneStageDirected(uint64_t (&v)[E], const bool ascending, const uint32_t j) {
+#pragma unroll
+    for (uint32_t e = 0; e < static_cast<uint32_t>(E); ++e) {
+        if (e & j) continue;
+        const uint64_t x = v[e], y = v[e | j];
+        const bool swap = (x > y) == ascending;
+        v[e] = swap ? y : x;
+        v[e | j] = swap ? x : y;
+    }
+}
+
+// Thread t of a group of WAVES wavefronts holds the elements t E .. t E + E - 1 of a bitonic network over 64 WAVES E words
+// (segment_sort_plan.hpp); afterwards they ascend with the element index.  WAVES > 1: the group is the whole workgroup, `lds`
+// holds 64 WAVES E words nobody else uses, and every thread of the workgroup calls.  The stages between lanes are a loop with
+// one body per lane distance, not the unrolled network: thirteen instantiations of up to 66 stages each would not fit the
+// instruction cache side by side.
+template <int E, int WAVES>
+__device__ __forceinline__ void sortWordsInRegisters(uint64_t (&v)[E], uint64_t * lds, const uint32_t t) {
+    constexpr uint32_t N = rpvg_sort::kWaveLanes * WAVES * E;
+    (void) lds;
+#pragma unroll
+    for (uint32_t k = 2; k <= static_cast<uint32_t>(E); k <<= 1) {
+#pragma unroll
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) inLaneStage<E>(v, t, k, j);
+    }
+#pragma unroll 1
+    for (uint32_t k = 2 * E; k <= N; k <<= 1) {
+        const bool ascending = rpvg_sort::ascendingAt(t * E, k);  // (k > E: the same for every word of the lane)
+#pragma unroll 1
+        for (uint32_t j = k >> 1; j >= static_cast<uint32_t>(E); j >>= 1) {
+            const uint32_t distance = rpvg_sort::laneDistance(j, E);
+            const bool keep_smaller = ((t & distance) == 0) == ascending;  // rpvg_sort::keepsSmaller(t E + e, k, j)
+            if (rpvg_sort::stageKind(j, E) == rpvg_sort::kAcrossWaves) {
+                if constexpr (WAVES > 1) exchangeThroughLds<E, WAVES>(v, lds, t, distance, keep_smaller);
+            } else {
+                switch (distance) {
+                    case 1: exchangeStage<E, 1>(v, keep_smaller); break;
+                    case 2: exchangeStage<E, 2>(v, keep_smaller); break;
+                    case 4: exchangeStage<E, 4>(v, keep_smaller); break;
+                    case 8: exchangeStage<E, 8>(v, keep_smaller); break;
+                    case 16: exchangeStage<E, 16>(v, keep_smaller); break;
+                    default: exchangeStage<E, 32>(v, keep_smaller); break;
                 }
             }
+        }
+#pragma unroll
+        for (uint32_t j = static_cast<uint32_t>(E) >> 1; j > 0; j >>= 1) inLaneStageDirected<E>(v, ascending, j);
+    }
+}
+
+// what one wavefront wrote to LDS is seen by its other lanes (the LDS runs a wavefront's accesses in order: nothing to wait for,
+// the compiler must only keep the order); WAVES > 1: a workgroup barrier
+template <int WAVES>
+__device__ __forceinline__ void sortGroupSync() {
+    if constexpr (WAVES > 1) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// The rows [c0, c0 + n) of matrix m, n <= 64 WAVES E, sorted by the calling group of WAVES wavefronts (thread t of it) into
+// image[0 .. n).  A thread loads the rows t, t + 64 WAVES .. (coalesced; for the EM problems their keys are computed here, by
+// the lane that owns the word) — which word starts in which element of the network does not matter to a sort — pads with
+// ~0, runs the network and writes its E consecutive words of the result to the image, from which the caller's threads read
+// them side by side together with their predecessors.  WAVES > 1: the whole workgroup calls, behind a barrier that
+// separates it from the image's last readers.
+template <typename Arrays, int E, int WAVES>
+__device__ __forceinline__ void sortSegmentWords(const SegmentSortArgs<Arrays> & a, const uint32_t m, const uint64_t r0, const uint64_t c0, const uint32_t n,
+                                                 uint64_t * image, const uint32_t t) {
+    constexpr uint32_t T = rpvg_sort::kWaveLanes * WAVES;
+    uint64_t v[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint32_t i = e * T + t;
+        v[e] = i < n ? sortWordOfRow(a, m, r0, static_cast<uint32_t>(c0 + i)) : rpvg_sort::kPaddingWord;
+    }
+    sortWordsInRegisters<E, WAVES>(v, image, t);
+#pragma unroll
+    for (int e = 0; e < E; ++e) image[t * E + e] = v[e];
+    sortGroupSync<WAVES>();
+}
+
+// ... with the size class chosen by n (uniform in the group)
+template <typename Arrays, int WAVES>
+__device__ __forceinline__ void sortSegmentOfGroup(const SegmentSortArgs<Arrays> & a, const uint32_t m, const uint64_t r0, const uint64_t c0, const uint32_t n,
+                                                   uint64_t * image, const uint32_t t) {
+    switch (rpvg_sort::classOfGroup(n, WAVES).words_per_lane) {
+        case 1: sortSegmentWords<Arrays, 1, WAVES>(a, m, r0, c0, n, image, t); break;
+        case 2: sortSegmentWords<Arrays, 2, WAVES>(a, m, r0, c0, n, image, t); break;
+        case 4: sortSegmentWords<Arrays, 4, WAVES>(a, m, r0, c0, n, image, t); break;
+        default: sortSegmentWords<Arrays, 8, WAVES>(a, m, r0, c0, n, image, t); break;
+    }
+}
+
+// Matrices of up to kSmallSortRows rows — nearly all of a batch.  A workgroup of two wavefronts draws two matrices at a time
+// with a grid-stride loop: a matrix of up to 512 rows is sorted by ONE wavefront in its half of the 8 KB of LDS, without a
+// workgroup barrier, next to the other wavefront's; a matrix of 513 .. 1 024 rows then takes both.  Sixteen workgroups per CU.
+// A larger matrix lists its chunks for the kernel below.  (amdgpu_waves_per_eu(4): left alone the compiler takes 138 VGPRs for
+// the EM problems' instantiation, three wavefronts per SIMD — fewer than a launch of 3 800 problems puts on 1 024 SIMDs; 128 cost
+// it no spill.  A floor of five spills.)
+template <typename Arrays>
+__global__ __launch_bounds__(kSmallSortThreads) __attribute__((amdgpu_waves_per_eu(4))) void collapseSmallSortKernel(const SegmentSortArgs<Arrays> a) {
+    __shared__ uint64_t words[kSmallSortRows];
+    const uint32_t M = a.num_matrices_dev ? min(*a.num_matrices_dev, a.num_matrices) : a.num_matrices;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / rpvg_sort::kWaveLanes), lane = threadIdx.x % rpvg_sort::kWaveLanes;
+    for (uint64_t m0 = static_cast<uint64_t>(blockIdx.x) * rpvg_sort::kSmallSortWaves; m0 < M; m0 += static_cast<uint64_t>(gridDim.x) * rpvg_sort::kSmallSortWaves) {
+        if (m0 + wave < M) {  // this wavefront's matrix
+            const uint32_t m = static_cast<uint32_t>(m0 + wave);
+            const uint64_t R = a.g.numRows(m);
+            if (R > kSmallSortRows) {
+                if (lane == 0) {
+                    const uint32_t chunks = static_cast<uint32_t>((R + kSortChunkRows - 1) / kSortChunkRows);
+                    const uint32_t first = atomicAdd(a.chunk_count, chunks);
+                    for (uint32_t c = 0; c < chunks && first + c < a.chunk_capacity; ++c) {
+                        a.chunks[2 * static_cast<uint64_t>(first + c)] = m;
+                        a.chunks[2 * static_cast<uint64_t>(first + c) + 1] = c;
+                    }
+                }
+            } else if (R > 0 && R <= kOneWaveSortRows) {
+                const uint64_t r0 = a.g.rowOffset(m);
+                const uint32_t n = static_cast<uint32_t>(R);
+                uint64_t * image = words + wave * kOneWaveSortRows;
+                sortSegmentOfGroup<Arrays, 1>(a, m, r0, 0, n, image, lane);
+                for (uint32_t i = lane; i < n; i += rpvg_sort::kWaveLanes) writeSortedPosition(a, m, r0, r0 + i, image[i], i ? image[i - 1] : 0ull, i != 0);
+                sortGroupSync<1>();  // (the image is read before the wavefront's next matrix overwrites it)
+            }
+        }
+        for (uint32_t w = 0; w < rpvg_sort::kSmallSortWaves && m0 + w < M; ++w) {  // the pair's matrices of both wavefronts (uniform)
+            const uint32_t m = static_cast<uint32_t>(m0 + w);
+            const uint64_t R = a.g.numRows(m);
+            if (R <= kOneWaveSortRows || R > kSmallSortRows) continue;
+            const uint64_t r0 = a.g.rowOffset(m);
+            const uint32_t n = static_cast<uint32_t>(R);
+            __syncthreads();  // (the halves are free)
+            sortSegmentWords<Arrays, rpvg_sort::kMaxWordsPerLane, rpvg_sort::kSmallSortWaves>(a, m, r0, 0, n, words, threadIdx.x);
+            for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) writeSortedPosition(a, m, r0, r0 + i, words[i], i ? words[i - 1] : 0ull, i != 0);
             __syncthreads();
         }
     }
 }
 
-// Matrices of up to kSmallSortRows rows — nearly all of a batch: sixteen workgroups of two waves per CU, each with its matrix
-// in 8 KB of LDS, drawing matrices with a grid-stride loop.  A larger matrix lists its chunks for the kernel below.
-template <typename Arrays>
-__global__ __launch_bounds__(kSmallSortThreads) void collapseSmallSortKernel(const SegmentSortArgs<Arrays> a) {
-    __shared__ uint64_t words[kSmallSortRows];
-    const uint32_t M = a.num_matrices_dev ? min(*a.num_matrices_dev, a.num_matrices) : a.num_matrices;
-    for (uint32_t m = blockIdx.x; m < M; m += gridDim.x) {
-        const uint64_t R = a.g.numRows(m);
-        if (R == 0) continue;
-        if (R > kSmallSortRows) {
-            if (threadIdx.x == 0) {
-                const uint32_t chunks = static_cast<uint32_t>((R + kSortChunkRows - 1) / kSortChunkRows);
-                const uint32_t first = atomicAdd(a.chunk_count, chunks);
-                for (uint32_t c = 0; c < chunks && first + c < a.chunk_capacity; ++c) {
-                    a.chunks[2 * static_cast<uint64_t>(first + c)] = m;
-                    a.chunks[2 * static_cast<uint64_t>(first + c) + 1] = c;
-                }
-            }
-            continue;
-        }
-        const uint64_t r0 = a.g.rowOffset(m);
-        const uint32_t n = static_cast<uint32_t>(R);
-        uint32_t padded = 2;
-        while (padded < n) padded <<= 1;
-        __syncthreads();  // (the matrix before is done with the LDS)
-        sortChunkInLds(a, m, r0, 0, n, padded, words);
-        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) writeSortedPosition(a, m, r0, r0 + i, words[i], i ? words[i - 1] : 0ull, i != 0);
-    }
-}
-
-// the chunks of the larger matrices: sorted runs of kSortChunkRows words in words_a
+// the chunks of the larger matrices: sorted runs of kSortChunkRows words in words_a (four wavefronts, eight words per lane; a
+// matrix's short last chunk takes fewer words per lane)
 template <typename Arrays>
 __global__ __launch_bounds__(kSortChunkThreads) void collapseChunkSortKernel(const SegmentSortArgs<Arrays> a) {
     __shared__ uint64_t words[kSortChunkRows];
@@ -1538,10 +1729,8 @@ __global__ __launch_bounds__(kSortChunkThreads) void collapseChunkSortKernel(con
         const uint64_t R = a.g.numRows(m), r0 = a.g.rowOffset(m);
         const uint64_t c0 = static_cast<uint64_t>(chunk) * kSortChunkRows;
         const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kSortChunkRows), R - c0));
-        uint32_t padded = 64;
-        while (padded < n) padded <<= 1;
         __syncthreads();  // (the chunk before is done with the LDS)
-        sortChunkInLds(a, m, r0, c0, n, padded, words);
+        sortSegmentOfGroup<Arrays, rpvg_sort::kChunkWaves>(a, m, r0, c0, n, words, threadIdx.x);
         for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) a.words_a[r0 + c0 + i] = words[i];
     }
 }
@@ -1549,17 +1738,25 @@ __global__ __launch_bounds__(kSortChunkThreads) void collapseChunkSortKernel(con
 // One round of the merge: the sorted runs of length kSortChunkRows << round of every larger matrix, two by two.  Work item =
 // kMergeTile output words of a matrix (two per chunk of the list); a thread finds where its eight outputs begin in the two
 // runs by a binary search along its diagonal (merge path; the words are distinct: they carry the row) and merges them out.
+// The host launches the rounds the largest matrix it allows would need; a matrix whose runs are complete (round >=
+// mergeRoundsOf(rows)) touches no memory any more — its words stay in the buffer of its own last round, where
+// collapseMergedPositionsKernel looks for them — and while it has rounds in front of it, a last run without a partner is
+// copied (nB == 0 below), so that the runs of the next round all lie in one buffer.  (Leaving that run where it is and
+// reading it from the buffer of ITS last round would make a round merge in place: three chunks — the third waits in
+// buffer 0, which round 1 writes.)
 template <typename Arrays>
 __global__ __launch_bounds__(kMergeThreads) void collapseMergeRoundKernel(const SegmentSortArgs<Arrays> a) {
     constexpr uint32_t kPerThread = kMergeTile / kMergeThreads;
     constexpr uint32_t kTilesPerChunk = kSortChunkRows / kMergeTile;
     const uint32_t count = min(*a.chunk_count, a.chunk_capacity) * kTilesPerChunk;
-    const uint64_t * __restrict__ source = (a.round & 1) ? a.words_b : a.words_a;
-    uint64_t * __restrict__ target = (a.round & 1) ? a.words_a : a.words_b;
-    const uint64_t run = static_cast<uint64_t>(kSortChunkRows) << a.round;
+    const uint64_t * __restrict__ source = rpvg_sort::sourceBuffer(a.round) ? a.words_b : a.words_a;
+    uint64_t * __restrict__ target = rpvg_sort::targetBuffer(a.round) ? a.words_b : a.words_a;
+    const uint64_t run = rpvg_sort::runLength(a.round);
     for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
         const uint32_t m = a.chunks[2 * static_cast<uint64_t>(item / kTilesPerChunk)];
-        const uint64_t R = a.g.numRows(m), r0 = a.g.rowOffset(m);
+        const uint64_t R = a.g.numRows(m);
+        if (!rpvg_sort::roundHasWork(R, a.round)) continue;
+        const uint64_t r0 = a.g.rowOffset(m);
         const uint64_t out0 = static_cast<uint64_t>(a.chunks[2 * static_cast<uint64_t>(item / kTilesPerChunk) + 1]) * kSortChunkRows + (item % kTilesPerChunk) * kMergeTile;
         if (out0 >= R) continue;
         const uint64_t pair0 = out0 / (2 * run) * (2 * run);
@@ -1593,14 +1790,15 @@ __global__ __launch_bounds__(kMergeThreads) void collapseMergeRoundKernel(const 
     }
 }
 
-// the larger matrices' rows at their sorted positions (what the small kernel writes itself)
+// the larger matrices' rows at their sorted positions (what the small kernel writes itself), each matrix read from the buffer in
+// which its own last round left it
 template <typename Arrays>
 __global__ __launch_bounds__(256) void collapseMergedPositionsKernel(const SegmentSortArgs<Arrays> a) {
     const uint32_t count = min(*a.chunk_count, a.chunk_capacity);
-    const uint64_t * __restrict__ sorted = (a.rounds & 1) ? a.words_b : a.words_a;
     for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
         const uint32_t m = a.chunks[2 * static_cast<uint64_t>(item)], chunk = a.chunks[2 * static_cast<uint64_t>(item) + 1];
         const uint64_t R = a.g.numRows(m), r0 = a.g.rowOffset(m);
+        const uint64_t * __restrict__ sorted = rpvg_sort::finalBuffer(R) ? a.words_b : a.words_a;
         const uint64_t c0 = static_cast<uint64_t>(chunk) * kSortChunkRows;
         const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kSortChunkRows), R - c0));
         for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
@@ -1692,6 +1890,27 @@ struct SegmentSortPlan {
     uint64_t max_segment_rows = 0;                 // a bound of the rows of the largest matrix (the rounds of the merge)
 };
 
+// The launches of the segment sort: the small kernel over all matrices; for the matrices beyond it — a few dozen per batch —
+// the chunks of their list, the merge rounds and their positions.  The host does not know every matrix's rows (the EM
+// problems' kept rows are counted on the device): it launches the rounds the largest matrix its bound allows would need, and a
+// round in which no matrix has work is a dispatch and nothing else.  With no such matrix possible, nothing.
+inline uint32_t segmentSortChunkCapacity(const uint64_t total_rows, const uint32_t M) {
+    return static_cast<uint32_t>(std::min<uint64_t>(total_rows / kSortChunkRows + M + 1, 0x7fffffffull));
+}
+template <typename Arrays>
+void launchSegmentSort(SegmentSortArgs<Arrays> c, const uint32_t M, const uint64_t max_segment_rows, const uint32_t small_grid, hipStream_t st) {
+    const uint32_t pairs = (M + rpvg_sort::kSmallSortWaves - 1) / rpvg_sort::kSmallSortWaves;
+    collapseSmallSortKernel<Arrays><<<dim3(std::max<uint32_t>(1, std::min<uint32_t>(pairs, 16 * small_grid))), dim3(kSmallSortThreads), 0, st>>>(c);
+    if (max_segment_rows <= kSmallSortRows) return;
+    collapseChunkSortKernel<Arrays><<<dim3(4 * small_grid), dim3(kSortChunkThreads), 0, st>>>(c);
+    const uint32_t merge_rounds = rpvg_sort::mergeRoundsOf(max_segment_rows);
+    for (uint32_t round = 0; round < merge_rounds; ++round) {
+        c.round = round;
+        collapseMergeRoundKernel<Arrays><<<dim3(8 * small_grid), dim3(kMergeThreads), 0, st>>>(c);
+    }
+    collapseMergedPositionsKernel<Arrays><<<dim3(4 * small_grid), dim3(256), 0, st>>>(c);
+}
+
 // The stages behind the keys, for group matrices and for EM problems alike: `key` / `row` hold, per row slot, the sort key
 // (matrix, projection, largest value) and the slot itself; `info` receives [counters | zeroed words | active bytes | list sizes].
 template <typename Arrays>
@@ -1753,11 +1972,9 @@ hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const ui
     if (e == hipSuccess) ok(scan(nullptr));
     ok(tmp->sort_tmp.alloc(std::max(sort_bytes, scan_bytes)));
     // the hand-written segment sort: the chunk list of the matrices beyond the small sort, the two buffers of their merge
-    uint32_t chunk_capacity = 0, merge_rounds = 0;
+    uint32_t chunk_capacity = 0;
     if (plan) {
-        chunk_capacity = static_cast<uint32_t>(std::min<uint64_t>(total_rows / kSortChunkRows + M + 1, 0x7fffffffull));
-        const uint64_t max_chunks = (plan->max_segment_rows + kSortChunkRows - 1) / kSortChunkRows;
-        while ((1ull << merge_rounds) < max_chunks) ++merge_rounds;
+        chunk_capacity = segmentSortChunkCapacity(total_rows, M);
         ok(tmp->words_a.alloc(total_rows));
         ok(tmp->words_b.alloc(total_rows));
         ok(tmp->chunks.alloc(2 * static_cast<size_t>(chunk_capacity)));
@@ -1822,21 +2039,10 @@ hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const ui
         c.chunk_count = tmp->chunk_count.ptr;
         c.chunk_capacity = chunk_capacity;
         c.round = 0;
-        c.rounds = merge_rounds;
         if (Arrays::kHashBits) {
             collapseUnusedSlotsKernel<Arrays><<<dim3(std::max<uint32_t>(1, std::min<uint32_t>(plan->num_items_bound, 8 * small_grid))), dim3(256), 0, st>>>(c);
         }
-        collapseSmallSortKernel<Arrays><<<dim3(std::max<uint32_t>(1, std::min<uint32_t>(M, 16 * small_grid))), dim3(kSmallSortThreads), 0, st>>>(c);
-        // (the matrices beyond the small sort — a few dozen per batch: the chunks of their list, log2(chunks of the largest) rounds
-        // of merging, their positions; with no such matrix possible, nothing)
-        if (plan->max_segment_rows > kSmallSortRows) {
-            collapseChunkSortKernel<Arrays><<<dim3(4 * small_grid), dim3(kSortChunkThreads), 0, st>>>(c);
-            for (uint32_t round = 0; round < merge_rounds; ++round) {
-                c.round = round;
-                collapseMergeRoundKernel<Arrays><<<dim3(8 * small_grid), dim3(kMergeThreads), 0, st>>>(c);
-            }
-            collapseMergedPositionsKernel<Arrays><<<dim3(4 * small_grid), dim3(256), 0, st>>>(c);
-        }
+        launchSegmentSort(c, M, plan->max_segment_rows, small_grid, st);
     } else {
         collapseSamePrevKernel<Arrays><<<dim3(row_blocks), dim3(256), 0, st>>>(a);
     }
@@ -2110,5 +2316,52 @@ extern "C" int rpvg_hip_groups_collapse_info(rpvg_hip_ctx * ctx, const rpvg_hip_
     if (rows_replaced) *rows_replaced = info[kInfoRowsReplaced];
     if (matrices_sorted_whole) *matrices_sorted_whole = info[kInfoWholeMatrices];
     if (active_rows) *active_rows = info[kInfoActiveRows];
+    return RPVG_HIP_OK;
+}
+
+// The segment sort of the collapse on caller-supplied words, for its test (include/rpvg_hip.h): the launches of
+// launchSegmentSort — small kernel, chunk kernel, the rounds the longest segment needs, the read-back of every chunked segment
+// from its own final buffer — with the words as they are in place of the rows' keys and `out` in place of the positions.
+extern "C" int rpvg_hip_segment_sort_words(rpvg_hip_ctx * ctx, const uint64_t * words, const uint64_t * segment_off, uint32_t num_segments, uint64_t * out) {
+    RPVG_REQUIRE(ctx && segment_off, "rpvg_hip_segment_sort_words: NULL argument");
+    if (num_segments == 0) return RPVG_HIP_OK;
+    uint64_t longest = 0;
+    for (uint32_t s = 0; s < num_segments; ++s) {
+        RPVG_REQUIRE(segment_off[s] <= segment_off[s + 1], "rpvg_hip_segment_sort_words: segment_off descends at segment %u", s);
+        longest = std::max(longest, segment_off[s + 1] - segment_off[s]);
+    }
+    const uint64_t total = segment_off[num_segments];
+    RPVG_REQUIRE(segment_off[0] == 0 && total <= 0x7fffffffull, "rpvg_hip_segment_sort_words: segment_off must start at 0 and end below 2^31");
+    if (total == 0) return RPVG_HIP_OK;
+    RPVG_REQUIRE(words && out, "rpvg_hip_segment_sort_words: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DeviceBuffer<uint64_t> d_words, d_off, d_out, words_a, words_b;
+    DeviceBuffer<uint32_t> chunks, chunk_count;
+    const uint32_t chunk_capacity = segmentSortChunkCapacity(total, num_segments);
+    RPVG_HIP_CHECK(d_words.upload(words, total, st));
+    RPVG_HIP_CHECK(d_off.upload(segment_off, static_cast<size_t>(num_segments) + 1, st));
+    RPVG_HIP_CHECK(d_out.alloc(total));
+    RPVG_HIP_CHECK(words_a.alloc(total));
+    RPVG_HIP_CHECK(words_b.alloc(total));
+    RPVG_HIP_CHECK(chunks.alloc(2 * static_cast<size_t>(chunk_capacity)));
+    RPVG_HIP_CHECK(chunk_count.alloc(1));
+    RPVG_HIP_CHECK(zeroAsync(chunk_count.ptr, sizeof(uint32_t), st));
+    SegmentSortArgs<WordArrays> c{};
+    c.g.words = d_words.ptr;
+    c.g.segment_off = d_off.ptr;
+    c.g.out = d_out.ptr;
+    c.num_matrices = num_segments;
+    c.total_rows = total;
+    c.words_a = words_a.ptr;
+    c.words_b = words_b.ptr;
+    c.chunks = chunks.ptr;
+    c.chunk_count = chunk_count.ptr;
+    c.chunk_capacity = chunk_capacity;
+    launchSegmentSort(c, num_segments, longest, 256, st);
+    RPVG_HIP_CHECK(hipGetLastError());
+    RPVG_HIP_CHECK(d_out.download(out, st));
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
     return RPVG_HIP_OK;
 }

@@ -45,6 +45,7 @@ EXPORTS = [
     "rpvg_hip_estimates_table_free",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
+    "rpvg_hip_segment_sort_words",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -764,6 +765,17 @@ class Context:
                                              C.c_void_p(off.ctypes.data), C.c_void_p(cover.ctypes.data),
                                              C.c_void_p(size.ctypes.data)), "rpvg_hip_min_path_cover")
         return [[int(x) for x in cover[int(off[i]):int(off[i]) + int(size[i])]] for i in range(len(cl))]
+
+    def segment_sort_words(self, words, segment_off) -> np.ndarray:
+        """rpvg_hip_segment_sort_words: every segment words[segment_off[s]:segment_off[s + 1]] in ascending order, by the segment
+        sort of the row collapse (a test entry: the words of a segment distinct and below 2^64 - 1)."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(segment_off, dtype=np.uint64)
+        assert len(off) >= 1 and int(off[-1]) == len(w)
+        out = np.zeros(len(w), dtype=np.uint64)
+        _check(lib().rpvg_hip_segment_sort_words(self.handle, C.c_void_p(w.ctypes.data), C.c_void_p(off.ctypes.data),
+                                                 C.c_uint32(len(off) - 1), C.c_void_p(out.ctypes.data)), "rpvg_hip_segment_sort_words")
+        return out
 
     def min_path_cover_any(self, batch: DeviceBatch, clusters: Sequence[int], extra: Optional[Sequence[int]] = None, grid_min_work: int = 0,
                            order: bool = False):
