@@ -483,6 +483,51 @@ int rpvg_hip_nested_subset_em(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, 
 int rpvg_hip_subset_em_get(const rpvg_hip_subset_em * result, rpvg_hip_subset_em_view * view_out);
 void rpvg_hip_subset_em_free(rpvg_hip_subset_em * result);
 
+/* ---- full enumeration -> retained sets -> path subsets -> EM -> weighted merge, in one call: group sizes 1 and 3 .. 8 ---- */
+/* NestedPathAbundanceEstimator::inferAbundancesCollapsedGroups (src/path_abundance_estimator.cpp:428-471) with exact posteriors at
+ * any ploidy but two (rpvg_hip_nested_subset_em is the diploid call): the posteriors of rpvg_hip_group_full_posteriors (same kernels,
+ * same launches of at most 2^27 sets, log_freq as there: the columns of every matrix of `groups` back to back), the sets with
+ * posterior >= min_hap_prob kept per matrix in ascending rank (src/path_abundance_estimator.cpp:574-600), each expanded to the
+ * ascending concatenation of the path lists of its group_size columns, identical lists merged (masses added in ascending rank, then
+ * one division by the sum over the kept sets), subsets in lexicographic order of their lists, the EM of rpvg_hip_em_solve on every
+ * subset's distinct paths, and the posterior-weighted merge (:702-749) for sets of up to group_size paths of one transcript.  No
+ * array proportional to the number of sets reaches the host or outlives its launch.
+ * Returns RPVG_HIP_ERR_UNSUPPORTED, having changed nothing, with rpvg_hip_last_error naming the reason: group size 0, 2 or above 8;
+ * min_hap_prob below 1/1024; a matrix with more than RPVG_HIP_FULL_MAX_SETS sets; a cluster too wide for LDS-resident EM vectors; a
+ * batch uploaded without path_group_id; RPVG_HIP_NO_DEVICE_SUBSETS in the environment (read per call); capacities that did not
+ * fit after one retry; a transcript with more than group_size paths in one subset. */
+typedef struct rpvg_hip_subset_em_sets_view {
+    uint32_t num_matrices;
+    uint32_t group_size;
+    const uint64_t * subset_off;   /* [M+1]  as rpvg_hip_subset_em_view, from here ...                              */
+    const double * weight;         /* [S]                                                                            */
+    const uint64_t * path_off;     /* [S+1]                                                                          */
+    const uint32_t * path;         /*        sorted cluster-local paths, a path once per column of the set that lists it */
+    const uint64_t * col_off;      /* [S+1]                                                                          */
+    const uint32_t * col_path;
+    const double * abundances;
+    const double * noise_count;    /* [S]                                                                            */
+    const double * total_count;    /* [S]                                                                            */
+    const uint32_t * iterations;   /* [S]    ... to here                                                             */
+    /* the sets the first stage kept: of matrix m [retained_off[m], retained_off[m + 1]), ascending by rank; the rank is the set's
+     * position in the order of rpvg_hip_group_full_posteriors (lexicographic among the multisets of the matrix's columns) */
+    const uint64_t * retained_off;        /* [M+1] */
+    const uint64_t * retained_rank;
+    const double * retained_posterior;
+    /* the merged path group sets: those of matrix m in the slots [path_off[subset_off[m]], + set_count[m]), in lexicographic order of
+     * their member lists (a shorter list before its extensions); members in list order, repeats kept */
+    const uint32_t * set_count;           /* [M]                                                   */
+    const double * cluster_noise_count;   /* [M]                                                   */
+    const uint32_t * set_size;            /* members of the set: 1 .. group_size                   */
+    const uint32_t * set_member;          /* group_size per slot, unused cells UINT32_MAX          */
+    const double * set_posterior;
+    const double * set_abundance;         /* group_size per slot, unused cells 0                   */
+} rpvg_hip_subset_em_sets_view;
+int rpvg_hip_nested_full_subset_em(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_groups * groups,
+                                   uint32_t group_size, const double * log_freq, double min_hap_prob, uint32_t max_em_its,
+                                   double max_rel_em_conv, double collapse_precision, rpvg_hip_subset_em ** result_out);
+int rpvg_hip_subset_em_get_sets(const rpvg_hip_subset_em * result, rpvg_hip_subset_em_sets_view * view_out);
+
 /* ---- minimum path cover (`-i strains`) ------------------------------------ */
 /* For every listed cluster: the read-path cover and path weights of MinimumPathAbundanceEstimator::estimate
  * (src/path_abundance_estimator.cpp:233-257) and the greedy weightedMinimumPathCover (:297-340) on the GPU.
@@ -766,6 +811,11 @@ typedef struct rpvg_hip_kernel_stats {
     /* rpvg_hip_min_path_cover_any: clusters that took the whole-GPU route (path_cover_grid.hip) and the paths their greedy rounds chose */
     uint64_t cover_grid_problems;
     uint64_t cover_grid_rounds;
+    /* rpvg_hip_nested_full_subset_em: calls that returned RPVG_HIP_OK with at least one matrix, the sets they enumerated and the
+     * sets they retained (posterior >= min_hap_prob) */
+    uint64_t nested_full_calls;
+    uint64_t nested_full_sets;
+    uint64_t nested_full_retained;
 } rpvg_hip_kernel_stats;
 
 int rpvg_hip_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_kernel_stats * stats_out);

@@ -646,6 +646,7 @@ struct SubsetEmHints {
 struct rpvg_hip_ctx {
     static constexpr int kAuxStreams = 6;
     rpvg_hip_detail::SubsetEmHints subset_hints;
+    rpvg_hip_detail::SubsetEmHints subset_full_hints;  // the same for rpvg_hip_nested_full_subset_em (subset_full.hip): its lists are longer
     bool search_gate_held = false;  // the search this context has queued takes part in "one search at a time" (bounded_search.hip)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -886,6 +887,15 @@ struct rpvg_hip_groups {
 
 namespace rpvg_hip_detail {
 using namespace rpvg_em;  // the size rule and the plan of a solve (em_plan.hpp)
+// ---- one launch of the full enumeration of the group posteriors (group_full.hip) -----------------------
+struct GroupFullLaunch {  // the small device arrays of a launch (alive until the stream is waited for) and what it covered
+    DeviceBuffer<uint32_t> d_matrix;
+    DeviceBuffer<uint64_t> d_prefix_off, d_set_off, d_lf_off;
+    DeviceBuffer<double> d_lf;
+    uint64_t launch_sets = 0, lf_count = 0;
+};
+int queueGroupFullLaunch(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const uint32_t * matrix, uint32_t P, const uint64_t * sets,
+                         uint32_t group_size, const double * log_freq, GroupFullLaunch & work, double * d_out);
 // ---- EM solves on problem lists in device memory (em_sparse.hip) -------------------------------------
 // The problems may come from the host (rpvg_hip_em_solve) or be written by kernels (subset_em.hip: the path subsets the
 // diploid search retains): everything behind the list — compaction of the problems' rows, size bins, work queues, the EM

@@ -17,6 +17,7 @@
 // two runs give the same bits.
 
 #include "common.hpp"
+#include "subset_full_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,7 +29,6 @@ namespace {
 
 constexpr int kFullCand = 4;            // candidate last members per pass over the rows
 constexpr int kFullNormBlock = 256;     // threads of the per-problem normalisation
-constexpr uint64_t kFullSetsPerLaunch = uint64_t(1) << 27;  // output doubles per launch (1 GiB), a larger single problem alone
 
 struct FullLogPerm {
     double v[8];
@@ -189,6 +189,74 @@ extern "C" uint64_t rpvg_hip_full_set_count(uint32_t columns, uint32_t group_siz
     return static_cast<uint64_t>(r);
 }
 
+// One launch of the enumeration: the P problems matrix[0 .. P) with sets[0 .. P) sets each, their log frequencies back to back in
+// log_freq, posteriors (normalised per problem) back to back in d_out, which holds the sum of `sets`.  Queued on the context's
+// stream, which the caller has made wait for the matrices' collapse; `work` keeps the small device arrays until the stream is waited
+// for.  rpvg_hip_group_full_posteriors and rpvg_hip_nested_full_subset_em (subset_full.hip) both go through here: one set of kernels,
+// one order of additions.
+int rpvg_hip_detail::queueGroupFullLaunch(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const uint32_t * matrix, const uint32_t P,
+                                          const uint64_t * sets, const uint32_t group_size, const double * log_freq, GroupFullLaunch & work,
+                                          double * d_out) {
+    hipStream_t st = ctx->stream;
+    // log(numPermutations) by the number of distinct members: n! / (n - u + 1)! truncated to an integer (src/utils.hpp:95-117)
+    FullLogPerm log_perm;
+    for (uint32_t u = 1; u <= 8; ++u) {
+        double perm = 1.0;
+        if (group_size > 1 && u <= group_size) {
+            perm = static_cast<double>(static_cast<uint32_t>(std::tgamma(group_size + 1) / std::tgamma(group_size - u + 2)));
+        }
+        log_perm.v[u - 1] = std::log(perm);
+    }
+    std::vector<uint64_t> prefix_off(P + 1, 0), set_off(P + 1, 0), lf_off(P, 0);
+    uint64_t lf_count = 0;
+    double evals = 0;
+    for (uint32_t j = 0; j < P; ++j) {
+        const uint32_t G = groups->h_num_cols[matrix[j]];
+        prefix_off[j + 1] = prefix_off[j] + (G ? rpvg_hip_full_set_count(G, group_size - 1) : 0);
+        set_off[j + 1] = set_off[j] + sets[j];
+        lf_off[j] = lf_count;
+        lf_count += G;
+        evals += static_cast<double>(sets[j]) * static_cast<double>(groups->h_num_rows[matrix[j]]);
+    }
+    work.launch_sets = set_off[P];
+    work.lf_count = lf_count;
+    const uint64_t num_items = prefix_off[P];
+    const uint64_t blocks = (num_items + 3) / 4;
+    RPVG_REQUIRE(blocks <= 0x7fffffffull, "rpvg_hip_group_full_posteriors: %llu prefixes exceed one launch",
+                 static_cast<unsigned long long>(num_items));
+    int span = ctx->spanBegin(FAM_H2D);
+    RPVG_HIP_CHECK(work.d_matrix.upload(matrix, P, st));
+    RPVG_HIP_CHECK(work.d_prefix_off.upload(prefix_off.data(), P + 1, st));
+    RPVG_HIP_CHECK(work.d_set_off.upload(set_off.data(), P + 1, st));
+    RPVG_HIP_CHECK(work.d_lf_off.upload(lf_off.data(), P, st));
+    RPVG_HIP_CHECK(work.d_lf.upload(log_freq, lf_count, st));
+    ctx->spanEnd(span);
+    ctx->stats.h2d_bytes += static_cast<double>(P) * 28 + 8 + static_cast<double>(lf_count) * 8;
+    if (num_items == 0) return RPVG_HIP_OK;
+    span = ctx->spanBegin(FAM_LOGLIK);
+#define RPVG_LAUNCH_FULL(W)                                                                                                     \
+    groupFullKernel<W><<<dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st>>>(                                              \
+        P, num_items, work.d_prefix_off.ptr, work.d_set_off.ptr, work.d_lf_off.ptr, work.d_matrix.ptr, work.d_lf.ptr, log_perm, \
+        groups->view(), d_out)
+    switch (group_size) {
+        case 1: RPVG_LAUNCH_FULL(1); break;
+        case 2: RPVG_LAUNCH_FULL(2); break;
+        case 3: RPVG_LAUNCH_FULL(3); break;
+        case 4: RPVG_LAUNCH_FULL(4); break;
+        case 5: RPVG_LAUNCH_FULL(5); break;
+        case 6: RPVG_LAUNCH_FULL(6); break;
+        case 7: RPVG_LAUNCH_FULL(7); break;
+        default: RPVG_LAUNCH_FULL(8); break;
+    }
+#undef RPVG_LAUNCH_FULL
+    groupFullNormaliseKernel<<<dim3(P), dim3(kFullNormBlock), 0, st>>>(work.d_set_off.ptr, d_out);
+    ctx->spanEnd(span);
+    ctx->stats.loglik_launches += 2;
+    ctx->stats.loglik_evals += evals;
+    RPVG_HIP_CHECK(hipGetLastError());
+    return RPVG_HIP_OK;
+}
+
 extern "C" int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t num_problems,
                                               const uint32_t * matrix, uint32_t group_size, const double * log_freq,
                                               double * posteriors) {
@@ -196,7 +264,7 @@ extern "C" int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip
     if (num_problems == 0) return RPVG_HIP_OK;
     RPVG_REQUIRE(matrix && log_freq && posteriors, "rpvg_hip_group_full_posteriors: NULL request arrays");
     RPVG_REQUIRE(group_size >= 1 && group_size <= 8, "rpvg_hip_group_full_posteriors: group size %u outside [1, 8]", group_size);
-    std::vector<uint64_t> sets(num_problems), prefixes(num_problems);
+    std::vector<uint64_t> sets(num_problems);
     for (uint32_t q = 0; q < num_problems; ++q) {
         RPVG_REQUIRE(matrix[q] < groups->num_matrices, "rpvg_hip_group_full_posteriors: problem %u refers to matrix %u of %u", q,
                      matrix[q], groups->num_matrices);
@@ -207,16 +275,6 @@ extern "C" int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip
                                       q, matrix[q], G, static_cast<unsigned long long>(RPVG_HIP_FULL_MAX_SETS), group_size);
             return RPVG_HIP_ERR_UNSUPPORTED;
         }
-        prefixes[q] = G ? rpvg_hip_full_set_count(G, group_size - 1) : 0;
-    }
-    // log(numPermutations) by the number of distinct members: n! / (n - u + 1)! truncated to an integer (src/utils.hpp:95-117)
-    FullLogPerm log_perm;
-    for (uint32_t u = 1; u <= 8; ++u) {
-        double perm = 1.0;
-        if (group_size > 1 && u <= group_size) {
-            perm = static_cast<double>(static_cast<uint32_t>(std::tgamma(group_size + 1) / std::tgamma(group_size - u + 2)));
-        }
-        log_perm.v[u - 1] = std::log(perm);
     }
 
     std::lock_guard<std::mutex> lock(ctx->mutex);
@@ -227,65 +285,19 @@ extern "C" int rpvg_hip_group_full_posteriors(rpvg_hip_ctx * ctx, const rpvg_hip
     uint64_t out_first = 0, lf_first = 0;
     uint32_t first = 0;
     while (first < num_problems) {
-        // the problems of one launch: up to kFullSetsPerLaunch outputs, a larger one alone
-        uint32_t end = first;
+        // the problems of one launch: up to kSetsPerLaunch outputs, a larger one alone
+        const uint32_t end = rpvg_subset_full::chunkEnd(sets.data(), first, num_problems);
         uint64_t launch_sets = 0;
-        while (end < num_problems && (end == first || launch_sets + sets[end] <= kFullSetsPerLaunch)) launch_sets += sets[end++];
-        const uint32_t P = end - first;
-        std::vector<uint64_t> prefix_off(P + 1, 0), set_off(P + 1, 0), lf_off(P, 0);
-        uint64_t lf_count = 0;
-        double evals = 0;
-        for (uint32_t j = 0; j < P; ++j) {
-            const uint32_t G = groups->h_num_cols[matrix[first + j]];
-            prefix_off[j + 1] = prefix_off[j] + prefixes[first + j];
-            set_off[j + 1] = set_off[j] + sets[first + j];
-            lf_off[j] = lf_count;
-            lf_count += G;
-            evals += static_cast<double>(sets[first + j]) * static_cast<double>(groups->h_num_rows[matrix[first + j]]);
-        }
-        const uint64_t num_items = prefix_off[P];
-        const uint64_t blocks = (num_items + 3) / 4;
-        RPVG_REQUIRE(blocks <= 0x7fffffffull, "rpvg_hip_group_full_posteriors: %llu prefixes exceed one launch",
-                     static_cast<unsigned long long>(num_items));
-        DeviceBuffer<uint32_t> d_matrix;
-        DeviceBuffer<uint64_t> d_prefix_off, d_set_off, d_lf_off;
-        DeviceBuffer<double> d_lf, d_out;
-        int span = ctx->spanBegin(FAM_H2D);
-        RPVG_HIP_CHECK(d_matrix.upload(matrix + first, P, st));
-        RPVG_HIP_CHECK(d_prefix_off.upload(prefix_off.data(), P + 1, st));
-        RPVG_HIP_CHECK(d_set_off.upload(set_off.data(), P + 1, st));
-        RPVG_HIP_CHECK(d_lf_off.upload(lf_off.data(), P, st));
-        RPVG_HIP_CHECK(d_lf.upload(log_freq + lf_first, lf_count, st));
-        ctx->spanEnd(span);
-        ctx->stats.h2d_bytes += static_cast<double>(P) * 28 + 8 + static_cast<double>(lf_count) * 8;
+        for (uint32_t q = first; q < end; ++q) launch_sets += sets[q];
+        GroupFullLaunch work;
+        DeviceBuffer<double> d_out;
         RPVG_HIP_CHECK(d_out.alloc(launch_sets));
-
-        if (num_items) {
-            span = ctx->spanBegin(FAM_LOGLIK);
-#define RPVG_LAUNCH_FULL(W)                                                                                                     \
-    groupFullKernel<W><<<dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st>>>(                                              \
-        P, num_items, d_prefix_off.ptr, d_set_off.ptr, d_lf_off.ptr, d_matrix.ptr, d_lf.ptr, log_perm, groups->view(), d_out.ptr)
-            switch (group_size) {
-                case 1: RPVG_LAUNCH_FULL(1); break;
-                case 2: RPVG_LAUNCH_FULL(2); break;
-                case 3: RPVG_LAUNCH_FULL(3); break;
-                case 4: RPVG_LAUNCH_FULL(4); break;
-                case 5: RPVG_LAUNCH_FULL(5); break;
-                case 6: RPVG_LAUNCH_FULL(6); break;
-                case 7: RPVG_LAUNCH_FULL(7); break;
-                default: RPVG_LAUNCH_FULL(8); break;
-            }
-#undef RPVG_LAUNCH_FULL
-            groupFullNormaliseKernel<<<dim3(P), dim3(kFullNormBlock), 0, st>>>(d_set_off.ptr, d_out.ptr);
-            ctx->spanEnd(span);
-            ctx->stats.loglik_launches += 2;
-            ctx->stats.loglik_evals += evals;
-            RPVG_HIP_CHECK(hipGetLastError());
-            RPVG_HIP_CHECK(d_out.download(posteriors + out_first, st));
-        }
+        const int rc = queueGroupFullLaunch(ctx, groups, matrix + first, end - first, sets.data() + first, group_size, log_freq + lf_first, work, d_out.ptr);
+        if (rc != RPVG_HIP_OK) return rc;
+        if (launch_sets) RPVG_HIP_CHECK(d_out.download(posteriors + out_first, st));
         RPVG_HIP_CHECK(waitStream(st));  // the buffers of this launch go back to the pool on the next round
         out_first += launch_sets;
-        lf_first += lf_count;
+        lf_first += work.lf_count;
         first = end;
     }
     return groups->buildError(st);  // the matrices were built without a host sync

@@ -30,6 +30,7 @@ EXPORTS = [
     "rpvg_hip_alignments_upload", "rpvg_hip_alignments_free", "rpvg_hip_read_rows_build", "rpvg_hip_read_rows_to_batch",
     "rpvg_hip_read_rows_view", "rpvg_hip_read_rows_sizes", "rpvg_hip_read_rows_free", "rpvg_hip_path_clusters", "rpvg_hip_debug_log",
     "rpvg_hip_nested_subset_em", "rpvg_hip_subset_em_get", "rpvg_hip_subset_em_free",
+    "rpvg_hip_nested_full_subset_em", "rpvg_hip_subset_em_get_sets",
     "rpvg_hip_batch_cluster_totals", "rpvg_hip_batch_has_source_columns", "rpvg_hip_batch_source_columns_sizes",
     "rpvg_hip_batch_source_columns_get", "rpvg_hip_groups_build_from_sources", "rpvg_hip_groups_build_single_paths", "rpvg_hip_batch_upload_begin", "rpvg_hip_batch_upload_finish", "rpvg_hip_create_with_streams",
     "rpvg_hip_batch_upload_finish_queue", "rpvg_hip_batch_upload_finish_wait",
@@ -89,6 +90,18 @@ class CPairPosteriorsView(C.Structure):
                 ("second", C.POINTER(C.c_uint32)), ("posterior", C.POINTER(C.c_double))]
 
 
+class CSubsetEmSetsView(C.Structure):
+    """rpvg_hip_subset_em_sets_view"""
+    _fields_ = [("num_matrices", C.c_uint32), ("group_size", C.c_uint32), ("subset_off", C.POINTER(C.c_uint64)),
+                ("weight", C.POINTER(C.c_double)), ("path_off", C.POINTER(C.c_uint64)), ("path", C.POINTER(C.c_uint32)),
+                ("col_off", C.POINTER(C.c_uint64)), ("col_path", C.POINTER(C.c_uint32)), ("abundances", C.POINTER(C.c_double)),
+                ("noise_count", C.POINTER(C.c_double)), ("total_count", C.POINTER(C.c_double)), ("iterations", C.POINTER(C.c_uint32)),
+                ("retained_off", C.POINTER(C.c_uint64)), ("retained_rank", C.POINTER(C.c_uint64)),
+                ("retained_posterior", C.POINTER(C.c_double)), ("set_count", C.POINTER(C.c_uint32)),
+                ("cluster_noise_count", C.POINTER(C.c_double)), ("set_size", C.POINTER(C.c_uint32)), ("set_member", C.POINTER(C.c_uint32)),
+                ("set_posterior", C.POINTER(C.c_double)), ("set_abundance", C.POINTER(C.c_double))]
+
+
 EM_KERNELS = 12  # RPVG_HIP_EM_KERNELS
 
 
@@ -112,6 +125,7 @@ class CKernelStats(C.Structure):
         ("gibbs_calls_completed", C.c_uint64),
         ("gibbs_count_grid_problems", C.c_uint64), ("gibbs_count_grid_iterations", C.c_uint64),
         ("cover_grid_problems", C.c_uint64), ("cover_grid_rounds", C.c_uint64),
+        ("nested_full_calls", C.c_uint64), ("nested_full_sets", C.c_uint64), ("nested_full_retained", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -574,6 +588,67 @@ class DeviceGroups:
                                                     C.c_void_p(out.ctypes.data if out.size else None)),
                "rpvg_hip_group_full_posteriors")
         return np.split(out, np.cumsum(sizes)[:-1]) if sizes else []
+
+    def nested_full_subset_em(self, group_size: int, log_freq, min_hap_prob: float, max_em_its: int = 10000, max_rel_em_conv: float = 1e-3,
+                              collapse_precision: float = 0.0) -> dict:
+        """rpvg_hip_nested_full_subset_em on every matrix: full enumeration, retained sets, path subsets, EM and the weighted merge
+        in one call (group sizes 1 and 3 .. 8).  log_freq[m] = the log frequencies of matrix m's columns.  Returns the fields of
+        rpvg_hip_subset_em_sets_view as numpy arrays (copies; set_member and set_abundance as [slots, group_size]), plus
+        num_matrices and group_size.  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
+        lf = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in log_freq]) if len(log_freq) else np.zeros(0))
+        h = C.c_void_p()
+        _check(lib().rpvg_hip_nested_full_subset_em(self.ctx.handle, self.batch.handle, self.handle, C.c_uint32(group_size),
+                                                    C.c_void_p(lf.ctypes.data if lf.size else None), C.c_double(float(min_hap_prob)),
+                                                    C.c_uint32(max_em_its), C.c_double(float(max_rel_em_conv)),
+                                                    C.c_double(float(collapse_precision)), C.byref(h)), "rpvg_hip_nested_full_subset_em")
+        try:
+            v = CSubsetEmSetsView()
+            _check(lib().rpvg_hip_subset_em_get_sets(h, C.byref(v)), "rpvg_hip_subset_em_get_sets")
+            M, g = int(v.num_matrices), int(v.group_size)
+
+            def take(pointer, n, dtype, shape=None):
+                if n == 0 or not pointer:
+                    return np.zeros(shape if shape is not None else (0,), dtype=dtype)
+                a = np.ctypeslib.as_array(pointer, shape=(n,)).copy()
+                return a.reshape(shape) if shape is not None else a
+
+            out = {"num_matrices": M, "group_size": g}
+            if M == 0:
+                out.update({"subset_off": np.zeros(1, np.uint64), "path_off": np.zeros(1, np.uint64), "col_off": np.zeros(1, np.uint64),
+                            "retained_off": np.zeros(1, np.uint64)})
+                for name, dtype in (("weight", np.float64), ("path", np.uint32), ("col_path", np.uint32), ("abundances", np.float64),
+                                    ("noise_count", np.float64), ("total_count", np.float64), ("iterations", np.uint32),
+                                    ("retained_rank", np.uint64), ("retained_posterior", np.float64), ("set_count", np.uint32),
+                                    ("cluster_noise_count", np.float64), ("set_size", np.uint32), ("set_posterior", np.float64)):
+                    out[name] = np.zeros(0, dtype)
+                out["set_member"] = np.zeros((0, g), np.uint32)
+                out["set_abundance"] = np.zeros((0, g), np.float64)
+                return out
+            out["subset_off"] = take(v.subset_off, M + 1, np.uint64)
+            S = int(out["subset_off"][-1])
+            out["path_off"] = take(v.path_off, S + 1, np.uint64)
+            out["col_off"] = take(v.col_off, S + 1, np.uint64)
+            L, Cn = int(out["path_off"][-1]), int(out["col_off"][-1])
+            out["weight"] = take(v.weight, S, np.float64)
+            out["path"] = take(v.path, L, np.uint32)
+            out["col_path"] = take(v.col_path, Cn, np.uint32)
+            out["abundances"] = take(v.abundances, Cn, np.float64)
+            out["noise_count"] = take(v.noise_count, S, np.float64)
+            out["total_count"] = take(v.total_count, S, np.float64)
+            out["iterations"] = take(v.iterations, S, np.uint32)
+            out["retained_off"] = take(v.retained_off, M + 1, np.uint64)
+            R = int(out["retained_off"][-1])
+            out["retained_rank"] = take(v.retained_rank, R, np.uint64)
+            out["retained_posterior"] = take(v.retained_posterior, R, np.float64)
+            out["set_count"] = take(v.set_count, M, np.uint32)
+            out["cluster_noise_count"] = take(v.cluster_noise_count, M, np.float64)
+            out["set_size"] = take(v.set_size, L, np.uint32)
+            out["set_member"] = take(v.set_member, L * g, np.uint32, (L, g))
+            out["set_posterior"] = take(v.set_posterior, L, np.float64)
+            out["set_abundance"] = take(v.set_abundance, L * g, np.float64, (L, g))
+            return out
+        finally:
+            lib().rpvg_hip_subset_em_free(h)
 
     def gibbs(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
         """rpvg_hip_group_gibbs: per problem ([sorted member tuples in order of first appearance], counts); plus the words each

@@ -166,6 +166,9 @@ void HipEngine::stats(const std::vector<const HipEngine *> & engines, rpvg_hip_k
         stats_out->gibbs_count_grid_iterations += lane_stats.gibbs_count_grid_iterations;
         stats_out->cover_grid_problems += lane_stats.cover_grid_problems;
         stats_out->cover_grid_rounds += lane_stats.cover_grid_rounds;
+        stats_out->nested_full_calls += lane_stats.nested_full_calls;
+        stats_out->nested_full_sets += lane_stats.nested_full_sets;
+        stats_out->nested_full_retained += lane_stats.nested_full_retained;
 
         for (int i = 0; i < RPVG_HIP_EM_KERNELS; ++i) {
 

@@ -515,6 +515,36 @@ void NestedPathAbundanceEstimator::estimateClusters(std::vector<PathClusterEstim
             }
         }
 
+        // Exact posteriors at ploidy 5 .. 8, no read-count samples: enumeration, retained sets, subsets, EM and the weighted merge
+        // are one device call; no posterior reaches the host.  (Ploidy 1, 3 and 4 normalise with the host's add_log fold on the
+        // separate route and stay there: a cluster's estimates do not depend on the route its batch took.)  When the device does
+        // not take the batch, the calls below run unchanged.
+        if (!use_group_post_gibbs && group_size >= 5 && num_gibbs_samples == 0) {
+
+            SubsetEmResult device_result;
+
+            if (nestedFullSubsetAbundances(&device_result, cluster_batch, problems, group_size, min_hap_prob, max_em_its, max_rel_em_conv)) {
+
+                unpackMergedSetSolutions(path_cluster_estimates, cluster_batch, clusters, device_result.sets_view);
+
+                ScopedPhase teardown_phase("nested: teardown posterior containers");
+                auto old_problems = std::make_shared<std::vector<GroupPosteriorProblem> >(std::move(problems));
+
+                dropNowOrLater([old_problems](const int threads) {
+
+                    #pragma omp parallel for schedule(static) num_threads(threads)
+                    for (size_t i = 0; i < old_problems->size(); ++i) {
+
+                        std::vector<uint32_t>().swap(old_problems->at(i).column_path);
+                        std::vector<uint32_t>().swap(old_problems->at(i).column_path_off);
+                        std::vector<uint32_t>().swap(old_problems->at(i).column_counts);
+                    }
+                });
+
+                return;
+            }
+        }
+
         std::vector<GroupPosteriors> group_posteriors;
         pathGroupPosteriors(&group_posteriors, cluster_batch, problems, rngs);
 
@@ -1220,6 +1250,52 @@ void NestedPathAbundanceEstimator::unpackMergedSolutions(std::vector<PathCluster
                 estimates.abundances.emplace_back(subsets.set_abundance[2 * slot]);
                 estimates.abundances.emplace_back(subsets.set_abundance[2 * slot + 1]);
             }
+        }
+
+        estimates.em_iterations.assign(subsets.iterations + first_subset, subsets.iterations + first_subset + num_subsets);
+        estimates.em_problem_paths.resize(num_subsets);
+
+        for (uint64_t s = 0; s < num_subsets; ++s) {
+
+            estimates.em_problem_paths[s].assign(subsets.col_path + subsets.col_off[first_subset + s], subsets.col_path + subsets.col_off[first_subset + s + 1]);
+        }
+    }
+}
+
+void NestedPathAbundanceEstimator::unpackMergedSetSolutions(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters, const rpvg_hip_subset_em_sets_view & subsets) const {
+
+    assert(subsets.num_matrices == clusters.size());
+    assert(subsets.set_count && subsets.group_size == group_size);
+
+    ScopedPhase unpack_phase("nested: estimates out of the device block");
+
+    const uint32_t width = subsets.group_size;
+
+    // Every field of the estimates is overwritten, as unpackMergedSolutions does it.
+    for (size_t i = 0; i < clusters.size(); ++i) {
+
+        auto & estimates = path_cluster_estimates->at(clusters[i]);
+
+        const uint64_t first_subset = subsets.subset_off[i];
+        const uint64_t num_subsets = subsets.subset_off[i + 1] - first_subset;
+        const uint64_t first_set = subsets.path_off[first_subset];
+        const uint32_t num_sets = subsets.set_count[i];
+
+        estimates.total_count = cluster_batch.totalReadCount(clusters[i]);
+        estimates.noise_count = (num_subsets > 0) ? subsets.cluster_noise_count[i] : estimates.total_count;  // (:749 with no subset kept)
+        estimates.gibbs_read_count_samples.clear();
+
+        estimates.path_group_sets.resize(num_sets);
+        estimates.posteriors.assign(subsets.set_posterior + first_set, subsets.set_posterior + first_set + num_sets);
+        estimates.abundances.clear();
+
+        for (uint32_t q = 0; q < num_sets; ++q) {
+
+            const uint64_t slot = first_set + q;
+            const uint32_t size = subsets.set_size[slot];
+
+            estimates.path_group_sets[q].assign(subsets.set_member + slot * width, subsets.set_member + slot * width + size);
+            estimates.abundances.insert(estimates.abundances.end(), subsets.set_abundance + slot * width, subsets.set_abundance + slot * width + size);
         }
 
         estimates.em_iterations.assign(subsets.iterations + first_subset, subsets.iterations + first_subset + num_subsets);

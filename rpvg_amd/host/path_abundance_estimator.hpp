@@ -89,7 +89,9 @@ class NestedPathAbundanceEstimator : public PathAbundanceEstimator {
         bool usesRandomNumbers() const { return !infer_collapsed || use_group_post_gibbs || num_gibbs_samples > 0; }
 
         // (the one-call device path of estimateClusters: collapsed groups, diploid, branch and bound, no read-count samples)
-        bool wantsSourceColumns() const { return infer_collapsed && !use_group_post_gibbs && group_size == 2 && num_gibbs_samples == 0; }
+        // (ploidy 5 .. 8 with exact posteriors: the one-call route, rpvg_hip_nested_full_subset_em, merges on the device and needs the
+        // transcript of every path there; the clusters of estimate() then travel with their ids as the diploid ones do)
+        bool wantsSourceColumns() const { return infer_collapsed && !use_group_post_gibbs && (group_size == 2 || group_size >= 5) && num_gibbs_samples == 0; }
 
         bool sourceColumnsOf(GroupPosteriorProblem * columns, const std::vector<PathInfo> & paths) const;
 
@@ -123,6 +125,9 @@ class NestedPathAbundanceEstimator : public PathAbundanceEstimator {
         // The estimates of a device call that merged on the device too (rpvg_hip_subset_em_view::set_*): copied into the
         // clusters' containers in place — a caller that hands the same containers in again pays no allocation.
         void unpackMergedSolutions(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters, const rpvg_hip_subset_em_view & subsets) const;
+
+        // The same for the sets of up to group_size paths that rpvg_hip_nested_full_subset_em merges (ploidy 5 .. 8).
+        void unpackMergedSetSolutions(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters, const rpvg_hip_subset_em_sets_view & subsets) const;
 
         void inferPathSubsetAbundance(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters, const std::vector<PathSubsetWeights> & path_subset_samples, std::vector<std::mt19937> * rngs, bool reset_first) const;
 };

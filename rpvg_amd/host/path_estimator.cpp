@@ -1426,6 +1426,46 @@ bool PathEstimator::nestedSubsetAbundances(SubsetEmResult * result, const Device
     return true;
 }
 
+bool PathEstimator::nestedFullSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv) const {
+
+    assert(!result->result);
+
+    if (problems.empty()) {
+
+        return false;
+    }
+
+    ScopedPhase whole_phase("nested: enumeration + subsets + EM + merge on the device");
+
+    // calcPathLogFrequences of every problem's columns, back to back (as calculatePathGroupPosteriorsFullOnDevice lays them out)
+    std::vector<double> log_freqs;
+
+    for (auto & problem: problems) {
+
+        if (rpvg_hip_full_set_count(problem.numColumns(), group_size) > RPVG_HIP_FULL_MAX_SETS) {
+
+            return false;
+        }
+
+        const auto path_log_freqs = calcPathLogFrequences(problem.column_counts);
+        log_freqs.insert(log_freqs.end(), path_log_freqs.begin(), path_log_freqs.end());
+    }
+
+    const GroupMatrices matrices(engine, cluster_batch, problems, true, prob_precision);
+
+    const int status = rpvg_hip_nested_full_subset_em(engine->ctx(), cluster_batch.handle(), matrices.handle(), group_size, log_freqs.data(), min_hap_prob, max_em_its, max_rel_em_conv, prob_precision, &result->result);
+
+    if (status == RPVG_HIP_ERR_UNSUPPORTED) {
+
+        return false;
+    }
+
+    HipEngine::check(status, "rpvg_hip_nested_full_subset_em");
+    HipEngine::check(rpvg_hip_subset_em_get_sets(result->result, &result->sets_view), "rpvg_hip_subset_em_get_sets");
+
+    return true;
+}
+
 namespace {
 
 // A seed sequence that hands out the 624 words it was given: std::mt19937::seed(sequence) copies them into the

@@ -222,6 +222,7 @@ class PathEstimator {
                 SubsetEmResult & operator=(const SubsetEmResult &) = delete;
 
                 rpvg_hip_subset_em_view view;
+                rpvg_hip_subset_em_sets_view sets_view;  // nestedFullSubsetAbundances fills this one
 
             private:
 
@@ -235,6 +236,11 @@ class PathEstimator {
         // the result belongs to clusters.at(i); nothing but the cluster list goes up, and the result carries the
         // posterior-weighted merge of the solutions as well (rpvg_hip_subset_em_view::set_*).
         bool nestedSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters, const double min_rel_likelihood, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv) const;
+
+        // Exact posteriors at ploidy 1 and 3 .. 8: full enumeration, retained sets, path subsets, EM and the posterior-weighted merge
+        // in ONE device call (rpvg_hip_nested_full_subset_em): problem i of `problems` is matrix i of result->sets_view.  False when
+        // the device does not take the input — a problem over RPVG_HIP_FULL_MAX_SETS among them: the separate calls name its cluster.
+        bool nestedFullSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv) const;
 
         // src/path_estimator.cpp:315-330
         static std::vector<double> calcPathLogFrequences(const std::vector<uint32_t> & path_counts);
