@@ -849,7 +849,6 @@ struct rpvg_hip_groups {
     rpvg_hip_detail::DeviceBuffer<uint64_t> collapse_key;  // [sum R_m]
     rpvg_hip_detail::DeviceBuffer<uint32_t> collapse_row;  // [sum R_m]
     rpvg_hip_detail::DeviceBuffer<uint64_t> collapse_mask; // [sum R_m] zero pattern of the first 64 columns
-    rpvg_hip_detail::DeviceBuffer<uint32_t> collapse_segment_off;  // [M + 1] mat_row_off as 32-bit segment offsets
     rpvg_hip_detail::DeviceBuffer<uint32_t> collapse_info;
     // The row collapse runs on the building context's collapse stream behind the build; whoever reads the matrices
     // makes its stream wait for it (waitCollapse): what a consumer queues before its kernels — uploads, allocations —

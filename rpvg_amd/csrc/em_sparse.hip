@@ -38,6 +38,7 @@
 
 #include "common.hpp"
 
+#include "collapse_plan.hpp"
 #include "em_block.hpp"
 
 #include <algorithm>
@@ -1467,18 +1468,18 @@ int queueEmGridAndJoin(rpvg_hip_ctx * ctx, const uint32_t P, const EmProblemsVie
 int dumpEmCollapse(rpvg_hip_ctx * ctx, const EmProblemList & list, const EmSolveWork & work) {
     const CsrCollapseWork * cw = static_cast<const CsrCollapseWork *>(work.collapse.get());
     const uint32_t P = list.P_bound;
-    uint32_t info[6] = {0}, merged = 0, problems = P, counts[3] = {0};
+    using namespace rpvg_collapse;
+    const InfoLayout layout = infoLayout(P, list.rows_capacity);
+    uint32_t info[kInfoWords] = {0}, merged = 0, problems = P, counts[3] = {0};  // counts: the marked list, the forward pairs, the around pairs
     RPVG_HIP_CHECK(waitStream(ctx->stream));
-    RPVG_HIP_CHECK(hipMemcpy(info, cw->info.ptr, sizeof(info), hipMemcpyDeviceToHost));
+    RPVG_HIP_CHECK(hipMemcpy(info, cw->info.ptr + layout.info, sizeof(info), hipMemcpyDeviceToHost));
     RPVG_HIP_CHECK(hipMemcpy(&merged, cw->problem_merged.ptr + P, sizeof(merged), hipMemcpyDeviceToHost));
     if (list.d_num_problems) RPVG_HIP_CHECK(hipMemcpy(&problems, list.d_num_problems, sizeof(problems), hipMemcpyDeviceToHost));
-    {   // (layout of the zeroed words: queueCollapseStages)
-        const uint64_t mark_words = (list.rows_capacity + 31) / 32;
-        RPVG_HIP_CHECK(hipMemcpy(counts, cw->info.ptr + 6 + 2 + 2 * static_cast<uint64_t>(P) + 1 + mark_words, sizeof(counts), hipMemcpyDeviceToHost));
-    }
-    std::fprintf(stderr, "[em collapse] marked rows %u forward pairs %u (equal up to rounding %u, apart %u) around pairs %u\n", counts[0], counts[1], info[4], info[5], counts[2]);
-    std::fprintf(stderr, "[em collapse] problems %u (bound %u) row slots %llu: replayed %u whole %u active rows %u rows replaced %u problems merged %u\n",
-                 problems, P, static_cast<unsigned long long>(list.rows_capacity), info[0], info[2], info[3], info[1], merged);
+    RPVG_HIP_CHECK(hipMemcpy(counts, cw->info.ptr + layout.marked_count, sizeof(counts), hipMemcpyDeviceToHost));  // (marked_count, pair_counts[2]: side by side)
+    std::fprintf(stderr, "[em collapse] marked rows %u forward pairs %u (equal up to rounding %u, apart %u) around pairs %u\n", counts[0], counts[1],
+                 info[kInfoPairsEquivalent], info[kInfoPairsApart], counts[2]);
+    std::fprintf(stderr, "[em collapse] problems %u (bound %u) row slots %llu: replayed %u whole %u active rows %u rows replaced %u problems merged %u\n", problems, P,
+                 static_cast<unsigned long long>(list.rows_capacity), info[kInfoMatrices], info[kInfoWholeMatrices], info[kInfoActiveRows], info[kInfoRowsReplaced], merged);
     return RPVG_HIP_OK;
 }
 

@@ -1161,14 +1161,7 @@ static int buildGroups(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const r
         pack.add(tmp->word_off, word_off.data(), M);
         pack.addZero(tmp->path_words, word_total);
     }
-    std::vector<uint32_t> segment_off;
-    if (collapse) {
-        segment_off.resize(M + 1);
-        for (uint32_t m = 0; m < M; ++m) segment_off[m] = static_cast<uint32_t>(row_off[m]);
-        segment_off[M] = static_cast<uint32_t>(row_total);
-        if (row_total > 0x7fffffffull) e = hipErrorInvalidValue;
-        pack.add(g->collapse_segment_off, segment_off.data(), M + 1);
-    }
+    if (collapse && row_total > 0x7fffffffull) e = hipErrorInvalidValue;
     DeviceBuffer<uint32_t> & d_cluster = tmp->cluster;
     pack.add(d_cluster, spec->cluster, M);
     if (lists_needed) {

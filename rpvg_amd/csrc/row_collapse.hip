@@ -32,8 +32,8 @@
 // The tolerant comparison is not a strict weak order; where it is inconsistent the reference's own result is
 // whatever std::sort makes of it.
 
+#include "collapse_plan.hpp"
 #include "common.hpp"
-#include "segment_sort_plan.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -43,28 +43,26 @@ using namespace rpvg_hip_detail;
 
 namespace {
 
+using namespace rpvg_collapse;
+static_assert(kKeyLargestBits == kCollapseLargestBits && kKeyMatrixShift == kCollapseMatrixShift && kMaxMatrices == kCollapseMaxMatrices,
+              "collapse_plan.hpp restates these");
+
 constexpr int kKeyFractionBits = kCollapseKeyFractionBits;
 constexpr uint32_t kMaxWindowCompares = 256;   // a row with more candidates than this sends its matrix to the full sort
 enum : uint8_t { kRowListed = 1, kRowStoodFor = 2 };
-constexpr int kCsrCellHashBits = 8;  // of the sort key's low field, for the rows of EM problems (CsrArrays)
 constexpr double kEquivalentRelative = 1e-13;  // close rows that differ by no more than this are interchangeable
 // (8 192 in rounds 2-3: 96 KB of static LDS and 1 024 threads, a whole CU per workgroup — on a batch without a single big list
 // the kernel still waited 0.2-0.4 ms for CUs the other lane's kernels held, on the collapse's critical path)
 constexpr uint32_t kListLdsRows = 2048;        // row lists up to this size live (and are sorted) in LDS
-constexpr uint32_t kSortThreads = 256;  // (1 024 in rounds 2-3: sixteen waves' worth of registers to find on one CU before the kernel could even see that it has no big list)
-constexpr uint32_t kBetweenThreads = 256;
-constexpr uint32_t kBetweenRows = 2 * kBetweenThreads;  // rows of a matrix per work item of step b
 constexpr uint32_t kPairChunk = 256;           // neighbour pairs staged in LDS at a time
 constexpr uint32_t kWholeMatrixBit = 0x80000000u;  // mat_list: every row of the matrix is listed
 constexpr uint32_t kBigListBit = 0x40000000u;      // mat_list: sorted by the bitonic kernel, compared in depth (no pair table)
 constexpr uint32_t kListSizeMask = 0x3FFFFFFFu;
 constexpr uint32_t kPairwiseRows = 1024;           // lists up to this size get a table of all their pairs
-constexpr uint64_t kPairTableBytes = 16ull << 20;
 constexpr uint8_t kPairLess = 1, kPairClose = 2;
 constexpr uint32_t kLdsTableRows = 128;            // pair tables of lists up to this size are read from LDS (16 KB)
 
 enum : uint32_t { kFlagNone = 0, kFlagActiveRows = 1, kFlagWholeMatrix = 2 };
-enum : uint32_t { kInfoMatrices = 0, kInfoRowsReplaced = 1, kInfoWholeMatrices = 2, kInfoActiveRows = 3, kInfoPairsEquivalent = 4, kInfoPairsApart = 5, kInfoWords = 6 };
 
 __device__ __forceinline__ bool tolerantEqual(const double a, const double b) {  // Utils::doubleCompare, src/utils.hpp:87-93
     return a == b || fabs(a - b) < fabs(fmin(a, b)) * (DBL_EPSILON * 100);
@@ -1368,32 +1366,24 @@ namespace {
 // rounds a segment needs — and sortWordsInRegisters below runs it with the words in registers: a lane holds up to eight
 // consecutive elements, stages inside a lane are register compare-exchanges, stages inside a wavefront lane exchanges, and only
 // the stages across wavefronts go through LDS behind a barrier.  docs/design/kernels-collapse.md, "Segment sort in registers".)
-constexpr uint32_t kSmallSortRows = rpvg_sort::kSmallSortRows;
-constexpr uint32_t kOneWaveSortRows = rpvg_sort::kOneWaveRows;
-constexpr uint32_t kSmallSortThreads = rpvg_sort::kSmallSortWaves * rpvg_sort::kWaveLanes;
-constexpr uint32_t kSortChunkRows = rpvg_sort::kChunkRows;
-constexpr uint32_t kSortChunkThreads = rpvg_sort::kChunkWaves * rpvg_sort::kWaveLanes;
 constexpr uint32_t kMergeTile = 1024;                       // output words of a merge round per work item
-constexpr uint32_t kMergeThreads = 128;
-constexpr uint32_t kSortRowBits = rpvg_sort::kRowBits;      // rows of a matrix the packed word can tell apart
-constexpr uint64_t kSortMaxSegmentRows = (1ull << kSortRowBits) - 1;
 
 template <int HASH>
 __device__ __forceinline__ uint64_t packSortWord(const uint64_t key, const uint32_t row) {
     constexpr int low = kCollapseLargestBits - HASH;  // bits of the key that are not sorted on
     const uint64_t sorted = (key & ((1ull << kCollapseMatrixShift) - 1)) >> low;
-    return (sorted << (kSortRowBits + low)) | (static_cast<uint64_t>(row) << low) | (key & ((1ull << low) - 1));
+    return (sorted << (rpvg_sort::kRowBits + low)) | (static_cast<uint64_t>(row) << low) | (key & ((1ull << low) - 1));
 }
 template <int HASH>
-__device__ __forceinline__ uint32_t sortWordRow(const uint64_t word) { return static_cast<uint32_t>(word >> (kCollapseLargestBits - HASH)) & ((1u << kSortRowBits) - 1); }
+__device__ __forceinline__ uint32_t sortWordRow(const uint64_t word) { return static_cast<uint32_t>(word >> (kCollapseLargestBits - HASH)) & ((1u << rpvg_sort::kRowBits) - 1); }
 template <int HASH>
 __device__ __forceinline__ uint64_t sortWordKey(const uint64_t word, const uint32_t matrix) {
     constexpr int low = kCollapseLargestBits - HASH;
-    return (static_cast<uint64_t>(matrix) << kCollapseMatrixShift) | ((word >> (kSortRowBits + low)) << low) | (word & ((1ull << low) - 1));
+    return (static_cast<uint64_t>(matrix) << kCollapseMatrixShift) | ((word >> (rpvg_sort::kRowBits + low)) << low) | (word & ((1ull << low) - 1));
 }
 template <int HASH>
 __device__ __forceinline__ bool sortWordsSameSortedPart(const uint64_t x, const uint64_t y) {
-    constexpr int shift = kSortRowBits + kCollapseLargestBits - HASH;
+    constexpr int shift = rpvg_sort::kRowBits + kCollapseLargestBits - HASH;
     return HASH ? (x >> shift) == (y >> shift) : ((x >> shift) == (y >> shift) && ((x ^ y) & ((1ull << (kCollapseLargestBits - HASH)) - 1)) == 0);
 }
 
@@ -1412,10 +1402,10 @@ __device__ __forceinline__ uint64_t sortKeyOfRow(const MatrixArrays & g, const u
     (void) g; (void) m; (void) pattern_out;
     return key_in[r0 + i];
 }
-__device__ __forceinline__ uint64_t sortKeyOfRow(const CsrArrays & g, const uint32_t p, const uint64_t r0, const uint32_t i, const uint64_t * key_in,
-                                                 uint64_t * pattern_out) {
-    (void) key_in;
-    const CsrView mv = g.view(p);
+struct CsrRowKey {  // of row i of EM problem p: the one place that computes it (the segment sort, and csrCollapseKeysKernel of the library route)
+    uint64_t key, pattern;
+};
+__device__ __forceinline__ CsrRowKey csrRowKey(const CsrView & mv, const uint32_t p, const uint32_t i) {
     const double noise = mv.noise[i];
     double projection = collapseWeight(mv.G) * noise, largest = 0.0;
     uint64_t cells = cellHashTerm(mv.G, noise), pattern = 0;
@@ -1427,12 +1417,18 @@ __device__ __forceinline__ uint64_t sortKeyOfRow(const CsrArrays & g, const uint
         cells += cellHashTerm(c, v);
         if (c < 64 && v != 0.0) pattern |= 1ull << c;
     }
-    pattern_out[r0 + i] = pattern;
     // the top of the low field: a hash of the row's cells, sorted on (rows of equal cells end up next to each other)
     constexpr int low_bits = kCollapseLargestBits - kCsrCellHashBits;
     uint64_t k = collapseSortKey(p, projection, largest);
     k = (k & ~((1ull << kCollapseLargestBits) - 1)) | (((cells * 0x9E3779B97F4A7C15ull) >> (64 - kCsrCellHashBits)) << low_bits) | (k & ((1ull << low_bits) - 1));
-    return k;
+    return CsrRowKey{k, pattern};
+}
+__device__ __forceinline__ uint64_t sortKeyOfRow(const CsrArrays & g, const uint32_t p, const uint64_t r0, const uint32_t i, const uint64_t * key_in,
+                                                 uint64_t * pattern_out) {
+    (void) key_in;
+    const CsrRowKey row = csrRowKey(g.view(p), p, i);
+    pattern_out[r0 + i] = row.pattern;
+    return row.key;
 }
 
 // caller-supplied words instead of rows (rpvg_hip_segment_sort_words: the sort alone, for its test)
@@ -1464,7 +1460,7 @@ struct SegmentSortArgs {
     uint8_t * same_prev;
     uint32_t * stretch_start;
     uint64_t * words_a, * words_b;       // [total rows] each: buffers 0 and 1 of the merge rounds (segment_sort_plan.hpp); the chunk sort writes words_a
-    uint32_t * chunks;                   // [2 x capacity] (matrix, chunk of kSortChunkRows rows) of the matrices beyond kSmallSortRows rows
+    uint32_t * chunks;                   // [2 x capacity] (matrix, chunk of rpvg_sort::kChunkRows rows) of the matrices beyond rpvg_sort::kSmallSortRows rows
     uint32_t * chunk_count;
     uint32_t chunk_capacity;
     uint32_t round;                      // of the merge
@@ -1671,7 +1667,7 @@ __device__ __forceinline__ void sortSegmentOfGroup(const SegmentSortArgs<Arrays>
     }
 }
 
-// Matrices of up to kSmallSortRows rows — nearly all of a batch.  A workgroup of two wavefronts draws two matrices at a time
+// Matrices of up to rpvg_sort::kSmallSortRows rows — nearly all of a batch.  A workgroup of two wavefronts draws two matrices at a time
 // with a grid-stride loop: a matrix of up to 512 rows is sorted by ONE wavefront in its half of the 8 KB of LDS, without a
 // workgroup barrier, next to the other wavefront's; a matrix of 513 .. 1 024 rows then takes both.  Sixteen workgroups per CU.
 // A larger matrix lists its chunks for the kernel below.  (amdgpu_waves_per_eu(4): left alone the compiler takes 138 VGPRs for
@@ -1679,26 +1675,26 @@ __device__ __forceinline__ void sortSegmentOfGroup(const SegmentSortArgs<Arrays>
 // it no spill.  A floor of five spills.)
 template <typename Arrays>
 __global__ __launch_bounds__(kSmallSortThreads) __attribute__((amdgpu_waves_per_eu(4))) void collapseSmallSortKernel(const SegmentSortArgs<Arrays> a) {
-    __shared__ uint64_t words[kSmallSortRows];
+    __shared__ uint64_t words[rpvg_sort::kSmallSortRows];
     const uint32_t M = a.num_matrices_dev ? min(*a.num_matrices_dev, a.num_matrices) : a.num_matrices;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / rpvg_sort::kWaveLanes), lane = threadIdx.x % rpvg_sort::kWaveLanes;
     for (uint64_t m0 = static_cast<uint64_t>(blockIdx.x) * rpvg_sort::kSmallSortWaves; m0 < M; m0 += static_cast<uint64_t>(gridDim.x) * rpvg_sort::kSmallSortWaves) {
         if (m0 + wave < M) {  // this wavefront's matrix
             const uint32_t m = static_cast<uint32_t>(m0 + wave);
             const uint64_t R = a.g.numRows(m);
-            if (R > kSmallSortRows) {
+            if (R > rpvg_sort::kSmallSortRows) {
                 if (lane == 0) {
-                    const uint32_t chunks = static_cast<uint32_t>((R + kSortChunkRows - 1) / kSortChunkRows);
+                    const uint32_t chunks = static_cast<uint32_t>((R + rpvg_sort::kChunkRows - 1) / rpvg_sort::kChunkRows);
                     const uint32_t first = atomicAdd(a.chunk_count, chunks);
                     for (uint32_t c = 0; c < chunks && first + c < a.chunk_capacity; ++c) {
                         a.chunks[2 * static_cast<uint64_t>(first + c)] = m;
                         a.chunks[2 * static_cast<uint64_t>(first + c) + 1] = c;
                     }
                 }
-            } else if (R > 0 && R <= kOneWaveSortRows) {
+            } else if (R > 0 && R <= rpvg_sort::kOneWaveRows) {
                 const uint64_t r0 = a.g.rowOffset(m);
                 const uint32_t n = static_cast<uint32_t>(R);
-                uint64_t * image = words + wave * kOneWaveSortRows;
+                uint64_t * image = words + wave * rpvg_sort::kOneWaveRows;
                 sortSegmentOfGroup<Arrays, 1>(a, m, r0, 0, n, image, lane);
                 for (uint32_t i = lane; i < n; i += rpvg_sort::kWaveLanes) writeSortedPosition(a, m, r0, r0 + i, image[i], i ? image[i - 1] : 0ull, i != 0);
                 sortGroupSync<1>();  // (the image is read before the wavefront's next matrix overwrites it)
@@ -1707,7 +1703,7 @@ __global__ __launch_bounds__(kSmallSortThreads) __attribute__((amdgpu_waves_per_
         for (uint32_t w = 0; w < rpvg_sort::kSmallSortWaves && m0 + w < M; ++w) {  // the pair's matrices of both wavefronts (uniform)
             const uint32_t m = static_cast<uint32_t>(m0 + w);
             const uint64_t R = a.g.numRows(m);
-            if (R <= kOneWaveSortRows || R > kSmallSortRows) continue;
+            if (R <= rpvg_sort::kOneWaveRows || R > rpvg_sort::kSmallSortRows) continue;
             const uint64_t r0 = a.g.rowOffset(m);
             const uint32_t n = static_cast<uint32_t>(R);
             __syncthreads();  // (the halves are free)
@@ -1718,24 +1714,24 @@ __global__ __launch_bounds__(kSmallSortThreads) __attribute__((amdgpu_waves_per_
     }
 }
 
-// the chunks of the larger matrices: sorted runs of kSortChunkRows words in words_a (four wavefronts, eight words per lane; a
+// the chunks of the larger matrices: sorted runs of rpvg_sort::kChunkRows words in words_a (four wavefronts, eight words per lane; a
 // matrix's short last chunk takes fewer words per lane)
 template <typename Arrays>
-__global__ __launch_bounds__(kSortChunkThreads) void collapseChunkSortKernel(const SegmentSortArgs<Arrays> a) {
-    __shared__ uint64_t words[kSortChunkRows];
+__global__ __launch_bounds__(kChunkSortThreads) void collapseChunkSortKernel(const SegmentSortArgs<Arrays> a) {
+    __shared__ uint64_t words[rpvg_sort::kChunkRows];
     const uint32_t count = min(*a.chunk_count, a.chunk_capacity);
     for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
         const uint32_t m = a.chunks[2 * static_cast<uint64_t>(item)], chunk = a.chunks[2 * static_cast<uint64_t>(item) + 1];
         const uint64_t R = a.g.numRows(m), r0 = a.g.rowOffset(m);
-        const uint64_t c0 = static_cast<uint64_t>(chunk) * kSortChunkRows;
-        const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kSortChunkRows), R - c0));
+        const uint64_t c0 = static_cast<uint64_t>(chunk) * rpvg_sort::kChunkRows;
+        const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(rpvg_sort::kChunkRows), R - c0));
         __syncthreads();  // (the chunk before is done with the LDS)
         sortSegmentOfGroup<Arrays, rpvg_sort::kChunkWaves>(a, m, r0, c0, n, words, threadIdx.x);
         for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) a.words_a[r0 + c0 + i] = words[i];
     }
 }
 
-// One round of the merge: the sorted runs of length kSortChunkRows << round of every larger matrix, two by two.  Work item =
+// One round of the merge: the sorted runs of length rpvg_sort::kChunkRows << round of every larger matrix, two by two.  Work item =
 // kMergeTile output words of a matrix (two per chunk of the list); a thread finds where its eight outputs begin in the two
 // runs by a binary search along its diagonal (merge path; the words are distinct: they carry the row) and merges them out.
 // The host launches the rounds the largest matrix it allows would need; a matrix whose runs are complete (round >=
@@ -1747,7 +1743,7 @@ __global__ __launch_bounds__(kSortChunkThreads) void collapseChunkSortKernel(con
 template <typename Arrays>
 __global__ __launch_bounds__(kMergeThreads) void collapseMergeRoundKernel(const SegmentSortArgs<Arrays> a) {
     constexpr uint32_t kPerThread = kMergeTile / kMergeThreads;
-    constexpr uint32_t kTilesPerChunk = kSortChunkRows / kMergeTile;
+    constexpr uint32_t kTilesPerChunk = rpvg_sort::kChunkRows / kMergeTile;
     const uint32_t count = min(*a.chunk_count, a.chunk_capacity) * kTilesPerChunk;
     const uint64_t * __restrict__ source = rpvg_sort::sourceBuffer(a.round) ? a.words_b : a.words_a;
     uint64_t * __restrict__ target = rpvg_sort::targetBuffer(a.round) ? a.words_b : a.words_a;
@@ -1757,7 +1753,7 @@ __global__ __launch_bounds__(kMergeThreads) void collapseMergeRoundKernel(const 
         const uint64_t R = a.g.numRows(m);
         if (!rpvg_sort::roundHasWork(R, a.round)) continue;
         const uint64_t r0 = a.g.rowOffset(m);
-        const uint64_t out0 = static_cast<uint64_t>(a.chunks[2 * static_cast<uint64_t>(item / kTilesPerChunk) + 1]) * kSortChunkRows + (item % kTilesPerChunk) * kMergeTile;
+        const uint64_t out0 = static_cast<uint64_t>(a.chunks[2 * static_cast<uint64_t>(item / kTilesPerChunk) + 1]) * rpvg_sort::kChunkRows + (item % kTilesPerChunk) * kMergeTile;
         if (out0 >= R) continue;
         const uint64_t pair0 = out0 / (2 * run) * (2 * run);
         const uint64_t a1 = min(R, pair0 + run), b1 = min(R, pair0 + 2 * run);
@@ -1799,8 +1795,8 @@ __global__ __launch_bounds__(256) void collapseMergedPositionsKernel(const Segme
         const uint32_t m = a.chunks[2 * static_cast<uint64_t>(item)], chunk = a.chunks[2 * static_cast<uint64_t>(item) + 1];
         const uint64_t R = a.g.numRows(m), r0 = a.g.rowOffset(m);
         const uint64_t * __restrict__ sorted = rpvg_sort::finalBuffer(R) ? a.words_b : a.words_a;
-        const uint64_t c0 = static_cast<uint64_t>(chunk) * kSortChunkRows;
-        const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kSortChunkRows), R - c0));
+        const uint64_t c0 = static_cast<uint64_t>(chunk) * rpvg_sort::kChunkRows;
+        const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(rpvg_sort::kChunkRows), R - c0));
         for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
             const uint64_t i = c0 + e;
             writeSortedPosition(a, m, r0, r0 + i, sorted[r0 + i], i ? sorted[r0 + i - 1] : 0ull, i != 0);
@@ -1841,25 +1837,7 @@ __global__ __launch_bounds__(256) void collapseUnusedSlotsKernel(const SegmentSo
     for (uint64_t r = tail + blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; r < a.total_rows; r += static_cast<uint64_t>(gridDim.x) * blockDim.x) fill(r);
 }
 
-}  // namespace
-
-namespace {
-
-inline void launchAdjustAndRewrite(const ReplayArgs<MatrixArrays> & r, const uint32_t grid, hipStream_t on) {
-    collapseAdjustSumsKernel<<<dim3(grid * 4), dim3(256), 0, on>>>(r);
-    ReplayArgs<MatrixArrays> rewrite = r;
-    rewrite.walk_only = false;
-    collapseRewriteKernel<<<dim3(grid), dim3(256), 0, on>>>(rewrite);
-}
-inline void launchAdjustAndRewrite(const ReplayArgs<CsrArrays> &, const uint32_t, hipStream_t) {}
-// the rows of the runs take their heads' values, behind a walk-only collapseRunsKernel (no search has read the matrices as built)
-inline void launchRewrite(const ReplayArgs<MatrixArrays> & r, const uint32_t grid, hipStream_t on) {
-    ReplayArgs<MatrixArrays> rewrite = r;
-    rewrite.walk_only = false;
-    collapseRewriteKernel<<<dim3(grid), dim3(256), 0, on>>>(rewrite);
-}
-inline void launchRewrite(const ReplayArgs<CsrArrays> &, const uint32_t, hipStream_t) {}
-
+// ---- the host side: a plan (collapse_plan.hpp) and the stages over it --------------------------------------------------------------
 struct CollapseTemporaries {
     DeviceBuffer<uint32_t> rewritten_count;
     DeviceBuffer<uint64_t> key_out, pair_pattern;
@@ -1876,251 +1854,242 @@ struct CollapseTemporaries {
     // the hand-written segment sort (stage 0)
     DeviceBuffer<uint64_t> words_a, words_b;
     DeviceBuffer<uint32_t> chunks, chunk_count;
+    // the slices of `stretch` and `bytes`
+    uint32_t * stretchStart(const uint64_t) const { return stretch.ptr; }
+    uint32_t * stretchFirst(const uint64_t T) const { return stretch.ptr + T; }
+    uint32_t * stretchEnd(const uint64_t T) const { return stretch.ptr + 2 * T; }
+    uint32_t * positionOf(const uint64_t T) const { return stretch.ptr + 3 * T; }
+    uint8_t * samePrev() const { return bytes.ptr; }
+    uint8_t * close(const uint64_t T) const { return bytes.ptr + T; }
+    uint8_t * barrier(const uint64_t T) const { return bytes.ptr + 2 * T; }
 };
 
-// the hand-written segment sort instead of the library's (null): what it needs beyond the stages' own arguments
-struct SegmentSortPlan {
-    const uint32_t * num_matrices_dev = nullptr;   // EM problems: their number on the device, and the work items of the fill
-    uint32_t num_items_bound = 0;
-    const uint32_t * num_items_dev = nullptr;
-    const uint64_t * seg_first = nullptr;
-    const uint32_t * item_problem = nullptr;
-    uint32_t segment_rows = 0;
-    uint64_t * pattern_out = nullptr;
-    uint64_t max_segment_rows = 0;                 // a bound of the rows of the largest matrix (the rounds of the merge)
+// What is the caller's own.  Group matrices: the keys the build wrote, the outputs for the search, and where the held-back part
+// of the runs goes (null: the runs are not held back).
+struct MatrixCaller {
+    const uint64_t * key;
+    const uint32_t * row;
+    double * rowmax;
+    uint32_t * mat_fast, * mat_mid;
+    std::function<hipError_t(hipStream_t, const SearchParts *)> * held_back_runs;
+};
+// EM problems: the work items of the fill
+struct ProblemCaller {
+    const CsrCollapseInput & in;
 };
 
-// The launches of the segment sort: the small kernel over all matrices; for the matrices beyond it — a few dozen per batch —
-// the chunks of their list, the merge rounds and their positions.  The host does not know every matrix's rows (the EM
-// problems' kept rows are counted on the device): it launches the rounds the largest matrix its bound allows would need, and a
-// round in which no matrix has work is a dispatch and nothing else.  With no such matrix possible, nothing.
-inline uint32_t segmentSortChunkCapacity(const uint64_t total_rows, const uint32_t M) {
-    return static_cast<uint32_t>(std::min<uint64_t>(total_rows / kSortChunkRows + M + 1, 0x7fffffffull));
-}
-template <typename Arrays>
-void launchSegmentSort(SegmentSortArgs<Arrays> c, const uint32_t M, const uint64_t max_segment_rows, const uint32_t small_grid, hipStream_t st) {
-    const uint32_t pairs = (M + rpvg_sort::kSmallSortWaves - 1) / rpvg_sort::kSmallSortWaves;
-    collapseSmallSortKernel<Arrays><<<dim3(std::max<uint32_t>(1, std::min<uint32_t>(pairs, 16 * small_grid))), dim3(kSmallSortThreads), 0, st>>>(c);
-    if (max_segment_rows <= kSmallSortRows) return;
-    collapseChunkSortKernel<Arrays><<<dim3(4 * small_grid), dim3(kSortChunkThreads), 0, st>>>(c);
-    const uint32_t merge_rounds = rpvg_sort::mergeRoundsOf(max_segment_rows);
-    for (uint32_t round = 0; round < merge_rounds; ++round) {
-        c.round = round;
-        collapseMergeRoundKernel<Arrays><<<dim3(8 * small_grid), dim3(kMergeThreads), 0, st>>>(c);
-    }
-    collapseMergedPositionsKernel<Arrays><<<dim3(4 * small_grid), dim3(256), 0, st>>>(c);
+hipError_t queueStretchScan(const CollapseTemporaries & t, const uint64_t total_rows, void * scratch, size_t & bytes, hipStream_t st) {
+    return hipcub::DeviceScan::InclusiveScan(scratch, bytes, t.stretchStart(total_rows), t.stretchFirst(total_rows), hipcub::Max(), static_cast<int>(total_rows), st);
 }
 
-// The stages behind the keys, for group matrices and for EM problems alike: `key` / `row` hold, per row slot, the sort key
-// (matrix, projection, largest value) and the slot itself; `info` receives [counters | zeroed words | active bytes | list sizes].
-template <typename Arrays>
-hipError_t queueCollapseStages(const Arrays & arrays, const uint32_t M, const uint64_t total_rows, const double precision, const uint64_t * key,
-                               const uint32_t * row, const uint32_t * segment_begin, const uint32_t * segment_end, const bool segmented, DeviceBuffer<uint32_t> & info, double * rowmax, uint32_t * mat_fast,
-                               uint32_t * mat_mid, CollapseTemporaries * tmp, hipStream_t st, const SegmentSortPlan * plan = nullptr, hipEvent_t sorted = nullptr,
-                               std::function<hipError_t(hipStream_t, const SearchParts *)> * held_back_runs = nullptr) {
+// The keys carry the matrix above the projection and the rows of a matrix are contiguous: ONE (stable) radix sort of the whole array
+// on the projection and as many matrix bits as there are matrices orders every matrix's rows by their projection.  (Round 2 sorted
+// segment by segment, hipcub::DeviceSegmentedRadixSort: 0.33 ms per 1.6 M rows in 2 500 segments, the longest kernel of the
+// collapse, and no better on the group matrices since.)
+hipError_t queueLibrarySort(const MatrixCaller & caller, const CollapsePlan & plan, const CollapseTemporaries & t, void * scratch, size_t & bytes, hipStream_t st) {
+    return hipcub::DeviceRadixSort::SortPairs(scratch, bytes, caller.key, t.key_out.ptr, caller.row, t.row_out.ptr, static_cast<int>(plan.total_rows),
+                                              plan.begin_bit, plan.end_bit, st);
+}
+// The rows of a problem are sorted as a segment, behind csrCollapseKeysKernel: a handful of launches against the global sort's seven
+// passes of three launches each (same box, configs[2] batch: 12.0-12.5 ms per step against 14.6).
+// (hipcub's segmented sort partitions the segments by size and reads the partition sizes back — the lane's thread waits there for
+// the fill; rocprim's unpartitioned configuration, one kernel and no wait, was 1 ms slower per lane all the same)
+hipError_t queueLibrarySort(const ProblemCaller &, const CollapsePlan & plan, const CollapseTemporaries & t, void * scratch, size_t & bytes, hipStream_t st) {
+    const uint32_t * segment_begin = t.csr_segments.ptr, * segment_end = segment_begin + plan.M;
+    return hipcub::DeviceSegmentedRadixSort::SortPairs(scratch, bytes, t.csr_key.ptr, t.key_out.ptr, t.csr_row.ptr, t.row_out.ptr, static_cast<int>(plan.total_rows),
+                                                       static_cast<int>(plan.M), segment_begin, segment_end, plan.begin_bit, plan.end_bit, st);
+}
+
+// every buffer of the plan's counts, and the library's scratch for the scan and (library routes) the sort
+template <typename Caller>
+hipError_t allocateCollapse(const CollapsePlan & plan, const Caller & caller, CollapseTemporaries & t, DeviceBuffer<uint32_t> & info, hipStream_t st) {
     hipError_t e = hipSuccess;
     auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-    // zeroed words: the pair table's byte counter (8 bytes, first: aligned), matrix flags [M], replay list [M] + its
-    // count, marked bits, then the counters of the marked list, the two pair lists, the between items, the row items
-    const uint64_t mark_words = (total_rows + 31) / 32;
-    const uint64_t num_words = 2 + 2 * static_cast<uint64_t>(M) + 1 + mark_words + 5;
-    const uint32_t pair_capacity = static_cast<uint32_t>(std::min<uint64_t>(4 * total_rows + 4096, 0x20000000ull));
-    if (tmp->key_out.count != total_rows) ok(tmp->key_out.alloc(total_rows));  // (the EM problems' caller has them already)
-    if (tmp->row_out.count != total_rows) ok(tmp->row_out.alloc(total_rows));
-    // one block, one memset: [info | the zeroed words | active bytes] + list sizes [M] (written by the list kernel)
-    const uint64_t active_words = (total_rows + 3) / 4;
-    ok(info.alloc(kInfoWords + num_words + active_words + M));
-    ok(tmp->order.alloc(2 * total_rows));
-    ok(tmp->head.alloc(total_rows));
-    ok(tmp->pair_column.alloc(total_rows));
-    ok(tmp->pair_bound.alloc(2 * total_rows));
-    ok(tmp->pair_pattern.alloc(total_rows));
-    ok(tmp->marked_list.alloc(total_rows));
-    ok(tmp->pairs.alloc(2 * static_cast<size_t>(pair_capacity)));
-    ok(tmp->between_items.alloc(2 * (total_rows / kBetweenRows + M)));
-    ok(tmp->row_items.alloc(2 * total_rows));
-    ok(tmp->list_index.alloc(total_rows));
-    ok(tmp->pair_base.alloc(M));
-    ok(tmp->pair_table.alloc(kPairTableBytes));
-    ok(tmp->bytes.alloc(3 * total_rows));
-    ok(tmp->stretch.alloc(4 * total_rows));
-    // The keys carry the matrix above the projection and the rows of a matrix are contiguous: ONE (stable) radix sort of
-    // the whole array on the projection and as many matrix bits as there are matrices orders every matrix's rows by their
-    // projection.  (The library path: RPVG_HIP_COLLAPSE_LIBRARY_SORT=1 for A/B, and matrices of 2^20 rows or more.  Round 2
-    // sorted segment by segment, hipcub::DeviceSegmentedRadixSort: 0.33 ms per 1.6 M rows in 2 500
-    // segments, the longest kernel of the collapse; RPVG_HIP_COLLAPSE_SEGMENTED_SORT=1 keeps it for A/B on the group matrices.)
-    int matrix_bits = 1;
-    while ((1u << matrix_bits) < M + 1) ++matrix_bits;  // (+ 1: the index unused row slots of the EM problems carry)
-    const int begin_bit = kCollapseLargestBits - Arrays::kHashBits, end_bit = segmented ? kCollapseMatrixShift : kCollapseMatrixShift + matrix_bits;
-    size_t sort_bytes = 0;
-    auto sort = [&](void * scratch) {
-        // (hipcub's segmented sort partitions the segments by size and reads the partition sizes back — the lane's thread waits
-        // there for the fill; rocprim's unpartitioned configuration, one kernel and no wait, was 1 ms slower per lane all the same)
-        return segmented ? hipcub::DeviceSegmentedRadixSort::SortPairs(scratch, sort_bytes, key, tmp->key_out.ptr, row,
-                                                                       tmp->row_out.ptr, static_cast<int>(total_rows), static_cast<int>(M),
-                                                                       segment_begin, segment_end, begin_bit, end_bit, st)
-                         : hipcub::DeviceRadixSort::SortPairs(scratch, sort_bytes, key, tmp->key_out.ptr, row,
-                                                              tmp->row_out.ptr, static_cast<int>(total_rows), begin_bit, end_bit, st);
-    };
-    if (e == hipSuccess && !plan) ok(sort(nullptr));
-    uint32_t * stretch_start = tmp->stretch.ptr, * stretch_first = stretch_start + total_rows, * stretch_end = stretch_first + total_rows,
-             * position_of = stretch_end + total_rows;
-    size_t scan_bytes = 0;
-    auto scan = [&](void * scratch) {
-        return hipcub::DeviceScan::InclusiveScan(scratch, scan_bytes, stretch_start, stretch_first, hipcub::Max(), static_cast<int>(total_rows), st);
-    };
-    if (e == hipSuccess) ok(scan(nullptr));
-    ok(tmp->sort_tmp.alloc(std::max(sort_bytes, scan_bytes)));
-    // the hand-written segment sort: the chunk list of the matrices beyond the small sort, the two buffers of their merge
-    uint32_t chunk_capacity = 0;
-    if (plan) {
-        chunk_capacity = segmentSortChunkCapacity(total_rows, M);
-        ok(tmp->words_a.alloc(total_rows));
-        ok(tmp->words_b.alloc(total_rows));
-        ok(tmp->chunks.alloc(2 * static_cast<size_t>(chunk_capacity)));
-        ok(tmp->chunk_count.alloc(1));
+    const BufferCounts & c = plan.counts;
+    ok(info.alloc(plan.info.total_words));
+    ok(t.key_out.alloc(c.sorted_key));
+    ok(t.row_out.alloc(c.sorted_row));
+    ok(t.order.alloc(c.order));
+    ok(t.head.alloc(c.head));
+    ok(t.pair_column.alloc(c.pair_column));
+    ok(t.pair_bound.alloc(c.pair_bound));
+    ok(t.pair_pattern.alloc(c.pair_pattern));
+    ok(t.marked_list.alloc(c.marked_list));
+    ok(t.pairs.alloc(c.pairs));
+    ok(t.between_items.alloc(c.between_items));
+    ok(t.row_items.alloc(c.row_items));
+    ok(t.list_index.alloc(c.list_index));
+    ok(t.pair_base.alloc(c.pair_base));
+    ok(t.pair_table.alloc(c.pair_table));
+    ok(t.bytes.alloc(c.bytes));
+    ok(t.stretch.alloc(c.stretch));
+    ok(t.words_a.alloc(c.words));
+    ok(t.words_b.alloc(c.words));
+    ok(t.chunks.alloc(c.chunks));
+    ok(t.chunk_count.alloc(c.chunk_count));
+    ok(t.csr_pattern.alloc(c.pattern));
+    ok(t.csr_key.alloc(c.keys));
+    ok(t.csr_row.alloc(c.rows));
+    ok(t.csr_segments.alloc(c.segments));
+    size_t sort_bytes = 0, scan_bytes = 0;
+    if (e == hipSuccess && plan.route != HandSort) ok(queueLibrarySort(caller, plan, t, nullptr, sort_bytes, st));
+    if (e == hipSuccess) ok(queueStretchScan(t, plan.total_rows, nullptr, scan_bytes, st));
+    ok(t.sort_tmp.alloc(std::max(sort_bytes, scan_bytes)));
+    return e;
+}
+
+template <typename Arrays>
+void launchSegmentSort(SegmentSortArgs<Arrays> c, const SegmentSortPlan & s, hipStream_t st) {
+    collapseSmallSortKernel<Arrays><<<dim3(s.small_sort.grid), dim3(s.small_sort.block), 0, st>>>(c);
+    if (s.chunk_sort.grid == 0) return;
+    collapseChunkSortKernel<Arrays><<<dim3(s.chunk_sort.grid), dim3(s.chunk_sort.block), 0, st>>>(c);
+    for (uint32_t round = 0; round < s.merge_rounds; ++round) {
+        c.round = round;
+        collapseMergeRoundKernel<Arrays><<<dim3(s.merge_round.grid), dim3(s.merge_round.block), 0, st>>>(c);
     }
-    if (e != hipSuccess) return e;
-    uint32_t * pair_bytes = info.ptr + kInfoWords, * mat_flag = pair_bytes + 2, * replay_list = mat_flag + M, * marked_bits = replay_list + M + 1,
-             * marked_count = marked_bits + mark_words, * pair_counts = marked_count + 1, * between_count = pair_counts + 2,
-             * row_item_count = between_count + 1, * mat_list = pair_bytes + num_words + active_words;
-    uint8_t * same_prev = tmp->bytes.ptr, * close = same_prev + total_rows, * barrier = close + total_rows;
-    uint8_t * active = reinterpret_cast<uint8_t *>(pair_bytes + num_words);
-    ok(zeroAsync(info.ptr, (kInfoWords + num_words + active_words) * sizeof(uint32_t), st));
-    if (!plan) ok(sort(tmp->sort_tmp.ptr));
+    collapseMergedPositionsKernel<Arrays><<<dim3(s.merged_positions.grid), dim3(s.merged_positions.block), 0, st>>>(c);
+}
+
+// ---- the argument structs, each from (view, plan, temporaries) ---------------------------------------------------------------------
+template <typename Arrays>
+SegmentSortArgs<Arrays> segmentSortArgs(const Arrays & arrays, const CollapsePlan & plan, const CollapseTemporaries & t) {
+    const uint64_t T = plan.total_rows;
+    SegmentSortArgs<Arrays> c{};
+    c.g = arrays;
+    c.num_matrices = plan.M;
+    c.total_rows = T;
+    c.sort_key = t.key_out.ptr;
+    c.sort_row = t.row_out.ptr;
+    c.position_of = t.positionOf(T);
+    c.same_prev = t.samePrev();
+    c.stretch_start = t.stretchStart(T);
+    c.words_a = t.words_a.ptr;
+    c.words_b = t.words_b.ptr;
+    c.chunks = t.chunks.ptr;
+    c.chunk_count = t.chunk_count.ptr;
+    c.chunk_capacity = plan.segment_sort.chunk_capacity;
+    return c;
+}
+// ... and where the rows' keys come from: the build's, or computed by the sort over the work items of the fill
+void setKeySource(SegmentSortArgs<MatrixArrays> & c, const MatrixCaller & caller, const CollapseTemporaries &) { c.key_in = caller.key; }
+void setKeySource(SegmentSortArgs<CsrArrays> & c, const ProblemCaller & caller, const CollapseTemporaries & t) {
+    c.num_matrices_dev = caller.in.num_problems_dev;
+    c.num_items_bound = caller.in.num_items_bound;
+    c.num_items_dev = caller.in.num_items_dev;
+    c.seg_first = caller.in.seg_first;
+    c.item_problem = caller.in.item_problem;
+    c.segment_rows = caller.in.segment_rows;
+    c.pattern_out = t.csr_pattern.ptr;
+}
+
+template <typename Arrays>
+PairScanArgs<Arrays> pairScanArgs(const Arrays & arrays, const CollapsePlan & plan, const CollapseKnobs & knobs, const double precision, const CollapseTemporaries & t,
+                                  uint32_t * info) {
+    const InfoLayout & l = plan.info;
+    const uint64_t T = plan.total_rows;
     PairScanArgs<Arrays> a;
-    a.total_rows = total_rows;
+    a.num_matrices = plan.M;
+    a.total_rows = T;
     a.precision = precision;
-    a.sort_key = tmp->key_out.ptr;
-    a.sort_row = tmp->row_out.ptr;
+    a.sort_key = t.key_out.ptr;
+    a.sort_row = t.row_out.ptr;
     a.g = arrays;
-    a.same_prev = same_prev;
-    a.stretch_first = stretch_start;  // (the kernel in front of the scan writes the starts)
-    a.stretch_end = stretch_end;
-    a.position_of = position_of;
-    a.marked_bits = marked_bits;
-    a.marked_list = tmp->marked_list.ptr;
-    a.marked_count = marked_count;
-    a.pairs = tmp->pairs.ptr;
-    a.pair_count = pair_counts;
-    a.pair_capacity = pair_capacity;
-    a.active = active;
-    a.mat_flag = mat_flag;
-    a.info = info.ptr;
-    a.num_matrices = M;
-    a.count_pairs = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_COLLAPSE_DEBUG") != nullptr;
-    const uint32_t row_blocks = static_cast<uint32_t>((total_rows + 255) / 256);
-    // The kernels over pairs, lists and matrices with a list draw their (few) items from device-side counts with grid-stride
-    // loops: a workgroup per CU or two, not thousands that find nothing (a workgroup costs the dispatcher ~40 ns whatever it does:
-    // 4 096 of them were most of a 60 us kernel).  RPVG_HIP_COLLAPSE_GRID overrides (A/B).
-    static const uint32_t small_grid = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_GRID") ? std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_GRID"))) : 256;
-    if (plan) {
-        ok(zeroAsync(tmp->chunk_count.ptr, sizeof(uint32_t), st));
-        SegmentSortArgs<Arrays> c;
-        c.g = arrays;
-        c.num_matrices = M;
-        c.num_matrices_dev = plan->num_matrices_dev;
-        c.num_items_bound = plan->num_items_bound;
-        c.num_items_dev = plan->num_items_dev;
-        c.seg_first = plan->seg_first;
-        c.item_problem = plan->item_problem;
-        c.segment_rows = plan->segment_rows;
-        c.total_rows = total_rows;
-        c.key_in = key;
-        c.pattern_out = plan->pattern_out;
-        c.sort_key = tmp->key_out.ptr;
-        c.sort_row = tmp->row_out.ptr;
-        c.position_of = position_of;
-        c.same_prev = same_prev;
-        c.stretch_start = stretch_start;
-        c.words_a = tmp->words_a.ptr;
-        c.words_b = tmp->words_b.ptr;
-        c.chunks = tmp->chunks.ptr;
-        c.chunk_count = tmp->chunk_count.ptr;
-        c.chunk_capacity = chunk_capacity;
-        c.round = 0;
-        if (Arrays::kHashBits) {
-            collapseUnusedSlotsKernel<Arrays><<<dim3(std::max<uint32_t>(1, std::min<uint32_t>(plan->num_items_bound, 8 * small_grid))), dim3(256), 0, st>>>(c);
-        }
-        launchSegmentSort(c, M, plan->max_segment_rows, small_grid, st);
-    } else {
-        collapseSamePrevKernel<Arrays><<<dim3(row_blocks), dim3(256), 0, st>>>(a);
-    }
-    if (sorted) ok(hipEventRecord(sorted, st));
-    ok(scan(tmp->sort_tmp.ptr));
-    a.stretch_first = stretch_first;
-    collapseStretchEndKernel<Arrays><<<dim3(row_blocks), dim3(256), 0, st>>>(a);
-    collapseForwardPairsKernel<Arrays><<<dim3(row_blocks), dim3(256), 0, st>>>(a);
-    collapseMarkPairsKernel<Arrays><<<dim3(small_grid), dim3(64), 0, st>>>(a);
-    a.pair_count = pair_counts + 1;  // the list is free again
-    collapseAroundPairsKernel<Arrays><<<dim3(256), dim3(64), 0, st>>>(a);
-    collapseActivePairsKernel<Arrays><<<dim3(small_grid), dim3(64), 0, st>>>(a);
-    ReplayArgs<Arrays> r;
-    r.num_matrices = M;
+    a.same_prev = t.samePrev();
+    a.stretch_first = t.stretchStart(T);  // (the kernel in front of the scan writes the starts; behind it: stretchFirst)
+    a.stretch_end = t.stretchEnd(T);
+    a.position_of = t.positionOf(T);
+    a.marked_bits = info + l.marked_bits;
+    a.marked_list = t.marked_list.ptr;
+    a.marked_count = info + l.marked_count;
+    a.pairs = t.pairs.ptr;
+    a.pair_count = info + l.pair_counts;  // (the forward list; the around list: + 1)
+    a.pair_capacity = plan.pair_capacity;
+    a.active = reinterpret_cast<uint8_t *>(info + l.active);
+    a.mat_flag = info + l.mat_flag;
+    a.info = info + l.info;
+    a.count_pairs = knobs.debug;
+    return a;
+}
+
+// (no sums, nothing held back; the outputs for the search — rowmax, mat_fast, mat_mid — are the group matrices' own: setOutputs)
+template <typename Arrays>
+ReplayArgs<Arrays> replayArgs(const Arrays & arrays, const CollapsePlan & plan, const CollapseKnobs & knobs, const double precision, const CollapseTemporaries & t,
+                              uint32_t * info) {
+    const InfoLayout & l = plan.info;
+    const uint64_t T = plan.total_rows;
+    ReplayArgs<Arrays> r{};
+    r.num_matrices = plan.M;
     r.precision = precision;
     r.g = arrays;
-    r.mat_flag = mat_flag;
-    r.active = active;
-    r.sort_row = tmp->row_out.ptr;
-    r.position_of = position_of;
-    r.stretch_end = stretch_end;
-    r.rowmax = rowmax;
-    r.mat_fast = mat_fast;
-    r.mat_mid = mat_mid;
-    r.mat_list = mat_list;
-    r.replay_list = replay_list;
-    r.between_items = tmp->between_items.ptr;
-    r.between_count = between_count;
-    r.row_items = tmp->row_items.ptr;
-    r.row_item_count = row_item_count;
-    r.pair_base = tmp->pair_base.ptr;
-    r.pair_bytes = reinterpret_cast<unsigned long long *>(pair_bytes);
-    r.pair_table = tmp->pair_table.ptr;
-    r.list_index = tmp->list_index.ptr;
-    r.order = tmp->order.ptr;
-    r.head_of = tmp->head.ptr;
-    r.close = close;
-    r.barrier = barrier;
-    r.pair_column = tmp->pair_column.ptr;
-    r.pair_lo = tmp->pair_bound.ptr;
-    r.pair_hi = tmp->pair_bound.ptr + total_rows;
-    r.pair_pattern = tmp->pair_pattern.ptr;
-    r.info = info.ptr;
-    r.debug = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_COLLAPSE_DEBUG") != nullptr;
-    r.no_lds_tables = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_NO_LDS_TABLES") != nullptr;
-    collapseListKernel<Arrays><<<dim3(std::min<uint32_t>(M, small_grid)), dim3(256), 0, st>>>(r);
-    const uint32_t staged_grid = small_grid;
-    collapsePairTableKernel<Arrays><<<dim3(staged_grid), dim3(64), 0, st>>>(r);
-    collapseRankKernel<Arrays><<<dim3(staged_grid), dim3(256), 0, st>>>(r);
-    collapseSortKernel<Arrays><<<dim3(std::min<uint32_t>(M, 32)), dim3(kSortThreads), 0, st>>>(r);
-    collapseBetweenKernel<Arrays><<<dim3(2 * staged_grid), dim3(kBetweenThreads), 0, st>>>(r);
-    r.sums = SearchParts();
-    r.rewritten_count = nullptr;
+    r.mat_flag = info + l.mat_flag;
+    r.active = reinterpret_cast<uint8_t *>(info + l.active);
+    r.sort_row = t.row_out.ptr;
+    r.position_of = t.positionOf(T);
+    r.stretch_end = t.stretchEnd(T);
+    r.mat_list = info + l.mat_list;
+    r.replay_list = info + l.replay_list;
+    r.between_items = t.between_items.ptr;
+    r.between_count = info + l.between_count;
+    r.row_items = t.row_items.ptr;
+    r.row_item_count = info + l.row_item_count;
+    r.pair_base = t.pair_base.ptr;
+    r.pair_bytes = reinterpret_cast<unsigned long long *>(info + l.pair_bytes);
+    r.pair_table = t.pair_table.ptr;
+    r.list_index = t.list_index.ptr;
+    r.order = t.order.ptr;
+    r.head_of = t.head.ptr;
+    r.close = t.close(T);
+    r.barrier = t.barrier(T);
+    r.pair_column = t.pair_column.ptr;
+    r.pair_lo = t.pair_bound.ptr;
+    r.pair_hi = t.pair_bound.ptr + T;
+    r.pair_pattern = t.pair_pattern.ptr;
+    r.info = info + l.info;
+    r.debug = knobs.debug;
+    r.no_lds_tables = knobs.no_lds_tables;
+    return r;
+}
+void setOutputs(ReplayArgs<MatrixArrays> & r, const MatrixCaller & caller) {
+    r.rowmax = caller.rowmax;
+    r.mat_fast = caller.mat_fast;
+    r.mat_mid = caller.mat_mid;
+}
+void setOutputs(ReplayArgs<CsrArrays> &, const ProblemCaller &) {}  // (the merged counts: CsrArrays)
+
+// ---- the runs ------------------------------------------------------------------------------------------------------------------------
+// What was held back behind a walk-only collapseRunsKernel, on the stream of whoever read the matrices: the search has read them as
+// built (sums): its sums are adjusted, then the rows of the runs take their heads' values; nobody has (null): the rows only.
+hipError_t launchHeldBackRuns(ReplayArgs<MatrixArrays> r, const SearchParts * sums, const Launch adjust_sums, const Launch rewrite, hipStream_t on) {
+    if (sums) {
+        r.sums = *sums;
+        collapseAdjustSumsKernel<<<dim3(adjust_sums.grid), dim3(adjust_sums.block), 0, on>>>(r);
+    }
     r.walk_only = false;
-    if (held_back_runs) {
+    collapseRewriteKernel<<<dim3(rewrite.grid), dim3(rewrite.block), 0, on>>>(r);
+    return hipGetLastError();
+}
+
+hipError_t queueRuns(ReplayArgs<MatrixArrays> r, const CollapsePlan & plan, const MatrixCaller & caller, CollapseTemporaries & t, hipStream_t st) {
+    if (caller.held_back_runs) {
         // The walk over the runs writes nothing a reader of the matrices sees (the heads of the list positions, the list of the
         // rows that will take their head's values): it runs here, on the collapse's stream, beside the search — one matrix of a
         // configs[2] batch walks for 0.8 ms, which stood behind the tile kernel on the search's stream (round 5) — and what is
         // held back is the adjustment of the search's sums and the rewrite of the rows.
-        ok(tmp->rewritten_count.alloc(M));
-        r.rewritten_count = tmp->rewritten_count.ptr;
+        const hipError_t e = t.rewritten_count.alloc(plan.M);
+        if (e != hipSuccess) return e;
+        r.rewritten_count = t.rewritten_count.ptr;
         r.walk_only = true;
-        collapseRunsKernel<Arrays><<<dim3(staged_grid), dim3(256), 0, st>>>(r);
-        *held_back_runs = [=](hipStream_t on, const SearchParts * sums) {
-            ReplayArgs<Arrays> mine = r;
-            if (sums) {  // the search has read the matrices as built: its sums, then the rows
-                mine.sums = *sums;
-                launchAdjustAndRewrite(mine, staged_grid, on);
-            } else {
-                launchRewrite(mine, staged_grid, on);
-            }
-            return hipGetLastError();
-        };
-    } else {
-        collapseRunsKernel<Arrays><<<dim3(staged_grid), dim3(256), 0, st>>>(r);
     }
-    ok(hipGetLastError());
-    return e;
+    collapseRunsKernel<MatrixArrays><<<dim3(plan.runs.grid), dim3(plan.runs.block), 0, st>>>(r);
+    if (caller.held_back_runs) {
+        const Launch adjust_sums = plan.adjust_sums, rewrite = plan.rewrite;
+        *caller.held_back_runs = [=](hipStream_t on, const SearchParts * sums) { return launchHeldBackRuns(r, sums, adjust_sums, rewrite, on); };
+    }
+    return hipSuccess;
+}
+hipError_t queueRuns(const ReplayArgs<CsrArrays> & r, const CollapsePlan & plan, const ProblemCaller &, CollapseTemporaries &, hipStream_t st) {
+    collapseRunsKernel<CsrArrays><<<dim3(plan.runs.grid), dim3(plan.runs.block), 0, st>>>(r);
+    return hipSuccess;
 }
 
 // sort key, slot and zero pattern of every row slot of the EM problems' storage: the slots of a problem's kept rows carry
@@ -2156,21 +2125,9 @@ __global__ __launch_bounds__(256) void csrCollapseKeysKernel(const CsrArrays g, 
         for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
             uint64_t k = unused, pattern = 0;
             if (i < mv.R) {
-                const double noise = mv.noise[i];
-                double projection = collapseWeight(mv.G) * noise, largest = 0.0;
-                uint64_t cells = cellHashTerm(mv.G, noise);
-                for (uint32_t e = mv.off[i]; e < mv.off[i + 1]; ++e) {
-                    const uint32_t c = mv.col[e];
-                    const double v = mv.val[e];
-                    projection = fma(collapseWeight(c), v, projection);
-                    largest = fmax(largest, v);
-                    cells += cellHashTerm(c, v);
-                    if (c < 64 && v != 0.0) pattern |= 1ull << c;
-                }
-                // the top of the low field: a hash of the row's cells, sorted on (rows of equal cells end up next to each other)
-                constexpr int low_bits = kCollapseLargestBits - kCsrCellHashBits;
-                k = collapseSortKey(p, projection, largest);
-                k = (k & ~((1ull << kCollapseLargestBits) - 1)) | (((cells * 0x9E3779B97F4A7C15ull) >> (64 - kCsrCellHashBits)) << low_bits) | (k & ((1ull << low_bits) - 1));
+                const CsrRowKey own = csrRowKey(mv, p, static_cast<uint32_t>(i));
+                k = own.key;
+                pattern = own.pattern;
             }
             key[r0 + i] = k;
             row[r0 + i] = static_cast<uint32_t>(r0 + i);
@@ -2198,23 +2155,98 @@ __global__ __launch_bounds__(256) void csrCollapseKeysKernel(const CsrArrays g, 
     }
 }
 
-}  // namespace
-
-// RPVG_HIP_COLLAPSE_LIBRARY_SORT = 1 | matrices | problems: the library's radix sorts instead of the hand-written segment sort (A/B)
-static bool librarySortFor(const char * what) {
-    const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_LIBRARY_SORT");
-    return env != nullptr && (std::strcmp(env, "1") == 0 || std::strcmp(env, what) == 0);
+// The experiment switches of the collapse (docs/design/knobs.md; the names exist in an EXPERIMENTS=1 build only).  The grid once per
+// process; the others per call: the tests take both ways of the sort in one process.
+CollapseKnobs collapseKnobs() {
+    static const uint32_t small_grid = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_GRID") ? std::max(1, std::atoi(RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_GRID"))) : 256;
+    CollapseKnobs k;
+    k.small_grid = small_grid;
+    // the library's radix sorts instead of the hand-written segment sort (A/B, and the only way to the library routes below 2^20 rows)
+    const char * library = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_LIBRARY_SORT");
+    k.library_sort_matrices = library != nullptr && (std::strcmp(library, "1") == 0 || std::strcmp(library, "matrices") == 0);
+    k.library_sort_problems = library != nullptr && (std::strcmp(library, "1") == 0 || std::strcmp(library, "problems") == 0);
+    k.no_lds_tables = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_NO_LDS_TABLES") != nullptr;
+    k.debug = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_COLLAPSE_DEBUG") != nullptr;
+    return k;
 }
+
+// ---- the sort, one function per route ------------------------------------------------------------------------------------------------
+// HandSort: the segment sort in registers; for the EM problems behind the kernel that fills the row slots no problem uses
+template <typename Arrays, typename Caller>
+hipError_t queueHandSort(const Arrays & arrays, const CollapsePlan & plan, const Caller & caller, const CollapseTemporaries & t, hipStream_t st) {
+    const hipError_t e = zeroAsync(t.chunk_count.ptr, sizeof(uint32_t), st);
+    SegmentSortArgs<Arrays> c = segmentSortArgs(arrays, plan, t);
+    setKeySource(c, caller, t);
+    if (Arrays::kHashBits) collapseUnusedSlotsKernel<Arrays><<<dim3(plan.unused_slots.grid), dim3(plan.unused_slots.block), 0, st>>>(c);
+    launchSegmentSort(c, plan.segment_sort, st);
+    return e;
+}
+// LibraryGlobal / LibrarySegmented (queueLibrarySort of the caller), then "equal to its predecessor" for every sorted position
+template <typename Arrays, typename Caller>
+hipError_t queueLibrarySortAndSamePrev(const PairScanArgs<Arrays> & a, const CollapsePlan & plan, const Caller & caller, const CollapseTemporaries & t, hipStream_t st) {
+    size_t bytes = t.sort_tmp.count;
+    const hipError_t e = queueLibrarySort(caller, plan, t, t.sort_tmp.ptr, bytes, st);
+    collapseSamePrevKernel<Arrays><<<dim3(plan.same_prev.grid), dim3(plan.same_prev.block), 0, st>>>(a);
+    return e;
+}
+
+// The stages of a collapse, for group matrices and for EM problems alike, behind allocateCollapse (and, on the EM problems' library
+// route, csrCollapseKeysKernel): `info` receives [counters | zeroed words | active bytes | list sizes] (InfoLayout).
+template <typename Arrays, typename Caller>
+hipError_t queueCollapseStages(const Arrays & arrays, const CollapsePlan & plan, const CollapseKnobs & knobs, const double precision, const Caller & caller,
+                               CollapseTemporaries & t, uint32_t * info, hipEvent_t sorted, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+    ok(zeroAsync(info, plan.info.zeroed_words * sizeof(uint32_t), st));
+    PairScanArgs<Arrays> a = pairScanArgs(arrays, plan, knobs, precision, t, info);
+    // the sort
+    if (plan.route == HandSort) ok(queueHandSort(arrays, plan, caller, t, st));
+    else ok(queueLibrarySortAndSamePrev(a, plan, caller, t, st));
+    if (sorted) ok(hipEventRecord(sorted, st));
+    // the pair scans
+    size_t scan_bytes = t.sort_tmp.count;
+    ok(queueStretchScan(t, plan.total_rows, t.sort_tmp.ptr, scan_bytes, st));
+    a.stretch_first = t.stretchFirst(plan.total_rows);
+    collapseStretchEndKernel<Arrays><<<dim3(plan.stretch_end.grid), dim3(plan.stretch_end.block), 0, st>>>(a);
+    collapseForwardPairsKernel<Arrays><<<dim3(plan.forward_pairs.grid), dim3(plan.forward_pairs.block), 0, st>>>(a);
+    collapseMarkPairsKernel<Arrays><<<dim3(plan.mark_pairs.grid), dim3(plan.mark_pairs.block), 0, st>>>(a);
+    a.pair_count += 1;  // the list is free again
+    collapseAroundPairsKernel<Arrays><<<dim3(plan.around_pairs.grid), dim3(plan.around_pairs.block), 0, st>>>(a);
+    collapseActivePairsKernel<Arrays><<<dim3(plan.active_pairs.grid), dim3(plan.active_pairs.block), 0, st>>>(a);
+    // the replay
+    ReplayArgs<Arrays> r = replayArgs(arrays, plan, knobs, precision, t, info);
+    setOutputs(r, caller);
+    collapseListKernel<Arrays><<<dim3(plan.list.grid), dim3(plan.list.block), 0, st>>>(r);
+    collapsePairTableKernel<Arrays><<<dim3(plan.pair_table.grid), dim3(plan.pair_table.block), 0, st>>>(r);
+    collapseRankKernel<Arrays><<<dim3(plan.rank.grid), dim3(plan.rank.block), 0, st>>>(r);
+    collapseSortKernel<Arrays><<<dim3(plan.list_sort.grid), dim3(plan.list_sort.block), 0, st>>>(r);
+    collapseBetweenKernel<Arrays><<<dim3(plan.between.grid), dim3(plan.between.block), 0, st>>>(r);
+    // the runs
+    ok(queueRuns(r, plan, caller, t, st));
+    ok(hipGetLastError());
+    return e;
+}
+
+}  // namespace
 
 // Queues the collapse of the matrices of `g` on `st` behind their build (rpvg_hip_groups_build).
 hipError_t rpvg_hip_detail::queueRowCollapse(rpvg_hip_ctx * ctx, rpvg_hip_groups * g, const uint64_t total_rows, const double precision,
                                              hipStream_t st, const bool hold_back_runs) {
-    (void) ctx;
-    const uint32_t M = g->num_matrices;
-    if (M == 0 || total_rows == 0) return hipSuccess;
-    if (total_rows > 0x7fffffffull || M >= kCollapseMaxMatrices) return hipErrorInvalidValue;
+    CollapseShape shape;
+    shape.M = g->num_matrices;
+    shape.total_rows = total_rows;
+    for (uint32_t m = 0; m < shape.M; ++m) shape.max_segment_rows = std::max<uint64_t>(shape.max_segment_rows, g->h_num_rows[m]);
+    shape.hash_bits = MatrixArrays::kHashBits;
+    shape.caller_keys = true;
+    (void) ctx;  // (the CU count sizes the keys kernel of the EM problems only)
+    const CollapseKnobs knobs = collapseKnobs();
+    const CollapsePlan plan = planCollapse(shape, knobs);
+    if (plan.verdict != kRun) return plan.verdict == kNothingToDo ? hipSuccess : hipErrorInvalidValue;
     std::shared_ptr<CollapseTemporaries> tmp = std::make_shared<CollapseTemporaries>();
     g->build_temporaries.emplace_back(tmp);
+    const MatrixCaller caller{g->collapse_key.ptr, g->collapse_row.ptr, g->rowmax.ptr, g->mat_fast.ptr, g->mat_mid.ptr, hold_back_runs ? &g->held_back_runs : nullptr};
+    const hipError_t e = allocateCollapse(plan, caller, *tmp, g->collapse_info, st);
+    if (e != hipSuccess) return e;
     MatrixArrays arrays;
     arrays.mat_val_off = g->mat_val_off.ptr;
     arrays.mat_row_off = g->mat_row_off.ptr;
@@ -2224,15 +2256,7 @@ hipError_t rpvg_hip_detail::queueRowCollapse(rpvg_hip_ctx * ctx, rpvg_hip_groups
     arrays.row_noise = g->row_noise.ptr;
     arrays.row_count = g->row_count.ptr;
     arrays.zero_pattern = g->collapse_mask.ptr;
-    static const bool segmented = RPVG_EXPERIMENT_ENV("RPVG_HIP_COLLAPSE_SEGMENTED_SORT") != nullptr;  // (A/B: slower on the group matrices)
-    const bool library_sort = librarySortFor("matrices") || segmented;  // A/B knob (read per call: the tests take both ways)
-    SegmentSortPlan plan;
-    for (uint32_t m = 0; m < M; ++m) plan.max_segment_rows = std::max<uint64_t>(plan.max_segment_rows, g->h_num_rows[m]);
-    const bool use_plan = !library_sort && plan.max_segment_rows <= kSortMaxSegmentRows;
-    return queueCollapseStages(arrays, M, total_rows, precision, g->collapse_key.ptr, g->collapse_row.ptr, g->collapse_segment_off.ptr,
-                               g->collapse_segment_off.ptr + 1, segmented && g->collapse_segment_off.ptr != nullptr, g->collapse_info,
-                               g->rowmax.ptr, g->mat_fast.ptr, g->mat_mid.ptr, tmp.get(), st, use_plan ? &plan : nullptr, nullptr,
-                               hold_back_runs ? &g->held_back_runs : nullptr);
+    return queueCollapseStages(arrays, plan, knobs, precision, caller, *tmp, g->collapse_info.ptr, nullptr, st);
 }
 
 // readCollapseProbabilityMatrix on the rows of every EM problem of a solve (src/path_abundance_estimator.cpp:266,668): queued
@@ -2242,23 +2266,26 @@ hipError_t rpvg_hip_detail::queueRowCollapse(rpvg_hip_ctx * ctx, rpvg_hip_groups
 hipError_t rpvg_hip_detail::queueCsrCollapse(rpvg_hip_ctx * ctx, const CsrCollapseInput & in, const double precision, CsrCollapseWork & work, hipStream_t st,
                                              hipEvent_t sorted) {
     const uint32_t P = in.num_problems_bound;
-    const uint64_t total_rows = in.rows_capacity;
-    if (P == 0 || total_rows == 0) return hipSuccess;
-    if (total_rows > 0x7fffffffull || P + 1 >= kCollapseMaxMatrices) return hipErrorInvalidValue;
-    std::shared_ptr<CollapseTemporaries> tmp = std::make_shared<CollapseTemporaries>();
-    work.temporaries = tmp;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-    const bool library_sort = librarySortFor("problems");  // A/B knob (read per call: the tests take both ways)
     // The hand-written segment sort computes the keys itself; problems of 2^20 rows or more (by the bound) and the A/B knob take
     // the library sort behind csrCollapseKeysKernel.
-    const bool use_plan = !library_sort && in.max_rows_bound <= kSortMaxSegmentRows && in.max_rows_bound > 0 && in.seg_first && in.item_problem;
-    ok(tmp->csr_pattern.alloc(total_rows));
-    if (!use_plan) {
-        ok(tmp->csr_key.alloc(total_rows));
-        ok(tmp->csr_row.alloc(total_rows));
-    }
-    ok(work.merged_count.alloc(total_rows));
+    CollapseShape shape;
+    shape.M = P;
+    shape.total_rows = in.rows_capacity;
+    shape.max_segment_rows = in.max_rows_bound;
+    shape.hash_bits = CsrArrays::kHashBits;
+    shape.caller_keys = false;
+    shape.num_items_bound = in.num_items_bound;
+    shape.cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
+    const CollapseKnobs knobs = collapseKnobs();
+    const CollapsePlan plan = planCollapse(shape, knobs);
+    if (plan.verdict != kRun) return plan.verdict == kNothingToDo ? hipSuccess : hipErrorInvalidValue;
+    std::shared_ptr<CollapseTemporaries> tmp = std::make_shared<CollapseTemporaries>();
+    work.temporaries = tmp;
+    const ProblemCaller caller{in};
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+    ok(allocateCollapse(plan, caller, *tmp, work.info, st));
+    ok(work.merged_count.alloc(plan.total_rows));
     ok(work.problem_merged.alloc(P + 1));  // [P]: the number of merged problems
     if (e != hipSuccess) return e;
     ok(zeroAsync(work.problem_merged.ptr, (P + 1) * sizeof(uint32_t), st));
@@ -2268,37 +2295,15 @@ hipError_t rpvg_hip_detail::queueCsrCollapse(rpvg_hip_ctx * ctx, const CsrCollap
     arrays.merged_count = work.merged_count.ptr;
     arrays.problem_merged = work.problem_merged.ptr;
     arrays.merged_problems = work.problem_merged.ptr + P;
-    if (use_plan) {
-        SegmentSortPlan plan;
-        plan.num_matrices_dev = in.num_problems_dev;
-        plan.num_items_bound = in.num_items_bound;
-        plan.num_items_dev = in.num_items_dev;
-        plan.seg_first = in.seg_first;
-        plan.item_problem = in.item_problem;
-        plan.segment_rows = in.segment_rows;
-        plan.pattern_out = tmp->csr_pattern.ptr;
-        plan.max_segment_rows = in.max_rows_bound;
-        return queueCollapseStages(arrays, P, total_rows, precision, nullptr, nullptr, nullptr, nullptr, false, work.info, nullptr, nullptr, nullptr, tmp.get(), st, &plan, sorted);
-    }
-    // The rows of a problem are sorted as a segment: a handful of launches against the global sort's seven passes of three
-    // launches each (same box, configs[2] batch: 12.0-12.5 ms per step against 14.6).  RPVG_HIP_EM_COLLAPSE_GLOBAL_SORT=1: the
-    // global sort (A/B).
-    static const bool segmented = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_COLLAPSE_GLOBAL_SORT") == nullptr;
-    if (segmented) {
-        ok(tmp->csr_segments.alloc(2 * static_cast<size_t>(P)));
-        ok(tmp->key_out.alloc(total_rows));
-        ok(tmp->row_out.alloc(total_rows));
+    if (plan.route == LibrarySegmented) {
+        uint32_t * segment_begin = tmp->csr_segments.ptr, * segment_end = segment_begin + P;
+        csrCollapseKeysKernel<<<dim3(plan.keys.grid), dim3(plan.keys.block), 0, st>>>(arrays, P, in.num_problems_dev, in.num_items_bound, in.num_items_dev, in.seg_first,
+                                                                                    in.item_problem, in.segment_rows, plan.total_rows, tmp->csr_key.ptr, tmp->csr_row.ptr,
+                                                                                    tmp->csr_pattern.ptr, segment_begin, segment_end, tmp->key_out.ptr, tmp->row_out.ptr);
+        ok(hipGetLastError());
         if (e != hipSuccess) return e;
     }
-    uint32_t * segment_begin = segmented ? tmp->csr_segments.ptr : nullptr, * segment_end = segmented ? segment_begin + P : nullptr;
-    const uint32_t keys_grid = std::max<uint32_t>(1, std::min<uint32_t>(in.num_items_bound, static_cast<uint32_t>(ctx->props.multiProcessorCount) * 8));
-    csrCollapseKeysKernel<<<dim3(keys_grid), dim3(256), 0, st>>>(arrays, P, in.num_problems_dev, in.num_items_bound, in.num_items_dev, in.seg_first, in.item_problem,
-                                                                in.segment_rows, total_rows, tmp->csr_key.ptr, tmp->csr_row.ptr, tmp->csr_pattern.ptr, segment_begin,
-                                                                segment_end, tmp->key_out.ptr, tmp->row_out.ptr);
-    ok(hipGetLastError());
-    if (e != hipSuccess) return e;
-    return queueCollapseStages(arrays, P, total_rows, precision, tmp->csr_key.ptr, tmp->csr_row.ptr, segment_begin, segment_end, segmented, work.info, nullptr,
-                               nullptr, nullptr, tmp.get(), st, nullptr, sorted);
+    return queueCollapseStages(arrays, plan, knobs, precision, caller, *tmp, work.info.ptr, sorted, st);
 }
 
 extern "C" int rpvg_hip_groups_collapse_info(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t * matrices_replayed,
@@ -2309,7 +2314,7 @@ extern "C" int rpvg_hip_groups_collapse_info(rpvg_hip_ctx * ctx, const rpvg_hip_
         std::lock_guard<std::mutex> lock(ctx->mutex);
         RPVG_HIP_CHECK(hipSetDevice(ctx->device));
         RPVG_HIP_CHECK(groups->waitCollapse(ctx->stream));
-        RPVG_HIP_CHECK(hipMemcpyAsync(info, groups->collapse_info.ptr, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
+        RPVG_HIP_CHECK(hipMemcpyAsync(info, groups->collapse_info.ptr + InfoLayout::info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
         RPVG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     if (matrices_replayed) *matrices_replayed = info[kInfoMatrices];
@@ -2339,13 +2344,13 @@ extern "C" int rpvg_hip_segment_sort_words(rpvg_hip_ctx * ctx, const uint64_t * 
     hipStream_t st = ctx->stream;
     DeviceBuffer<uint64_t> d_words, d_off, d_out, words_a, words_b;
     DeviceBuffer<uint32_t> chunks, chunk_count;
-    const uint32_t chunk_capacity = segmentSortChunkCapacity(total, num_segments);
+    const SegmentSortPlan plan = planSegmentSort(num_segments, total, longest, CollapseKnobs().small_grid);
     RPVG_HIP_CHECK(d_words.upload(words, total, st));
     RPVG_HIP_CHECK(d_off.upload(segment_off, static_cast<size_t>(num_segments) + 1, st));
     RPVG_HIP_CHECK(d_out.alloc(total));
     RPVG_HIP_CHECK(words_a.alloc(total));
     RPVG_HIP_CHECK(words_b.alloc(total));
-    RPVG_HIP_CHECK(chunks.alloc(2 * static_cast<size_t>(chunk_capacity)));
+    RPVG_HIP_CHECK(chunks.alloc(2 * static_cast<size_t>(plan.chunk_capacity)));
     RPVG_HIP_CHECK(chunk_count.alloc(1));
     RPVG_HIP_CHECK(zeroAsync(chunk_count.ptr, sizeof(uint32_t), st));
     SegmentSortArgs<WordArrays> c{};
@@ -2358,8 +2363,8 @@ extern "C" int rpvg_hip_segment_sort_words(rpvg_hip_ctx * ctx, const uint64_t * 
     c.words_b = words_b.ptr;
     c.chunks = chunks.ptr;
     c.chunk_count = chunk_count.ptr;
-    c.chunk_capacity = chunk_capacity;
-    launchSegmentSort(c, num_segments, longest, 256, st);
+    c.chunk_capacity = plan.chunk_capacity;
+    launchSegmentSort(c, plan, st);
     RPVG_HIP_CHECK(hipGetLastError());
     RPVG_HIP_CHECK(d_out.download(out, st));
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
