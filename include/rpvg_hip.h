@@ -28,6 +28,7 @@
 #include "rpvg_rows.h"
 #include "rpvg_index.h"
 #include "rpvg_table.h"
+#include "rpvg_samples.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -710,6 +711,44 @@ int rpvg_hip_estimates_table_tpm(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * 
 int rpvg_hip_estimates_table_view(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table, rpvg_estimates_table_view * view_out);
 void rpvg_hip_estimates_table_limits(rpvg_estimates_table_limits * limits_out);
 void rpvg_hip_estimates_table_free(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table);
+
+/* ---- Gibbs samples table (rpvg_samples.h; rpvg_amd/csrc/gibbs_table.hip) ---------------------------------------------------
+ *   rpvg_hip_gibbs_table_build           the table of `<prefix>_gibbs.txt.gz` for a batch, every value as rpvg_samples.h states it: per
+ *                                       path its N sample columns, what ReadCountGibbsSamplesWriter::addSamples reads transposed
+ *                                       through its per-path column vectors and fills with zeros (src/threaded_output_writer.cpp:114-214),
+ *                                       the rows it prints (listed), and the per-sample noise totals of its `Unknown` row (the chain
+ *                                       of `noise_counts.at(idx) +=` over the clusters, same lines).  Host arrays are copied as one
+ *                                       block; device arrays (on_device = 1) are read where they lie.  One kernel validates behind the
+ *                                       copy and before any table kernel: RPVG_HIP_ERR_INVALID for offsets that are not non-decreasing
+ *                                       from 0 to the stated sizes, a block whose abundance samples are not samples x columns, path ids
+ *                                       that do not ascend strictly or reach the cluster's number of paths, a cluster with more than N
+ *                                       samples, or N = 0; last_error names the smallest offending cluster, or else the smallest
+ *                                       offending block.
+ *   rpvg_hip_gibbs_table_view            host copies of samples, listed and noise_counts, and the clusters per route.
+ *   rpvg_hip_gibbs_table_rows            the sample rows of paths [first_path, first_path + num_paths) only (num_paths x N doubles to
+ *                                       host memory): a writer streams a table it could not hold twice.
+ *   rpvg_hip_gibbs_table_limits          the sizes at which a cluster changes its route (rpvg_amd/csrc/gibbs_table_plan.hpp).
+ *   rpvg_hip_gibbs_read_counts_resident  rpvg_hip_gibbs_read_counts (src/path_abundance_estimator.cpp:116-212) without its two
+ *                                       downloads: the same samples, left on the GPU in a handle with their two offset arrays.  A call
+ *                                       with no problem or no sample gives an empty handle.
+ *   rpvg_hip_gibbs_samples_get           the handle's samples to host memory, in the layout of rpvg_hip_gibbs_read_counts.
+ *   rpvg_hip_gibbs_table_build_resident  the table from a handle: the problems of the sampler call are the blocks (problem p: block p
+ *                                       of cluster problems->cluster[p], its col_path the block's path ids), which must come cluster
+ *                                       by cluster — RPVG_HIP_ERR_INVALID names the first problem whose cluster is below its
+ *                                       predecessor's.  cluster_path_off [K+1] and total_count [K] are host arrays. */
+int rpvg_hip_gibbs_table_build(rpvg_hip_ctx * ctx, const rpvg_gibbs_flat * samples, rpvg_hip_gibbs_table ** table_out);
+int rpvg_hip_gibbs_table_view(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_table * table, rpvg_gibbs_table_view * view_out);
+int rpvg_hip_gibbs_table_rows(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_table * table, uint64_t first_path, uint64_t num_paths, double * rows_out);
+void rpvg_hip_gibbs_table_limits(rpvg_gibbs_table_limits * limits_out);
+void rpvg_hip_gibbs_table_free(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_table * table);
+int rpvg_hip_gibbs_read_counts_resident(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_em_problems * problems,
+                                        const double * init_abundances, const double * init_noise_count, const uint32_t * num_samples,
+                                        const uint64_t * seeds, uint32_t gibbs_thin_its, double gamma, rpvg_hip_gibbs_samples ** samples_out);
+int rpvg_hip_gibbs_samples_get(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs_samples * samples, double * noise_samples, double * abundance_samples);
+void rpvg_hip_gibbs_samples_free(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_samples * samples);
+int rpvg_hip_gibbs_table_build_resident(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs_samples * samples, const rpvg_hip_em_problems * problems,
+                                        uint32_t num_clusters, const uint64_t * cluster_path_off, const double * total_count,
+                                        uint32_t num_gibbs_samples, rpvg_hip_gibbs_table ** table_out);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the

@@ -13,6 +13,7 @@
 
 #include "em_block.hpp"
 #include "gibbs_random.hpp"
+#include "gibbs_samples.hpp"
 
 #include <vector>
 
@@ -127,40 +128,52 @@ __global__ __launch_bounds__(256) void gibbsReadCountKernel(const GibbsLaunchArg
 }
 }  // namespace
 
-extern "C" int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch,
-                                          const rpvg_hip_em_problems * problems, const double * init_abundances,
-                                          const double * init_noise_count, const uint32_t * num_samples,
-                                          const uint64_t * seeds, uint32_t gibbs_thin_its, double gamma,
-                                          double * noise_samples, double * abundance_samples) {
-    RPVG_REQUIRE(ctx && batch && problems, "rpvg_hip_gibbs_read_counts: NULL argument");
-    const uint32_t P = problems->num_problems;
-    if (P == 0) return RPVG_HIP_OK;
-    RPVG_REQUIRE(problems->cluster && problems->col_off && problems->col_path, "rpvg_hip_gibbs_read_counts: NULL problem arrays");
-    RPVG_REQUIRE(init_abundances && init_noise_count && num_samples && seeds && noise_samples && abundance_samples,
-                 "rpvg_hip_gibbs_read_counts: NULL argument");
-    RPVG_REQUIRE(gibbs_thin_its > 0, "rpvg_hip_gibbs_read_counts: gibbs_thin_its must be positive");
-    RPVG_REQUIRE(gamma >= 1.0, "rpvg_hip_gibbs_read_counts: gamma must be >= 1 (the reference uses 1)");
+namespace {
 
-    std::vector<uint64_t> sample_off(P + 1, 0), abund_sample_off(P + 1, 0);
+// what a call needs on the device besides its samples; it goes back to the pool once the stream has been waited for
+struct GibbsCallBuffers {
+    DeviceBuffer<uint32_t> d_kept_rows, d_kept_ent, d_num_samples;
+    DeviceBuffer<double> d_total, d_init_abund, d_init_noise;
+    DeviceBuffer<uint64_t> d_seed;
+    HostProblemSet ps;
+};
+
+// Everything of rpvg_hip_gibbs_read_counts up to its two downloads: validates, draws every sample and leaves them in `s` with
+// their offsets (queued on the context's stream, not waited for).  The caller holds the context's lock, waits for the stream and
+// lets `call` go only then.  *drawn: whether anything was queued (a call with no problem or no sample leaves `s` empty).
+int drawGibbsSamples(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_em_problems * problems, const double * init_abundances,
+                     const double * init_noise_count, const uint32_t * num_samples, const uint64_t * seeds, const uint32_t gibbs_thin_its,
+                     const double gamma, const char * who, GibbsCallBuffers & call, rpvg_hip_gibbs_samples & s, bool * drawn) {
+    *drawn = false;
+    const uint32_t P = problems->num_problems;
+    s.num_problems = P;
+    s.sample_off.assign(static_cast<size_t>(P) + 1, 0);
+    s.abund_sample_off.assign(static_cast<size_t>(P) + 1, 0);
+    if (P == 0) return RPVG_HIP_OK;
+    RPVG_REQUIRE(problems->cluster && problems->col_off && problems->col_path, "%s: NULL problem arrays", who);
+    RPVG_REQUIRE(init_abundances && init_noise_count && num_samples && seeds, "%s: NULL argument", who);
+    RPVG_REQUIRE(gibbs_thin_its > 0, "%s: gibbs_thin_its must be positive", who);
+    RPVG_REQUIRE(gamma >= 1.0, "%s: gamma must be >= 1 (the reference uses 1)", who);
+
+    std::vector<uint64_t> & sample_off = s.sample_off, & abund_sample_off = s.abund_sample_off;
     for (uint32_t p = 0; p < P; ++p) {
         sample_off[p + 1] = sample_off[p] + num_samples[p];
         abund_sample_off[p + 1] = abund_sample_off[p] + static_cast<uint64_t>(num_samples[p]) * (problems->col_off[p + 1] - problems->col_off[p]);
     }
     if (sample_off[P] == 0) return RPVG_HIP_OK;
 
-    std::lock_guard<std::mutex> lock(ctx->mutex);
     RPVG_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
     // the compacted CSR of the problems, as for the EM (the first stage of a solve: no EM kernels)
-    DeviceBuffer<uint32_t> d_iters, d_kept_rows, d_kept_ent;
-    DeviceBuffer<double> d_total;
+    DeviceBuffer<uint32_t> & d_kept_rows = call.d_kept_rows, & d_kept_ent = call.d_kept_ent;
+    DeviceBuffer<double> & d_total = call.d_total;
     RPVG_HIP_CHECK(d_kept_rows.alloc(P));
     RPVG_HIP_CHECK(d_kept_ent.alloc(P));
     RPVG_HIP_CHECK(d_total.alloc(P));
     EmOutputs out{nullptr, nullptr, nullptr, d_kept_rows.ptr, d_kept_ent.ptr, d_total.ptr};
-    HostProblemSet ps;
-    int rc = prepareHostProblems(ctx, batch, problems, ps, out, "rpvg_hip_gibbs_read_counts");
+    HostProblemSet & ps = call.ps;
+    int rc = prepareHostProblems(ctx, batch, problems, ps, out, who);
     if (rc != RPVG_HIP_OK) return rc;
     {
         const EmSolveKnobs knobs = emSolveKnobs();
@@ -215,9 +228,10 @@ extern "C" int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_bat
         }
     }
 
-    DeviceBuffer<double> d_init_abund, d_init_noise, d_noise_samples, d_abund_samples;
-    DeviceBuffer<uint32_t> d_num_samples;
-    DeviceBuffer<uint64_t> d_seed, d_sample_off, d_abund_sample_off;
+    DeviceBuffer<double> & d_init_abund = call.d_init_abund, & d_init_noise = call.d_init_noise;
+    DeviceBuffer<double> & d_noise_samples = s.d_noise_samples, & d_abund_samples = s.d_abund_samples;
+    DeviceBuffer<uint32_t> & d_num_samples = call.d_num_samples;
+    DeviceBuffer<uint64_t> & d_seed = call.d_seed, & d_sample_off = s.d_sample_off, & d_abund_sample_off = s.d_abund_sample_off;
     RPVG_HIP_CHECK(d_init_abund.upload(init_abundances, ps.n_cols_total, st));
     RPVG_HIP_CHECK(d_init_noise.upload(init_noise_count, P, st));
     RPVG_HIP_CHECK(d_num_samples.upload(grid_problems.empty() ? num_samples : staying_samples.data(), P, st));
@@ -272,15 +286,82 @@ extern "C" int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_bat
         storage.init_noise_count = d_init_noise.ptr;
         storage.noise_samples = d_noise_samples.ptr;
         storage.abundance_samples = d_abund_samples.ptr;
-        // (waits for grid_st behind every problem: their samples are in place when the downloads below are queued)
+        // (waits for grid_st behind every problem: their samples are in place when the caller queues its downloads)
         rc = runGibbsGridProblems(ctx, grid_st, grid_problems.data(), static_cast<uint32_t>(grid_problems.size()), storage, gibbs_thin_its, gamma);
         if (rc != RPVG_HIP_OK) {
             (void) hipDeviceSynchronize();  // (the buffers of this call go back to the pool on return)
             return rc;
         }
     }
-    RPVG_HIP_CHECK(d_noise_samples.download(noise_samples, st));
-    RPVG_HIP_CHECK(d_abund_samples.download(abundance_samples, st));
+    *drawn = true;
+    return RPVG_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int rpvg_hip_gibbs_read_counts(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch,
+                                          const rpvg_hip_em_problems * problems, const double * init_abundances,
+                                          const double * init_noise_count, const uint32_t * num_samples,
+                                          const uint64_t * seeds, uint32_t gibbs_thin_its, double gamma,
+                                          double * noise_samples, double * abundance_samples) {
+    RPVG_REQUIRE(ctx && batch && problems, "rpvg_hip_gibbs_read_counts: NULL argument");
+    RPVG_REQUIRE(problems->num_problems == 0 || (noise_samples && abundance_samples), "rpvg_hip_gibbs_read_counts: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    GibbsCallBuffers call;
+    rpvg_hip_gibbs_samples samples;
+    bool drawn = false;
+    const int rc = drawGibbsSamples(ctx, batch, problems, init_abundances, init_noise_count, num_samples, seeds, gibbs_thin_its, gamma,
+                                    "rpvg_hip_gibbs_read_counts", call, samples, &drawn);
+    if (rc != RPVG_HIP_OK || !drawn) return rc;
+    hipStream_t st = ctx->stream;
+    RPVG_HIP_CHECK(samples.d_noise_samples.download(noise_samples, st));
+    RPVG_HIP_CHECK(samples.d_abund_samples.download(abundance_samples, st));
     RPVG_HIP_CHECK(waitStream(st));
     return RPVG_HIP_OK;
+}
+
+extern "C" int rpvg_hip_gibbs_read_counts_resident(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_em_problems * problems,
+                                                   const double * init_abundances, const double * init_noise_count,
+                                                   const uint32_t * num_samples, const uint64_t * seeds, uint32_t gibbs_thin_its,
+                                                   double gamma, rpvg_hip_gibbs_samples ** samples_out) {
+    RPVG_REQUIRE(ctx && batch && problems && samples_out, "rpvg_hip_gibbs_read_counts_resident: NULL argument");
+    *samples_out = nullptr;
+    std::unique_ptr<rpvg_hip_gibbs_samples> samples(new (std::nothrow) rpvg_hip_gibbs_samples());
+    if (!samples) {
+        setError("rpvg_hip_gibbs_read_counts_resident: out of host memory");
+        return RPVG_HIP_ERR_ALLOC;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    GibbsCallBuffers call;
+    bool drawn = false;
+    const int rc = drawGibbsSamples(ctx, batch, problems, init_abundances, init_noise_count, num_samples, seeds, gibbs_thin_its, gamma,
+                                    "rpvg_hip_gibbs_read_counts_resident", call, *samples, &drawn);
+    if (rc != RPVG_HIP_OK) return rc;
+    if (drawn) RPVG_HIP_CHECK(waitStream(ctx->stream));  // (the buffers of the call go back to the pool on return)
+    *samples_out = samples.release();
+    return RPVG_HIP_OK;
+}
+
+extern "C" int rpvg_hip_gibbs_samples_get(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs_samples * samples, double * noise_samples,
+                                          double * abundance_samples) {
+    RPVG_REQUIRE(ctx && samples, "rpvg_hip_gibbs_samples_get: NULL argument");
+    RPVG_REQUIRE((samples->d_noise_samples.count == 0 || noise_samples) && (samples->d_abund_samples.count == 0 || abundance_samples),
+                 "rpvg_hip_gibbs_samples_get: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    RPVG_HIP_CHECK(samples->d_noise_samples.download(noise_samples, st));
+    RPVG_HIP_CHECK(samples->d_abund_samples.download(abundance_samples, st));
+    RPVG_HIP_CHECK(waitStream(st));
+    return RPVG_HIP_OK;
+}
+
+extern "C" void rpvg_hip_gibbs_samples_free(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_samples * samples) {
+    if (!samples) return;
+    if (ctx) {  // nothing queued on the context's stream may still use the buffers
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        (void) hipSetDevice(ctx->device);
+        (void) hipStreamSynchronize(ctx->stream);
+    }
+    delete samples;
 }

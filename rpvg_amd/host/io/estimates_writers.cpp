@@ -582,6 +582,48 @@ void ReadCountGibbsSamplesWriter::addSamples(const std::pair<uint32_t, PathClust
     }
 }
 
+void ReadCountGibbsSamplesWriter::addTable(const rpvg_gibbs_table_view & table, const TableLabels & labels) {
+
+    if (table.num_gibbs_samples != num_gibbs_samples) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addTable: the table has " + std::to_string(table.num_gibbs_samples) + " samples per path, the writer " + std::to_string(num_gibbs_samples));
+    }
+
+    if (labels.names.size() != table.num_paths || labels.cluster_ids.size() != table.num_clusters || !table.cluster_path_off || table.cluster_path_off[table.num_clusters] != table.num_paths) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addTable: one name per path and one ClusterID per cluster");
+    }
+
+    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+        noise_counts.at(idx) += table.noise_counts[idx];
+    }
+
+    out << std::setprecision(out_precision_digits);
+
+    for (uint32_t k = 0; k < table.num_clusters; ++k) {
+
+        for (uint64_t g = table.cluster_path_off[k]; g < table.cluster_path_off[k + 1]; ++g) {
+
+            if (!table.listed[g]) {
+
+                continue;
+            }
+
+            out << labels.names.at(g) << "\t" << labels.cluster_ids.at(k);
+
+            const double * row = table.samples + g * static_cast<uint64_t>(num_gibbs_samples);
+
+            for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+                out << "\t" << row[idx];
+            }
+
+            out << std::endl;
+        }
+    }
+}
+
 void ReadCountGibbsSamplesWriter::addNoiseTranscript(const uint32_t unaligned_read_count) {
 
     out << std::setprecision(out_precision_digits);

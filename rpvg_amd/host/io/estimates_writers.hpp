@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/rpvg_table.h"
+#include "../../../include/rpvg_samples.h"
 #include "../path_cluster_estimates.hpp"
 
 namespace rpvg_amd {
@@ -150,6 +151,15 @@ class ReadCountGibbsSamplesWriter : public EstimatesWriter {
 
         void addSamples(const std::pair<uint32_t, PathClusterEstimates> & path_cluster_estimate);
         void addNoiseTranscript(const uint32_t unaligned_read_count);
+
+        // The same rows from the table the GPU built of the samples of a batch (rpvg_amd/host/gibbs_samples_table.hpp): the listed
+        // rows of the view in path order, named by the labels.
+        // For ONE table per writer the text is what addSamples() writes cluster by cluster from the containers, byte for byte, the
+        // `Unknown` row included: the table's noise_counts are the writer's own chains.  With several tables into one writer a
+        // table's noise_counts join the writer's in one addition per column, where addSamples() adds cluster by cluster onto the
+        // running values, so the `Unknown` row can then differ in its last digit.  Throws EngineError for a view of another number
+        // of samples or labels of another size.
+        void addTable(const rpvg_gibbs_table_view & table, const TableLabels & labels);
 
     private:
 

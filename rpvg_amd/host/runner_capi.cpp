@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <algorithm>
 #include <memory>
 #include <stdexcept>
@@ -20,6 +21,7 @@
 #include "device_group.hpp"
 #include "estimates_table.hpp"
 #include "estimator_factory.hpp"
+#include "gibbs_samples_table.hpp"
 #include "io/estimates_writers.hpp"
 #include "align_index.hpp"
 #include "read_rows.hpp"
@@ -1576,6 +1578,28 @@ TableLabels labelsOf(const std::vector<std::vector<PathInfo> > & paths) {
     return labels;
 }
 
+// the containers of a prepared batch as the writers take them, the rows called as labelsOf() calls them
+template <typename Prepared>
+ClusterEstimatesList gibbsListOf(const Prepared & prepared) {
+
+    const TableLabels labels = labelsOf(prepared.paths);
+    ClusterEstimatesList list;
+    size_t g = 0;
+
+    for (size_t k = 0; k < prepared.estimates.size(); ++k) {
+
+        list.emplace_back(labels.cluster_ids[k], prepared.estimates[k]);
+
+        for (auto & path: list.back().second.paths) {
+
+            path.name = labels.names[g];
+            ++g;
+        }
+    }
+
+    return list;
+}
+
 // "abundance": <prefix>.txt of AbundanceEstimatesWriter; "haplotype": <prefix>.txt of HaplotypeAbundanceEstimatesWriter; "joint":
 // <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter.  add(writer) adds the rows.
 template <typename AddRows>
@@ -1786,6 +1810,217 @@ int rpvg_amd_estimates_write_from_containers(void * prepared_batch, const char *
             if (write_seconds_out) {
 
                 *write_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - write_start).count();
+            }
+        }
+
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+// ---- the Gibbs samples table of a prepared batch (gibbs_samples_table.hpp) -------------------------------------------------------
+
+// The table of the Gibbs samples the last run (-n > 0) left in the containers of the prepared batch, built on the engine's GPU; the
+// rows are called as rpvg_amd_estimates_table_build calls them.  seconds_out: flattening the containers and the build.
+void * rpvg_amd_gibbs_table_build(void * engine, void * prepared_batch, uint32_t num_gibbs_samples, double * seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const ClusterEstimatesList list = gibbsListOf(*prepared);
+        const auto start = std::chrono::steady_clock::now();
+        std::unique_ptr<GibbsSamplesTable> table(new GibbsSamplesTable(static_cast<Engine *>(engine)->hip, list, num_gibbs_samples));
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return table.release();
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return nullptr;
+    }
+}
+
+// valid until the table's end
+int rpvg_amd_gibbs_table_view(void * table_handle, rpvg_gibbs_table_view * view_out) {
+
+    try {
+
+        *view_out = static_cast<GibbsSamplesTable *>(table_handle)->view();
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+// <prefix>.txt.gz from the table by ReadCountGibbsSamplesWriter::addTable
+int rpvg_amd_gibbs_table_write(void * table_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    try {
+
+        GibbsSamplesTable * table = static_cast<GibbsSamplesTable *>(table_handle);
+        ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+        out.addTable(table->view(), table->labels());
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+        return 0;
+
+    } catch (const std::exception & e) {
+
+        last_error = e.what();
+        return -1;
+    }
+}
+
+void rpvg_amd_gibbs_table_free(void * table_handle) {
+
+    delete static_cast<GibbsSamplesTable *>(table_handle);
+}
+
+// The same from the containers on ONE thread.  With a prefix: the file by the writer's addSamples(), cluster by cluster.  With
+// samples_out [P * N], listed_out [P] and noise_counts_out [N]: the writer's loops with every stream insertion replaced by a store
+// into a dense table (the host comparison of tools/gibbs_table_ab.py); seconds_out is the time of those loops alone.
+int rpvg_amd_gibbs_from_containers(void * prepared_batch, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count,
+                                   double * samples_out, uint8_t * listed_out, double * noise_counts_out, double * seconds_out) {
+
+    try {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const ClusterEstimatesList list = gibbsListOf(*prepared);
+
+        if (output_prefix && output_prefix[0]) {
+
+            ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+
+            for (auto & entry: list) {
+
+                out.addSamples(entry);
+            }
+
+            out.addNoiseTranscript(unaligned_read_count);
+            out.close();
+        }
+
+        if (samples_out && listed_out && noise_counts_out) {
+
+            const auto start = std::chrono::steady_clock::now();
+            const uint32_t no_column = std::numeric_limits<uint32_t>::max();
+            uint64_t g0 = 0;
+
+            for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+                noise_counts_out[idx] = 0;
+            }
+
+            for (auto & entry: list) {
+
+                const auto & estimates = entry.second;
+                const size_t num_paths = estimates.paths.size();
+                std::fill(samples_out + g0 * num_gibbs_samples, samples_out + (g0 + num_paths) * num_gibbs_samples, 0.0);
+                std::fill(listed_out + g0, listed_out + g0 + num_paths, 0);
+
+                if (estimates.gibbs_read_count_samples.empty()) {
+
+                    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+                        noise_counts_out[idx] += estimates.total_count;
+                    }
+
+                    g0 += num_paths;
+                    continue;
+                }
+
+                std::vector<std::vector<uint32_t> > path_gibbs_sampling_index(num_paths);
+                uint32_t noise_count_idx = 0;
+
+                for (size_t i = 0; i < estimates.gibbs_read_count_samples.size(); ++i) {
+
+                    const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(i);
+
+                    for (auto & noise_sample: count_samples.noise_samples) {
+
+                        noise_counts_out[noise_count_idx] += noise_sample;
+                        ++noise_count_idx;
+                    }
+
+                    for (size_t j = 0; j < count_samples.path_ids.size(); ++j) {
+
+                        auto & sampling_indices = path_gibbs_sampling_index.at(count_samples.path_ids.at(j));
+
+                        if (sampling_indices.empty()) {
+
+                            sampling_indices.assign(estimates.gibbs_read_count_samples.size(), no_column);
+                        }
+
+                        sampling_indices.at(i) = j;
+                    }
+                }
+
+                while (noise_count_idx < num_gibbs_samples) {
+
+                    noise_counts_out[noise_count_idx] += estimates.total_count;
+                    ++noise_count_idx;
+                }
+
+                for (size_t i = 0; i < num_paths; ++i) {
+
+                    const auto & sampling_indices = path_gibbs_sampling_index.at(i);
+
+                    if (sampling_indices.empty()) {
+
+                        continue;
+                    }
+
+                    listed_out[g0 + i] = 1;
+                    double * row = samples_out + (g0 + i) * num_gibbs_samples;
+                    uint32_t num_samples = 0;
+
+                    for (size_t j = 0; j < sampling_indices.size(); ++j) {
+
+                        const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(j);
+                        const size_t num_columns = count_samples.path_ids.size();
+
+                        for (size_t k = 0; k < count_samples.noise_samples.size(); ++k) {
+
+                            if (sampling_indices.at(j) != no_column) {
+
+                                row[num_samples] = count_samples.abundance_samples.at(k * num_columns + sampling_indices.at(j));
+                            }
+
+                            ++num_samples;
+                        }
+                    }
+                }
+
+                g0 += num_paths;
+            }
+
+            if (seconds_out) {
+
+                *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
             }
         }
 
