@@ -26,6 +26,7 @@
 #include "device_algos.hpp"
 #include "path_clusters.hpp"
 #include "path_table.hpp"
+#include "table_kit.hpp"
 
 using namespace rpvg_hip_detail;
 
@@ -116,7 +117,7 @@ __device__ __forceinline__ bool listsEqual(const StreamView & v, const uint32_t 
 // ---- add: validation of a chunk and its offsets moved behind the stream --------------------------------------------
 enum BadReason { kBadListOffsets = 1, kBadNoise, kBadAlignOffsets, kBadPathId, kBadFragLength };
 
-// one thread per list of the chunk; bad = min over the offending lists of (list * 16 + reason)
+// one thread per list of the chunk; bad = min over the offending lists (table_kit.hpp)
 __global__ __launch_bounds__(256) void validateChunkKernel(const uint64_t num_lists, const uint64_t num_aligns, const uint64_t num_entries,
                                                            const uint8_t * __restrict__ is_simple, const uint8_t * __restrict__ min_mapq,
                                                            const int32_t * __restrict__ noise_score, const uint64_t * __restrict__ list_align_off,
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void validateChunkKernel(const uint64_t num_li
             if (fl == 0 || fl > max_frag_length) why = kBadFragLength;
         }
     }
-    if (why) atomicMin(bad, static_cast<unsigned long long>(i) * 16ull + static_cast<unsigned long long>(why));
+    if (why) reportOffender(bad, i, why);
 }
 
 // out[base_index + i] = raw[i] + base_value for i = 0 .. n (n + 1 offsets)
@@ -506,11 +507,7 @@ extern "C" int rpvg_hip_align_index_create(rpvg_hip_ctx * ctx, const rpvg_index_
 
 extern "C" void rpvg_hip_align_index_free(rpvg_hip_ctx * ctx, rpvg_hip_align_index * index) {
     if (!index) return;
-    if (ctx) {
-        std::lock_guard<std::mutex> lock(ctx->mutex);
-        (void) hipSetDevice(ctx->device);
-        (void) hipStreamSynchronize(ctx->stream);
-    }
+    waitAndDelete(ctx);
     delete index;
 }
 
@@ -548,8 +545,7 @@ extern "C" int rpvg_hip_align_index_add(rpvg_hip_ctx * ctx, rpvg_hip_align_index
     StagingBlocks staging;
     DeviceBuffer<uint64_t> raw_list_off, raw_align_off;
     DeviceBuffer<unsigned long long> d_bad;
-    const unsigned long long no_bad = ~0ull;
-    unsigned long long bad = no_bad;
+    unsigned long long bad = kNoBad;
     int span = ctx->spanBegin(FAM_H2D);
     RPVG_HIP_CHECK(appendFromHost(ix->is_simple.ptr + F, chunk->list_is_simple, Fc, st, staging.blocks));
     RPVG_HIP_CHECK(appendFromHost(ix->min_mapq.ptr + F, chunk->list_min_mapq, Fc, st, staging.blocks));
@@ -560,7 +556,7 @@ extern "C" int rpvg_hip_align_index_add(rpvg_hip_ctx * ctx, rpvg_hip_align_index
     RPVG_HIP_CHECK(appendFromHost(ix->path_id.ptr + E, chunk->align_path_id, Ec, st, staging.blocks));
     RPVG_HIP_CHECK(raw_list_off.upload(chunk->list_align_off, Fc + 1, st));
     RPVG_HIP_CHECK(raw_align_off.upload(chunk->align_path_off, Ac + 1, st));
-    RPVG_HIP_CHECK(d_bad.upload(&no_bad, 1, st));
+    RPVG_HIP_CHECK(d_bad.upload(&kNoBad, 1, st));
     ctx->spanEnd(span);
     ctx->stats.h2d_bytes += static_cast<double>(Fc) * 14 + static_cast<double>(Ac) * 16 + static_cast<double>(Ec) * 4;
 
@@ -574,17 +570,17 @@ extern "C" int rpvg_hip_align_index_add(rpvg_hip_ctx * ctx, rpvg_hip_align_index
     ctx->spanEnd(span);
     ctx->stats.build_launches += 3;
     RPVG_HIP_CHECK(hipGetLastError());
-    RPVG_HIP_CHECK(hipMemcpyAsync(&bad, d_bad.ptr, sizeof(bad), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    if (bad != no_bad) {
+    if (const int rc = fetchDescribed(st, d_bad.ptr, &bad)) return rc;
+    if (bad != kNoBad) {
         // the cells behind the stream's end were written and are not part of it (the offset AT its end was rewritten with its own value)
         static const char * const reasons[] = {"", "has no alignments or its offsets are not monotone", "has a positive noise score",
                                                "has an alignment without paths or with offsets that are not monotone",
                                                "has path ids that are not ascending or not below num_paths",
                                                "is counted for the fragment lengths with a length of 0 or above max_frag_length"};
-        const unsigned long long list = bad / 16;
+        const Offender o = offenderOf(bad, kBadFragLength);
+        const unsigned long long list = o.index;
         setError("rpvg_hip_align_index_add: list %llu of the chunk (%llu of the stream) %s", list, static_cast<unsigned long long>(F) + list,
-                 reasons[bad % 16]);
+                 reasons[o.why]);
         return RPVG_HIP_ERR_INVALID;
     }
     ix->F = F + Fc;

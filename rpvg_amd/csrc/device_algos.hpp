@@ -1,5 +1,6 @@
-// Whole-array scans and sorts (hipcub) and small host helpers shared by align_index.hip and path_table.hip.  Each call allocates
-// its temporary storage from the pool and waits for the stream before it goes back.
+// Whole-array scans and sorts (hipcub) and small host helpers shared by align_index.hip, path_table.hip, estimates_table.hip,
+// gibbs_table.hip and path_cover_grid.hip.  Each scan or sort allocates its temporary storage from the pool and waits for the
+// stream before it goes back.
 #ifndef RPVG_HIP_DEVICE_ALGOS_HPP
 #define RPVG_HIP_DEVICE_ALGOS_HPP
 

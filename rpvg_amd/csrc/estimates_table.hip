@@ -30,6 +30,7 @@
 
 #include "device_algos.hpp"
 #include "estimates_plan.hpp"
+#include "table_kit.hpp"
 #include "../../include/rpvg_table.h"
 
 #pragma clang fp contract(off)
@@ -56,13 +57,12 @@ struct rpvg_hip_estimates_table {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr unsigned long long kNoBad = ~0ull;
 constexpr uint32_t kCounted = 1u << 31;    // member info: the member adds its set's posterior to its path
 constexpr uint32_t kPositive = 1u << 30;   // ... its transcript count takes part in the cluster's sum (abundances and eff > 0)
 constexpr uint32_t kSetMask = kPositive - 1u;
 constexpr uint64_t kMaxSets = kSetMask, kMaxItems = 0x7fffffffull;
 
-// bad = min over the offenders of (cluster * 8 + reason)
+// bad = min over the offending clusters (table_kit.hpp)
 enum TableBad { kBadSetOff = 1, kBadPathOff = 2, kBadAbundOff = 3, kBadMemberOff = 4, kBadMember = 5, kBadAbundCount = 6 };
 
 struct TableArgs {
@@ -88,20 +88,7 @@ struct TableArgs {
     double * cluster_transcript_count;                          // [K]
 };
 
-// the last index i in [0, n) with off[i] <= x (0 when there is none); any contents of `off` leave the result inside [0, n)
-__device__ __forceinline__ uint64_t lastAtMost(const uint64_t * __restrict__ off, const uint64_t n, const uint64_t x) {
-    uint64_t lo = 0, hi = n;  // first index with off > x
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo ? lo - 1 : 0;
-}
-
-__device__ __forceinline__ void reportBad(const TableArgs & a, const uint64_t cluster, const int why) {
-    atomicMin(a.bad, static_cast<unsigned long long>(cluster) * 8ull + static_cast<unsigned long long>(why));
-}
+__device__ __forceinline__ void reportBad(const TableArgs & a, const uint64_t cluster, const int why) { reportOffender(a.bad, cluster, why); }
 
 // thread i: cluster i, set i (and the end of member_off) and member i.  Every index is checked before it is used: the kernel is the
 // validation, nothing it reads is trusted.
@@ -112,11 +99,10 @@ __global__ __launch_bounds__(kBlock) void describeKernel(const TableArgs a) {
         const uint64_t k = i;
         const uint64_t s0 = a.set_off[k], s1 = a.set_off[k + 1], a0 = a.abund_off[k], a1 = a.abund_off[k + 1];
         const uint64_t p0 = a.cluster_path_off[k], p1 = a.cluster_path_off[k + 1];
-        const bool first = k == 0, last = k + 1 == a.K;
         int why = 0;
-        if (s0 > s1 || s1 > a.S || (first && s0 != 0) || (last && s1 != a.S)) why = kBadSetOff;
-        else if (p0 > p1 || p1 > a.P || (first && p0 != 0) || (last && p1 != a.P)) why = kBadPathOff;
-        else if (a0 > a1 || a1 > a.A || (first && a0 != 0) || (last && a1 != a.A)) why = kBadAbundOff;
+        if (offsetsBad(a.set_off, k, a.K, a.S)) why = kBadSetOff;
+        else if (offsetsBad(a.cluster_path_off, k, a.K, a.P)) why = kBadPathOff;
+        else if (offsetsBad(a.abund_off, k, a.K, a.A)) why = kBadAbundOff;
         else {
             const uint64_t m0 = a.member_off[s0], m1 = a.member_off[s1];
             if (m0 > m1 || m1 > a.M) why = kBadMemberOff;
@@ -125,20 +111,7 @@ __global__ __launch_bounds__(kBlock) void describeKernel(const TableArgs a) {
         }
         if (why) reportBad(a, k, why);
     }
-    // the work lists: one atomic per wavefront and route (tens of thousands of clusters on one counter took 0.55 ms), the
-    // wavefront's clusters behind one another in lane order
-    for (int route = 0; route < kRoutes; ++route) {
-        const unsigned long long with_route = __ballot(my_route == route);
-        if (with_route == 0) continue;
-        const int lane = threadIdx.x & 63, leader = __ffsll(static_cast<long long>(with_route)) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&a.counters[route], static_cast<uint32_t>(__popcll(with_route)));
-        base = __shfl(base, leader, 64);
-        if (my_route == route) {
-            const uint32_t at = base + __popcll(with_route & ((1ull << lane) - 1ull));
-            if (at < a.K) a.route_list[static_cast<uint64_t>(route) * a.K + at] = static_cast<uint32_t>(i);
-        }
-    }
+    appendToRouteList<kRoutes>(my_route, static_cast<uint32_t>(i), a.counters, a.route_list, a.K);  // the work lists
     if (i <= a.S) {
         const uint64_t s = i;
         bool bad = false;
@@ -411,27 +384,6 @@ __global__ __launch_bounds__(kBlock) void tpmKernel(const uint64_t P, const uint
     }
 }
 
-// a timed span that is closed on every way out
-struct Span {
-    rpvg_hip_ctx * ctx;
-    int span;
-    Span(rpvg_hip_ctx * ctx_in, const int family) : ctx(ctx_in), span(ctx_in->spanBegin(family)) {}
-    Span(const Span &) = delete;
-    Span & operator=(const Span &) = delete;
-    void end() {
-        if (ctx) ctx->spanEnd(span);
-        ctx = nullptr;
-    }
-    ~Span() { end(); }
-};
-
-// an input array: copied with the pack, or the caller's device memory where it lies
-template <typename T>
-void takeInput(UploadPack & pack, DeviceBuffer<T> & buffer, const T * from, const size_t n, const bool on_device) {
-    if (on_device) buffer.borrow(const_cast<T *>(from), n);
-    else pack.add(buffer, from, n);
-}
-
 const char * const kReasons[] = {"",
                                  "set_off is not a non-decreasing sequence of offsets from 0 to num_sets",
                                  "cluster_path_off is not a non-decreasing sequence of offsets from 0 to num_paths",
@@ -511,18 +463,18 @@ int rpvg_hip_estimates_table_build(rpvg_hip_ctx * ctx, const rpvg_estimates_flat
     DeviceBuffer<uint32_t> members, info, key, position, route_list, counters;
     DeviceBuffer<double> posteriors, abundances, noise_count, eff;
     DeviceBuffer<unsigned long long> d_bad;
-    takeInput(inputs, set_off, in->set_off, static_cast<size_t>(K) + 1, on_device);
-    takeInput(inputs, member_off, in->member_off, S + 1, on_device);
-    takeInput(inputs, members, in->members, M, on_device);
-    takeInput(inputs, posteriors, in->posteriors, S, on_device);
-    takeInput(inputs, abund_off, in->abund_off, static_cast<size_t>(K) + 1, on_device);
-    takeInput(inputs, abundances, in->abundances, A, on_device);
-    takeInput(inputs, noise_count, in->noise_count, K, on_device);
-    takeInput(inputs, cluster_path_off, in->cluster_path_off, static_cast<size_t>(K) + 1, on_device);
-    takeInput(inputs, eff, in->path_effective_length, P, on_device);
+    takeInput(inputs, set_off, {in->set_off, on_device}, static_cast<size_t>(K) + 1);
+    takeInput(inputs, member_off, {in->member_off, on_device}, S + 1);
+    takeInput(inputs, members, {in->members, on_device}, M);
+    takeInput(inputs, posteriors, {in->posteriors, on_device}, S);
+    takeInput(inputs, abund_off, {in->abund_off, on_device}, static_cast<size_t>(K) + 1);
+    takeInput(inputs, abundances, {in->abundances, on_device}, A);
+    takeInput(inputs, noise_count, {in->noise_count, on_device}, K);
+    takeInput(inputs, cluster_path_off, {in->cluster_path_off, on_device}, static_cast<size_t>(K) + 1);
+    takeInput(inputs, eff, {in->path_effective_length, on_device}, P);
     inputs.add(d_bad, &kNoBad, 1);
     inputs.addZero(counters, kRoutes);
-    Span copies(ctx, FAM_H2D);
+    SpanScope copies(ctx, FAM_H2D);
     RPVG_HIP_CHECK(inputs.commit(st));
     copies.end();
     if (!on_device) ctx->stats.h2d_bytes += static_cast<double>(inputs.copied_bytes);
@@ -558,25 +510,22 @@ int rpvg_hip_estimates_table_build(rpvg_hip_ctx * ctx, const rpvg_estimates_flat
     a.member_transcript_count = t->member_transcript_count.ptr;
     a.cluster_transcript_count = t->cluster_transcript_count.ptr;
 
-    Span span(ctx, FAM_BUILD);
+    SpanScope span(ctx, FAM_BUILD);
     const uint64_t describe_threads = std::max<uint64_t>(std::max<uint64_t>(K, S + 1), M);
     describeKernel<<<gridFor(describe_threads), dim3(kBlock), 0, st>>>(a);
     RPVG_HIP_CHECK(hipGetLastError());
     ctx->stats.build_launches += 1;
-    struct {
-        unsigned long long bad;
-        uint32_t counters[kRoutes];
-    } described = {kNoBad, {0, 0, 0}};
-    RPVG_HIP_CHECK(hipMemcpyAsync(&described.bad, d_bad.ptr, sizeof(described.bad), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipMemcpyAsync(described.counters, counters.ptr, sizeof(described.counters), hipMemcpyDeviceToHost, st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    if (described.bad != kNoBad) {
+    word64 bad = kNoBad;
+    uint32_t listed[kRoutes] = {0, 0, 0};
+    if (const int rc = fetchDescribed(st, d_bad.ptr, &bad, counters.ptr, listed, kRoutes)) return rc;
+    if (bad != kNoBad) {
         span.end();
         RPVG_HIP_CHECK(hipStreamSynchronize(st));
-        setError("rpvg_hip_estimates_table_build: cluster %llu: %s", described.bad / 8, kReasons[described.bad % 8 <= kBadAbundCount ? described.bad % 8 : 0]);
+        const Offender o = offenderOf(bad, kBadAbundCount);
+        setError("rpvg_hip_estimates_table_build: cluster %llu: %s", static_cast<unsigned long long>(o.index), kReasons[o.why]);
         return RPVG_HIP_ERR_INVALID;
     }
-    const uint32_t waves = described.counters[kRouteWave], groups = described.counters[kRouteLds], global = described.counters[kRouteGlobal];
+    const uint32_t waves = listed[kRouteWave], groups = listed[kRouteLds], global = listed[kRouteGlobal];
     if (static_cast<uint64_t>(waves) + groups + global != K) {
         span.end();
         (void) hipDeviceSynchronize();
@@ -622,7 +571,7 @@ int rpvg_hip_estimates_table_tpm(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * 
     hipStream_t st = ctx->stream;
     const uint64_t n = table->num_paths + table->num_members;
     if (n) {
-        Span span(ctx, FAM_BUILD);
+        SpanScope span(ctx, FAM_BUILD);
         tpmKernel<<<gridFor(n), dim3(kBlock), 0, st>>>(table->num_paths, table->num_members, denominator, table->transcript_count.ptr,
                                                        table->member_transcript_count.ptr, table->tpm.ptr, table->member_tpm.ptr);
         RPVG_HIP_CHECK(hipGetLastError());
@@ -669,11 +618,7 @@ int rpvg_hip_estimates_table_view(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table *
 
 void rpvg_hip_estimates_table_free(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table) {
     if (!table) return;
-    if (ctx) {  // nothing queued on the context's stream may still use the table's block
-        std::lock_guard<std::mutex> lock(ctx->mutex);
-        (void) hipSetDevice(ctx->device);
-        (void) hipStreamSynchronize(ctx->stream);
-    }
+    waitAndDelete(ctx);
     delete table;
 }
 

@@ -30,14 +30,13 @@
 #include "device_algos.hpp"
 #include "gibbs_table_plan.hpp"
 #include "gibbs_samples.hpp"
+#include "table_kit.hpp"
 #include "../../include/rpvg_samples.h"
 
 #pragma clang fp contract(off)
 
 using namespace rpvg_hip_detail;
 using namespace rpvg_gibbs_table;
-
-typedef unsigned long long word64;
 
 // the table of a batch
 struct rpvg_hip_gibbs_table {
@@ -55,8 +54,7 @@ struct rpvg_hip_gibbs_table {
 
 namespace {
 
-constexpr word64 kNoBad = ~0ull;
-constexpr word64 kBlockOffence = 1ull << 62;  // bad = min over the offenders of (cluster * 16 + reason) and (kBlockOffence + block * 16 + reason)
+// bad = min over the offending clusters and blocks (table_kit.hpp: a block is the second kind, so a cluster comes before every block)
 
 enum TableBad {
     kBadGibbsOff = 1, kBadClusterPathOff = 2, kBadTooManySamples = 3,                                        // a cluster's
@@ -90,29 +88,8 @@ struct TableArgs {
     double * noise_counts;              // [N]
 };
 
-// the last index i in [0, n) with off[i] <= x (0 when there is none); any contents of `off` leave the result inside [0, n)
-__device__ __forceinline__ uint64_t lastAtMost(const uint64_t * __restrict__ off, const uint64_t n, const uint64_t x) {
-    uint64_t lo = 0, hi = n;  // first index with off > x
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo ? lo - 1 : 0;
-}
-
-__device__ __forceinline__ void reportCluster(const TableArgs & a, const uint64_t cluster, const int why) {
-    atomicMin(a.bad, static_cast<word64>(cluster) * 16ull + static_cast<word64>(why));
-}
-__device__ __forceinline__ void reportBlock(const TableArgs & a, const uint64_t block, const int why) {
-    atomicMin(a.bad, kBlockOffence + static_cast<word64>(block) * 16ull + static_cast<word64>(why));
-}
-
-// off[i] .. off[i + 1] of an array of n + 1 offsets that must run from 0 to `total` without decreasing
-__device__ __forceinline__ bool offsetsBad(const uint64_t * __restrict__ off, const uint64_t i, const uint64_t n, const uint64_t total) {
-    const uint64_t o0 = off[i], o1 = off[i + 1];
-    return o0 > o1 || o1 > total || (i == 0 && o0 != 0) || (i + 1 == n && o1 != total);
-}
+__device__ __forceinline__ void reportCluster(const TableArgs & a, const uint64_t cluster, const int why) { reportOffender(a.bad, cluster, why); }
+__device__ __forceinline__ void reportBlock(const TableArgs & a, const uint64_t block, const int why) { reportOffender(a.bad, block, why, true); }
 
 // thread i: cluster i, block i and path id i.  Every index is checked before it is used: the kernel is the validation, nothing it
 // reads is trusted, and every write goes to a slot the checks have placed inside its array.
@@ -172,23 +149,6 @@ __global__ __launch_bounds__(kBlock) void describeKernel(const TableArgs a) {
     }
 }
 
-// appends the threads of the workgroup for which `mine` holds to the list of `route`: one atomic per wavefront and route, the
-// wavefront's items behind one another in lane order
-__device__ __forceinline__ void appendToRoute(const TableArgs & a, const int my_route, const uint64_t item) {
-    for (int route = 0; route < kRoutes; ++route) {
-        const word64 with_route = __ballot(my_route == route);
-        if (with_route == 0) continue;
-        const int lane = threadIdx.x & 63, leader = __ffsll(static_cast<long long>(with_route)) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&a.counters[kBlocksOfRoute + route], static_cast<uint32_t>(__popcll(with_route)));
-        base = __shfl(base, leader, 64);
-        if (my_route == route) {
-            const uint32_t at = base + __popcll(with_route & ((1ull << lane) - 1ull));
-            if (at < a.B) a.block_list[static_cast<uint64_t>(route) * a.B + at] = static_cast<uint32_t>(item);
-        }
-    }
-}
-
 // behind a describe pass without offence.  thread i: the route of cluster i; block i, when it has samples, onto its cluster's list
 __global__ __launch_bounds__(kBlock) void routeKernel(const TableArgs a) {
     const uint64_t i = blockIdx.x * static_cast<uint64_t>(kBlock) + threadIdx.x;
@@ -209,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void routeKernel(const TableArgs a) {
         const uint32_t k = a.block_cluster[i];
         if (k < a.K) block_route = routeOf(a.cluster_path_off[k + 1] - a.cluster_path_off[k], a.cluster_max_columns[k]);
     }
-    appendToRoute(a, block_route, i);
+    appendToRouteList<kRoutes>(block_route, static_cast<uint32_t>(i), a.counters + kBlocksOfRoute, a.block_list, a.B);
 }
 
 // what a scatter kernel knows of its block
@@ -345,33 +305,6 @@ __global__ __launch_bounds__(64) void noiseKernel(const TableArgs a) {
     a.noise_counts[s] = sum;
 }
 
-// a timed span that is closed on every way out
-struct Span {
-    rpvg_hip_ctx * ctx;
-    int span;
-    Span(rpvg_hip_ctx * ctx_in, const int family) : ctx(ctx_in), span(ctx_in->spanBegin(family)) {}
-    Span(const Span &) = delete;
-    Span & operator=(const Span &) = delete;
-    void end() {
-        if (ctx) ctx->spanEnd(span);
-        ctx = nullptr;
-    }
-    ~Span() { end(); }
-};
-
-// an input array and where it lies
-template <typename T>
-struct Source {
-    const T * from = nullptr;
-    bool on_device = false;
-};
-
-template <typename T>
-void takeInput(UploadPack & pack, DeviceBuffer<T> & buffer, const Source<T> & source, const size_t n) {
-    if (source.on_device) buffer.borrow(const_cast<T *>(source.from), n);
-    else pack.add(buffer, source.from, n);
-}
-
 struct TableInputs {
     uint32_t K = 0, N = 0;
     uint64_t B = 0, P = 0, L = 0, NS = 0, AS = 0;
@@ -436,7 +369,7 @@ int buildTable(rpvg_hip_ctx * ctx, const TableInputs & in, const char * who, rpv
     inputs.addZero(counters, kCounters);
     inputs.addZero(cluster_max_columns, K);
     {
-        Span copies(ctx, FAM_H2D);
+        SpanScope copies(ctx, FAM_H2D);
         RPVG_HIP_CHECK(inputs.commit(st));
     }
     ctx->stats.h2d_bytes += static_cast<double>(inputs.copied_bytes);
@@ -485,20 +418,18 @@ int buildTable(rpvg_hip_ctx * ctx, const TableInputs & in, const char * who, rpv
     a.listed = t->listed.ptr;
     a.noise_counts = t->noise_counts.ptr;
 
-    Span span(ctx, FAM_BUILD);
+    SpanScope span(ctx, FAM_BUILD);
     if (K > 0) {
         const uint64_t threads = std::max<uint64_t>(std::max<uint64_t>(K, B), in.L);
         describeKernel<<<gridFor(threads), dim3(kBlock), 0, st>>>(a);
         RPVG_HIP_CHECK(hipGetLastError());
         ctx->stats.build_launches += 1;
         word64 bad = kNoBad;
-        RPVG_HIP_CHECK(hipMemcpyAsync(&bad, d_bad.ptr, sizeof(bad), hipMemcpyDeviceToHost, st));
-        RPVG_HIP_CHECK(hipStreamSynchronize(st));
+        if (const int rc = fetchDescribed(st, d_bad.ptr, &bad)) return rc;
         if (bad != kNoBad) {
             span.end();
-            const bool of_block = bad >= kBlockOffence;
-            const word64 word = of_block ? bad - kBlockOffence : bad;
-            setError("%s: %s %llu: %s", who, of_block ? "block" : "cluster", word / 16, kReasons[word % 16 <= kBadPathOrder ? word % 16 : 0]);
+            const Offender o = offenderOf(bad, kBadPathOrder);
+            setError("%s: %s %llu: %s", who, o.second_kind ? "block" : "cluster", static_cast<unsigned long long>(o.index), kReasons[o.why]);
             return RPVG_HIP_ERR_INVALID;
         }
         routeKernel<<<gridFor(std::max<uint64_t>(K, B)), dim3(kBlock), 0, st>>>(a);
@@ -674,11 +605,7 @@ int rpvg_hip_gibbs_table_rows(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_table * table, 
 
 void rpvg_hip_gibbs_table_free(rpvg_hip_ctx * ctx, rpvg_hip_gibbs_table * table) {
     if (!table) return;
-    if (ctx) {  // nothing queued on the context's stream may still use the table's blocks
-        std::lock_guard<std::mutex> lock(ctx->mutex);
-        (void) hipSetDevice(ctx->device);
-        (void) hipStreamSynchronize(ctx->stream);
-    }
+    waitAndDelete(ctx);
     delete table;
 }
 

@@ -27,6 +27,7 @@
 
 #include "device_algos.hpp"
 #include "path_table.hpp"
+#include "table_kit.hpp"
 
 using namespace rpvg_hip_detail;
 
@@ -37,9 +38,8 @@ constexpr uint32_t kLdsPaths = 4096;   // ... one workgroup with 48 KiB of LDS (
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr uint32_t kLdsGrid = 256;     // workgroups that walk the list of the second route
-constexpr unsigned long long kNoBad = ~0ull;
 
-// bad = min over the offending paths of (path * 4 + reason)
+// bad = min over the offending paths (table_kit.hpp)
 enum TableBad { kBadOffsets = 1, kBadEnd = 2 };
 __global__ void validateTableKernel(const uint32_t num_paths, const uint64_t num_sources, const uint64_t * __restrict__ source_off,
                                     unsigned long long * __restrict__ bad) {
@@ -48,7 +48,7 @@ __global__ void validateTableKernel(const uint32_t num_paths, const uint64_t num
     int why = 0;
     if (source_off[p] > source_off[p + 1] || source_off[p + 1] > num_sources || (p == 0 && source_off[0] != 0)) why = kBadOffsets;
     else if (p + 1 == num_paths && source_off[num_paths] != num_sources) why = kBadEnd;
-    if (why) atomicMin(bad, static_cast<unsigned long long>(p) * 4ull + static_cast<unsigned long long>(why));
+    if (why) reportOffender(bad, p, why);
 }
 
 template <typename T>
@@ -276,7 +276,7 @@ struct CollapseArgs {
     const double * effective_length;
     uint32_t * out_first_path, * out_name_id, * out_group_id, * out_source_count, * out_length;  // [G]
     double * out_effective_length;
-    unsigned long long * bad;        // min of (group * 4 + reason)
+    unsigned long long * bad;        // min over the offending groups (table_kit.hpp)
 };
 
 // one thread per group: src/main.cpp:914-948 over the members in their order
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void collapseGroupsKernel(const CollapseArg
         if (!(mean_length <= 4294967295.0)) why = kBadLength;
     }
     if (why) {
-        atomicMin(a.bad, static_cast<unsigned long long>(g) * 4ull + static_cast<unsigned long long>(why));
+        reportOffender(a.bad, g, why);
         return;
     }
     const uint32_t first = a.cluster_paths[a.member[j0]];
@@ -331,13 +331,6 @@ int bitsFor(uint64_t values) {  // bits that hold 0 .. values - 1
     int bits = 1;
     while (bits < 64 && (values - 1) >> bits) ++bits;
     return bits;
-}
-
-void waitAndDelete(rpvg_hip_ctx * ctx) {
-    if (!ctx) return;
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    (void) hipSetDevice(ctx->device);
-    (void) hipStreamSynchronize(ctx->stream);
 }
 
 }  // namespace
@@ -450,8 +443,9 @@ int rpvg_hip_path_table_upload(rpvg_hip_ctx * ctx, const rpvg_path_table * in, r
     }
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
     if (bad != kNoBad) {
-        const unsigned long long path = bad / 4;
-        if (bad % 4 == kBadEnd) {
+        const Offender o = offenderOf(bad, kBadEnd);
+        const unsigned long long path = o.index;
+        if (o.why == kBadEnd) {
             setError("rpvg_hip_path_table_upload: path %llu: source_off ends at another value than num_sources = %llu", path,
                      static_cast<unsigned long long>(S));
         } else {
@@ -623,13 +617,14 @@ int rpvg_hip_align_index_name_groups(rpvg_hip_ctx * ctx, const rpvg_hip_align_in
     span.end();
     RPVG_HIP_CHECK(hipStreamSynchronize(st));
     if (bad != kNoBad) {
-        const uint64_t group = bad / 4;
+        const Offender o = offenderOf(bad, kBadLength);
+        const uint64_t group = o.index;
         const uint32_t cluster = static_cast<uint32_t>(std::upper_bound(g->h_cluster_group_off.begin(), g->h_cluster_group_off.end(), group) -
                                                        g->h_cluster_group_off.begin()) - 1;
         static const char * const reasons[] = {"", "has a path with a source count of 0", "has a summed source count beyond 32 bits",
                                                "has a length beyond 32 bits"};
         setError("rpvg_hip_align_index_name_groups: group %llu of cluster %u %s", static_cast<unsigned long long>(group - g->h_cluster_group_off[cluster]),
-                 cluster, reasons[bad % 4]);
+                 cluster, reasons[o.why]);
         return RPVG_HIP_ERR_INVALID;
     }
     *groups_out = g.release();

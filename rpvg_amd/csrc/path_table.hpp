@@ -32,20 +32,6 @@ struct rpvg_hip_name_groups {
 
 namespace rpvg_hip_detail {
 
-// a timed span that is closed on every way out of a function, the error returns included
-struct SpanScope {
-    rpvg_hip_ctx * ctx;
-    int span;
-    SpanScope(rpvg_hip_ctx * ctx_in, const int family) : ctx(ctx_in), span(ctx_in->spanBegin(family)) {}
-    SpanScope(const SpanScope &) = delete;
-    SpanScope & operator=(const SpanScope &) = delete;
-    void end() {
-        if (ctx) ctx->spanEnd(span);
-        ctx = nullptr;
-    }
-    ~SpanScope() { end(); }
-};
-
 // what the kernels of path_table.hip read of a finished index (align_index.hip owns the arrays)
 struct AlignIndexParts {
     uint32_t num_clusters = 0, num_paths = 0;

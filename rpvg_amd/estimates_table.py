@@ -10,11 +10,12 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Sequence
 
 import numpy as np
 
 from . import hip
+from ._flat import FlatArrays, HandleOwner, ctx_handle
 
 u32p, u64p, f64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)
 
@@ -52,12 +53,12 @@ def limits() -> CEstimatesTableLimits:
     return out
 
 
-_FIELDS = (("set_off", np.uint64), ("member_off", np.uint64), ("members", np.uint32), ("posteriors", np.float64), ("abund_off", np.uint64),
+_ESTIMATES_FIELDS = (("set_off", np.uint64), ("member_off", np.uint64), ("members", np.uint32), ("posteriors", np.float64), ("abund_off", np.uint64),
            ("abundances", np.float64), ("noise_count", np.float64), ("cluster_path_off", np.uint64), ("path_effective_length", np.float64))
 
 
 @dataclass
-class FlatEstimates:
+class FlatEstimates(FlatArrays):
     """The estimates of K clusters in the flat form of rpvg_estimates_flat, host arrays."""
     set_off: np.ndarray
     member_off: np.ndarray
@@ -68,10 +69,7 @@ class FlatEstimates:
     noise_count: np.ndarray
     cluster_path_off: np.ndarray
     path_effective_length: np.ndarray
-
-    def __post_init__(self):
-        for name, dt in _FIELDS:
-            setattr(self, name, np.ascontiguousarray(getattr(self, name), dtype=dt))
+    _FIELDS, _C_STRUCT = _ESTIMATES_FIELDS, CEstimatesFlat
 
     @staticmethod
     def from_estimates(batch, estimates: Sequence) -> "FlatEstimates":
@@ -97,24 +95,6 @@ class FlatEstimates:
         return dict(num_clusters=len(self.noise_count), num_sets=len(self.posteriors), num_members=len(self.members),
                     num_abundances=len(self.abundances), num_paths=len(self.path_effective_length))
 
-    def as_c(self, device_pointers: Optional[dict] = None, **sizes) -> CEstimatesFlat:
-        """Host pointers into the arrays (which must outlive the call), or the given device pointers.  sizes: num_* overrides."""
-        flat = CEstimatesFlat()
-        for name, value in {**self.sizes(), **sizes}.items():
-            setattr(flat, name, value)
-        for name, _ in _FIELDS:
-            if device_pointers is not None:
-                setattr(flat, name, device_pointers[name])
-            else:
-                a = getattr(self, name)
-                setattr(flat, name, a.ctypes.data if len(a) else None)
-        flat.on_device = 0 if device_pointers is None else 1
-        return flat
-
-
-def _ctx_handle(ctx_or_engine):
-    return ctx_or_engine.handle if isinstance(ctx_or_engine, hip.Context) else ctx_or_engine._ctx()
-
 
 def _arr(ptr, n):
     return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dtype=np.float64)
@@ -130,7 +110,7 @@ def _decode(v: CEstimatesTableView) -> dict:
                 clusters_by_route=[int(x) for x in v.clusters_by_route])
 
 
-class EstimatesTable:
+class EstimatesTable(HandleOwner):
     """A table resident on the GPU (rpvg_hip_estimates_table)."""
 
     def __init__(self, ctx_handle, handle):
@@ -146,7 +126,7 @@ class EstimatesTable:
     @classmethod
     def build_flat(cls, ctx_or_engine, flat: CEstimatesFlat, ploidy: int) -> "EstimatesTable":
         """flat: host pointers (on_device = 0) or device pointers of the context's GPU (on_device = 1)."""
-        ctx = _ctx_handle(ctx_or_engine)
+        ctx = ctx_handle(ctx_or_engine)
         handle = C.c_void_p()
         hip._check(hip.lib().rpvg_hip_estimates_table_build(ctx, C.byref(flat), C.c_uint32(ploidy), C.byref(handle)),
                    "rpvg_hip_estimates_table_build")
@@ -163,16 +143,8 @@ class EstimatesTable:
         hip._check(hip.lib().rpvg_hip_estimates_table_view(self.ctx_handle, self.handle, C.byref(v)), "rpvg_hip_estimates_table_view")
         return _decode(v)
 
-    def free(self):
-        if self.handle:
-            hip.lib().rpvg_hip_estimates_table_free(self.ctx_handle, self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        hip.lib().rpvg_hip_estimates_table_free(self.ctx_handle, self.handle)
 
 
 # ---- the harness: the table of a prepared batch's estimates and the result files from it -----------------------------------------
@@ -194,7 +166,7 @@ def _harness():
     return L, engine
 
 
-class HarnessTable:
+class HarnessTable(HandleOwner):
     """The table of the estimates the last run left in a PreparedBatch (or of a result handle), through the host classes
     (rpvg_amd/host/estimates_table.hpp) and the writers' addTable()."""
 
@@ -222,16 +194,8 @@ class HarnessTable:
         if L.rpvg_amd_estimates_table_write(self.handle, writer.encode(), min_posterior, prefix.encode(), unaligned_read_count) != 0:
             raise hip.EngineError(f"estimates table write({writer}) failed: {eng._err()}")
 
-    def free(self):
-        if self.handle:
-            _harness()[0].rpvg_amd_estimates_table_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        _harness()[0].rpvg_amd_estimates_table_free(self.handle)
 
 
 def write_from_containers(prepared, writer: str, ploidy: int, prefix: str, denominator: float = 0.0, min_posterior: float = 1e-8,

@@ -17,6 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import hip
+from ._flat import FlatArrays, HandleOwner, ctx_handle
 
 u8p, u64p, f64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_double)
 
@@ -54,13 +55,13 @@ def limits() -> CGibbsTableLimits:
     return out
 
 
-_FIELDS = (("gibbs_off", np.uint64), ("gibbs_path_off", np.uint64), ("gibbs_path", np.uint32), ("gibbs_noise_off", np.uint64),
+_GIBBS_FIELDS = (("gibbs_off", np.uint64), ("gibbs_path_off", np.uint64), ("gibbs_path", np.uint32), ("gibbs_noise_off", np.uint64),
            ("gibbs_noise", np.float64), ("gibbs_abund_off", np.uint64), ("gibbs_abund", np.float64), ("cluster_path_off", np.uint64),
            ("total_count", np.float64))
 
 
 @dataclass
-class FlatGibbs:
+class FlatGibbs(FlatArrays):
     """The Gibbs samples of K clusters in the flat form of rpvg_gibbs_flat, host arrays."""
     gibbs_off: np.ndarray
     gibbs_path_off: np.ndarray
@@ -72,10 +73,7 @@ class FlatGibbs:
     cluster_path_off: np.ndarray
     total_count: np.ndarray
     num_gibbs_samples: int = 0
-
-    def __post_init__(self):
-        for name, dt in _FIELDS:
-            setattr(self, name, np.ascontiguousarray(getattr(self, name), dtype=dt))
+    _FIELDS, _C_STRUCT = _GIBBS_FIELDS, CGibbsFlat
 
     @staticmethod
     def from_estimates(batch, estimates: Sequence, num_gibbs_samples: int) -> "FlatGibbs":
@@ -99,26 +97,8 @@ class FlatGibbs:
                     if len(self.cluster_path_off) else 0, num_gibbs_samples=int(self.num_gibbs_samples), num_path_ids=len(self.gibbs_path),
                     num_noise_samples=len(self.gibbs_noise), num_abundance_samples=len(self.gibbs_abund))
 
-    def as_c(self, device_pointers: Optional[dict] = None, **sizes) -> CGibbsFlat:
-        """Host pointers into the arrays (which must outlive the call), or the given device pointers.  sizes: num_* overrides."""
-        flat = CGibbsFlat()
-        for name, value in {**self.sizes(), **sizes}.items():
-            setattr(flat, name, value)
-        for name, _ in _FIELDS:
-            if device_pointers is not None:
-                setattr(flat, name, device_pointers[name])
-            else:
-                a = getattr(self, name)
-                setattr(flat, name, a.ctypes.data if len(a) else None)
-        flat.on_device = 0 if device_pointers is None else 1
-        return flat
 
-
-def _ctx_handle(ctx_or_engine):
-    return ctx_or_engine.handle if isinstance(ctx_or_engine, hip.Context) else ctx_or_engine._ctx()
-
-
-class GibbsSamples:
+class GibbsSamples(HandleOwner):
     """The samples of one call of the read-count Gibbs sampler, left on the GPU (rpvg_hip_gibbs_samples)."""
 
     def __init__(self, ctx_handle, handle, problems, keep):
@@ -156,19 +136,11 @@ class GibbsSamples:
                                                         C.c_void_p(abund.ctypes.data if abund.size else None)), "rpvg_hip_gibbs_samples_get")
         return noise, abund
 
-    def free(self):
-        if self.handle:
-            hip.lib().rpvg_hip_gibbs_samples_free(self.ctx_handle, self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        hip.lib().rpvg_hip_gibbs_samples_free(self.ctx_handle, self.handle)
 
 
-class GibbsTable:
+class GibbsTable(HandleOwner):
     """A table resident on the GPU (rpvg_hip_gibbs_table)."""
 
     def __init__(self, ctx_handle, handle):
@@ -181,7 +153,7 @@ class GibbsTable:
     @classmethod
     def build_flat(cls, ctx_or_engine, flat: CGibbsFlat) -> "GibbsTable":
         """flat: host pointers (on_device = 0) or device pointers of the context's GPU (on_device = 1)."""
-        ctx = _ctx_handle(ctx_or_engine)
+        ctx = ctx_handle(ctx_or_engine)
         handle = C.c_void_p()
         hip._check(hip.lib().rpvg_hip_gibbs_table_build(ctx, C.byref(flat), C.byref(handle)), "rpvg_hip_gibbs_table_build")
         return cls(ctx, handle)
@@ -190,7 +162,7 @@ class GibbsTable:
     def build_resident(cls, ctx_or_engine, samples: GibbsSamples, cluster_path_off, total_count, num_gibbs_samples: int,
                        problems: Optional[hip.CEmProblems] = None) -> "GibbsTable":
         """The table of a sampler call's samples: its problems are the blocks (rpvg_hip_gibbs_table_build_resident)."""
-        ctx = _ctx_handle(ctx_or_engine)
+        ctx = ctx_handle(ctx_or_engine)
         cpo = np.ascontiguousarray(cluster_path_off, dtype=np.uint64)
         total = np.ascontiguousarray(total_count, dtype=np.float64)
         assert len(cpo) == len(total) + 1
@@ -213,16 +185,8 @@ class GibbsTable:
                                                        C.c_void_p(out.ctypes.data if out.size else None)), "rpvg_hip_gibbs_table_rows")
         return out
 
-    def free(self):
-        if self.handle:
-            hip.lib().rpvg_hip_gibbs_table_free(self.ctx_handle, self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        hip.lib().rpvg_hip_gibbs_table_free(self.ctx_handle, self.handle)
 
 
 # ---- the harness: the table of a prepared batch's Gibbs samples and the file from it ---------------------------------------------
@@ -248,7 +212,7 @@ def _decode(v: CGibbsTableView) -> dict:
                 clusters_by_route=[int(x) for x in v.clusters_by_route])
 
 
-class HarnessGibbsTable:
+class HarnessGibbsTable(HandleOwner):
     """The table of the Gibbs samples the last run (-n > 0) left in a PreparedBatch, through the host class
     (rpvg_amd/host/gibbs_samples_table.hpp) and the writer's addTable()."""
 
@@ -274,16 +238,8 @@ class HarnessGibbsTable:
         if L.rpvg_amd_gibbs_table_write(self.handle, self.num_gibbs_samples, prefix.encode(), unaligned_read_count) != 0:
             raise hip.EngineError(f"gibbs table write failed: {eng._err()}")
 
-    def free(self):
-        if self.handle:
-            _harness()[0].rpvg_amd_gibbs_table_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        _harness()[0].rpvg_amd_gibbs_table_free(self.handle)
 
 
 def from_containers(prepared, num_gibbs_samples: int, num_paths: int, prefix: str = "", unaligned_read_count: int = 0, table: bool = True):

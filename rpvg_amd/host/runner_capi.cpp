@@ -19,56 +19,18 @@
 #include "../../include/rpvg_batch.h"
 #include "batch_pipeline.hpp"
 #include "device_group.hpp"
-#include "estimates_table.hpp"
 #include "estimator_factory.hpp"
-#include "gibbs_samples_table.hpp"
-#include "io/estimates_writers.hpp"
 #include "align_index.hpp"
 #include "read_rows.hpp"
+#include "runner_handles.hpp"
 #include "trace.hpp"
 
 using namespace rpvg_amd;
+using namespace rpvg_amd_harness;
+
+thread_local std::string rpvg_amd_harness::last_error;
 
 namespace {
-
-thread_local std::string last_error;
-
-struct Engine {
-
-    std::shared_ptr<HipEngine> hip;
-};
-
-// A batch resident on the GPU together with the host-side PathInfo of its clusters.
-struct PreparedBatch {
-
-    std::unique_ptr<DeviceClusterBatch> device;
-
-    // batches that start from alignment-path lists keep the lists resident: rows can be rebuilt on the device
-    std::unique_ptr<DeviceAlignmentBatch> alignments;
-    std::unique_ptr<FragmentLengthDist> fragment_length_dist;
-    std::unique_ptr<DeviceFragmentLengthTable> fragment_length_table;  // batches whose distribution was fitted on the device
-    bool is_single_end = false;
-    double min_noise_prob = 0;
-    double prob_precision = 1e-8;
-
-    std::vector<std::vector<PathInfo> > paths;
-
-    // kept for the per-cluster estimate() mode
-    std::vector<std::vector<ReadPathProbabilities> > rows;
-
-    std::vector<PathClusterEstimates> estimates;
-};
-
-struct Result {
-
-    std::vector<uint64_t> set_off, member_off, abund_off, em_off, em_col_off;
-    std::vector<uint32_t> members, em_iters, em_cols;
-    std::vector<double> posteriors, abundances, noise_count, total_count;
-
-    std::vector<uint64_t> gibbs_off, gibbs_path_off, gibbs_noise_off, gibbs_abund_off;
-    std::vector<uint32_t> gibbs_path;
-    std::vector<double> gibbs_noise, gibbs_abund;
-};
 
 std::vector<std::vector<PathInfo> > unpackPaths(const rpvg_cluster_batch & batch) {
 
@@ -342,33 +304,23 @@ const char * rpvg_amd_last_error(void) {
 
 void * rpvg_amd_engine_create(int device) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         Engine * engine = new Engine();
         engine->hip = std::make_shared<HipEngine>(device);
         return engine;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // an engine for rpvg_amd_batch_reupload next to the engine that estimates (HipEngine(device, uploader = true))
 void * rpvg_amd_engine_create_uploader(int device) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         Engine * engine = new Engine();
         engine->hip = std::make_shared<HipEngine>(device, true);
         return engine;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 void rpvg_amd_engine_destroy(void * engine) {
@@ -385,30 +337,20 @@ void * rpvg_amd_engine_ctx(void * engine) {
 // Kernel statistics of the engine, both host lanes together.
 int rpvg_amd_engine_stats_get(void * engine, rpvg_hip_kernel_stats * stats_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         static_cast<Engine *>(engine)->hip->stats(stats_out);
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 int rpvg_amd_engine_stats_reset(void * engine) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         static_cast<Engine *>(engine)->hip->resetStats();
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // The OpenMP team of one host lane of this process (trace.hpp, hostThreads()): what bench.py prints as host_threads_per_lane.
@@ -427,7 +369,7 @@ int rpvg_amd_generator_state_check(uint32_t rounds) {
 // objects of every cluster for the per-cluster estimate() mode.
 void * rpvg_amd_batch_prepare(void * engine, const rpvg_cluster_batch * batch, int keep_rows) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = new PreparedBatch();
         std::unique_ptr<PreparedBatch> guard(prepared);
@@ -447,12 +389,7 @@ void * rpvg_amd_batch_prepare(void * engine, const rpvg_cluster_batch * batch, i
         }
 
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The same, starting one step earlier: the batch's reads arrive as alignment-path lists (include/rpvg_rows.h) and
@@ -461,7 +398,7 @@ void * rpvg_amd_batch_prepare(void * engine, const rpvg_cluster_batch * batch, i
 // with the alignment lists in host memory (upload included).
 void * rpvg_amd_batch_prepare_from_alignments(void * engine, const rpvg_alignment_batch * alignments, const rpvg_cluster_batch * path_info, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, int is_single_end, double min_noise_prob, double prob_precision, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = new PreparedBatch();
         std::unique_ptr<PreparedBatch> guard(prepared);
@@ -487,12 +424,7 @@ void * rpvg_amd_batch_prepare_from_alignments(void * engine, const rpvg_alignmen
         }
 
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The same for a paired-end run that brings neither a fitted distribution nor effective lengths: the counts of the
@@ -503,7 +435,7 @@ void * rpvg_amd_batch_prepare_from_alignments(void * engine, const rpvg_alignmen
 // not a valid distribution (fewer than two samples) is an error.
 void * rpvg_amd_batch_prepare_from_alignments_fit(void * engine, const rpvg_alignment_batch * alignments, const rpvg_cluster_batch * path_info, const uint32_t * frag_length_counts, uint32_t num_frag_length_counts, int skew_normal, const uint32_t * path_length, double min_noise_prob, double prob_precision, rpvg_frag_length_fit * fit_out, double * effective_length_out, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = new PreparedBatch();
         std::unique_ptr<PreparedBatch> guard(prepared);
@@ -577,12 +509,7 @@ void * rpvg_amd_batch_prepare_from_alignments_fit(void * engine, const rpvg_alig
         }
 
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The rows of a distribution that was fitted earlier (rpvg_hip_frag_length_fit: it has a maximum length, not the
@@ -590,7 +517,7 @@ void * rpvg_amd_batch_prepare_from_alignments_fit(void * engine, const rpvg_alig
 // rpvg_amd_batch_prepare_from_alignments_fit; the effective lengths are path_info's.
 void * rpvg_amd_batch_prepare_from_alignments_fitted(void * engine, const rpvg_alignment_batch * alignments, const rpvg_cluster_batch * path_info, double frag_loc, double frag_scale, double frag_shape, double min_noise_prob, double prob_precision, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = new PreparedBatch();
         std::unique_ptr<PreparedBatch> guard(prepared);
@@ -624,12 +551,7 @@ void * rpvg_amd_batch_prepare_from_alignments_fitted(void * engine, const rpvg_a
         }
 
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The same, starting two steps earlier: the reads arrive as the stream of per-fragment alignment-path lists (include/rpvg_index.h),
@@ -642,7 +564,7 @@ void * rpvg_amd_batch_prepare_from_alignments_fitted(void * engine, const rpvg_a
 // first chunk to the rows.
 void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * index_params, const uint64_t * extra_set_off, const uint32_t * extra_set_path, uint64_t num_extra_sets, const rpvg_cluster_batch * path_info, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, double min_noise_prob, double prob_precision, rpvg_index_info * info_out, uint32_t * frag_counts_out, uint64_t * cluster_path_off_out, uint32_t * cluster_paths_out, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         std::vector<PathInfo> global_paths;
 
@@ -655,12 +577,7 @@ void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_
         }
 
         return prepareFromFragments(engine, chunks, num_chunks, index_params, extra_set_off, extra_set_path, num_extra_sets, global_paths, nullptr, false, frag_loc, frag_scale, frag_shape, frag_sd_max_multi, min_noise_prob, prob_precision, info_out, frag_counts_out, cluster_path_off_out, cluster_paths_out, seconds_out);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The same with the PathInfo of the global paths as a path table (include/rpvg_index.h) that is made resident once: the path side
@@ -670,7 +587,7 @@ void * rpvg_amd_batch_prepare_from_fragments(void * engine, const rpvg_fragment_
 // the batch and its paths are the collapsed ones (src/main.cpp:853-887,909-951); a path named by name_id n is called "n<n>".
 void * rpvg_amd_batch_prepare_from_fragments_table(void * engine, const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * index_params, const uint64_t * extra_set_off, const uint32_t * extra_set_path, uint64_t num_extra_sets, const rpvg_path_table * table, int collapse_names, double frag_loc, double frag_scale, double frag_shape, uint32_t frag_sd_max_multi, double min_noise_prob, double prob_precision, rpvg_index_info * info_out, uint32_t * frag_counts_out, uint64_t * cluster_path_off_out, uint32_t * cluster_paths_out, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         if (collapse_names && !table->name_id) {
 
@@ -695,12 +612,7 @@ void * rpvg_amd_batch_prepare_from_fragments_table(void * engine, const rpvg_fra
         }
 
         return prepareFromFragments(engine, chunks, num_chunks, index_params, extra_set_off, extra_set_path, num_extra_sets, global_paths, table, collapse_names != 0, frag_loc, frag_scale, frag_shape, frag_sd_max_multi, min_noise_prob, prob_precision, info_out, frag_counts_out, cluster_path_off_out, cluster_paths_out, seconds_out);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // 1 when the resident batch holds the haplotype columns of its clusters (DeviceClusterBatch::hasSourceColumns)
@@ -718,7 +630,7 @@ int rpvg_amd_batch_has_source_columns(void * prepared) {
 // group (capacity P) source_count, length, effective_length; seconds_out: wall time of the two loops.
 int rpvg_amd_path_table_host_line(const rpvg_path_table * table, uint32_t num_clusters, const uint64_t * cluster_path_off, const uint32_t * cluster_paths, uint32_t * path_group_out, uint64_t * cluster_group_off_out, uint32_t * group_source_count_out, uint32_t * group_length_out, double * group_effective_length_out, double * seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         if (!table->name_id) {
 
@@ -782,12 +694,7 @@ int rpvg_amd_path_table_host_line(const rpvg_path_table * table, uint32_t num_cl
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // A measurement line for the index, not product: the structure of addAlignmentPathsBufferToIndexes (src/main.cpp:200-237) on ONE
@@ -825,7 +732,7 @@ struct HostLineKeyHash {
 
 int rpvg_amd_align_index_host_line(const rpvg_fragment_lists * chunks, uint32_t num_chunks, const rpvg_index_params * params, uint32_t * frag_counts_out, uint64_t * num_distinct_out, uint64_t * first_occurrence_out, uint32_t * multiplicity_out, double * seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         std::vector<uint32_t> frag_length_counts(static_cast<size_t>(params->max_frag_length) + 1, 0);
         std::unordered_map<HostLineKey, std::pair<uint64_t, uint32_t>, HostLineKeyHash> index;  // contents -> (first occurrence, multiplicity)
@@ -901,12 +808,7 @@ int rpvg_amd_align_index_host_line(const rpvg_fragment_lists * chunks, uint32_t 
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // BASELINE.json configs[1] for the estimator classes: one cluster of `num_rows` rows that each touch all `num_paths` paths,
@@ -914,7 +816,7 @@ int rpvg_amd_align_index_host_line(const rpvg_fragment_lists * chunks, uint32_t 
 // adopted as a resident batch — the caller runs `transcripts` on it like on any other batch.
 void * rpvg_amd_batch_prepare_synth_dense(void * engine, uint64_t seed, uint64_t num_rows, uint32_t num_paths) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = new PreparedBatch();
         std::unique_ptr<PreparedBatch> guard(prepared);
@@ -957,12 +859,7 @@ void * rpvg_amd_batch_prepare_synth_dense(void * engine, uint64_t seed, uint64_t
         batch_guard.batch = nullptr;
 
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // A new resident copy of the rows of a prepared batch from the same host arrays (what arrives per batch in a
@@ -971,7 +868,7 @@ void * rpvg_amd_batch_prepare_synth_dense(void * engine, uint64_t seed, uint64_t
 // the kernels of batch n.  seconds_out = wall time of validation + H2D + expansion on the device.
 int rpvg_amd_batch_reupload(void * engine, void * prepared_batch, const rpvg_cluster_batch * batch, double * seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
         const auto start = std::chrono::steady_clock::now();
@@ -985,12 +882,7 @@ int rpvg_amd_batch_reupload(void * engine, void * prepared_batch, const rpvg_clu
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 void rpvg_amd_batch_free(void * prepared) {
@@ -1002,7 +894,7 @@ void rpvg_amd_batch_free(void * prepared) {
 // call(s) only (inputs already resident on the GPU in batch mode).
 void * rpvg_amd_run(void * engine, void * prepared_batch, const char * model, const rpvg_params * params, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
         auto estimator = makePathEstimator(model, *params, static_cast<Engine *>(engine)->hip);
@@ -1048,12 +940,7 @@ void * rpvg_amd_run(void * engine, void * prepared_batch, const char * model, co
         PhaseTrace::report();
 
         return packResult(estimates);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // The reference's cluster loop (src/main.cpp:829,976-977) on a batch prepared with keep_rows: estimate() once per cluster
@@ -1061,7 +948,7 @@ void * rpvg_amd_run(void * engine, void * prepared_batch, const char * model, co
 // The estimates stay in the prepared batch's containers (rpvg_amd_run_team_result flattens them).
 int rpvg_amd_run_team(void * engine, void * prepared_batch, const char * model, const rpvg_params * params, int threads, double * seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
 
@@ -1123,32 +1010,22 @@ int rpvg_amd_run_team(void * engine, void * prepared_batch, const char * model, 
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 void * rpvg_amd_run_team_result(void * prepared_batch) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         return packResult(static_cast<PreparedBatch *>(prepared_batch)->estimates);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // Same run, estimates left in the prepared batch's containers and not flattened
 // (timing loops).  Returns 0 on success.
 int rpvg_amd_run_inplace(void * engine, void * prepared_batch, const char * model, const rpvg_params * params, double * seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
 
@@ -1183,12 +1060,7 @@ int rpvg_amd_run_inplace(void * engine, void * prepared_batch, const char * mode
         PhaseTrace::report();
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // One pass of the widened path with the alignment-path lists resident on the GPU: rows are constructed and merged on
@@ -1196,7 +1068,7 @@ int rpvg_amd_run_inplace(void * engine, void * prepared_batch, const char * mode
 // rows_seconds_out / estimate_seconds_out = wall time of the two stages.
 int rpvg_amd_run_from_alignments_inplace(void * engine, void * prepared_batch, const char * model, const rpvg_params * params, double * rows_seconds_out, double * estimate_seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
 
@@ -1227,12 +1099,7 @@ int rpvg_amd_run_from_alignments_inplace(void * engine, void * prepared_batch, c
         }
 
         return rpvg_amd_run_inplace(engine, prepared_batch, model, params, estimate_seconds_out);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // ---- the GPUs of a node behind one call (device_group.hpp) -------------------------------------------------------
@@ -1245,18 +1112,13 @@ struct Group {
 
 void * rpvg_amd_group_create(const int * devices, int num_devices) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         Group * group = new Group();
         std::unique_ptr<Group> guard(group);
         group->devices.reset(new DeviceGroup(std::vector<int>(devices, devices + num_devices)));
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 void rpvg_amd_group_destroy(void * group) {
@@ -1272,7 +1134,7 @@ int rpvg_amd_group_has_communicator(void * group) {
 // Estimates of every cluster of a host batch, its clusters sharded over the group's GPUs.
 void * rpvg_amd_group_run(void * group_handle, const rpvg_cluster_batch * batch, const char * model, const rpvg_params * params, double * seconds_out) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         Group * group = static_cast<Group *>(group_handle);
         const auto paths = unpackPaths(*batch);
@@ -1293,12 +1155,7 @@ void * rpvg_amd_group_run(void * group_handle, const rpvg_cluster_batch * batch,
         }
 
         return packResult(group->estimates);
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 // GPU of every cluster in the last run.
@@ -1328,7 +1185,7 @@ int rpvg_amd_group_partition(void * group_handle, uint32_t * device_of_cluster, 
 // number, and the TPM denominator.
 int rpvg_amd_group_gather(void * group_handle, double * abundances_out, uint64_t capacity, uint64_t * count_out, double * total_transcript_count_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         Group * group = static_cast<Group *>(group_handle);
         const auto gathered = group->devices->gatherAbundances(group->estimates, total_transcript_count_out);
@@ -1342,12 +1199,7 @@ int rpvg_amd_group_gather(void * group_handle, double * abundances_out, uint64_t
         std::copy(gathered.begin(), gathered.end(), abundances_out);
         *count_out = gathered.size();
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // ---- several batches in flight on one GPU (batch_pipeline.hpp) --------------------------------------------------------
@@ -1363,18 +1215,13 @@ struct Pipeline {
 
 void * rpvg_amd_pipeline_create(int device, const char * model, const rpvg_params * params, int workers) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         Pipeline * pipeline = new Pipeline();
         std::unique_ptr<Pipeline> guard(pipeline);
         pipeline->pipeline.reset(new BatchPipeline(device, model, *params, workers));
         return guard.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 void rpvg_amd_pipeline_destroy(void * pipeline) {
@@ -1390,7 +1237,7 @@ int rpvg_amd_pipeline_workers(void * pipeline) {
 // `slots` sets of estimates containers with the PathInfo of the batch's clusters filled in (src/main.cpp:855-887).
 int rpvg_amd_pipeline_prepare_slots(void * pipeline_handle, const rpvg_cluster_batch * batch, int slots) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         Pipeline * pipeline = static_cast<Pipeline *>(pipeline_handle);
         pipeline->pipeline->wait();
@@ -1407,19 +1254,14 @@ int rpvg_amd_pipeline_prepare_slots(void * pipeline_handle, const rpvg_cluster_b
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // The containers of ONE slot, for the clusters (paths) of `batch` — slots may hold different batches (the parts of one data set,
 // submitted one behind the other); the slots in front of it exist afterwards, empty if they were not prepared.
 int rpvg_amd_pipeline_prepare_slot(void * pipeline_handle, const rpvg_cluster_batch * batch, int slot) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         Pipeline * pipeline = static_cast<Pipeline *>(pipeline_handle);
         pipeline->pipeline->wait();
@@ -1440,61 +1282,41 @@ int rpvg_amd_pipeline_prepare_slot(void * pipeline_handle, const rpvg_cluster_ba
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // Queues one batch (its arrays stay the caller's until rpvg_amd_pipeline_wait returns) with the containers of `slot`.
 int rpvg_amd_pipeline_submit(void * pipeline_handle, const rpvg_cluster_batch * batch, int slot) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         Pipeline * pipeline = static_cast<Pipeline *>(pipeline_handle);
         pipeline->pipeline->submit(*batch, &pipeline->slots.at(slot));
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 int rpvg_amd_pipeline_wait(void * pipeline_handle) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         static_cast<Pipeline *>(pipeline_handle)->pipeline->wait();
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // The estimates a finished batch left in the containers of `slot` (call after rpvg_amd_pipeline_wait).
 void * rpvg_amd_pipeline_result(void * pipeline_handle, int slot) {
 
-    try {
+    return guardedHandle([&]() -> void * {
 
         return packResult(static_cast<Pipeline *>(pipeline_handle)->slots.at(slot));
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
+    });
 }
 
 int rpvg_amd_pipeline_stats_get(void * pipeline_handle, rpvg_hip_kernel_stats * stats_out, double * mean_upload_seconds_out) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         Pipeline * pipeline = static_cast<Pipeline *>(pipeline_handle);
         pipeline->pipeline->stats(stats_out);
@@ -1514,12 +1336,7 @@ int rpvg_amd_pipeline_stats_get(void * pipeline_handle, rpvg_hip_kernel_stats * 
         }
 
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 // Completion times of the batches since the last statistics reset (seconds since that reset, in order of completion).
@@ -1533,504 +1350,11 @@ int rpvg_amd_pipeline_completions(void * pipeline_handle, double * seconds_out, 
 
 int rpvg_amd_pipeline_stats_reset(void * pipeline_handle) {
 
-    try {
+    return guardedInt([&]() -> int {
 
         static_cast<Pipeline *>(pipeline_handle)->pipeline->resetStats();
         return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-}
-
-// ---- estimates table (estimates_table.hpp; include/rpvg_table.h) ------------------------------------------------------------------
-
-namespace {
-
-struct TableHandle {
-
-    std::unique_ptr<EstimatesTable> table;
-    TableLabels labels;
-    uint32_t ploidy = 0;
-};
-
-// rows are called as the existing writers would call them from the prepared batch: the PathInfo's name ("c<k>_p<j>" for a batch
-// that came without names) and length, ClusterID k + 1
-TableLabels labelsOf(const std::vector<std::vector<PathInfo> > & paths) {
-
-    TableLabels labels;
-
-    for (size_t k = 0; k < paths.size(); ++k) {
-
-        for (size_t j = 0; j < paths[k].size(); ++j) {
-
-            labels.names.emplace_back(paths[k][j].name.empty() ? "c" + std::to_string(k) + "_p" + std::to_string(j) : paths[k][j].name);
-            labels.lengths.emplace_back(paths[k][j].length);
-        }
-
-        labels.cluster_ids.emplace_back(k + 1);
-    }
-
-    return labels;
-}
-
-// the containers of a prepared batch as the writers take them, the rows called as labelsOf() calls them
-template <typename Prepared>
-ClusterEstimatesList gibbsListOf(const Prepared & prepared) {
-
-    const TableLabels labels = labelsOf(prepared.paths);
-    ClusterEstimatesList list;
-    size_t g = 0;
-
-    for (size_t k = 0; k < prepared.estimates.size(); ++k) {
-
-        list.emplace_back(labels.cluster_ids[k], prepared.estimates[k]);
-
-        for (auto & path: list.back().second.paths) {
-
-            path.name = labels.names[g];
-            ++g;
-        }
-    }
-
-    return list;
-}
-
-// "abundance": <prefix>.txt of AbundanceEstimatesWriter; "haplotype": <prefix>.txt of HaplotypeAbundanceEstimatesWriter; "joint":
-// <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter.  add(writer) adds the rows.
-template <typename AddRows>
-void writeWith(const std::string & writer, const uint32_t ploidy, const double min_posterior, const double denominator, const std::string & prefix, const uint32_t unaligned_read_count, AddRows add) {
-
-    if (writer == "abundance") {
-
-        AbundanceEstimatesWriter out(prefix, denominator);
-        add(out);
-        out.addNoiseTranscript(unaligned_read_count);
-        out.close();
-
-    } else if (writer == "haplotype") {
-
-        HaplotypeAbundanceEstimatesWriter out(prefix, ploidy, denominator);
-        add(out);
-        out.addNoiseTranscript(unaligned_read_count);
-        out.close();
-
-    } else if (writer == "joint") {
-
-        JointHaplotypeAbundanceEstimatesWriter out(prefix + "_joint", ploidy, min_posterior, denominator);
-        add(out);
-        out.addNoiseTranscript(unaligned_read_count);
-        out.close();
-
-    } else {
-
-        throw std::runtime_error("no such writer: " + writer);
-    }
-}
-
-}
-
-extern "C" {
-
-// The table of the estimates of a prepared batch, built on the engine's GPU: from a result handle (rpvg_amd_run and the like)
-// when there is one, else from the containers the last run on the prepared batch left in it.
-void * rpvg_amd_estimates_table_build(void * engine, void * result_handle, void * prepared_batch, uint32_t ploidy) {
-
-    try {
-
-        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
-        std::unique_ptr<TableHandle> handle(new TableHandle());
-        handle->labels = labelsOf(prepared->paths);
-        handle->ploidy = ploidy;
-
-        if (result_handle) {
-
-            const Result * result = static_cast<const Result *>(result_handle);
-
-            if (result->noise_count.size() != prepared->paths.size()) {
-
-                throw std::runtime_error("the result is not that of the prepared batch");
-            }
-
-            std::vector<uint64_t> cluster_path_off(1, 0);
-            std::vector<double> effective_length;
-
-            for (auto & paths: prepared->paths) {
-
-                for (auto & path: paths) {
-
-                    effective_length.emplace_back(path.effective_length);
-                }
-
-                cluster_path_off.emplace_back(effective_length.size());
-            }
-
-            rpvg_estimates_flat flat = {};
-            flat.num_clusters = result->noise_count.size();
-            flat.num_sets = result->posteriors.size();
-            flat.num_members = result->members.size();
-            flat.num_abundances = result->abundances.size();
-            flat.num_paths = effective_length.size();
-            flat.set_off = result->set_off.data();
-            flat.member_off = result->member_off.data();
-            flat.members = result->members.data();
-            flat.posteriors = result->posteriors.data();
-            flat.abund_off = result->abund_off.data();
-            flat.abundances = result->abundances.data();
-            flat.noise_count = result->noise_count.data();
-            flat.cluster_path_off = cluster_path_off.data();
-            flat.path_effective_length = effective_length.data();
-
-            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, flat, ploidy));
-
-        } else {
-
-            if (prepared->estimates.size() != prepared->paths.size()) {
-
-                throw std::runtime_error("the prepared batch has no estimates yet");
-            }
-
-            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, prepared->estimates, ploidy));
-        }
-
-        return handle.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
-}
-
-int rpvg_amd_estimates_table_tpm(void * table_handle, double denominator) {
-
-    try {
-
-        static_cast<TableHandle *>(table_handle)->table->tpm(denominator);
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-// valid until the next rpvg_amd_estimates_table_tpm or the table's end
-int rpvg_amd_estimates_table_view(void * table_handle, rpvg_estimates_table_view * view_out) {
-
-    try {
-
-        *view_out = static_cast<TableHandle *>(table_handle)->table->view();
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-// One of the three files from the table (after rpvg_amd_estimates_table_tpm): writer = "abundance", "haplotype" or "joint".
-int rpvg_amd_estimates_table_write(void * table_handle, const char * writer, double min_posterior, const char * output_prefix, uint32_t unaligned_read_count) {
-
-    try {
-
-        TableHandle * handle = static_cast<TableHandle *>(table_handle);
-        const rpvg_estimates_flat estimates = handle->table->estimates();
-        const rpvg_estimates_table_view & view = handle->table->view();
-
-        writeWith(writer, handle->ploidy, min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addTable(estimates, view, handle->labels); });
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-void rpvg_amd_estimates_table_free(void * table_handle) {
-
-    delete static_cast<TableHandle *>(table_handle);
-}
-
-// The same file from the containers of the prepared batch by the writer's addEstimates(), the rows called as the table's are;
-// total_transcript_count_out: totalTranscriptCount() of the containers (one running sum over all members) and seconds_out the
-// time of that sum; write_seconds_out: the writer from its constructor to close().  A denominator of 0 stands for that sum.
-int rpvg_amd_estimates_write_from_containers(void * prepared_batch, const char * writer, uint32_t ploidy, double min_posterior, double denominator, const char * output_prefix, uint32_t unaligned_read_count, double * total_transcript_count_out, double * seconds_out, double * write_seconds_out) {
-
-    try {
-
-        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
-
-        if (prepared->estimates.size() != prepared->paths.size()) {
-
-            throw std::runtime_error("the prepared batch has no estimates yet");
-        }
-
-        const TableLabels labels = labelsOf(prepared->paths);
-        ClusterEstimatesList list;
-        size_t g = 0;
-
-        for (size_t k = 0; k < prepared->estimates.size(); ++k) {
-
-            list.emplace_back(labels.cluster_ids[k], prepared->estimates[k]);
-
-            for (auto & path: list.back().second.paths) {
-
-                path.name = labels.names[g];
-                ++g;
-            }
-        }
-
-        const auto start = std::chrono::steady_clock::now();
-        const double total = totalTranscriptCount(list);
-        const auto stop = std::chrono::steady_clock::now();
-
-        if (total_transcript_count_out) {
-
-            *total_transcript_count_out = total;
-        }
-
-        if (seconds_out) {
-
-            *seconds_out = std::chrono::duration<double>(stop - start).count();
-        }
-
-        if (writer && writer[0]) {
-
-            const auto write_start = std::chrono::steady_clock::now();
-            writeWith(writer, ploidy, min_posterior, denominator == 0 ? total : denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addEstimates(list); });
-
-            if (write_seconds_out) {
-
-                *write_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - write_start).count();
-            }
-        }
-
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-// ---- the Gibbs samples table of a prepared batch (gibbs_samples_table.hpp) -------------------------------------------------------
-
-// The table of the Gibbs samples the last run (-n > 0) left in the containers of the prepared batch, built on the engine's GPU; the
-// rows are called as rpvg_amd_estimates_table_build calls them.  seconds_out: flattening the containers and the build.
-void * rpvg_amd_gibbs_table_build(void * engine, void * prepared_batch, uint32_t num_gibbs_samples, double * seconds_out) {
-
-    try {
-
-        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
-
-        if (prepared->estimates.size() != prepared->paths.size()) {
-
-            throw std::runtime_error("the prepared batch has no estimates yet");
-        }
-
-        const ClusterEstimatesList list = gibbsListOf(*prepared);
-        const auto start = std::chrono::steady_clock::now();
-        std::unique_ptr<GibbsSamplesTable> table(new GibbsSamplesTable(static_cast<Engine *>(engine)->hip, list, num_gibbs_samples));
-
-        if (seconds_out) {
-
-            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
-        }
-
-        return table.release();
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return nullptr;
-    }
-}
-
-// valid until the table's end
-int rpvg_amd_gibbs_table_view(void * table_handle, rpvg_gibbs_table_view * view_out) {
-
-    try {
-
-        *view_out = static_cast<GibbsSamplesTable *>(table_handle)->view();
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-// <prefix>.txt.gz from the table by ReadCountGibbsSamplesWriter::addTable
-int rpvg_amd_gibbs_table_write(void * table_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
-
-    try {
-
-        GibbsSamplesTable * table = static_cast<GibbsSamplesTable *>(table_handle);
-        ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
-        out.addTable(table->view(), table->labels());
-        out.addNoiseTranscript(unaligned_read_count);
-        out.close();
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
-}
-
-void rpvg_amd_gibbs_table_free(void * table_handle) {
-
-    delete static_cast<GibbsSamplesTable *>(table_handle);
-}
-
-// The same from the containers on ONE thread.  With a prefix: the file by the writer's addSamples(), cluster by cluster.  With
-// samples_out [P * N], listed_out [P] and noise_counts_out [N]: the writer's loops with every stream insertion replaced by a store
-// into a dense table (the host comparison of tools/gibbs_table_ab.py); seconds_out is the time of those loops alone.
-int rpvg_amd_gibbs_from_containers(void * prepared_batch, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count,
-                                   double * samples_out, uint8_t * listed_out, double * noise_counts_out, double * seconds_out) {
-
-    try {
-
-        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
-
-        if (prepared->estimates.size() != prepared->paths.size()) {
-
-            throw std::runtime_error("the prepared batch has no estimates yet");
-        }
-
-        const ClusterEstimatesList list = gibbsListOf(*prepared);
-
-        if (output_prefix && output_prefix[0]) {
-
-            ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
-
-            for (auto & entry: list) {
-
-                out.addSamples(entry);
-            }
-
-            out.addNoiseTranscript(unaligned_read_count);
-            out.close();
-        }
-
-        if (samples_out && listed_out && noise_counts_out) {
-
-            const auto start = std::chrono::steady_clock::now();
-            const uint32_t no_column = std::numeric_limits<uint32_t>::max();
-            uint64_t g0 = 0;
-
-            for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
-
-                noise_counts_out[idx] = 0;
-            }
-
-            for (auto & entry: list) {
-
-                const auto & estimates = entry.second;
-                const size_t num_paths = estimates.paths.size();
-                std::fill(samples_out + g0 * num_gibbs_samples, samples_out + (g0 + num_paths) * num_gibbs_samples, 0.0);
-                std::fill(listed_out + g0, listed_out + g0 + num_paths, 0);
-
-                if (estimates.gibbs_read_count_samples.empty()) {
-
-                    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
-
-                        noise_counts_out[idx] += estimates.total_count;
-                    }
-
-                    g0 += num_paths;
-                    continue;
-                }
-
-                std::vector<std::vector<uint32_t> > path_gibbs_sampling_index(num_paths);
-                uint32_t noise_count_idx = 0;
-
-                for (size_t i = 0; i < estimates.gibbs_read_count_samples.size(); ++i) {
-
-                    const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(i);
-
-                    for (auto & noise_sample: count_samples.noise_samples) {
-
-                        noise_counts_out[noise_count_idx] += noise_sample;
-                        ++noise_count_idx;
-                    }
-
-                    for (size_t j = 0; j < count_samples.path_ids.size(); ++j) {
-
-                        auto & sampling_indices = path_gibbs_sampling_index.at(count_samples.path_ids.at(j));
-
-                        if (sampling_indices.empty()) {
-
-                            sampling_indices.assign(estimates.gibbs_read_count_samples.size(), no_column);
-                        }
-
-                        sampling_indices.at(i) = j;
-                    }
-                }
-
-                while (noise_count_idx < num_gibbs_samples) {
-
-                    noise_counts_out[noise_count_idx] += estimates.total_count;
-                    ++noise_count_idx;
-                }
-
-                for (size_t i = 0; i < num_paths; ++i) {
-
-                    const auto & sampling_indices = path_gibbs_sampling_index.at(i);
-
-                    if (sampling_indices.empty()) {
-
-                        continue;
-                    }
-
-                    listed_out[g0 + i] = 1;
-                    double * row = samples_out + (g0 + i) * num_gibbs_samples;
-                    uint32_t num_samples = 0;
-
-                    for (size_t j = 0; j < sampling_indices.size(); ++j) {
-
-                        const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(j);
-                        const size_t num_columns = count_samples.path_ids.size();
-
-                        for (size_t k = 0; k < count_samples.noise_samples.size(); ++k) {
-
-                            if (sampling_indices.at(j) != no_column) {
-
-                                row[num_samples] = count_samples.abundance_samples.at(k * num_columns + sampling_indices.at(j));
-                            }
-
-                            ++num_samples;
-                        }
-                    }
-                }
-
-                g0 += num_paths;
-            }
-
-            if (seconds_out) {
-
-                *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
-            }
-        }
-
-        return 0;
-
-    } catch (const std::exception & e) {
-
-        last_error = e.what();
-        return -1;
-    }
+    });
 }
 
 void rpvg_amd_result_view(void * result_handle, rpvg_estimates_view * out) {

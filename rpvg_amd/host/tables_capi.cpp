@@ -1,0 +1,449 @@
+// C entry points of the harness for the two output tables of a prepared batch: the estimates table (estimates_table.hpp;
+// include/rpvg_table.h) and the Gibbs samples table (gibbs_samples_table.hpp; include/rpvg_samples.h), each beside the same file
+// or table made from the containers by the writers' own loops.  Nothing here runs a batch (runner_capi.cpp does).
+
+#include <algorithm>
+#include <chrono>
+#include <limits>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "estimates_table.hpp"
+#include "gibbs_samples_table.hpp"
+#include "io/estimates_writers.hpp"
+#include "runner_handles.hpp"
+
+using namespace rpvg_amd;
+using namespace rpvg_amd_harness;
+
+// ---- estimates table (estimates_table.hpp; include/rpvg_table.h) ------------------------------------------------------------------
+
+namespace {
+
+struct TableHandle {
+
+    std::unique_ptr<EstimatesTable> table;
+    TableLabels labels;
+    uint32_t ploidy = 0;
+};
+
+// rows are called as the existing writers would call them from the prepared batch: the PathInfo's name ("c<k>_p<j>" for a batch
+// that came without names) and length, ClusterID k + 1
+TableLabels labelsOf(const std::vector<std::vector<PathInfo> > & paths) {
+
+    TableLabels labels;
+
+    for (size_t k = 0; k < paths.size(); ++k) {
+
+        for (size_t j = 0; j < paths[k].size(); ++j) {
+
+            labels.names.emplace_back(paths[k][j].name.empty() ? "c" + std::to_string(k) + "_p" + std::to_string(j) : paths[k][j].name);
+            labels.lengths.emplace_back(paths[k][j].length);
+        }
+
+        labels.cluster_ids.emplace_back(k + 1);
+    }
+
+    return labels;
+}
+
+// the containers of a prepared batch as the writers take them, the rows called as labelsOf() calls them
+template <typename Prepared>
+ClusterEstimatesList labelledListOf(const Prepared & prepared) {
+
+    const TableLabels labels = labelsOf(prepared.paths);
+    ClusterEstimatesList list;
+    size_t g = 0;
+
+    for (size_t k = 0; k < prepared.estimates.size(); ++k) {
+
+        list.emplace_back(labels.cluster_ids[k], prepared.estimates[k]);
+
+        for (auto & path: list.back().second.paths) {
+
+            path.name = labels.names[g];
+            ++g;
+        }
+    }
+
+    return list;
+}
+
+// "abundance": <prefix>.txt of AbundanceEstimatesWriter; "haplotype": <prefix>.txt of HaplotypeAbundanceEstimatesWriter; "joint":
+// <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter.  add(writer) adds the rows.
+template <typename AddRows>
+void writeWith(const std::string & writer, const uint32_t ploidy, const double min_posterior, const double denominator, const std::string & prefix, const uint32_t unaligned_read_count, AddRows add) {
+
+    if (writer == "abundance") {
+
+        AbundanceEstimatesWriter out(prefix, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else if (writer == "haplotype") {
+
+        HaplotypeAbundanceEstimatesWriter out(prefix, ploidy, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else if (writer == "joint") {
+
+        JointHaplotypeAbundanceEstimatesWriter out(prefix + "_joint", ploidy, min_posterior, denominator);
+        add(out);
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+
+    } else {
+
+        throw std::runtime_error("no such writer: " + writer);
+    }
+}
+
+}
+
+extern "C" {
+
+// The table of the estimates of a prepared batch, built on the engine's GPU: from a result handle (rpvg_amd_run and the like)
+// when there is one, else from the containers the last run on the prepared batch left in it.
+void * rpvg_amd_estimates_table_build(void * engine, void * result_handle, void * prepared_batch, uint32_t ploidy) {
+
+    return guardedHandle([&]() -> void * {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+        std::unique_ptr<TableHandle> handle(new TableHandle());
+        handle->labels = labelsOf(prepared->paths);
+        handle->ploidy = ploidy;
+
+        if (result_handle) {
+
+            const Result * result = static_cast<const Result *>(result_handle);
+
+            if (result->noise_count.size() != prepared->paths.size()) {
+
+                throw std::runtime_error("the result is not that of the prepared batch");
+            }
+
+            std::vector<uint64_t> cluster_path_off(1, 0);
+            std::vector<double> effective_length;
+
+            for (auto & paths: prepared->paths) {
+
+                for (auto & path: paths) {
+
+                    effective_length.emplace_back(path.effective_length);
+                }
+
+                cluster_path_off.emplace_back(effective_length.size());
+            }
+
+            rpvg_estimates_flat flat = {};
+            flat.num_clusters = result->noise_count.size();
+            flat.num_sets = result->posteriors.size();
+            flat.num_members = result->members.size();
+            flat.num_abundances = result->abundances.size();
+            flat.num_paths = effective_length.size();
+            flat.set_off = result->set_off.data();
+            flat.member_off = result->member_off.data();
+            flat.members = result->members.data();
+            flat.posteriors = result->posteriors.data();
+            flat.abund_off = result->abund_off.data();
+            flat.abundances = result->abundances.data();
+            flat.noise_count = result->noise_count.data();
+            flat.cluster_path_off = cluster_path_off.data();
+            flat.path_effective_length = effective_length.data();
+
+            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, flat, ploidy));
+
+        } else {
+
+            if (prepared->estimates.size() != prepared->paths.size()) {
+
+                throw std::runtime_error("the prepared batch has no estimates yet");
+            }
+
+            handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, prepared->estimates, ploidy));
+        }
+
+        return handle.release();
+    });
+}
+
+int rpvg_amd_estimates_table_tpm(void * table_handle, double denominator) {
+
+    return guardedInt([&]() -> int {
+
+        static_cast<TableHandle *>(table_handle)->table->tpm(denominator);
+        return 0;
+    });
+}
+
+// valid until the next rpvg_amd_estimates_table_tpm or the table's end
+int rpvg_amd_estimates_table_view(void * table_handle, rpvg_estimates_table_view * view_out) {
+
+    return guardedInt([&]() -> int {
+
+        *view_out = static_cast<TableHandle *>(table_handle)->table->view();
+        return 0;
+    });
+}
+
+// One of the three files from the table (after rpvg_amd_estimates_table_tpm): writer = "abundance", "haplotype" or "joint".
+int rpvg_amd_estimates_table_write(void * table_handle, const char * writer, double min_posterior, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    return guardedInt([&]() -> int {
+
+        TableHandle * handle = static_cast<TableHandle *>(table_handle);
+        const rpvg_estimates_flat estimates = handle->table->estimates();
+        const rpvg_estimates_table_view & view = handle->table->view();
+
+        writeWith(writer, handle->ploidy, min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addTable(estimates, view, handle->labels); });
+        return 0;
+    });
+}
+
+void rpvg_amd_estimates_table_free(void * table_handle) {
+
+    delete static_cast<TableHandle *>(table_handle);
+}
+
+// The same file from the containers of the prepared batch by the writer's addEstimates(), the rows called as the table's are;
+// total_transcript_count_out: totalTranscriptCount() of the containers (one running sum over all members) and seconds_out the
+// time of that sum; write_seconds_out: the writer from its constructor to close().  A denominator of 0 stands for that sum.
+int rpvg_amd_estimates_write_from_containers(void * prepared_batch, const char * writer, uint32_t ploidy, double min_posterior, double denominator, const char * output_prefix, uint32_t unaligned_read_count, double * total_transcript_count_out, double * seconds_out, double * write_seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const ClusterEstimatesList list = labelledListOf(*prepared);
+
+        const auto start = std::chrono::steady_clock::now();
+        const double total = totalTranscriptCount(list);
+        const auto stop = std::chrono::steady_clock::now();
+
+        if (total_transcript_count_out) {
+
+            *total_transcript_count_out = total;
+        }
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(stop - start).count();
+        }
+
+        if (writer && writer[0]) {
+
+            const auto write_start = std::chrono::steady_clock::now();
+            writeWith(writer, ploidy, min_posterior, denominator == 0 ? total : denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addEstimates(list); });
+
+            if (write_seconds_out) {
+
+                *write_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - write_start).count();
+            }
+        }
+
+        return 0;
+    });
+}
+
+// ---- the Gibbs samples table of a prepared batch (gibbs_samples_table.hpp) -------------------------------------------------------
+
+// The table of the Gibbs samples the last run (-n > 0) left in the containers of the prepared batch, built on the engine's GPU; the
+// rows are called as rpvg_amd_estimates_table_build calls them.  seconds_out: flattening the containers and the build.
+void * rpvg_amd_gibbs_table_build(void * engine, void * prepared_batch, uint32_t num_gibbs_samples, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const ClusterEstimatesList list = labelledListOf(*prepared);
+        const auto start = std::chrono::steady_clock::now();
+        std::unique_ptr<GibbsSamplesTable> table(new GibbsSamplesTable(static_cast<Engine *>(engine)->hip, list, num_gibbs_samples));
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return table.release();
+    });
+}
+
+// valid until the table's end
+int rpvg_amd_gibbs_table_view(void * table_handle, rpvg_gibbs_table_view * view_out) {
+
+    return guardedInt([&]() -> int {
+
+        *view_out = static_cast<GibbsSamplesTable *>(table_handle)->view();
+        return 0;
+    });
+}
+
+// <prefix>.txt.gz from the table by ReadCountGibbsSamplesWriter::addTable
+int rpvg_amd_gibbs_table_write(void * table_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    return guardedInt([&]() -> int {
+
+        GibbsSamplesTable * table = static_cast<GibbsSamplesTable *>(table_handle);
+        ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+        out.addTable(table->view(), table->labels());
+        out.addNoiseTranscript(unaligned_read_count);
+        out.close();
+        return 0;
+    });
+}
+
+void rpvg_amd_gibbs_table_free(void * table_handle) {
+
+    delete static_cast<GibbsSamplesTable *>(table_handle);
+}
+
+// The same from the containers on ONE thread.  With a prefix: the file by the writer's addSamples(), cluster by cluster.  With
+// samples_out [P * N], listed_out [P] and noise_counts_out [N]: the writer's loops with every stream insertion replaced by a store
+// into a dense table (the host comparison of tools/gibbs_table_ab.py); seconds_out is the time of those loops alone.
+int rpvg_amd_gibbs_from_containers(void * prepared_batch, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count,
+                                   double * samples_out, uint8_t * listed_out, double * noise_counts_out, double * seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            throw std::runtime_error("the prepared batch has no estimates yet");
+        }
+
+        const ClusterEstimatesList list = labelledListOf(*prepared);
+
+        if (output_prefix && output_prefix[0]) {
+
+            ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+
+            for (auto & entry: list) {
+
+                out.addSamples(entry);
+            }
+
+            out.addNoiseTranscript(unaligned_read_count);
+            out.close();
+        }
+
+        if (samples_out && listed_out && noise_counts_out) {
+
+            const auto start = std::chrono::steady_clock::now();
+            const uint32_t no_column = std::numeric_limits<uint32_t>::max();
+            uint64_t g0 = 0;
+
+            for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+                noise_counts_out[idx] = 0;
+            }
+
+            for (auto & entry: list) {
+
+                const auto & estimates = entry.second;
+                const size_t num_paths = estimates.paths.size();
+                std::fill(samples_out + g0 * num_gibbs_samples, samples_out + (g0 + num_paths) * num_gibbs_samples, 0.0);
+                std::fill(listed_out + g0, listed_out + g0 + num_paths, 0);
+
+                if (estimates.gibbs_read_count_samples.empty()) {
+
+                    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+                        noise_counts_out[idx] += estimates.total_count;
+                    }
+
+                    g0 += num_paths;
+                    continue;
+                }
+
+                std::vector<std::vector<uint32_t> > path_gibbs_sampling_index(num_paths);
+                uint32_t noise_count_idx = 0;
+
+                for (size_t i = 0; i < estimates.gibbs_read_count_samples.size(); ++i) {
+
+                    const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(i);
+
+                    for (auto & noise_sample: count_samples.noise_samples) {
+
+                        noise_counts_out[noise_count_idx] += noise_sample;
+                        ++noise_count_idx;
+                    }
+
+                    for (size_t j = 0; j < count_samples.path_ids.size(); ++j) {
+
+                        auto & sampling_indices = path_gibbs_sampling_index.at(count_samples.path_ids.at(j));
+
+                        if (sampling_indices.empty()) {
+
+                            sampling_indices.assign(estimates.gibbs_read_count_samples.size(), no_column);
+                        }
+
+                        sampling_indices.at(i) = j;
+                    }
+                }
+
+                while (noise_count_idx < num_gibbs_samples) {
+
+                    noise_counts_out[noise_count_idx] += estimates.total_count;
+                    ++noise_count_idx;
+                }
+
+                for (size_t i = 0; i < num_paths; ++i) {
+
+                    const auto & sampling_indices = path_gibbs_sampling_index.at(i);
+
+                    if (sampling_indices.empty()) {
+
+                        continue;
+                    }
+
+                    listed_out[g0 + i] = 1;
+                    double * row = samples_out + (g0 + i) * num_gibbs_samples;
+                    uint32_t num_samples = 0;
+
+                    for (size_t j = 0; j < sampling_indices.size(); ++j) {
+
+                        const CountSamples & count_samples = estimates.gibbs_read_count_samples.at(j);
+                        const size_t num_columns = count_samples.path_ids.size();
+
+                        for (size_t k = 0; k < count_samples.noise_samples.size(); ++k) {
+
+                            if (sampling_indices.at(j) != no_column) {
+
+                                row[num_samples] = count_samples.abundance_samples.at(k * num_columns + sampling_indices.at(j));
+                            }
+
+                            ++num_samples;
+                        }
+                    }
+                }
+
+                g0 += num_paths;
+            }
+
+            if (seconds_out) {
+
+                *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+            }
+        }
+
+        return 0;
+    });
+}
+
+}

@@ -235,6 +235,15 @@ def test_invalid_input_names_the_cluster(hip_ctx):
     refused(flat_of(short), 1)
     flat = flat_of(clusters)
     refused(flat, 4, num_members=len(flat.members) - 1)      # member_off ends beyond the array
+    flat = flat_of(clusters)
+    for k in (3, 1):
+        flat.members[int(flat.member_off[int(flat.set_off[k])])] = 8   # the same offence in clusters 3 and 1: the smaller one is named
+    refused(flat, 1)
+    flat = flat_of(clusters)
+    s = int(flat.set_off[2]) + 3
+    flat.member_off[s] = flat.member_off[s - 1] - 1          # decreasing member_off inside cluster 2 (the smaller reason) ...
+    flat.members[int(flat.member_off[int(flat.set_off[1])])] = 8   # ... and a member beyond its paths in cluster 1: the cluster decides
+    refused(flat, 1)
     with pytest.raises(hip.EngineError):
         EstimatesTable.build(hip_ctx, None, flat_of(clusters), 0)
     check(hip_ctx, clusters)                                   # the context is usable afterwards

@@ -187,6 +187,20 @@ def test_invalid_input_names_the_cluster_or_block(hip_ctx):
     flat.gibbs_path[int(flat.gibbs_path_off[12]) - 1] = 8        # an id equal to the path count, last of block 11
     refused(flat, "block 11")
     refused(flat_of(clusters, 5), "cluster 0")                   # S_k = 6 > N = 5 in every cluster
+    flat = flat_of(clusters, N)
+    flat.gibbs_off[4] = flat.gibbs_off[3] - 1                    # gibbs_off decreases at the end of cluster 3 (the smaller reason) ...
+    flat.cluster_path_off[2] = flat.cluster_path_off[1] - 1      # ... and cluster_path_off at the end of cluster 1: the cluster decides
+    refused(flat, "cluster 1")
+    flat = flat_of(clusters, N)
+    at = int(flat.gibbs_path_off[10])
+    flat.gibbs_path[at + 1] = flat.gibbs_path[at]                # equal ids in block 10 (cluster 3) ...
+    flat.gibbs_path_off[5] = flat.gibbs_path_off[4] - 1          # ... and gibbs_path_off decreases at the end of block 4 (cluster 1)
+    refused(flat, "block 4")
+    flat = flat_of(clusters, N)
+    at = int(flat.gibbs_path_off[1])
+    flat.gibbs_path[at + 1] = flat.gibbs_path[at]                # equal ids in block 1 (cluster 0) ...
+    flat.cluster_path_off[4] = flat.cluster_path_off[3] - 1      # ... and a cluster offence behind it: a cluster comes before every block
+    refused(flat, "cluster 3")
     with pytest.raises(hip.EngineError, match=r"\(-3\).*num_gibbs_samples is 0"):
         GibbsTable.build(hip_ctx, flat_of(clusters, 0))
     check(hip_ctx, clusters, N)                                  # the context is usable afterwards

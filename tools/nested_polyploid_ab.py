@@ -19,50 +19,16 @@ import json
 import math
 import os
 import pickle
-import re
 import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _resources import resource_usage  # noqa: E402
 
 # haplotypes of the generator (an upper bound of a cluster's columns) by ploidy and shape
 HAPLOTYPES = {5: dict(small=8, mid=24, large=40), 6: dict(small=7, mid=18, large=28), 8: dict(small=6, mid=13, large=18)}
-
-
-def resource_usage(out):
-    """Registers, LDS and scratch of every kernel of subset_full.hip from hipcc's resource remarks (gfx950)."""
-    csrc = os.path.join(ROOT, "rpvg_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(csrc, "subset_full.hip"),
-           "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, current = [], None
-    for line in text.splitlines():
-        m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|"
-                      r"SGPRs Spill|VGPRs Spill): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            current = {"name": m.group(2)}
-            kernels.append(current)
-        elif current is not None:
-            current[m.group(1)] = m.group(2)
-    lines = ["subset_full.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (subsetOffsetsKernel and packResultsKernel: "
-             "subset_pack.hpp, shared with subset_em.hip)",
-             f"{'kernel':<32}{'VGPRs':>7}{'SGPRs':>7}{'LDS B':>8}{'scratch B/lane':>16}{'waves/SIMD':>12}{'SGPR spills':>13}{'VGPR spills':>13}"]
-    for k in kernels:
-        name = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip() or k["name"]
-        short = re.sub(r"^.*?(\w+Kernel)(<[^(]*>)?\(.*$", r"\1\2", name)
-        lines.append(f"{short:<32}{k.get('VGPRs', '?'):>7}{k.get('TotalSGPRs', '?'):>7}{k.get('LDS Size [bytes/block]', '?'):>8}"
-                     f"{k.get('ScratchSize [bytes/lane]', '?'):>16}{k.get('Occupancy [waves/SIMD]', '?'):>12}{k.get('SGPRs Spill', '?'):>13}"
-                     f"{k.get('VGPRs Spill', '?'):>13}")
-    lines.append("No kernel uses scratch memory.  fullSelectKernel<8> parks 6 scalar registers in lanes of a vector register (two list walks of eight")
-    lines.append("cursors each are live in a comparison): no memory traffic, accepted.")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
 
 
 def make_batch(ploidy, shape, clusters):
@@ -148,7 +114,10 @@ def main():
     ap.add_argument("--child-out", default=None)
     args = ap.parse_args()
     if args.resources:
-        resource_usage(args.resources)
+        resource_usage("subset_full.hip", args.resources, width=32, spills=True,
+                       header_note=" (subsetOffsetsKernel and packResultsKernel: subset_pack.hpp, shared with subset_em.hip)",
+                       footer=("No kernel uses scratch memory.  fullSelectKernel<8> parks 6 scalar registers in lanes of a vector register (two list walks of eight",
+                               "cursors each are live in a comparison): no memory traffic, accepted."))
         return 0
     if args.child:
         return child(args)

@@ -17,7 +17,6 @@ from which the grid is at least twice as fast for every measured cover length.
 """
 import argparse
 import os
-import re
 import subprocess
 import sys
 import time
@@ -26,38 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def resource_usage(out):
-    """Registers, LDS and scratch of every kernel of path_cover_grid.hip from hipcc's resource remarks (gfx950)."""
-    csrc = os.path.join(ROOT, "rpvg_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(csrc, "path_cover_grid.hip"),
-           "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, current = [], None
-    for line in text.splitlines():
-        m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            current = {"name": m.group(2)}
-            kernels.append(current)
-        elif current is not None:
-            current[m.group(1).split(" ")[0]] = m.group(2)
-    lines = ["path_cover_grid.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (hipcub's own kernels left out;",
-             "LDS is the static part: coverStrikeKernel<true> adds 8 bytes per path of the cluster, at most 16 384)",
-             f"{'kernel':<34}{'VGPRs':>7}{'SGPRs':>7}{'LDS B':>8}{'scratch B/lane':>16}{'waves/SIMD':>12}"]
-    for k in kernels:
-        name = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip() or k["name"]
-        if "hipcub" in name or "rocprim" in name or "Kernel" not in name:
-            continue
-        short = re.sub(r"^.*?(\w+Kernel)(<[^(]*>)?\(.*$", r"\1\2", name).replace("(anonymous namespace)::", "")
-        lines.append(f"{short:<34}{k.get('VGPRs', '?'):>7}{k.get('TotalSGPRs', '?'):>7}{k.get('LDS', '?'):>8}{k.get('ScratchSize', '?'):>16}{k.get('Occupancy', '?'):>12}")
-        assert k.get("ScratchSize") == "0", f"{short} uses scratch"
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+from _resources import resource_usage  # noqa: E402
 
 
 def planted_cluster(seed, n_rows, n_paths, n_cover):
@@ -114,7 +82,8 @@ def main():
     ap.add_argument("--resources", nargs="?", const=os.path.join(ROOT, "profiles", "path_cover_grid", "resource_usage.txt"), default=None)
     args = ap.parse_args()
     if args.resources:
-        resource_usage(args.resources)
+        resource_usage("path_cover_grid.hip", args.resources,
+                       header_note=" (hipcub's own kernels left out;\nLDS is the static part: coverStrikeKernel<true> adds 8 bytes per path of the cluster, at most 16 384)")
         return 0
 
     from rpvg_amd import hip

@@ -18,8 +18,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import re
-import subprocess
 import sys
 import time
 
@@ -27,37 +25,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _resources import resource_usage  # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-def resource_usage(out):
-    """Registers, LDS and scratch of every kernel of path_table.hip from hipcc's resource remarks (gfx950)."""
-    csrc = os.path.join(ROOT, "rpvg_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(csrc, "path_table.hip"),
-           "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, current = [], None
-    for line in text.splitlines():
-        m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            current = {"name": m.group(2)}
-            kernels.append(current)
-        elif current is not None:
-            current[m.group(1).split(" ")[0]] = m.group(2)
-    lines = ["path_table.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (hipcub's own kernels left out)",
-             f"{'kernel':<34}{'VGPRs':>7}{'SGPRs':>7}{'LDS B':>8}{'scratch B/lane':>16}{'waves/SIMD':>12}"]
-    for k in kernels:
-        name = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip() or k["name"]
-        if "hipcub" in name or "rocprim" in name or "Kernel" not in name:
-            continue
-        short = re.sub(r"^.*?(\w+Kernel)(<[^(]*>)?\(.*$", r"\1\2", name).replace("(anonymous namespace)::", "")
-        lines.append(f"{short:<34}{k.get('VGPRs', '?'):>7}{k.get('TotalSGPRs', '?'):>7}{k.get('LDS', '?'):>8}{k.get('ScratchSize', '?'):>16}{k.get('Occupancy', '?'):>12}")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
 
 
 def draw_names(rng, cluster_path_off, quantiles):
@@ -104,7 +73,7 @@ def main():
     ap.add_argument("--resources", nargs="?", const=os.path.join(ROOT, "profiles", "path_table", "resource_usage.txt"), default=None)
     args = ap.parse_args()
     if args.resources:
-        resource_usage(args.resources)
+        resource_usage("path_table.hip", args.resources, header_note=" (hipcub's own kernels left out)")
         return 0
 
     from align_index_ab import stream_chunks
