@@ -53,6 +53,11 @@ constexpr uint32_t kRegColsMax = 32;  // the widest register-resident variant
 // The register-resident bins in ONE launch: workgroup b serves bin kRegisterBins[b % variants] (emRegisterKernel)
 constexpr uint32_t kRegisterBins[5] = {6, 4, 5, 8, 9};  // <4,16> <1,16> <2,16> <1,32> <2,32>: rpvg_hip_em_kernel_name
 constexpr uint32_t kRegisterKernelIndex = 4;             // the launch's slot in rpvg_hip_kernel_stats::em_kernel
+// Launches of equal workgroup size in ONE launch (EmSolveKnobs::merged_launches): the wave launch — the register bins and bin 0 —
+// under kRegisterKernelIndex, and the 1 024-thread launch (bins 7, 3 and, if possible, 10) under its first bin's slot
+constexpr uint32_t kWaveSparseBin = 0;
+constexpr uint32_t kSparse1024Bins[3] = {7, 3, 10};      // <1024,true> <1024,false> <1024,false,WIDE>
+constexpr size_t kSparse1024ResidentLds = 152 * 1024;    // what bin 7 holds (emBinOf)
 
 // LDS bytes of a problem: the abundance vector, one accumulator vector PER WAVEFRONT of the workgroup (the M-step's sums have one
 // order of additions: emSparseProblem) and scratch, plus its CSR when resident
@@ -147,6 +152,8 @@ struct EmSolveKnobs {
     bool no_fused_dense = false;       // RPVG_HIP_NO_FUSED_DENSE
     bool register_copies = true;       // RPVG_HIP_EM_COPIES
     bool one_register_launch = true;   // RPVG_HIP_EM_REGISTER_LAUNCHES=5 clears it
+    bool merged_launches = false;      // the 64-thread and the 1 024-thread bins in one launch each (with one_register_launch): the library sets it (emSolveKnobs),
+                                       // RPVG_HIP_EM_SEPARATE_LAUNCHES=1 clears it
     bool fill_thread_rows = false;     // RPVG_HIP_FILL_THREAD_ROWS: never a wavefront per row in the fill
     double grid_scale = 1.0;           // RPVG_HIP_EM_GRID_SCALE
     bool few_streams = false;          // RPVG_HIP_EM_FEW_STREAMS
@@ -234,11 +241,14 @@ inline EmFillPlan planEmFill(const EmSolveShape & s, const EmSolveKnobs & knobs)
 enum class EmVariant : uint8_t {
     kSparse64Resident, kSparse256Resident, kSparse1024Resident, kSparse256Streamed, kSparse1024Streamed, kSparseWide,
     kRegisterBins,   // the register-resident bins in one launch (emRegisterKernel)
-    kRegister1x16, kRegister2x16, kRegister4x16, kRegister1x32, kRegister2x32   // one launch per bin (emRegisterBinKernel)
+    kRegister1x16, kRegister2x16, kRegister4x16, kRegister1x32, kRegister2x32,   // one launch per bin (emRegisterBinKernel)
+    // merged launches of one workgroup size (emRegisterKernel, emSparseRolesKernel): their roles are emLaunchRoles
+    kWaveBins,         // the register-resident bins and bin 0
+    kSparse1024Bins    // bins 7 and 3, and 10 if a problem can be that wide
 };
 constexpr int kEmMainStream = -1;
 struct EmLaunch {
-    uint32_t bin;        // the bin the launch serves, and its slot in the statistics
+    uint32_t bin;        // the bin the launch serves (a merged launch: the first of its bins), and the slot of its span in the statistics
     EmVariant variant;
     uint32_t grid;       // workgroups of the persistent launch
     size_t lds;          // dynamic LDS bytes
@@ -248,6 +258,16 @@ inline bool operator==(const EmLaunch & a, const EmLaunch & b) {
     return a.bin == b.bin && a.variant == b.variant && a.grid == b.grid && a.lds == b.lds && a.stream == b.stream;
 }
 constexpr int kEmMaxLaunches = 11;
+
+// The roles of a launch that serves several bins: workgroup b serves bin[b % variants] as that bin's workgroup b / variants — the roles
+// side by side from the first workgroup on, `grid` workgroups each; a workgroup keeps its role for its lifetime (a launch of one bin:
+// one role)
+constexpr uint32_t kEmMaxRoles = 6;
+struct EmRoles {
+    uint32_t variants = 0;
+    uint32_t grid = 0;   // workgroups per role: the launch has variants * grid
+    uint32_t bin[kEmMaxRoles] = {};
+};
 
 struct EmSolvePlan {
     EmFillPlan fill;
@@ -276,13 +296,23 @@ inline uint32_t emLaunchGrid(const EmSolveShape & s, const EmSolveKnobs & knobs,
 
 // The bins are independent, so their tails (a small problem that needs thousands of iterations, a giant one with
 // many rows) should overlap — but only as many kernels run side by side as the runtime has hardware queues.
-// One persistent launch per kernel variant; chains of launches that share a stream run one after the other: balanced by
-// the kernels' usual durations.
-// (the default) the register-resident bins in one launch, first — they are the long ones —, the others balanced over the side
-// streams: with six side streams everybody has a stream of its own, with three (the contexts of the batch pipeline) the launch of
+// Default-constructed knobs: one persistent launch per kernel variant; chains of launches that share a stream run one after the
+// other: balanced by the kernels' usual durations.  The register-resident bins in one launch, first — they are the long
+// ones —, the others balanced over the side streams: with six side streams everybody has a stream of its own, with three (the contexts of the batch pipeline) the launch of
 // the register bins (1.3 ms on the configs[2] batch) and <1024,true> (0.2) share one, <64,true> (0.9) and <256,true> (0.5)
 // another, and <1024,false> (0.8) and the wide one have the third.
 // RPVG_HIP_EM_REGISTER_LAUNCHES=5: a launch per register bin; with eight hardware queues the first three get streams of their own.
+// EmSolveKnobs::merged_launches (what the library runs; RPVG_HIP_EM_SEPARATE_LAUNCHES=1 gives the table above): a chain of two
+// launches lasts as long as both, and every launch holds a hardware queue that other batches' streams share, for as long as its
+// slowest problem iterates.  Launches of equal workgroup size therefore share a launch, as the register bins do, and every launch
+// of a side stream has a side stream of its own (0, 1, 2 with three side streams; 3, 5, 4 with six):
+//   64 threads    the register bins and bin 0 (<64,true>), under the LDS of the largest staging tile
+//   256 threads   bin 1 (<256,true>)
+//   1 024 threads bins 7 (<1024,true>), 3 (<1024,false>) and, if possible, 10 (the wide one) under the largest of their LDS
+// A workgroup's role is fixed by its index (EmRoles); the grid is the sum of the roles' grids, which are equal.  <256,false> (bin 2) stays a launch
+// of its own on the main stream: with no launch there at all — bins 1 and 2 in one launch on a side stream — the configs[2]
+// pipeline ran 0.2 ms per batch SLOWER than with this empty launch in place (profiles/em_launches/ab.txt), and a problem reaches
+// bin 2 only from 1 174 columns on, where its vectors would not fit next to bin 1's 40 KB anyway.
 inline EmSolvePlan planEmSolve(const EmSolveShape & s, const EmSolveKnobs & knobs) {
     EmSolvePlan p;
     p.fill = planEmFill(s, knobs);
@@ -305,6 +335,16 @@ inline EmSolvePlan planEmSolve(const EmSolveShape & s, const EmSolveKnobs & knob
     auto add = [&p](const uint32_t bin, const EmVariant v, const uint32_t grid, const size_t lds, const int stream) {
         p.launches[p.num_launches++] = EmLaunch{bin, v, grid, lds, stream};
     };
+    if (knobs.one_register_launch && knobs.merged_launches) {
+        const bool own = s.side_streams >= kEmSideStreams;
+        const uint32_t wave_roles = (p.with_32_columns ? 5u : 3u) + 1u;
+        add(kRegisterKernelIndex, EmVariant::kWaveBins, g2 * wave_roles, emRegisterLdsBytes(4, 16), own ? 3 : 0);
+        add(2, EmVariant::kSparse256Streamed, g1, lds_256, kEmMainStream);
+        add(1, EmVariant::kSparse256Resident, g2, 40 * 1024, own ? 5 : 1);
+        add(kSparse1024Bins[0], EmVariant::kSparse1024Bins, g1 * (p.wide_possible ? 3u : 2u), std::max(kSparse1024ResidentLds, std::max(lds_1024, lds_wide)),
+            own ? 4 : 2);
+        return p;
+    }
     if (knobs.one_register_launch) {
         const bool own = s.side_streams >= kEmSideStreams;
         add(kRegisterKernelIndex, EmVariant::kRegisterBins, g2, emRegisterLdsBytes(4, 16), own ? 3 : 0);  // (the largest staging tile: 4 x 16 = 2 x 32)
@@ -332,6 +372,25 @@ inline EmSolvePlan planEmSolve(const EmSolveShape & s, const EmSolveKnobs & knob
     }
     if (p.wide_possible) add(kEmWideBin, EmVariant::kSparseWide, g1, lds_wide, s_reg2);
     return p;
+}
+
+// the roles of a row of the plan's table (a row of one bin: that bin with the row's grid)
+inline EmRoles emLaunchRoles(const EmSolvePlan & p, const EmLaunch & l) {
+    EmRoles r;
+    const uint32_t register_bins = p.with_32_columns ? 5u : 3u;
+    switch (l.variant) {
+        case EmVariant::kRegisterBins:   // (its grid is the grid per bin)
+        case EmVariant::kWaveBins:
+            for (uint32_t v = 0; v < register_bins; ++v) r.bin[r.variants++] = kRegisterBins[v];
+            if (l.variant == EmVariant::kWaveBins) r.bin[r.variants++] = kWaveSparseBin;
+            break;
+        case EmVariant::kSparse1024Bins:
+            for (uint32_t v = 0; v < (p.wide_possible ? 3u : 2u); ++v) r.bin[r.variants++] = kSparse1024Bins[v];
+            break;
+        default: r.bin[r.variants++] = l.bin; break;
+    }
+    r.grid = l.variant == EmVariant::kRegisterBins ? l.grid : l.grid / r.variants;
+    return r;
 }
 
 }  // namespace rpvg_em

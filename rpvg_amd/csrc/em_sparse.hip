@@ -18,11 +18,15 @@
 //      then emOrderKernel: the histogram becomes offsets, the problems are listed bin by bin, large first
 //   2. queueEmCollapse        (with a collapse precision) readCollapseProbabilityMatrix on the problems' rows, on the
 //                             collapse stream (row_collapse.hip); the EM reads the merged read counts
-//   3. queueEmLaunches        one persistent launch per kernel variant, from the plan's table, on the side streams:
-//        emSparseKernel<BLOCK>  ONE workgroup per problem runs the whole EM loop on the GPU: abundance vector a[] and the
+//   3. queueEmLaunches        the persistent launches of the plan's table, on the side streams — the bins of 64 and of 1 024
+//                             threads in one launch each, whose workgroups serve one size bin for their lifetime
+//                             (RPVG_HIP_EM_SEPARATE_LAUNCHES=1: one launch per kernel variant):
+//        emSparseProblem<BLOCK> ONE workgroup per problem runs the whole EM loop on the GPU: abundance vector a[] and the
 //                               M-step accumulators t[] live in LDS, the problem's CSR is resident in LDS or streams from
 //                               L2/HBM every iteration, convergence is decided on-device
-//        emRegisterKernel       small problems dense in the registers of one wavefront
+//                               (emSparseRolesKernel: bins 7, 3 and 10 in one launch; emSparseKernel: one bin)
+//        emRegisterProblem      small problems dense in the registers of one wavefront
+//                               (emRegisterKernel: the register bins and, merged, bin 0's sparse problems of one wavefront)
 //   4. queueEmGridAndJoin     the problems of the grid bin, described to the host and solved over the whole GPU (em_grid.hip),
 //                             and the join of the side streams
 //
@@ -802,14 +806,53 @@ __device__ __forceinline__ void emSparseProblem(const EmLaunchArgs & args, const
     }
 }
 
+// the bin of a role (selects, not an indexed read: the table stays in the launch's arguments)
+__device__ __forceinline__ uint32_t roleBin(const EmRoles & roles, const uint32_t role) {
+    uint32_t bin = roles.bin[0];
+#pragma unroll
+    for (uint32_t v = 1; v < kEmMaxRoles; ++v) bin = v == role ? roles.bin[v] : bin;
+    return bin;
+}
+
+// workgroup `block` of the ones that serve args.bin (the whole workgroup: every barrier inside is uniform over it)
+template <int BLOCK, bool RESIDENT, bool WIDE = false>
+__device__ __forceinline__ void emSparseBin(const EmLaunchArgs & args, const uint32_t block, unsigned char * smem_raw, uint32_t * next_slot) {
+    if (block >= args.queues->bin_count[args.bin]) return;  // more workgroups than the bin has problems
+    for (uint32_t p = nextProblem<BLOCK>(args, next_slot); p != UINT32_MAX; p = nextProblem<BLOCK>(args, next_slot)) {
+        emSparseProblem<BLOCK, RESIDENT, WIDE>(args, p, smem_raw);
+        if (BLOCK == 64) __syncthreads();  // (the LDS is reused; wider workgroups meet in nextProblem)
+    }
+}
+
 template <int BLOCK, bool RESIDENT, bool WIDE = false>
 __global__ __launch_bounds__(BLOCK) void emSparseKernel(const EmLaunchArgs args) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ uint32_t next_slot;
-    if (blockIdx.x >= args.queues->bin_count[args.bin]) return;  // more workgroups than the bin has problems
-    for (uint32_t p = nextProblem<BLOCK>(args, &next_slot); p != UINT32_MAX; p = nextProblem<BLOCK>(args, &next_slot)) {
-        emSparseProblem<BLOCK, RESIDENT, WIDE>(args, p, smem_raw);
-        if (BLOCK == 64) __syncthreads();  // (the LDS is reused; wider workgroups meet in nextProblem)
+    emSparseBin<BLOCK, RESIDENT, WIDE>(args, blockIdx.x, smem_raw, &next_slot);
+}
+
+// The bins of 1 024 threads in ONE launch (the plan's merged launches: emLaunchRoles): a workgroup serves one bin for its lifetime —
+// role blockIdx.x % variants, as that bin's workgroup blockIdx.x / variants — with that bin's code, guard and cursor: no workgroup mixes roles,
+// so every barrier stays uniform over its workgroup, and a problem's arithmetic is what its own launch did.  Bins 7 and 3, and with
+// WITH_WIDE bin 10 — a kernel of its own, for the solves that can have such a problem: the wide variant's code costs the others
+// registers (profiles/em_launches/resource_usage.txt).
+template <bool WITH_WIDE>
+__global__ __launch_bounds__(1024) void emSparseRolesKernel(const EmLaunchArgs launch_args, const EmRoles roles) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    __shared__ uint32_t next_slot;
+    const uint32_t role = blockIdx.x % roles.variants, block = blockIdx.x / roles.variants;
+    EmLaunchArgs args = launch_args;
+    const uint32_t bin = roleBin(roles, role);
+    // (the bin a constant inside each role's code, as it is a launch argument in a launch of its own)
+    if (bin == kSparse1024Bins[0]) {
+        args.bin = kSparse1024Bins[0];
+        emSparseBin<1024, true>(args, block, smem_raw, &next_slot);
+    } else if (bin == kSparse1024Bins[1]) {
+        args.bin = kSparse1024Bins[1];
+        emSparseBin<1024, false>(args, block, smem_raw, &next_slot);
+    } else if (WITH_WIDE && bin == kSparse1024Bins[2]) {
+        args.bin = kSparse1024Bins[2];
+        emSparseBin<1024, false, true>(args, block, smem_raw, &next_slot);
     }
 }
 
@@ -823,6 +866,20 @@ hipError_t launchEm(const EmLaunchArgs & args, uint32_t grid, size_t lds, hipStr
         if (e != hipSuccess) return e;
     }
     emSparseKernel<BLOCK, RESIDENT, WIDE><<<dim3(grid), dim3(BLOCK), lds, stream>>>(args);
+    return hipGetLastError();
+}
+
+// `lds`: the largest of the roles' dynamic LDS
+template <bool WITH_WIDE>
+hipError_t launchEmRoles(const EmLaunchArgs & args, const EmRoles & roles, size_t lds, hipStream_t stream) {
+    const uint32_t grid = roles.variants * roles.grid;
+    if (grid == 0) return hipSuccess;
+    if (lds > kLdsOptIn) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&emSparseRolesKernel<WITH_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    emSparseRolesKernel<WITH_WIDE><<<dim3(grid), dim3(1024), lds, stream>>>(args, roles);
     return hipGetLastError();
 }
 
@@ -1081,19 +1138,23 @@ __global__ __launch_bounds__(64) void emRegisterBinKernel(const EmLaunchArgs arg
 // — a millisecond per bin on the configs[2] batch, on a few wavefronts —, and launches that share a stream, or, with batches
 // in flight, a hardware queue with other contexts' streams, run one after the other: five bins in five launches were 4.1 ms
 // of queue time per batch, in one launch they are 1.3.
+// The wave launch of the plan's merged launches adds bin 0 — the LDS-resident sparse problems of one wavefront, emSparseProblem<64,
+// true> — as one more role: its 8 KB lie inside the staging tile.  (`roles`: emLaunchRoles.)
 // (kRegisterBins, kRegisterKernelIndex: em_plan.hpp)
 
-__global__ __launch_bounds__(64) void emRegisterKernel(const EmLaunchArgs launch_args, const uint32_t variants) {
+__global__ __launch_bounds__(64) void emRegisterKernel(const EmLaunchArgs launch_args, const EmRoles roles) {
     extern __shared__ __attribute__((aligned(16))) double reg_lds[];
     EmLaunchArgs args = launch_args;
-    const uint32_t variant = blockIdx.x % variants, block = blockIdx.x / variants;
-    args.bin = kRegisterBins[variant];
-    switch (variant) {
-        case 0: emRegisterBin<4, 16>(args, block, reg_lds); break;
-        case 1: emRegisterBin<1, 16>(args, block, reg_lds); break;
-        case 2: emRegisterBin<2, 16>(args, block, reg_lds); break;
-        case 3: emRegisterBin<1, 32>(args, block, reg_lds); break;
-        default: emRegisterBin<2, 32>(args, block, reg_lds); break;
+    const uint32_t role = blockIdx.x % roles.variants, block = blockIdx.x / roles.variants;
+    args.bin = roleBin(roles, role);
+    switch (args.bin) {
+        case 6: emRegisterBin<4, 16>(args, block, reg_lds); break;
+        case 4: emRegisterBin<1, 16>(args, block, reg_lds); break;
+        case 5: emRegisterBin<2, 16>(args, block, reg_lds); break;
+        case 8: emRegisterBin<1, 32>(args, block, reg_lds); break;
+        case 9: emRegisterBin<2, 32>(args, block, reg_lds); break;
+        case kWaveSparseBin: emSparseBin<64, true>(args, block, reinterpret_cast<unsigned char *>(reg_lds), nullptr); break;
+        default: break;
     }
 }
 
@@ -1104,11 +1165,11 @@ hipError_t launchEmRegister(const EmLaunchArgs & args, uint32_t grid, size_t lds
     return hipGetLastError();
 }
 
-// grid_per_bin workgroups for each of the bins (three without problems of more than 16 columns, else five)
-hipError_t launchEmRegisterBins(const EmLaunchArgs & args, const uint32_t grid_per_bin, const bool with_32_columns, const size_t lds, hipStream_t stream) {
-    if (grid_per_bin == 0) return hipSuccess;
-    const uint32_t variants = with_32_columns ? 5u : 3u;
-    emRegisterKernel<<<dim3(grid_per_bin * variants), dim3(64), lds, stream>>>(args, variants);
+// the register bins (three without problems of more than 16 columns, else five), and bin 0 in the wave launch: the roles' grids
+hipError_t launchEmRegisterBins(const EmLaunchArgs & args, const EmRoles & roles, const size_t lds, hipStream_t stream) {
+    const uint32_t grid = roles.variants * roles.grid;
+    if (grid == 0) return hipSuccess;
+    emRegisterKernel<<<dim3(grid), dim3(64), lds, stream>>>(args, roles);
     return hipGetLastError();
 }
 
@@ -1147,6 +1208,9 @@ EmSolveKnobs emSolveKnobs() {
     k.rule.grid_min_work = emGridMinWork();  // RPVG_HIP_EM_GRID_MIN_WORK
     k.no_collapse = k.no_collapse || RPVG_EXPERIMENT_ENV("RPVG_HIP_NO_COLLAPSE") != nullptr;
     k.no_fused_dense = std::getenv("RPVG_HIP_NO_FUSED_DENSE") != nullptr;
+    // the bins of 64 and of 1 024 threads in one launch each (planEmSolve); RPVG_HIP_EM_SEPARATE_LAUNCHES=1: a launch per kernel variant (A/B and tests)
+    const char * separate = std::getenv("RPVG_HIP_EM_SEPARATE_LAUNCHES");
+    k.merged_launches = !(separate && std::atoi(separate) != 0);
     const char * copies = std::getenv("RPVG_HIP_EM_COPIES");
     k.register_copies = copies ? std::atoi(copies) != 0 : true;
     // (storage by the bound up to this budget; by default two fifths of the free device memory and at most 32 GiB: prepareHostProblems)
@@ -1390,7 +1454,11 @@ int queueEmLaunches(rpvg_hip_ctx * ctx, const EmSolvePlan & plan, EmLaunchArgs &
             case EmVariant::kSparse256Streamed: e = launchEm<256, false>(args, l.grid, l.lds, on); break;
             case EmVariant::kSparse1024Streamed: e = launchEm<1024, false>(args, l.grid, l.lds, on); break;
             case EmVariant::kSparseWide: e = launchEm<1024, false, true>(args, l.grid, l.lds, on); break;
-            case EmVariant::kRegisterBins: e = launchEmRegisterBins(args, l.grid, plan.with_32_columns, l.lds, on); break;
+            case EmVariant::kRegisterBins:
+            case EmVariant::kWaveBins: e = launchEmRegisterBins(args, emLaunchRoles(plan, l), l.lds, on); break;
+            case EmVariant::kSparse1024Bins:
+                e = plan.wide_possible ? launchEmRoles<true>(args, emLaunchRoles(plan, l), l.lds, on) : launchEmRoles<false>(args, emLaunchRoles(plan, l), l.lds, on);
+                break;
             case EmVariant::kRegister1x16: e = launchEmRegister<1, 16>(args, l.grid, l.lds, on); break;
             case EmVariant::kRegister2x16: e = launchEmRegister<2, 16>(args, l.grid, l.lds, on); break;
             case EmVariant::kRegister4x16: e = launchEmRegister<4, 16>(args, l.grid, l.lds, on); break;
@@ -1714,6 +1782,8 @@ extern "C" const char * rpvg_hip_em_kernel_name(int index) {
     // (the size bins of rpvg_hip_em_solve, in bin order)
     // (emRegisterKernel: the five register-resident bins — <1,16> <2,16> <4,16> <1,32> <2,32> — in one launch, under the first
     // one's index; with RPVG_HIP_EM_REGISTER_LAUNCHES=5 every bin has its own launch of emRegisterBinKernel and its own index)
+    // (merged launches — the bins of 64 and of 1 024 threads — keep the names: a slot's problems and iterations are its bin's, and
+    // the device time of a launch stands under one of its bins' slots, 4 and 7: docs/design/kernels-em.md)
     static const char * const names[RPVG_HIP_EM_KERNELS] = {
         "emSparseKernel<64,true>", "emSparseKernel<256,true>", "emSparseKernel<256,false>", "emSparseKernel<1024,false>",
         "emRegisterBinKernel<1,16>", "emRegisterBinKernel<2,16>", "emRegisterBinKernel<4,16>", "emSparseKernel<1024,true>",
