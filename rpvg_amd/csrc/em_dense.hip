@@ -521,15 +521,13 @@ int emDenseIterate(rpvg_hip_ctx * ctx, const char * who, DenseEmRun & run) {
     DeviceBuffer<double> & d_a = run.d_a;
 
     const uint32_t cus = ctx->props.multiProcessorCount;
-    const bool wide = C > 256;  // row split over the block's waves (emDenseAccumWideKernel)
-    // enough waves to cover HBM latency, few enough partial vectors to reduce cheaply
-    uint32_t blocks_per_cu = wide ? 4 : 2;
-    if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_DENSE_BLOCKS_PER_CU")) blocks_per_cu = std::max(1, std::atoi(env));
-    uint32_t grid = wide ? std::min<uint64_t>((num_rows + 1) / 2, static_cast<uint64_t>(cus) * blocks_per_cu)
-                         : std::min<uint64_t>((num_rows + 3) / 4, static_cast<uint64_t>(cus) * blocks_per_cu);
-    grid = std::max<uint32_t>(grid, 1);
-    const uint32_t partial_ld = wide ? ((C + 511) / 512) * 512 : ((C + 1) & ~1u);
-    const uint32_t reduce_slices = 16;
+    // wide or narrow kernel, its chunk count, workgroups, strides: planEmDense (em_plan.hpp)
+    uint32_t blocks_per_cu_knob = 0;
+    if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_DENSE_BLOCKS_PER_CU")) blocks_per_cu_knob = static_cast<uint32_t>(std::max(1, std::atoi(env)));  // A/B knob
+    const EmDensePlan plan = planEmDense(C, num_rows, cus, blocks_per_cu_knob);
+    const bool wide = plan.wide;  // row split over the block's waves (emDenseAccumWideKernel)
+    const uint32_t grid = plan.grid, partial_ld = plan.partial_ld;
+    const uint32_t reduce_slices = kEmDenseReduceSlices;
 
     DeviceBuffer<double> d_partials, d_reduced, d_t;
     if (wide) RPVG_HIP_CHECK(d_reduced.alloc(static_cast<size_t>(reduce_slices) * partial_ld));
@@ -551,8 +549,8 @@ int emDenseIterate(rpvg_hip_ctx * ctx, const char * who, DenseEmRun & run) {
     }
     fillConstantKernel<<<dim3((C + 255) / 256), dim3(256), 0, st>>>(d_a.ptr, C, a0);
 
-    const int nchunk = (C + 127) / 128;
-    const uint32_t chunk_its = 8;  // iterations queued between looks at the control word
+    const int nchunk = plan.nchunk;
+    const uint32_t chunk_its = plan.chunk_its;  // iterations queued between looks at the control word
     DenseControl & h_ctl = run.control;
     h_ctl = DenseControl{};
     uint32_t queued = 0;
@@ -562,7 +560,7 @@ int emDenseIterate(rpvg_hip_ctx * ctx, const char * who, DenseEmRun & run) {
         for (uint32_t i = 0; i < n; ++i) {
             const int span = ctx->spanBegin(FAM_EM_DENSE);
             if (wide) {
-                const int wchunk = (C + 511) / 512;
+                const int wchunk = nchunk;
                 if (wchunk <= 1) emDenseAccumWideKernel<1><<<dim3(grid), dim3(256), 0, st>>>(device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
                 else if (wchunk <= 2) emDenseAccumWideKernel<2><<<dim3(grid), dim3(256), 0, st>>>(device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
                 else if (wchunk <= 3) emDenseAccumWideKernel<3><<<dim3(grid), dim3(256), 0, st>>>(device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
@@ -585,11 +583,9 @@ int emDenseIterate(rpvg_hip_ctx * ctx, const char * who, DenseEmRun & run) {
                 emDenseControlKernel<<<dim3(1), dim3(1), 0, st>>>(d_ctl.ptr, max_em_its);
                 continue;
             }
+            // (the narrow kernel serves C <= 256: one or two chunks of 128 columns — the wide kernel takes everything above)
             if (nchunk <= 1) launchAccum<1>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
-            else if (nchunk <= 2) launchAccum<2>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
-            else if (nchunk <= 4) launchAccum<4>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
-            else if (nchunk <= 8) launchAccum<8>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
-            else launchAccum<16>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
+            else launchAccum<2>(grid, st, device_matrix, num_rows, C, ld, device_counts, d_a.ptr, d_partials.ptr, partial_ld, d_ctl.ptr);
             ctx->spanEnd(span);
             if (sharded) {
                 emDenseReducePartialsKernel<<<col_grid, dim3(256), 0, st>>>(C, grid, partial_ld, d_partials.ptr, d_t.ptr, d_ctl.ptr, d_t.ptr + C);

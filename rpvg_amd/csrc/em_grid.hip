@@ -274,11 +274,16 @@ hipError_t launchAccumVariant(const GridAccumArgs & args, const uint32_t grid, c
     return hipSuccess;
 }
 
-// lanes per row by the mean row length
-inline int gridRowLanes(const uint32_t rows, const uint32_t entries) {
-    if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_GRID_ROW_LANES")) return std::atoi(env);  // A/B knob: 1, 4, 16, 64
-    const double mean = static_cast<double>(entries) / std::max(1u, rows);
-    return mean < 6.0 ? 1 : mean < 24.0 ? 4 : mean < 96.0 ? 16 : 64;
+static_assert(kGridBlock == static_cast<int>(kEmGridBlock) && kUpdateBlock == static_cast<int>(kEmGridUpdateBlock) &&
+                  kUpdateColumns == static_cast<int>(kEmGridUpdateColumns),
+              "em_plan.hpp restates these");
+
+// the A/B knobs of the launch shape (planEmGridCsr, em_plan.hpp, takes them as numbers)
+inline EmGridCsrKnobs gridCsrKnobs() {
+    EmGridCsrKnobs k;
+    if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_GRID_ROW_LANES")) k.row_lanes = std::atoi(env);  // 1, 4, 16, 64
+    if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_GRID_BLOCKS")) k.blocks = std::max<uint64_t>(1, std::strtoull(env, nullptr, 10));
+    return k;
 }
 
 hipError_t launchAccum(const int lanes, const GridAccumArgs & args, const uint32_t grid, const size_t lds, hipStream_t st) {
@@ -424,20 +429,13 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
     auto start = [&](CsrRun & r, const EmGridProblem & d) -> hipError_t {
         const uint32_t p = d.problem, C = d.columns, rows = d.rows;
         r.d = &d;
-        r.row_lanes = gridRowLanes(rows, d.entries);
-        // workgroups: enough to fill the GPU, few enough that the partial vectors (written and read once per iteration,
-        // 16 B per column and workgroup) stay below the CSR's own bytes
-        const uint64_t csr_bytes = 12ull * d.entries + 20ull * rows;
-        const uint64_t slots = static_cast<uint64_t>(kGridBlock / r.row_lanes);
-        uint64_t blocks = (static_cast<uint64_t>(rows) + slots - 1) / slots;
-        blocks = std::min<uint64_t>(blocks, static_cast<uint64_t>(cus) * (r.row_lanes == 1 ? 2 : 4));
-        blocks = std::min<uint64_t>(blocks, std::max<uint64_t>(16, csr_bytes / (16ull * C)));
-        if (const char * env = RPVG_EXPERIMENT_ENV("RPVG_HIP_EM_GRID_BLOCKS")) blocks = std::max<uint64_t>(1, std::strtoull(env, nullptr, 10));  // A/B knob
-        blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, rows));
-        const uint32_t rows_per_block = static_cast<uint32_t>((static_cast<uint64_t>(rows) + blocks - 1) / blocks);
-        r.grid = (rows + rows_per_block - 1) / rows_per_block;
-        const uint32_t partial_ld = (C + 63) & ~63u;
-        r.lds = sizeof(double) * (1 + kGridBlock / 64) * static_cast<size_t>(C);
+        // lanes per row, workgroups, rows per workgroup, strides, LDS and the chunk of queued iterations: planEmGridCsr (em_plan.hpp)
+        const EmGridCsrPlan plan = planEmGridCsr(C, rows, d.entries, cus, gridCsrKnobs());
+        r.row_lanes = plan.lanes;
+        const uint32_t rows_per_block = plan.rows_per_block;
+        r.grid = plan.grid;
+        const uint32_t partial_ld = plan.partial_ld;
+        r.lds = plan.lds;
         hipError_t err = r.d_a.alloc(C);
         if (err == hipSuccess) err = r.d_partials.alloc(static_cast<size_t>(r.grid) * partial_ld);
         if (err == hipSuccess) err = r.d_ctl.alloc(1);
@@ -468,12 +466,8 @@ int runEmGridProblems(rpvg_hip_ctx * ctx, hipStream_t st, const EmGridProblem * 
         r.ua.max_rel_em_conv = max_rel_em_conv;
         r.ua.max_em_its = max_em_its;
         r.ua.ctl = r.d_ctl.ptr;
-        r.update_grid = (C + kUpdateColumns - 1) / kUpdateColumns;
-        // Iterations in chunks, two chunks in flight: the control word of chunk k is looked at while chunk k + 1 runs.
-        // A short problem's iteration is a few microseconds, a giant one's milliseconds: the chunk holds about half a
-        // millisecond of the problem's streaming time at the HBM rate, 4 to 32 iterations.
-        const double iteration_us = static_cast<double>(csr_bytes) / 4.0e6 + 8.0;
-        r.chunk_its = static_cast<uint32_t>(std::min(32.0, std::max(4.0, 500.0 / iteration_us)));
+        r.update_grid = plan.update_grid;
+        r.chunk_its = plan.chunk_its;  // (two chunks in flight: the control word of chunk k is looked at while chunk k + 1 runs)
         if (pinnedAlloc(reinterpret_cast<void **>(&r.h_ctl), 2 * sizeof(EmGridControl)) != hipSuccess) return hipErrorOutOfMemory;
         err = hipEventCreateWithFlags(&r.looked[0], hipEventDisableTiming);
         if (err == hipSuccess) err = hipEventCreateWithFlags(&r.looked[1], hipEventDisableTiming);

@@ -133,6 +133,84 @@ RPVG_PLAN_FN bool emDenseRule(const uint32_t columns, const uint32_t rows, const
     return 8ull * rows * ld <= 12ull * entries + 20ull * rows;
 }
 
+// ---- the launch shapes of the whole-GPU EM (em_grid.hip: runEmGridProblems; em_dense.hip: emDenseIterate) ----------------
+// Which kernel variant runs, over how many workgroups, with which strides and how many queued iterations per look at the control
+// word: numbers of the problem's sizes and the GPU's CUs alone.  Both hosts launch what these say (tests/cpp/em_grid_plan_check.cpp,
+// tests/em_grid_cases.py restates them).
+constexpr uint32_t kEmGridBlock = 256;          // emGridAccumKernel: four wavefronts
+constexpr uint32_t kEmGridUnroll = 4;           // rows a row slot walks at a time
+constexpr uint32_t kEmGridUpdateBlock = 1024;   // emGridUpdateKernel: kEmGridUpdateColumns columns x 64 slices of the partials
+constexpr uint32_t kEmGridUpdateColumns = 16;
+constexpr uint32_t kEmDenseChunkIts = 8;        // em_dense.hip: iterations queued between looks at the control word
+constexpr uint32_t kEmDenseReduceSlices = 16;   // the wide kernel's partials meet in this many slices first
+
+// lanes per row of emGridAccumKernel by the mean row length
+inline int emGridRowLanes(const uint32_t rows, const uint32_t entries) {
+    const double mean = static_cast<double>(entries) / std::max(1u, rows);
+    return mean < 6.0 ? 1 : mean < 24.0 ? 4 : mean < 96.0 ? 16 : 64;
+}
+
+struct EmGridCsrKnobs {     // A/B knobs of an EXPERIMENTS=1 build; 0: the rule
+    int row_lanes = 0;      // RPVG_HIP_EM_GRID_ROW_LANES: 1, 4, 16, 64
+    uint64_t blocks = 0;    // RPVG_HIP_EM_GRID_BLOCKS
+};
+struct EmGridCsrPlan {
+    int lanes = 1;                 // emGridAccumKernel<lanes, kEmGridUnroll>
+    uint32_t grid = 0;             // workgroups = partial vectors
+    uint32_t rows_per_block = 0;   // a workgroup's contiguous rows (the last workgroup: what is left)
+    uint32_t partial_ld = 0;       // doubles between two partial vectors
+    uint32_t update_grid = 0;      // workgroups of emGridUpdateKernel
+    size_t lds = 0;                // dynamic LDS of the pass
+    uint32_t chunk_its = 0;        // iterations queued per chunk (two chunks in flight)
+};
+inline EmGridCsrPlan planEmGridCsr(const uint32_t C, const uint32_t rows, const uint32_t entries, const uint32_t cus, const EmGridCsrKnobs & knobs = EmGridCsrKnobs()) {
+    EmGridCsrPlan p;
+    p.lanes = knobs.row_lanes != 0 ? knobs.row_lanes : emGridRowLanes(rows, entries);
+    // workgroups: enough to fill the GPU, few enough that the partial vectors (written and read once per iteration,
+    // 16 B per column and workgroup) stay below the CSR's own bytes
+    const uint64_t csr_bytes = 12ull * entries + 20ull * rows;
+    const uint64_t slots = static_cast<uint64_t>(kEmGridBlock) / static_cast<uint64_t>(p.lanes);
+    uint64_t blocks = (static_cast<uint64_t>(rows) + slots - 1) / slots;
+    blocks = std::min<uint64_t>(blocks, static_cast<uint64_t>(cus) * (p.lanes == 1 ? 2 : 4));
+    blocks = std::min<uint64_t>(blocks, std::max<uint64_t>(16, csr_bytes / (16ull * C)));
+    if (knobs.blocks != 0) blocks = knobs.blocks;
+    blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, rows));
+    p.rows_per_block = static_cast<uint32_t>((static_cast<uint64_t>(rows) + blocks - 1) / blocks);
+    p.grid = (rows + p.rows_per_block - 1) / p.rows_per_block;
+    p.partial_ld = (C + 63) & ~63u;
+    p.update_grid = (C + kEmGridUpdateColumns - 1) / kEmGridUpdateColumns;
+    p.lds = emGridLdsBytes(C);
+    // Iterations in chunks, two chunks in flight: the control word of chunk k is looked at while chunk k + 1 runs.
+    // A short problem's iteration is a few microseconds, a giant one's milliseconds: the chunk holds about half a
+    // millisecond of the problem's streaming time at the HBM rate, 4 to 32 iterations.
+    const double iteration_us = static_cast<double>(csr_bytes) / 4.0e6 + 8.0;
+    p.chunk_its = static_cast<uint32_t>(std::min(32.0, std::max(4.0, 500.0 / iteration_us)));
+    return p;
+}
+
+struct EmDensePlan {
+    bool wide = false;            // emDenseAccumWideKernel (a row split over the workgroup's four wavefronts) from 257 columns
+    int nchunk = 1;               // narrow: emDenseAccumKernel<nchunk>, 128 columns each; wide: emDenseAccumWideKernel<nchunk>, 512 columns each
+    uint32_t grid = 0;            // workgroups = partial vectors
+    uint32_t partial_ld = 0;
+    uint32_t reduce_slices = 0;   // wide: emDenseReducePartialsKernel's slices; narrow: none, the update reads the partials itself
+    uint32_t chunk_its = kEmDenseChunkIts;
+};
+// blocks_per_cu_knob: RPVG_HIP_DENSE_BLOCKS_PER_CU (A/B knob; 0: the rule)
+inline EmDensePlan planEmDense(const uint32_t C, const uint64_t rows, const uint32_t cus, const uint32_t blocks_per_cu_knob = 0) {
+    EmDensePlan p;
+    p.wide = C > 256;
+    // enough waves to cover HBM latency, few enough partial vectors to reduce cheaply
+    const uint32_t blocks_per_cu = blocks_per_cu_knob != 0 ? blocks_per_cu_knob : (p.wide ? 4u : 2u);
+    const uint64_t rows_per_trip = p.wide ? 2 : 4;   // wide: a workgroup takes two rows per trip; narrow: a row per wavefront
+    p.grid = static_cast<uint32_t>(std::min<uint64_t>((rows + rows_per_trip - 1) / rows_per_trip, static_cast<uint64_t>(cus) * blocks_per_cu));
+    p.grid = std::max<uint32_t>(p.grid, 1);
+    p.nchunk = p.wide ? static_cast<int>((C + 511) / 512) : static_cast<int>((C + 127) / 128);
+    p.partial_ld = p.wide ? ((C + 511) / 512) * 512 : ((C + 1) & ~1u);
+    p.reduce_slices = p.wide ? kEmDenseReduceSlices : 0;
+    return p;
+}
+
 // ---- the compaction (fillSegmentsKernel, fillDenseRowsKernel) --------------------------------------------
 constexpr uint32_t kLdsMapPaths = 16384;
 constexpr uint32_t kFillSegmentRows = 1024;
@@ -140,6 +218,13 @@ constexpr uint64_t kFillLongRowEntries = 32;   // mean entries per row from whic
 constexpr size_t kFillLongRowLds = kFillSegmentRows * (3 * sizeof(uint32_t) + sizeof(double));
 constexpr size_t kFillDenseLds = kFillSegmentRows * 2 * sizeof(uint32_t);   // + an image of a row per wavefront
 constexpr uint64_t kFillLongRowMinWork = 1ull << 18;
+// Whether the rows of a cluster take a wavefront each in the fill (and may go straight into a dense matrix): by the cluster's OWN rows + entries
+// and mean row length, in a launch that carries the scratch (EmFillPlan::long_row_scratch) — never by what else the call holds.  The two paths add
+// up a row's sum in different orders, so the normalised rows differ in their last bits: a cluster must take the same path in any company
+// (tests/test_hip_em_grid_edges.py: every case in one call, bit-equal to the case alone).
+RPVG_PLAN_FN bool emFillLongRows(const bool scratch, const uint64_t rows, const uint64_t entries) {
+    return scratch && rows + entries >= kFillLongRowMinWork && entries >= kFillLongRowEntries * rows;
+}
 // LDS of the fused build: the column map, the scratch, an image of the widest matrix row for each of the four wavefronts
 RPVG_PLAN_FN size_t emFillDenseLdsBytes(const uint32_t lds_map_paths, const uint64_t widest_ld) {
     return lds_map_paths * sizeof(int32_t) + kFillDenseLds + 4 * static_cast<size_t>(widest_ld) * sizeof(double);

@@ -122,7 +122,7 @@ struct FillArgs {
 // whether the rows of cluster k take a wavefront each in fillSegmentsKernel
 __device__ inline bool fillLongRows(const FillArgs & args, const uint32_t k) {
     const uint64_t c0 = args.cluster_row_off[k], c1 = args.cluster_row_off[k + 1];
-    return args.long_row_scratch && args.row_ent_off[c1] - args.row_ent_off[c0] >= kFillLongRowEntries * (c1 - c0);
+    return emFillLongRows(args.long_row_scratch != 0, c1 - c0, args.row_ent_off[c1] - args.row_ent_off[c0]);  // (em_plan.hpp: the cluster's own size)
 }
 
 template <bool WRITE>

@@ -331,7 +331,7 @@ void launchSplit(const bool lds_cols, const GibbsSplitArgs & args, const uint32_
     }
 }
 
-// lanes per row by the mean row length (em_grid.hip, gridRowLanes: a thread per row below six entries; the sampler has the
+// lanes per row by the mean row length (em_plan.hpp, emGridRowLanes: a thread per row below six entries; the sampler has the
 // two ends of that scale)
 inline int gibbsRowLanes(const uint32_t rows, const uint32_t entries) {
     return static_cast<double>(entries) < 12.0 * std::max(1u, rows) ? 1 : 64;
