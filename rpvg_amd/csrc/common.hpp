@@ -770,7 +770,7 @@ struct rpvg_hip_batch {
     std::unique_ptr<UploadInProgress> upload;  // null: the batch is complete
 };
 
-// Device-resident group matrices (loglik.hip builds them).
+// Device-resident group matrices (group_build.hip builds them, loglik.hip contracts them).
 // bounded_search.hip: the searches of different contexts of one device run one after the other on the device
 void searchGateForget(const rpvg_hip_ctx * ctx);
 

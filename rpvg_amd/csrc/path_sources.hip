@@ -19,7 +19,7 @@
 // consecutive integers) is left to the host's grouping (rpvg_hip_batch::has_source_columns stays false).
 //
 // The columns are laid out by bounds (a cluster has at most as many columns, and lists at most as many paths, as it has
-// incidences), so nothing is sized on the host in between; rpvg_hip_groups_build_from_sources (loglik.hip) gathers the
+// incidences), so nothing is sized on the host in between; rpvg_hip_groups_build_from_sources (group_build.hip) gathers the
 // columns of the clusters it is asked for into the compact arrays the build kernels take.
 
 #include "common.hpp"

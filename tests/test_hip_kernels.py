@@ -791,6 +791,63 @@ def test_matrices_from_path_masks_equal_the_matrices_from_path_lists(hip_ctx, no
         assert np.array_equal(results[0][0], other[0]) and np.array_equal(results[0][1], other[1])
 
 
+@pytest.mark.parametrize("normalise", [True, False])
+def test_one_build_with_matrices_on_all_four_routes_equals_its_matrices_built_alone(hip_ctx, normalise):
+    """One groups() call under the default switches whose matrices take the word, mask, tile and list kernels side by side — four
+    item lists and both kinds of `~0` sentinel in one upload (group_build_plan.hpp) — gives, to the bit, what every matrix gives
+    in a call of its own and what the whole call gives from the list kernels alone (RPVG_HIP_BUILD_MASKS=0): the log-likelihoods
+    of every column and of a fixed set of pairs, and the conditionals.  70 single-path columns on 70 paths: masks; a cluster of
+    1 100 paths (too many for masks) grouped into 40 columns: words, into 100: an LDS tile, into 300: no tile fits; small
+    clusters in between, one of them twice: words."""
+    rng = np.random.default_rng(971)
+    clusters = small_cases.make_batch_clusters(972, n_clusters=3, with_empty=False)
+    clusters.append(small_cases.make_cluster(rng, 1, [70], n_haps=70, n_reads=300))
+    clusters.append(small_cases.make_cluster(rng, 1, [1100], n_haps=1100, n_reads=700))
+    batch = ClusterBatch.from_clusters(clusters)
+    dev = hip_ctx.upload(batch)
+    num_rows = np.diff(batch.cluster_row_off.astype(np.int64))
+    num_paths = np.diff(batch.cluster_path_off.astype(np.int64))
+    single = lambda k: [[p] for p in range(int(num_paths[k]))]
+    modulo = lambda k, G: [[p for p in range(int(num_paths[k])) if p % G == c] for c in range(G)]
+    mats = [4, 0, 3, 4, 1, 0, 4]
+    groups = [modulo(4, 40), single(0), single(3), modulo(4, 100), single(1), single(0), modulo(4, 300)]
+    num_cols = [len(g) for g in groups]
+    # the route of every matrix, from its shape (planGroupBuild): up to 64 columns words; up to 1 024 columns and paths masks;
+    # the rest lists, through a tile of at least 16 rows in 4 096 doubles where there is one
+    def route(m):
+        G, N = num_cols[m], int(num_paths[mats[m]])
+        return "word" if G <= 64 else "mask" if G <= 1024 and N <= 1024 else "tile" if 16 * G <= 4096 else "list"
+    assert [route(m) for m in range(len(mats))] == ["word", "word", "mask", "tile", "word", "word", "list"]
+    assert num_rows[4] > 256 and num_rows[3] > 64  # (more than one work item on every route)
+    requests_m, pairs = [], []
+    for m, G in enumerate(num_cols):
+        for c in range(G):
+            requests_m.append(m)
+            pairs.append([c, (c * 7 + 3) % G])
+    cond_m = [m for m in range(len(mats)) for _ in range(2)]
+    others = [[(5 * i + 1) % num_cols[m]] for i, m in enumerate(cond_m)]
+
+    def results(dg, first, count):  # of the matrices [first, first + count) of the list, which `dg` holds from 0 on
+        keep = [i for i, m in enumerate(requests_m) if first <= m < first + count]
+        req = [requests_m[i] - first for i in keep]
+        cond = [i for i, m in enumerate(cond_m) if first <= m < first + count]
+        return (dg.loglik(req, [[pairs[i][0]] for i in keep], 1.0), dg.loglik(req, [pairs[i] for i in keep], 2.0),
+                np.concatenate(dg.conditionals([cond_m[i] - first for i in cond], [others[i] for i in cond], 2, 2.0, num_cols[first:first + count])))
+
+    together = results(hip_ctx.groups(dev, mats, groups, normalise), 0, len(mats))
+    assert all(np.all(np.isfinite(x)) for x in together)
+    alone = [results(hip_ctx.groups(dev, [mats[m]], [groups[m]], normalise), m, 1) for m in range(len(mats))]
+    os.environ["RPVG_HIP_BUILD_MASKS"] = "0"
+    try:
+        lists = results(hip_ctx.groups(dev, mats, groups, normalise), 0, len(mats))
+    finally:
+        os.environ.pop("RPVG_HIP_BUILD_MASKS", None)
+    for part in range(3):
+        assert np.array_equal(together[part], np.concatenate([a[part] for a in alone]))
+        assert np.array_equal(together[part], lists[part])
+    dev.free()
+
+
 def test_upload_from_counts_of_one_byte_equals_the_upload_from_offsets(hip_ctx):
     """rpvg_cluster_batch::row_grp_count8 / grp_idx_count8 (include/rpvg_batch.h): the groups of every row and the paths of every
     group as one byte each, summed up on the device behind the copy — the same batch as from the offsets (its matrices, through
