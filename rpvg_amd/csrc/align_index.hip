@@ -355,7 +355,7 @@ __global__ void orderedSizesKernel(const uint64_t num_distinct, const uint32_t *
     num_aligns[d] = list_align_off[l + 1] - list_align_off[l];
     const uint64_t ne = list_ent_off[l + 1] - list_ent_off[l];
     num_entries[d] = ne;
-    is_small[d] = ne <= static_cast<uint64_t>(kGroupLanes) ? 1u : 0u;
+    is_small[d] = rpvg_rows_plan::readIsSmall(ne, false) ? 1u : 0u;  // where the rows collapse, fillAlignments lists every read as large
 }
 
 // position of every path in its cluster's ascending member list (src/main.cpp:855-857) and the members in rank order
@@ -648,14 +648,7 @@ extern "C" int rpvg_hip_align_index_finish(rpvg_hip_ctx * ctx, rpvg_hip_align_in
         RPVG_HIP_CHECK(hipGetLastError());
         if (const int rc = sortPairs(st, key.ptr, key_sorted.ptr, list.ptr, list_sorted.ptr, F, static_cast<int>(hash_bits))) return rc;
         runFlagKernel<<<gridFor(F), block, 0, st>>>(F, key_sorted.ptr, run_flag.ptr);
-        {
-            size_t bytes = 0;
-            RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, run_flag.ptr, run_start.ptr, MaxU32(), static_cast<int>(F), st));
-            DeviceBuffer<uint8_t> tmp;
-            RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-            RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(tmp.ptr, bytes, run_flag.ptr, run_start.ptr, MaxU32(), static_cast<int>(F), st));
-            RPVG_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        if (const int rc = inclusiveScan(st, run_flag.ptr, run_start.ptr, MaxU32(), F)) return rc;
         compareWithHeadKernel<<<gridFor(F), block, 0, st>>>(F, v, list_sorted.ptr, run_start.ptr, rep.ptr, differs.ptr);
         RPVG_HIP_CHECK(hipGetLastError());
         if (const int rc = exclusiveSum(st, differs.ptr, differs_pos.ptr, F)) return rc;
@@ -899,11 +892,6 @@ bool alignIndexParts(const rpvg_hip_align_index * ix, AlignIndexParts & parts) {
 }  // namespace rpvg_hip_detail
 
 namespace {
-
-__global__ void iotaKernel(const uint64_t n, uint32_t * __restrict__ out) {
-    const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
-    if (i < n) out[i] = static_cast<uint32_t>(i);
-}
 
 // The lists of a finished index as a resident alignment batch; the path arrays are gathered from device arrays by GLOBAL path
 // (by_path_count may be NULL).  all_large: every read on the list of readRowKernel (collapsing).  The caller holds ctx->mutex.

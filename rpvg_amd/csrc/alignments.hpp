@@ -1,12 +1,13 @@
-// The device-resident alignment batch: made by rpvg_hip_alignments_upload (read_rows.hip) from host arrays and by
+// The device-resident alignment batch: made by rpvg_hip_alignments_upload (alignments.hip) from host arrays and by
 // rpvg_hip_align_index_alignments (align_index.hip) from a finished index; read by the row kernels.
 #ifndef RPVG_HIP_ALIGNMENTS_HPP
 #define RPVG_HIP_ALIGNMENTS_HPP
 
 #include "common.hpp"
+#include "rows_plan.hpp"
 
 namespace rpvg_hip_detail {
-constexpr int kGroupLanes = 16;  // lanes that share a read of at most that many (alignment, path) entries (readRowSmallKernel)
+using rpvg_rows_plan::kGroupLanes;  // lanes that share a read of at most that many (alignment, path) entries (readRowSmallKernel)
 }
 
 // Device-resident alignment batch (validated copy of a rpvg_alignment_batch).

@@ -28,6 +28,37 @@ int exclusiveSum(hipStream_t st, const In * in, Out * out, const uint64_t n) {
     return RPVG_HIP_OK;
 }
 
+template <typename In, typename Out, typename Op>
+int inclusiveScan(hipStream_t st, const In * in, Out * out, const Op op, const uint64_t n) {
+    if (n == 0) return RPVG_HIP_OK;
+    size_t bytes = 0;
+    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, in, out, op, static_cast<int>(n), st));
+    DeviceBuffer<uint8_t> tmp;
+    RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
+    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(tmp.ptr, bytes, in, out, op, static_cast<int>(n), st));
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    return RPVG_HIP_OK;
+}
+
+template <typename In, typename Out>
+int inclusiveSum(hipStream_t st, const In * in, Out * out, const uint64_t n) {
+    if (n == 0) return RPVG_HIP_OK;
+    size_t bytes = 0;
+    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, in, out, static_cast<int>(n), st));
+    DeviceBuffer<uint8_t> tmp;
+    RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
+    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.ptr, bytes, in, out, static_cast<int>(n), st));
+    RPVG_HIP_CHECK(hipStreamSynchronize(st));
+    return RPVG_HIP_OK;
+}
+
+// out[i] = i for i < n (a template so that only the files that queue it hold the kernel)
+template <typename Index>
+__global__ void iotaKernel(const uint64_t n, Index * __restrict__ out) {
+    const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    if (i < n) out[i] = static_cast<Index>(i);
+}
+
 template <typename Key, typename Value>
 int sortPairs(hipStream_t st, const Key * key_in, Key * key_out, const Value * value_in, Value * value_out, const uint64_t n, const int end_bit) {
     if (n == 0) return RPVG_HIP_OK;

@@ -316,17 +316,6 @@ __global__ __launch_bounds__(kBlock) void collapseGroupsKernel(const CollapseArg
     a.out_effective_length[g] = __ddiv_rn(eff_sum, static_cast<double>(count_sum));
 }
 
-int inclusiveMax(hipStream_t st, const uint32_t * in, uint32_t * out, const uint64_t n) {
-    if (n == 0) return RPVG_HIP_OK;
-    size_t bytes = 0;
-    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, in, out, MaxU32(), static_cast<int>(n), st));
-    DeviceBuffer<uint8_t> tmp;
-    RPVG_HIP_CHECK(tmp.alloc(bytes ? bytes : 1));
-    RPVG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(tmp.ptr, bytes, in, out, MaxU32(), static_cast<int>(n), st));
-    RPVG_HIP_CHECK(hipStreamSynchronize(st));
-    return RPVG_HIP_OK;
-}
-
 int bitsFor(uint64_t values) {  // bits that hold 0 .. values - 1
     int bits = 1;
     while (bits < 64 && (values - 1) >> bits) ++bits;
@@ -551,7 +540,7 @@ int rpvg_hip_align_index_name_groups(rpvg_hip_ctx * ctx, const rpvg_hip_align_in
         if (const int rc = sortPairs(st, key.ptr, key_sorted.ptr, position.ptr, position_sorted.ptr, P, 32 + bitsFor(K))) return rc;
         runHeadKernel<unsigned long long><<<gridFor(P), block, 0, st>>>(P, key_sorted.ptr, head.ptr);
         RPVG_HIP_CHECK(hipGetLastError());
-        if (const int rc = inclusiveMax(st, head.ptr, run_head.ptr, P)) return rc;
+        if (const int rc = inclusiveScan(st, head.ptr, run_head.ptr, MaxU32(), P)) return rc;
         firstPositionKernel<<<gridFor(P), block, 0, st>>>(P, position_sorted.ptr, run_head.ptr, first_position.ptr);
         headFlagKernel<<<gridFor(static_cast<uint64_t>(P) + 1), block, 0, st>>>(P, first_position.ptr, is_head.ptr);
         RPVG_HIP_CHECK(hipGetLastError());

@@ -312,6 +312,52 @@ def test_large_cluster_uses_the_global_sort_stages(hip_ctx):
     compare_merged(got_m, ref_m)
 
 
+def cluster_arrays(rows, k):
+    """The rows of cluster k as arrays with offsets relative to the cluster's first row, group and member."""
+    r0, r1 = int(rows.cluster_row_off[k]), int(rows.cluster_row_off[k + 1])
+    g0, g1 = int(rows.row_grp_off[r0]), int(rows.row_grp_off[r1])
+    m0, m1 = int(rows.grp_idx_off[g0]), int(rows.grp_idx_off[g1])
+    return [np.asarray(rows.row_count[r0:r1]), np.asarray(rows.row_noise[r0:r1]), np.asarray(rows.row_grp_off[r0:r1 + 1]) - g0,
+            np.asarray(rows.grp_prob[g0:g1]), np.asarray(rows.grp_idx_off[g0:g1 + 1]) - m0, np.asarray(rows.path_idx[m0:m1])]
+
+
+def test_clusters_of_every_sort_tier_in_one_call(hip_ctx):
+    """One call whose clusters sit on both sides of every edge of the sort's schedule: none, one and two reads (nothing to sort, the
+    smallest network), 2048 (the largest cluster of one workgroup), 2049 and 4096 (two tiles, one merge through global memory), 4097
+    (four tiles, two merges: the 2049 and 4096 clusters sit the second one out) — the two padded lengths apart, with small and empty
+    clusters between them.  Reads as in test_large_cluster_uses_the_global_sort_stages: operator< is a consistent order there and the
+    merged rows are well defined.  Against the oracle, merged and unmerged; and every cluster's merged rows are, bit for bit, those
+    of the cluster built alone: what the other clusters of a launch are does not reach a cluster's network."""
+    sizes = [2049, 1, 2048, 0, 4097, 2, 4096]
+    rng = np.random.default_rng(861)
+    clusters = []
+    for n_reads in sizes:
+        P = 8
+        paths = [dict(effective_length=float(rng.integers(500, 1500)), source_count=1) for _ in range(P)]
+        reads = []
+        for _ in range(n_reads):
+            n = int(rng.integers(1, 5))
+            idx = sorted(int(x) for x in rng.choice(P, size=n, replace=False))
+            reads.append(dict(count=int(rng.integers(1, 4)), min_mapq=int(rng.choice([10, 30, 60])), noise_score=INT32_LOWEST,
+                              aligns=[(int(rng.integers(100, 104)), 100, 10, idx)]))
+        clusters.append(dict(paths=paths, reads=reads))
+    batch = AlignmentBatch.from_clusters(clusters)
+    prm = params(min_noise=1e-4)
+    ref, _ = pyoracle.build_rows(batch, prm, merge=False)
+    ref_m, _ = pyoracle.build_rows(batch, prm, merge=True)
+    assert batch.num_reads == sum(sizes) and ref_m.num_rows < batch.num_reads
+    merged_sizes = np.diff(np.asarray(ref_m.cluster_row_off).astype(np.int64))
+    assert all(1 < m < n for m, n in zip(merged_sizes, sizes) if n > 2)  # merging shortens every cluster that can be, to more than one row
+    got, _, _ = hip_ctx.build_rows(batch, prm, merge=False)
+    compare_unmerged(got, ref)
+    got_m, _, _ = hip_ctx.build_rows(batch, prm, merge=True)
+    compare_merged(got_m, ref_m)
+    for k, cluster in enumerate(clusters):
+        alone, _, _ = hip_ctx.build_rows(AlignmentBatch.from_clusters([cluster]), prm, merge=True)
+        for in_company, by_itself in zip(cluster_arrays(got_m, k), cluster_arrays(alone, 0)):
+            assert in_company.dtype == by_itself.dtype and in_company.tobytes() == by_itself.tobytes(), k
+
+
 def test_rows_feed_the_estimators(hip_ctx):
     """alignment paths -> rows on the GPU -> EM on the GPU == oracle rows -> oracle EM."""
     clusters = make_alignment_clusters(841, n_clusters=8)
