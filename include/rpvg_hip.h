@@ -529,6 +529,93 @@ int rpvg_hip_nested_full_subset_em(rpvg_hip_ctx * ctx, const rpvg_hip_batch * ba
                                    double max_rel_em_conv, double collapse_precision, rpvg_hip_subset_em ** result_out);
 int rpvg_hip_subset_em_get_sets(const rpvg_hip_subset_em * result, rpvg_hip_subset_em_sets_view * view_out);
 
+/* ---- independent haplotype inference: posteriors -> draws -> path subsets -> EM -> weighted merge, in one call: group sizes 1 .. 8 ---- */
+/* NestedPathAbundanceEstimator::inferAbundancesIndependentGroups (src/path_abundance_estimator.cpp:356-426) with exact posteriors.
+ * The unit of the call is the CLUSTER: its transcripts are consecutive matrices of `groups`, each with one column per path of the
+ * transcript (one path per column), normalised and row-collapsed (:379-380).  Per transcript the posteriors of
+ * rpvg_hip_bounded_pair_posteriors (group size 2, min_rel_likelihood = min_hap_prob, :403; the kept pairs in the reference's order,
+ * late losers listed with posterior 0) or rpvg_hip_group_full_posteriors (every other group size; EVERY set is a weight) stay on the
+ * device; a std::discrete_distribution is constructed over them as libstdc++ does (rpvg_amd/csrc/gibbs_streams.hpp: one chain of
+ * additions for the sum, separately rounded quotients, one chain for the partial sums, the last one 1.0; fewer than two sets draw
+ * nothing), and S = floor(1 / min_hap_prob) sets per transcript are drawn from the cluster's std::mt19937 draw for draw (:548-567):
+ * the caller passes the NEXT 624 outputs of each cluster's generator, drawing transcript d of a cluster takes the words
+ * [2 S d, 2 S (d + 1)) of its stream, two per draw, the first one the low part.  Sample slot s of a cluster is the union over its
+ * transcripts of the paths of the set drawn for slot s, sorted (a homozygous path twice); identical samples are one subset whose
+ * weight is the CHAIN of as many additions of 1 / double(S) from 0.0 as samples produced it (:421) — 1 000 of 0.001 give
+ * 1.0000000000000007 —, retained when that weight is >= min_hap_prob (:627-630).  Subsets of a cluster come in lexicographic order
+ * of their path lists; the EM of rpvg_hip_em_solve on every subset's distinct paths and the posterior-weighted merge (:702-749) follow as
+ * in rpvg_hip_nested_full_subset_em.  cluster_noise_count is unclamped and may be a hair negative, as on the host.
+ * The caller moves every cluster's generator past words_consumed[k] words (discard(), or the state words of the view, as with
+ * rpvg_hip_gibbs_sets_view); the call itself moves nothing.  The caveat of the Gibbs sampler holds here too: posteriors that differ
+ * from another implementation's in their last bits can move a draw that falls within an ulp of a partial sum.
+ * Returns RPVG_HIP_ERR_UNSUPPORTED, having changed nothing, with rpvg_hip_last_error naming the reason: group size 0 or above 8;
+ * min_hap_prob below 1/1024 or above 1; a transcript with more than 65 536 sets (one wavefront adds its sums as one chain); a matrix
+ * with no set; a cluster too wide for LDS-resident EM vectors; a batch uploaded without path_group_id; RPVG_HIP_NO_DEVICE_SUBSETS
+ * in the environment (read per call); capacities that did not fit after one retry.  RPVG_HIP_ERR_INVALID when the matrices of one
+ * unit are not of one cluster, and when the columns of a unit's transcripts do not partition the cluster's paths by path_group_id. */
+typedef struct rpvg_hip_independent_spec {
+    uint32_t num_clusters;
+    const uint32_t * matrix_off;      /* [K+1] the transcripts of unit k are the matrices [matrix_off[k], matrix_off[k+1]) of
+                                         `groups`, in findPathGroups order (:473-491); all of one cluster of the batch */
+    uint32_t group_size;              /* 1 .. 8 */
+    const uint32_t * column_counts;   /* path_counts of every column, matrices back to back (group size 2) */
+    const double * log_freq;          /* calcPathLogFrequences of every column (other group sizes) */
+    double min_hap_prob;
+    uint32_t max_em_its; double max_rel_em_conv; double collapse_precision;
+    const uint32_t * generator_words; /* [K x 624] the next 624 outputs of each cluster's std::mt19937 */
+    int32_t keep_draws;               /* tests: keep draw[k][slot][transcript] for rpvg_hip_independent_draws_get */
+} rpvg_hip_independent_spec;
+
+typedef struct rpvg_hip_subset_em_independent_view {
+    uint32_t num_clusters;
+    uint32_t group_size;
+    uint32_t num_samples;          /* S = floor(1 / min_hap_prob)                                                    */
+    const uint64_t * subset_off;   /* [K+1]  as rpvg_hip_subset_em_sets_view with clusters in place of matrices, from here ... */
+    const double * weight;         /* [S]    the chain of sample_count additions of 1 / double(num_samples)          */
+    const uint64_t * path_off;     /* [S+1]                                                                          */
+    const uint32_t * path;         /*        sorted cluster-local paths: group_size per transcript, a homozygous path twice */
+    const uint64_t * col_off;      /* [S+1]                                                                          */
+    const uint32_t * col_path;
+    const double * abundances;
+    const double * noise_count;    /* [S]                                                                            */
+    const double * total_count;    /* [S]                                                                            */
+    const uint32_t * iterations;   /* [S]                                                                            */
+    const uint32_t * set_count;           /* [K]                                                   */
+    const double * cluster_noise_count;   /* [K]                                                   */
+    const uint32_t * set_size;
+    const uint32_t * set_member;
+    const double * set_posterior;
+    const double * set_abundance;  /*        ... to here                                                             */
+    const uint32_t * sample_count;        /* [S]   samples that produced the subset                                  */
+    const uint64_t * words_consumed;      /* [K]   2 x num_samples x (transcripts of the cluster with at least two sets) */
+    const uint32_t * generator_state;     /* [K x 624] as rpvg_hip_gibbs_sets_view::generator_state, for words_consumed >= 624 */
+} rpvg_hip_subset_em_independent_view;
+
+typedef struct rpvg_independent_limits {
+    uint32_t max_group_size;         /* 8 */
+    uint32_t max_samples;            /* 1 024: min_hap_prob >= 1 / 1024 */
+    uint64_t max_transcript_sets;    /* 65 536 */
+    uint32_t words_per_draw;         /* 2 */
+    uint32_t state_words;            /* 624 */
+    uint64_t max_work_bytes;         /* draws and sample lists of one call */
+} rpvg_independent_limits;
+
+typedef struct rpvg_hip_independent_stats {
+    uint64_t calls_completed;        /* calls that returned RPVG_HIP_OK with at least one cluster */
+    uint64_t draws;                  /* sets drawn (two generator words each) */
+    uint64_t subsets;                /* retained subsets = EM problems */
+} rpvg_hip_independent_stats;
+
+int rpvg_hip_nested_independent_subset_em(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_hip_groups * groups,
+                                          const rpvg_hip_independent_spec * spec, rpvg_hip_subset_em ** result_out);
+int rpvg_hip_subset_em_get_independent(const rpvg_hip_subset_em * result, rpvg_hip_subset_em_independent_view * view_out);
+/* the draws of unit `unit` (spec.keep_draws != 0): draws_out[slot x T + transcript], the index of the drawn set among the
+ * transcript's posteriors; 0 for a transcript that draws nothing */
+int rpvg_hip_independent_draws_get(const rpvg_hip_subset_em * result, uint32_t unit, uint32_t * draws_out);
+void rpvg_hip_independent_limits(rpvg_independent_limits * limits_out);
+/* counters of this call, kept apart from rpvg_hip_kernel_stats; rpvg_hip_stats_reset zeroes them too */
+int rpvg_hip_independent_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_independent_stats * stats_out);
+
 /* ---- minimum path cover (`-i strains`) ------------------------------------ */
 /* For every listed cluster: the read-path cover and path weights of MinimumPathAbundanceEstimator::estimate
  * (src/path_abundance_estimator.cpp:233-257) and the greedy weightedMinimumPathCover (:297-340) on the GPU.

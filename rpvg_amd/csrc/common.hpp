@@ -683,6 +683,8 @@ struct rpvg_hip_ctx {
     void foldFinishedSpans();
     std::vector<rpvg_hip_detail::TimedInterval> intervals;  // folded spans since the last reset
     rpvg_hip_kernel_stats stats;
+    rpvg_hip_independent_stats independent_stats{};  // rpvg_hip_nested_independent_subset_em's (subset_independent.hip)
+    rpvg_hip_detail::SubsetEmHints subset_independent_hints;
 
     // Opens a timed span on `on` (the context's stream when null); returns its index (or -1 on failure).
     int spanBegin(int family, hipStream_t on = nullptr, int sub = -1);

@@ -98,6 +98,56 @@ RPVG_STREAM_FN uint32_t firstNotBelow(PartialSums cp, const uint32_t n, const do
     return lo;
 }
 
+// The construction of a std::discrete_distribution (bits/random.tcc:2656-2677, GCC 11): fewer than two weights give no
+// distribution (and no draw); otherwise the weights are added one after the other from 0.0 in index order, every weight is divided by
+// that sum, the quotients are added up the same way, and the last partial sum is overwritten with 1.0.  No product anywhere:
+// nothing a compiler could contract.  The two chains are written for a range so that a kernel can run them over the part of the
+// weights it holds; `weight(i)` reads and `store(i, v)` writes element i.
+template <typename Weights>
+RPVG_STREAM_FN double discreteSumRange(Weights weight, const uint32_t begin, const uint32_t end, double sum) {
+    for (uint32_t i = begin; i < end; ++i) sum += weight(i);
+    return sum;
+}
+
+template <typename Weights, typename Store>
+RPVG_STREAM_FN double discreteCumulateRange(Weights weight, const uint32_t begin, const uint32_t end, const double sum, double run, Store store) {
+    for (uint32_t i = begin; i < end; ++i) {
+        const double p = weight(i) / sum;
+        run += p;
+        store(i, run);
+    }
+    return run;
+}
+
+// does a distribution over n weights draw at all?
+RPVG_STREAM_FN bool discreteDraws(const uint32_t n) { return n >= 2; }
+
+// the whole construction; false (nothing stored) for fewer than two weights
+template <typename Weights, typename Store>
+RPVG_STREAM_FN bool discretePartialSums(Weights weight, const uint32_t n, Store store) {
+    if (!discreteDraws(n)) return false;
+    const double sum = discreteSumRange(weight, 0, n, 0.0);
+    discreteCumulateRange(weight, 0, n, sum, 0.0, store);
+    store(n - 1, 1.0);
+    return true;
+}
+
+// one draw: generate_canonical from two words, lower_bound over the partial sums
+template <typename PartialSums>
+RPVG_STREAM_FN uint32_t discreteDraw(PartialSums cp, const uint32_t n, const uint32_t first_word, const uint32_t second_word) {
+    return firstNotBelow(cp, n, canonicalFromWords(first_word, second_word));
+}
+
+// One block of the generator's recurrence, in the three steps a workgroup can take in place (gibbs_chains.hip's stream kernel takes
+// the same): word i of the next block from the state x (x_new: the words of the next block written so far).  Step 1 is i in
+// [0, 227), step 2 [227, 454), step 3 [454, 624); a step reads only old words and new words of earlier steps, except word 623,
+// whose second operand is the new word 0.
+RPVG_STREAM_FN uint32_t mtBlockWord(const uint32_t * x, const uint32_t i) {
+    const uint32_t x_k1 = (i + 1 < kMtWords) ? x[i + 1] : x[0];          // (i == 623: x[0] is new by then)
+    const uint32_t x_km = (i < kMtTail) ? x[i + kMtShift] : x[i - kMtTail];  // (i >= 227: new by then)
+    return mtNext(x[i], x_k1, x_km);
+}
+
 }  // namespace rpvg_streams
 
 #endif

@@ -714,6 +714,41 @@ struct RetainedSets {
 
 }  // namespace
 
+// fullMergeKernel for a caller in another file (subset_independent.hip: its units are clusters, and group size 2 is among them)
+void rpvg_hip_detail::queueFullMerge(const uint32_t group_size, const FullMergeLaunch & launch, hipStream_t st) {
+    FullMergeArgs ma;
+    ma.header = static_cast<const SubsetHeader *>(launch.header);
+    ma.num_matrices = launch.num_units;
+    ma.subset_off = launch.subset_off;
+    ma.weight = launch.weight;
+    ma.path_off = launch.path_off;
+    ma.path = launch.path;
+    ma.col_off = launch.col_off;
+    ma.col_path = launch.col_path;
+    ma.abundances = launch.abundances;
+    ma.noise = launch.noise;
+    ma.total = launch.total;
+    ma.cluster = launch.cluster;
+    ma.cluster_path_off = launch.cluster_path_off;
+    ma.path_group_id = launch.path_group_id;
+    ma.sort_key = launch.sort_key;
+    ma.sort_pos = launch.sort_pos;
+    ma.rec_abund = launch.rec_abund;
+    ma.merge_bad = launch.merge_bad;
+    ma.packed = launch.packed;
+    const dim3 grid(launch.num_units), block(256);
+    switch (group_size) {
+        case 1: fullMergeKernel<1><<<grid, block, 0, st>>>(ma); break;
+        case 2: fullMergeKernel<2><<<grid, block, 0, st>>>(ma); break;
+        case 3: fullMergeKernel<3><<<grid, block, 0, st>>>(ma); break;
+        case 4: fullMergeKernel<4><<<grid, block, 0, st>>>(ma); break;
+        case 5: fullMergeKernel<5><<<grid, block, 0, st>>>(ma); break;
+        case 6: fullMergeKernel<6><<<grid, block, 0, st>>>(ma); break;
+        case 7: fullMergeKernel<7><<<grid, block, 0, st>>>(ma); break;
+        default: fullMergeKernel<8><<<grid, block, 0, st>>>(ma); break;
+    }
+}
+
 // The first stage: every launch of the enumeration, each followed by the pass that keeps its sets at or above the threshold.  The
 // posterior buffer is one launch's and is reused; nothing proportional to the number of sets leaves the device.
 static int queueEnumerationAndRetain(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, const uint32_t group_size, const double * log_freq,

@@ -11,6 +11,33 @@ using rpvg_subset_full::PackedLayout;
 using rpvg_subset_full::packedLayout;
 using namespace rpvg_hip_detail;
 
+namespace rpvg_hip_detail {
+// fullMergeKernel<GS> (subset_full.hip) queued from another file: its arguments (header: the call's SubsetHeader on the device), with
+// units — matrices there, clusters in subset_independent.hip — that each have a cluster and a run of subsets
+struct FullMergeLaunch {
+    const void * header;
+    uint32_t num_units;
+    const uint64_t * subset_off;
+    const double * weight;
+    const uint64_t * path_off;
+    const uint32_t * path;
+    const uint64_t * col_off;
+    const uint32_t * col_path;
+    const double * abundances;
+    const double * noise;
+    const double * total;
+    const uint32_t * cluster;
+    const uint64_t * cluster_path_off;
+    const uint32_t * path_group_id;
+    uint32_t * sort_key;
+    uint32_t * sort_pos;
+    double * rec_abund;
+    uint32_t * merge_bad;
+    unsigned char * packed;
+};
+void queueFullMerge(uint32_t group_size, const FullMergeLaunch & launch, hipStream_t st);
+}  // namespace rpvg_hip_detail
+
 namespace {
 
 struct MatrixTotals {  // what subsetOffsetsKernel adds up over the matrices
@@ -197,6 +224,12 @@ struct rpvg_hip_subset_em {
     rpvg_hip_subset_em_view view{};
     rpvg_hip_subset_em_sets_view sets_view{};  // rpvg_hip_nested_full_subset_em's (has_sets)
     bool has_sets = false;
+    // rpvg_hip_nested_independent_subset_em's (subset_independent.hip); its units are clusters.  draws: kept for the tests
+    // (rpvg_hip_independent_spec::keep_draws), unit k's at draw_off[k], [slot][transcript]
+    rpvg_hip_subset_em_independent_view independent_view{};
+    bool has_independent = false;
+    std::vector<uint32_t> draws;
+    std::vector<uint64_t> draw_off;
     ~rpvg_hip_subset_em() {
         if (block) pinnedFree(block);
     }

@@ -41,6 +41,9 @@ def lib() -> C.CDLL:
         L.rpvg_amd_engine_ctx.argtypes = [C.c_void_p]
         L.rpvg_amd_engine_stats_get.argtypes = [C.c_void_p, C.c_void_p]
         L.rpvg_amd_engine_stats_reset.argtypes = [C.c_void_p]
+        L.rpvg_amd_engine_independent_stats_get.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpvg_amd_run_generators_after.restype = C.c_int
+        L.rpvg_amd_run_generators_after.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(CParams), C.POINTER(C.c_uint32)]
         L.rpvg_amd_host_threads.restype = C.c_int
         L.rpvg_amd_batch_prepare.restype = C.c_void_p
         L.rpvg_amd_batch_prepare.argtypes = [C.c_void_p, C.POINTER(CClusterBatch), C.c_int]
@@ -158,6 +161,13 @@ class Engine:
         if lib().rpvg_amd_engine_stats_get(self.handle, C.byref(s)) != 0:
             raise hip.EngineError(f"stats failed: {_err()}")
         return s.as_dict()
+
+    def independent_stats(self) -> dict:
+        """Calls of rpvg_hip_nested_independent_subset_em that completed, their draws and subsets, summed over the host lanes."""
+        s = hip.CIndependentStats()
+        if lib().rpvg_amd_engine_independent_stats_get(self.handle, C.byref(s)) != 0:
+            raise hip.EngineError(f"stats failed: {_err()}")
+        return {n: int(getattr(s, n)) for n, _ in s._fields_}
 
     def reset_stats(self):
         if lib().rpvg_amd_engine_stats_reset(self.handle) != 0:
@@ -321,6 +331,14 @@ class Engine:
         finally:
             lib().rpvg_amd_result_free(h)
         return out, secs.value
+
+    def generators_after(self, model: str, params: CParams, prepared: "PreparedBatch", num_clusters: int) -> List[int]:
+        """Runs the batch estimate with cluster i on mt19937(rng_seed + i) and returns every generator's next output (tests: where
+        a route leaves the callers' generators)."""
+        out = (C.c_uint32 * max(num_clusters, 1))()
+        if lib().rpvg_amd_run_generators_after(self.handle, prepared.handle, model.encode(), C.byref(params), out) != 0:
+            raise hip.EngineError(f"generators_after({model}) failed: {_err()}")
+        return [int(x) for x in out[:num_clusters]]
 
     def run_team(self, model: str, params: CParams, prepared: "PreparedBatch", threads: int, decode: bool = True):
         """The reference's cluster loop (src/main.cpp:829,976-977): PathEstimator::estimate() once per cluster from an OpenMP team

@@ -31,6 +31,8 @@ EXPORTS = [
     "rpvg_hip_read_rows_view", "rpvg_hip_read_rows_sizes", "rpvg_hip_read_rows_free", "rpvg_hip_path_clusters", "rpvg_hip_debug_log",
     "rpvg_hip_nested_subset_em", "rpvg_hip_subset_em_get", "rpvg_hip_subset_em_free",
     "rpvg_hip_nested_full_subset_em", "rpvg_hip_subset_em_get_sets",
+    "rpvg_hip_nested_independent_subset_em", "rpvg_hip_subset_em_get_independent", "rpvg_hip_independent_draws_get",
+    "rpvg_hip_independent_limits", "rpvg_hip_independent_stats_get",
     "rpvg_hip_batch_cluster_totals", "rpvg_hip_batch_has_source_columns", "rpvg_hip_batch_source_columns_sizes",
     "rpvg_hip_batch_source_columns_get", "rpvg_hip_groups_build_from_sources", "rpvg_hip_groups_build_single_paths", "rpvg_hip_batch_upload_begin", "rpvg_hip_batch_upload_finish", "rpvg_hip_create_with_streams",
     "rpvg_hip_batch_upload_finish_queue", "rpvg_hip_batch_upload_finish_wait",
@@ -104,6 +106,42 @@ class CSubsetEmSetsView(C.Structure):
                 ("set_posterior", C.POINTER(C.c_double)), ("set_abundance", C.POINTER(C.c_double))]
 
 
+class CIndependentSpec(C.Structure):
+    """rpvg_hip_independent_spec"""
+    _fields_ = [("num_clusters", C.c_uint32), ("matrix_off", C.c_void_p), ("group_size", C.c_uint32), ("column_counts", C.c_void_p),
+                ("log_freq", C.c_void_p), ("min_hap_prob", C.c_double), ("max_em_its", C.c_uint32), ("max_rel_em_conv", C.c_double),
+                ("collapse_precision", C.c_double), ("generator_words", C.c_void_p), ("keep_draws", C.c_int32)]
+
+
+class CSubsetEmIndependentView(C.Structure):
+    """rpvg_hip_subset_em_independent_view"""
+    _fields_ = [("num_clusters", C.c_uint32), ("group_size", C.c_uint32), ("num_samples", C.c_uint32), ("subset_off", C.POINTER(C.c_uint64)),
+                ("weight", C.POINTER(C.c_double)), ("path_off", C.POINTER(C.c_uint64)), ("path", C.POINTER(C.c_uint32)),
+                ("col_off", C.POINTER(C.c_uint64)), ("col_path", C.POINTER(C.c_uint32)), ("abundances", C.POINTER(C.c_double)),
+                ("noise_count", C.POINTER(C.c_double)), ("total_count", C.POINTER(C.c_double)), ("iterations", C.POINTER(C.c_uint32)),
+                ("set_count", C.POINTER(C.c_uint32)), ("cluster_noise_count", C.POINTER(C.c_double)), ("set_size", C.POINTER(C.c_uint32)),
+                ("set_member", C.POINTER(C.c_uint32)), ("set_posterior", C.POINTER(C.c_double)), ("set_abundance", C.POINTER(C.c_double)),
+                ("sample_count", C.POINTER(C.c_uint32)), ("words_consumed", C.POINTER(C.c_uint64)), ("generator_state", C.POINTER(C.c_uint32))]
+
+
+class CIndependentLimits(C.Structure):
+    """rpvg_independent_limits"""
+    _fields_ = [("max_group_size", C.c_uint32), ("max_samples", C.c_uint32), ("max_transcript_sets", C.c_uint64), ("words_per_draw", C.c_uint32),
+                ("state_words", C.c_uint32), ("max_work_bytes", C.c_uint64)]
+
+
+class CIndependentStats(C.Structure):
+    """rpvg_hip_independent_stats"""
+    _fields_ = [("calls_completed", C.c_uint64), ("draws", C.c_uint64), ("subsets", C.c_uint64)]
+
+
+def independent_limits() -> CIndependentLimits:
+    """The numbers of rpvg_hip_nested_independent_subset_em's plan (rpvg_amd/csrc/subset_independent_plan.hpp); needs no GPU."""
+    out = CIndependentLimits()
+    lib().rpvg_hip_independent_limits(C.byref(out))
+    return out
+
+
 EM_KERNELS = 12  # RPVG_HIP_EM_KERNELS
 
 
@@ -173,6 +211,7 @@ def lib() -> C.CDLL:
         L.rpvg_hip_last_error.restype = C.c_char_p
         L.rpvg_hip_full_set_count.restype = C.c_uint64
         L.rpvg_hip_cover_limits.restype = None
+        L.rpvg_hip_independent_limits.restype = None
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -652,6 +691,72 @@ class DeviceGroups:
         finally:
             lib().rpvg_hip_subset_em_free(h)
 
+    def nested_independent_subset_em(self, matrix_off, group_size: int, min_hap_prob: float, generator_words, column_counts=None, log_freq=None,
+                                     max_em_its: int = 10000, max_rel_em_conv: float = 1e-3, collapse_precision: float = 0.0,
+                                     keep_draws: bool = False) -> dict:
+        """rpvg_hip_nested_independent_subset_em: unit k is the cluster whose transcripts are the matrices
+        [matrix_off[k], matrix_off[k + 1]), one column per path.  column_counts (group size 2): the multiplicity of every column,
+        matrices back to back; log_freq[m] (other group sizes): the log frequencies of matrix m's columns; generator_words: [K, 624]
+        the next outputs of every cluster's std::mt19937.  Returns the fields of rpvg_hip_subset_em_independent_view as numpy arrays
+        (copies; set_member and set_abundance as [slots, group_size]) and, with keep_draws, "draws": per unit an array
+        [num_samples, transcripts].  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
+        mo = np.ascontiguousarray(matrix_off, dtype=np.uint32)
+        K = len(mo) - 1
+        gw = np.ascontiguousarray(generator_words, dtype=np.uint32).reshape(K, 624)
+        cc = None if column_counts is None else np.ascontiguousarray(column_counts, dtype=np.uint32)
+        lf = None
+        if log_freq is not None:
+            lf = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in log_freq]) if len(log_freq) else np.zeros(0))
+        spec = CIndependentSpec(K, mo.ctypes.data, group_size, cc.ctypes.data if cc is not None and cc.size else None,
+                                lf.ctypes.data if lf is not None and lf.size else None, float(min_hap_prob), max_em_its, float(max_rel_em_conv),
+                                float(collapse_precision), gw.ctypes.data if gw.size else None, 1 if keep_draws else 0)
+        h = C.c_void_p()
+        _check(lib().rpvg_hip_nested_independent_subset_em(self.ctx.handle, self.batch.handle, self.handle, C.byref(spec), C.byref(h)),
+               "rpvg_hip_nested_independent_subset_em")
+        try:
+            v = CSubsetEmIndependentView()
+            _check(lib().rpvg_hip_subset_em_get_independent(h, C.byref(v)), "rpvg_hip_subset_em_get_independent")
+            g = int(v.group_size)
+
+            def take(pointer, n, dtype, shape=None):
+                if n == 0 or not pointer:
+                    return np.zeros(shape if shape is not None else (0,), dtype=dtype)
+                a = np.ctypeslib.as_array(pointer, shape=(n,)).copy()
+                return a.reshape(shape) if shape is not None else a
+
+            out = {"num_clusters": K, "group_size": g, "num_samples": int(v.num_samples)}
+            out["subset_off"] = take(v.subset_off, K + 1, np.uint64) if K else np.zeros(1, np.uint64)
+            S = int(out["subset_off"][-1])
+            out["path_off"] = take(v.path_off, S + 1, np.uint64) if K else np.zeros(1, np.uint64)
+            out["col_off"] = take(v.col_off, S + 1, np.uint64) if K else np.zeros(1, np.uint64)
+            L, Cn = int(out["path_off"][-1]), int(out["col_off"][-1])
+            out["weight"] = take(v.weight, S, np.float64)
+            out["path"] = take(v.path, L, np.uint32)
+            out["col_path"] = take(v.col_path, Cn, np.uint32)
+            out["abundances"] = take(v.abundances, Cn, np.float64)
+            out["noise_count"] = take(v.noise_count, S, np.float64)
+            out["total_count"] = take(v.total_count, S, np.float64)
+            out["iterations"] = take(v.iterations, S, np.uint32)
+            out["set_count"] = take(v.set_count, K, np.uint32)
+            out["cluster_noise_count"] = take(v.cluster_noise_count, K, np.float64)
+            out["set_size"] = take(v.set_size, L, np.uint32)
+            out["set_member"] = take(v.set_member, L * g, np.uint32, (L, g))
+            out["set_posterior"] = take(v.set_posterior, L, np.float64)
+            out["set_abundance"] = take(v.set_abundance, L * g, np.float64, (L, g))
+            out["sample_count"] = take(v.sample_count, S, np.uint32)
+            out["words_consumed"] = take(v.words_consumed, K, np.uint64)
+            out["generator_state"] = take(v.generator_state, K * 624, np.uint32, (K, 624))
+            if keep_draws:
+                out["draws"] = []
+                for k in range(K):
+                    T = int(mo[k + 1]) - int(mo[k])
+                    d = np.zeros(max(out["num_samples"] * T, 1), dtype=np.uint32)
+                    _check(lib().rpvg_hip_independent_draws_get(h, C.c_uint32(k), C.c_void_p(d.ctypes.data)), "rpvg_hip_independent_draws_get")
+                    out["draws"].append(d[:out["num_samples"] * T].reshape(out["num_samples"], T))
+            return out
+        finally:
+            lib().rpvg_hip_subset_em_free(h)
+
     def gibbs(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
         """rpvg_hip_group_gibbs: per problem ([sorted member tuples in order of first appearance], counts); plus the words each
         generator gave, the state words of the generators that gave at least 624, and (rounds, conditionals)."""
@@ -1037,6 +1142,12 @@ class Context:
         s = CKernelStats()
         _check(lib().rpvg_hip_stats_get(self.handle, C.byref(s)), "rpvg_hip_stats_get")
         return s.as_dict()
+
+    def independent_stats(self) -> dict:
+        """rpvg_hip_independent_stats: calls of rpvg_hip_nested_independent_subset_em that completed, their draws and subsets."""
+        s = CIndependentStats()
+        _check(lib().rpvg_hip_independent_stats_get(self.handle, C.byref(s)), "rpvg_hip_independent_stats_get")
+        return {n: int(getattr(s, n)) for n, _ in s._fields_}
 
     def reset_stats(self):
         _check(lib().rpvg_hip_stats_reset(self.handle), "rpvg_hip_stats_reset")

@@ -121,6 +121,25 @@ void HipEngine::stats(rpvg_hip_kernel_stats * stats_out) const {
     stats(std::vector<const HipEngine *>(1, this), stats_out);
 }
 
+void HipEngine::independentStats(rpvg_hip_independent_stats * stats_out) const {
+
+    std::vector<rpvg_hip_ctx *> contexts(1, context);
+    const auto lane_contexts = laneContexts();
+    contexts.insert(contexts.end(), lane_contexts.begin(), lane_contexts.end());
+
+    *stats_out = rpvg_hip_independent_stats{0, 0, 0};
+
+    for (auto & ctx: contexts) {
+
+        rpvg_hip_independent_stats lane_stats;
+        check(rpvg_hip_independent_stats_get(ctx, &lane_stats), "rpvg_hip_independent_stats_get");
+
+        stats_out->calls_completed += lane_stats.calls_completed;
+        stats_out->draws += lane_stats.draws;
+        stats_out->subsets += lane_stats.subsets;
+    }
+}
+
 void HipEngine::stats(const std::vector<const HipEngine *> & engines, rpvg_hip_kernel_stats * stats_out) {
 
     std::vector<rpvg_hip_ctx *> contexts;

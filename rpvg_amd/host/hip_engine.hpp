@@ -73,6 +73,9 @@ class HipEngine {
         void stats(rpvg_hip_kernel_stats * stats_out) const;
         void resetStats() const;
 
+        // The counters of rpvg_hip_nested_independent_subset_em (rpvg_hip_independent_stats), summed over the lanes.
+        void independentStats(rpvg_hip_independent_stats * stats_out) const;
+
         // The same over several engines of one GPU (the workers of a BatchPipeline): sums, and the union of their busy spans.
         static void stats(const std::vector<const HipEngine *> & engines, rpvg_hip_kernel_stats * stats_out);
 

@@ -607,6 +607,28 @@ void NestedPathAbundanceEstimator::estimateClusters(std::vector<PathClusterEstim
             first_problem.at(i + 1) = problems.size();
         }
 
+        // Exact posteriors at ploidy 2 and 5 .. 8, no read-count samples: posteriors, draws, subsets, EM and the weighted merge are one
+        // device call, draw for draw on the clusters' generators; no posterior and no sample reaches the host.  (Ploidy 1, 3 and 4
+        // stay on the separate route for the reason given above; --use-hap-gibbs keeps its round per transcript.)  When the device
+        // does not take the batch, the code below runs unchanged, on generators nobody has moved.
+        if (!use_group_post_gibbs && num_gibbs_samples == 0 && (group_size == 2 || group_size >= 5)) {
+
+            std::vector<std::mt19937 *> generators;
+
+            for (auto & cluster: clusters) {
+
+                generators.emplace_back(&rngs->at(cluster));
+            }
+
+            SubsetEmResult device_result;
+
+            if (nestedIndependentSubsetAbundances(&device_result, cluster_batch, problems, first_problem, group_size, min_hap_prob, max_em_its, max_rel_em_conv, generators)) {
+
+                unpackMergedSetSolutions(path_cluster_estimates, cluster_batch, clusters, device_result.sets_view);
+                return;
+            }
+        }
+
         std::vector<std::vector<std::vector<uint32_t> > > cluster_samples(clusters.size());
 
         for (auto & samples: cluster_samples) {

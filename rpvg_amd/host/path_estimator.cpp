@@ -1828,6 +1828,134 @@ bool estimatePathGroupPosteriorsGibbsOnDevice(std::vector<GroupPosteriors> * gro
 
 }
 
+// Independent haplotype inference with exact posteriors (src/path_abundance_estimator.cpp:356-426) in ONE device call
+// (rpvg_hip_nested_independent_subset_em): unit i is cluster problems[first_problem[i]].cluster, its transcripts the problems
+// [first_problem[i], first_problem[i + 1]).  The generators' next 624 outputs go in; on success every generator is moved past the
+// words its cluster's draws took, which leaves it where sampleGroupPathIndices would.  False — and no generator moved — when the
+// device does not take the input.
+bool PathEstimator::nestedIndependentSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const std::vector<size_t> & first_problem, const uint32_t group_size, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv, const std::vector<std::mt19937 *> & generators) const {
+
+    assert(!result->result);
+    assert(first_problem.size() == generators.size() + 1);
+
+    if (problems.empty() || (group_size == 2 && std::getenv("RPVG_AMD_HOST_BOUNDED"))) {
+
+        return false;
+    }
+
+    const size_t num_units = generators.size();
+
+    std::vector<uint32_t> matrix_off(num_units + 1);
+
+    for (size_t i = 0; i <= num_units; ++i) {
+
+        matrix_off[i] = first_problem[i];
+
+        if (i < num_units && first_problem[i] == first_problem[i + 1]) {  // (a cluster without a transcript: the host route's business)
+
+            return false;
+        }
+    }
+
+    ScopedPhase whole_phase("nested: posteriors + draws + subsets + EM + merge on the device");
+
+    std::vector<uint32_t> column_counts;
+    std::vector<double> log_freqs;
+
+    for (auto & problem: problems) {
+
+        if (group_size == 2) {
+
+            column_counts.insert(column_counts.end(), problem.column_counts.begin(), problem.column_counts.end());
+
+        } else {
+
+            const auto path_log_freqs = calcPathLogFrequences(problem.column_counts);
+            log_freqs.insert(log_freqs.end(), path_log_freqs.begin(), path_log_freqs.end());
+        }
+    }
+
+    std::vector<uint32_t> generator_words(num_units * std::mt19937::state_size);
+
+    #pragma omp parallel for schedule(dynamic, 16) num_threads(shortLoopThreads())
+    for (size_t i = 0; i < num_units; ++i) {
+
+        nextGeneratorOutputs(*generators[i], generator_words.data() + i * std::mt19937::state_size);
+    }
+
+    const GroupMatrices matrices(engine, cluster_batch, problems, true, prob_precision);
+
+    rpvg_hip_independent_spec spec;
+    spec.num_clusters = num_units;
+    spec.matrix_off = matrix_off.data();
+    spec.group_size = group_size;
+    spec.column_counts = column_counts.empty() ? nullptr : column_counts.data();
+    spec.log_freq = log_freqs.empty() ? nullptr : log_freqs.data();
+    spec.min_hap_prob = min_hap_prob;
+    spec.max_em_its = max_em_its;
+    spec.max_rel_em_conv = max_rel_em_conv;
+    spec.collapse_precision = prob_precision;
+    spec.generator_words = generator_words.data();
+    spec.keep_draws = 0;
+
+    const int status = rpvg_hip_nested_independent_subset_em(engine->ctx(), cluster_batch.handle(), matrices.handle(), &spec, &result->result);
+
+    if (status == RPVG_HIP_ERR_UNSUPPORTED) {
+
+        if (PhaseTrace::enabled()) {
+
+            std::fprintf(stderr, "[rpvg_amd trace] independent groups: the device call leaves the batch to the separate route: %s\n", rpvg_hip_last_error());
+        }
+
+        return false;
+    }
+
+    HipEngine::check(status, "rpvg_hip_nested_independent_subset_em");
+
+    rpvg_hip_subset_em_independent_view view;
+    HipEngine::check(rpvg_hip_subset_em_get_independent(result->result, &view), "rpvg_hip_subset_em_get_independent");
+
+    // the view of unpackMergedSetSolutions: clusters in place of matrices, no retained-set arrays
+    rpvg_hip_subset_em_sets_view & sets = result->sets_view;
+    sets.num_matrices = view.num_clusters;
+    sets.group_size = view.group_size;
+    sets.subset_off = view.subset_off;
+    sets.weight = view.weight;
+    sets.path_off = view.path_off;
+    sets.path = view.path;
+    sets.col_off = view.col_off;
+    sets.col_path = view.col_path;
+    sets.abundances = view.abundances;
+    sets.noise_count = view.noise_count;
+    sets.total_count = view.total_count;
+    sets.iterations = view.iterations;
+    sets.retained_off = nullptr;
+    sets.retained_rank = nullptr;
+    sets.retained_posterior = nullptr;
+    sets.set_count = view.set_count;
+    sets.cluster_noise_count = view.cluster_noise_count;
+    sets.set_size = view.set_size;
+    sets.set_member = view.set_member;
+    sets.set_posterior = view.set_posterior;
+    sets.set_abundance = view.set_abundance;
+
+    // the generators end where the reference's draws leave them
+    #pragma omp parallel for schedule(dynamic, 16) num_threads(shortLoopThreads())
+    for (size_t i = 0; i < num_units; ++i) {
+
+        if (view.words_consumed[i] >= std::mt19937::state_size) {
+
+            setGeneratorBehind(generators[i], view.generator_state + i * std::mt19937::state_size);
+
+        } else {
+
+            generators[i]->discard(view.words_consumed[i]);
+        }
+    }
+
+    return true;
+}
+
 int PathEstimator::generatorStateSelfTest(const uint32_t rounds) {
 
     if (!rawGeneratorAccess()) {

@@ -242,6 +242,12 @@ class PathEstimator {
         // the device does not take the input — a problem over RPVG_HIP_FULL_MAX_SETS among them: the separate calls name its cluster.
         bool nestedFullSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const uint32_t group_size, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv) const;
 
+        // Independent haplotype inference with exact posteriors: posteriors, draws, path subsets, EM and the posterior-weighted merge in
+        // ONE device call (rpvg_hip_nested_independent_subset_em): unit i — generator i — has the transcripts
+        // [first_problem[i], first_problem[i + 1]) of `problems` and is matrix i of result->sets_view.  On success every generator
+        // stands where the reference's draws leave it; false, with no generator moved, when the device does not take the input.
+        bool nestedIndependentSubsetAbundances(SubsetEmResult * result, const DeviceClusterBatch & cluster_batch, const std::vector<GroupPosteriorProblem> & problems, const std::vector<size_t> & first_problem, const uint32_t group_size, const double min_hap_prob, const uint32_t max_em_its, const double max_rel_em_conv, const std::vector<std::mt19937 *> & generators) const;
+
         // src/path_estimator.cpp:315-330
         static std::vector<double> calcPathLogFrequences(const std::vector<uint32_t> & path_counts);
 

@@ -344,6 +344,16 @@ int rpvg_amd_engine_stats_get(void * engine, rpvg_hip_kernel_stats * stats_out) 
     });
 }
 
+// The counters of the independent one-call route (rpvg_hip_independent_stats), both host lanes together.
+int rpvg_amd_engine_independent_stats_get(void * engine, rpvg_hip_independent_stats * stats_out) {
+
+    return guardedInt([&]() -> int {
+
+        static_cast<Engine *>(engine)->hip->independentStats(stats_out);
+        return 0;
+    });
+}
+
 int rpvg_amd_engine_stats_reset(void * engine) {
 
     return guardedInt([&]() -> int {
@@ -940,6 +950,51 @@ void * rpvg_amd_run(void * engine, void * prepared_batch, const char * model, co
         PhaseTrace::report();
 
         return packResult(estimates);
+    });
+}
+
+// Where a batch estimate leaves the callers' generators: runs `model` on a device-resident prepared batch with cluster i on
+// mt19937(rng_seed + i) and writes every generator's NEXT output to next_out[i] (tests: two routes of a model that draw the same
+// numbers leave the generators in the same place).  The estimates stay in the prepared batch's containers.
+int rpvg_amd_run_generators_after(void * engine, void * prepared_batch, const char * model, const rpvg_params * params, uint32_t * next_out) {
+
+    return guardedInt([&]() -> int {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (!prepared->device) {
+
+            last_error = "rpvg_amd_run_generators_after needs a batch that is resident on the device";
+            return -1;
+        }
+
+        auto estimator = makePathEstimator(model, *params, static_cast<Engine *>(engine)->hip);
+
+        if (prepared->estimates.size() != prepared->paths.size()) {
+
+            prepared->estimates.assign(prepared->paths.size(), PathClusterEstimates());
+
+            for (size_t i = 0; i < prepared->estimates.size(); ++i) {
+
+                prepared->estimates.at(i).paths = prepared->paths.at(i);
+            }
+        }
+
+        std::vector<std::mt19937> rngs;
+
+        for (size_t i = 0; i < prepared->estimates.size(); ++i) {
+
+            rngs.emplace_back(params->rng_seed + i);
+        }
+
+        estimator->estimateBatch(&prepared->estimates, *prepared->device, &rngs);
+
+        for (size_t i = 0; i < rngs.size(); ++i) {
+
+            next_out[i] = rngs[i]();
+        }
+
+        return 0;
     });
 }
 
