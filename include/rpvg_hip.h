@@ -29,6 +29,7 @@
 #include "rpvg_index.h"
 #include "rpvg_table.h"
 #include "rpvg_samples.h"
+#include "rpvg_text.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -837,6 +838,32 @@ int rpvg_hip_gibbs_table_build_resident(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs
                                         uint32_t num_clusters, const uint64_t * cluster_path_off, const double * total_count,
                                         uint32_t num_gibbs_samples, rpvg_hip_gibbs_table ** table_out);
 
+/* ---- table text (rpvg_text.h; rpvg_amd/csrc/table_text.hip) ------------------------------------------------------------------
+ *   rpvg_hip_gibbs_table_text      the rows ReadCountGibbsSamplesWriter prints for a batch (src/threaded_output_writer.cpp:160-201),
+ *                                 `name \t ClusterID (\t sample){N} \n` for the listed paths in path order, formatted on the GPU from
+ *                                 the table's resident samples (a table built from arrays or from the sampler's handle alike).
+ *   rpvg_hip_estimates_table_text  RPVG_TEXT_PER_PATH: the rows of AbundanceEstimatesWriter (src/threaded_output_writer.cpp:295-322),
+ *                                 name, ClusterID, Length, EffectiveLength, abundance, member_tpm; set i of every cluster must be {i}
+ *                                 (checked on the device: RPVG_HIP_ERR_INVALID names the first offending cluster).
+ *                                 RPVG_TEXT_HAPLOTYPE: the rows of HaplotypeAbundanceEstimatesWriter (src/threaded_output_writer.cpp:358-411),
+ *                                 name, ClusterID, Length, EffectiveLength, haplotype_prob, read_count, tpm.  The table must have its
+ *                                 TPMs (rpvg_hip_estimates_table_tpm); `estimates` is the flat input the table was built from, host or device.
+ *                                 Both refuse, before anything is queued, a precision outside 1 .. 17 and labels whose sizes are not
+ *                                 the table's; a name_off that is not a non-decreasing sequence of offsets from 0 to num_name_bytes
+ *                                 is refused by a kernel before any text kernel runs (last_error names the smallest offending path).
+ *   rpvg_hip_table_text_view       row_off and ONE copy of the whole text into page-locked memory of the library's pool.
+ *   rpvg_hip_table_text_get        bytes [byte_begin, byte_end) of the text to host memory: a writer streams a text of gigabytes in pieces.
+ *   rpvg_hip_table_text_guards     test hook: the text lies in a device block between two runs of 64 pattern bytes; *intact_out says
+ *                                 whether both still hold the pattern. */
+int rpvg_hip_gibbs_table_text(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs_table * table, const rpvg_table_labels * labels, int32_t precision,
+                              rpvg_hip_table_text ** text_out);
+int rpvg_hip_estimates_table_text(rpvg_hip_ctx * ctx, const rpvg_hip_estimates_table * table, const rpvg_estimates_flat * estimates,
+                                  const rpvg_table_labels * labels, int32_t kind, int32_t precision, rpvg_hip_table_text ** text_out);
+int rpvg_hip_table_text_view(rpvg_hip_table_text * text, rpvg_table_text_view * view_out);
+int rpvg_hip_table_text_get(rpvg_hip_table_text * text, uint64_t byte_begin, uint64_t byte_end, char * dst);
+int rpvg_hip_table_text_guards(rpvg_hip_table_text * text, int32_t * intact_out);
+void rpvg_hip_table_text_free(rpvg_hip_table_text * text);
+
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the
  * only collectives of this engine are the per-iteration all-reduce of rpvg_hip_em_dense_sharded and
@@ -937,6 +964,9 @@ typedef struct rpvg_hip_kernel_stats {
     /* rpvg_hip_min_path_cover_any: clusters that took the whole-GPU route (path_cover_grid.hip) and the paths their greedy rounds chose */
     uint64_t cover_grid_problems;
     uint64_t cover_grid_rounds;
+    /* rpvg_hip_gibbs_table_text, rpvg_hip_estimates_table_text: cells whose rounding was decided by the exact multiword comparison
+     * (exact ties and doubles within 2^-60 relative of one; rpvg_amd/csrc/number_text.hpp) */
+    uint64_t text_exact_cells;
     /* rpvg_hip_nested_full_subset_em: calls that returned RPVG_HIP_OK with at least one matrix, the sets they enumerated and the
      * sets they retained (posterior >= min_hap_prob) */
     uint64_t nested_full_calls;

@@ -31,6 +31,7 @@
 #include "device_algos.hpp"
 #include "estimates_plan.hpp"
 #include "table_kit.hpp"
+#include "table_residents.hpp"
 #include "../../include/rpvg_table.h"
 
 #pragma clang fp contract(off)
@@ -393,6 +394,12 @@ const char * const kReasons[] = {"",
                                  "the abundances are neither one per member nor none"};
 
 }  // namespace
+
+// for table_text.hip
+rpvg_hip_detail::EstimatesTableResident rpvg_hip_detail::residentOf(const rpvg_hip_estimates_table * table) {
+    return EstimatesTableResident{table->num_clusters, table->num_paths, table->num_members, table->has_tpm, table->haplotype_prob.ptr,
+                                  table->read_count.ptr, table->tpm.ptr, table->member_tpm.ptr};
+}
 
 extern "C" {
 

@@ -31,6 +31,7 @@
 #include "gibbs_table_plan.hpp"
 #include "gibbs_samples.hpp"
 #include "table_kit.hpp"
+#include "table_residents.hpp"
 #include "../../include/rpvg_samples.h"
 
 #pragma clang fp contract(off)
@@ -478,6 +479,12 @@ int buildTable(rpvg_hip_ctx * ctx, const TableInputs & in, const char * who, rpv
 }
 
 }  // namespace
+
+// for table_text.hip
+rpvg_hip_detail::GibbsTableResident rpvg_hip_detail::residentOf(const rpvg_hip_gibbs_table * table) {
+    return GibbsTableResident{table->num_clusters, table->num_gibbs_samples, table->num_paths, reinterpret_cast<const double *>(table->samples.ptr),
+                              table->listed.ptr, table->h_cluster_path_off.data()};
+}
 
 extern "C" {
 

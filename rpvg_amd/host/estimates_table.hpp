@@ -124,6 +124,9 @@ class EstimatesTable {
         // what the table was made from (the writers print sets, posteriors and abundances from here)
         rpvg_estimates_flat estimates() const { return flat_estimates.view(); }
 
+        // the resident table, for the builders that read it where it lies (table_text.hpp)
+        rpvg_hip_estimates_table * handle() const { return table; }
+
     private:
 
         void build(const uint32_t ploidy);

@@ -102,6 +102,9 @@ class GibbsSamplesTable {
         // names of the rows and ClusterIDs of the clusters, for ReadCountGibbsSamplesWriter::addTable
         const TableLabels & labels() const { return flat_gibbs.labels; }
 
+        // the resident table, for the builders that read it where it lies (table_text.hpp)
+        rpvg_hip_gibbs_table * handle() const { return table; }
+
     private:
 
         std::shared_ptr<HipEngine> hip_engine;

@@ -185,6 +185,7 @@ void HipEngine::stats(const std::vector<const HipEngine *> & engines, rpvg_hip_k
         stats_out->gibbs_count_grid_iterations += lane_stats.gibbs_count_grid_iterations;
         stats_out->cover_grid_problems += lane_stats.cover_grid_problems;
         stats_out->cover_grid_rounds += lane_stats.cover_grid_rounds;
+        stats_out->text_exact_cells += lane_stats.text_exact_cells;
         stats_out->nested_full_calls += lane_stats.nested_full_calls;
         stats_out->nested_full_sets += lane_stats.nested_full_sets;
         stats_out->nested_full_retained += lane_stats.nested_full_retained;

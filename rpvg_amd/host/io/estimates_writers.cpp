@@ -330,6 +330,38 @@ void AbundanceEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, c
     noise_count += table.noise_count_total;
 }
 
+// what the two estimates writers' addText() require of their arguments
+static void requireText(const char * what, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) {
+
+    if (!table.has_tpm) {
+
+        throw EngineError(std::string(what) + "::addText: the table has no TPMs yet (EstimatesTable::tpm)");
+    }
+
+    if (text.num_paths != table.num_paths || (text.num_bytes > 0 && !text.bytes)) {
+
+        throw EngineError(std::string(what) + "::addText: the text is not that of the table");
+    }
+}
+
+void AbundanceEstimatesWriter::addText(const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) {
+
+    requireText("AbundanceEstimatesWriter", table, text);
+
+    out << std::setprecision(out_precision_digits);
+    out.write(text.bytes, text.num_bytes);
+    noise_count += table.noise_count_total;
+}
+
+void HaplotypeAbundanceEstimatesWriter::addText(const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) {
+
+    requireText("HaplotypeAbundanceEstimatesWriter", table, text);
+
+    out << std::setprecision(out_precision_digits);
+    out.write(text.bytes, text.num_bytes);
+    noise_count += table.noise_count_total;
+}
+
 void HaplotypeAbundanceEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) {
 
     requireTable("HaplotypeAbundanceEstimatesWriter", estimates, table, labels);
@@ -622,6 +654,27 @@ void ReadCountGibbsSamplesWriter::addTable(const rpvg_gibbs_table_view & table, 
             out << std::endl;
         }
     }
+}
+
+void ReadCountGibbsSamplesWriter::addText(const rpvg_gibbs_table_view & table, const rpvg_table_text_view & text) {
+
+    if (table.num_gibbs_samples != num_gibbs_samples) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addText: the table has " + std::to_string(table.num_gibbs_samples) + " samples per path, the writer " + std::to_string(num_gibbs_samples));
+    }
+
+    if (text.num_paths != table.num_paths || (text.num_bytes > 0 && !text.bytes)) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addText: the text is not that of the table");
+    }
+
+    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+        noise_counts.at(idx) += table.noise_counts[idx];
+    }
+
+    out << std::setprecision(out_precision_digits);
+    out.write(text.bytes, text.num_bytes);
 }
 
 void ReadCountGibbsSamplesWriter::addNoiseTranscript(const uint32_t unaligned_read_count) {

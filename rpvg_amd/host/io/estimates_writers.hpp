@@ -21,6 +21,7 @@
 
 #include "../../../include/rpvg_table.h"
 #include "../../../include/rpvg_samples.h"
+#include "../../../include/rpvg_text.h"
 #include "../path_cluster_estimates.hpp"
 
 namespace rpvg_amd {
@@ -75,6 +76,11 @@ class AbundanceEstimatesWriter : public EstimatesWriter {
         // whose set i is not {i} (what addEstimates() asserts).
         void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
 
+        // The rows as text the GPU formatted from the table (rpvg_amd/host/table_text.hpp): the writer's noise total moves on exactly as
+        // in addTable(), then the block is appended to the stream as it is.  Throws EngineError for a table without TPMs or a text
+        // of another number of paths.
+        void addText(const rpvg_estimates_table_view & table, const rpvg_table_text_view & text);
+
     private:
 
         const double total_transcript_count;
@@ -96,6 +102,11 @@ class HaplotypeAbundanceEstimatesWriter : public EstimatesWriter {
         // writer's in one addition, where addEstimates() adds cluster by cluster onto the running value, so with several batches
         // into one writer the noise of the `Unknown` row can differ in its last digit.  Throws EngineError for a table without TPMs or labels of another size.
         void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
+
+        // The rows as text the GPU formatted from the table (rpvg_amd/host/table_text.hpp): the writer's noise total moves on exactly as
+        // in addTable(), then the block is appended to the stream as it is.  Throws EngineError for a table without TPMs or a text
+        // of another number of paths.
+        void addText(const rpvg_estimates_table_view & table, const rpvg_table_text_view & text);
 
     private:
 
@@ -160,6 +171,11 @@ class ReadCountGibbsSamplesWriter : public EstimatesWriter {
         // running values, so the `Unknown` row can then differ in its last digit.  Throws EngineError for a view of another number
         // of samples or labels of another size.
         void addTable(const rpvg_gibbs_table_view & table, const TableLabels & labels);
+
+        // The rows as text the GPU formatted from the table (rpvg_amd/host/table_text.hpp): the table's noise_counts join the writer's
+        // exactly as in addTable(), then the block is appended to the stream as it is.  Throws EngineError for a view of another
+        // number of samples or a text of another number of paths.
+        void addText(const rpvg_gibbs_table_view & table, const rpvg_table_text_view & text);
 
     private:
 

@@ -1,0 +1,222 @@
+// The rows of a result file as text, formatted on the GPU from a resident table (include/rpvg_text.h, rpvg_amd/csrc/table_text.hip):
+// the rows of ReadCountGibbsSamplesWriter, AbundanceEstimatesWriter and HaplotypeAbundanceEstimatesWriter
+// (src/threaded_output_writer.cpp:160-201, :295-322, :358-411) as one block of bytes, which the writers' addText()
+// (io/estimates_writers.hpp) append as they are.  Nothing here formats: FlatLabels flattens TableLabels, TableText forwards to the
+// GPU and holds the view.  hostLine() is the comparison line: the same row descriptors (rpvg_amd/csrc/table_text_plan.hpp) walked on
+// one host thread, for the timing of tools/table_text_ab.py and for the CPU checks.
+#ifndef RPVG_AMD_TABLE_TEXT_HPP
+#define RPVG_AMD_TABLE_TEXT_HPP
+
+#include <cstdint>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/rpvg_text.h"
+#include "../csrc/table_text_plan.hpp"
+#include "estimates_table.hpp"
+#include "gibbs_samples_table.hpp"
+#include "hip_engine.hpp"
+#include "io/estimates_writers.hpp"
+
+namespace rpvg_amd {
+
+// TableLabels in the flat form of rpvg_table_labels (host memory)
+struct FlatLabels {
+
+    std::vector<uint64_t> name_off;
+    std::string name_bytes;
+    std::vector<uint32_t> lengths, cluster_ids;
+
+    explicit FlatLabels(const TableLabels & labels) : name_off(1, 0), lengths(labels.lengths), cluster_ids(labels.cluster_ids) {
+
+        for (auto & name: labels.names) {
+
+            name_bytes += name;
+            name_off.push_back(name_bytes.size());
+        }
+    }
+
+    // valid while this lives
+    rpvg_table_labels view() const {
+
+        rpvg_table_labels flat = {};
+        flat.num_clusters = cluster_ids.size();
+        flat.num_paths = name_off.size() - 1;
+        flat.num_name_bytes = name_bytes.size();
+        flat.name_off = name_off.data();
+        flat.name_bytes = name_bytes.data();
+        flat.path_length = lengths.size() == flat.num_paths ? lengths.data() : nullptr;
+        flat.cluster_id = cluster_ids.data();
+        flat.on_device = 0;
+
+        return flat;
+    }
+};
+
+class TableText {
+
+    public:
+
+        // the rows ReadCountGibbsSamplesWriter::addTable prints from the table
+        TableText(std::shared_ptr<HipEngine> engine_in, GibbsSamplesTable & table, const int32_t precision) : hip_engine(std::move(engine_in)), text(nullptr), text_view(), has_view(false) {
+
+            const FlatLabels labels(table.labels());
+            const rpvg_table_labels flat = labels.view();
+            HipEngine::check(rpvg_hip_gibbs_table_text(hip_engine->ctx(), table.handle(), &flat, precision, &text), "rpvg_hip_gibbs_table_text");
+        }
+
+        // kind RPVG_TEXT_PER_PATH: the rows of AbundanceEstimatesWriter::addTable; RPVG_TEXT_HAPLOTYPE: those of
+        // HaplotypeAbundanceEstimatesWriter::addTable.  After EstimatesTable::tpm().
+        TableText(std::shared_ptr<HipEngine> engine_in, EstimatesTable & table, const TableLabels & table_labels, const int32_t kind, const int32_t precision) : hip_engine(std::move(engine_in)), text(nullptr), text_view(), has_view(false) {
+
+            const FlatLabels labels(table_labels);
+            const rpvg_table_labels flat = labels.view();
+            const rpvg_estimates_flat estimates = table.estimates();
+            HipEngine::check(rpvg_hip_estimates_table_text(hip_engine->ctx(), table.handle(), &estimates, &flat, kind, precision, &text), "rpvg_hip_estimates_table_text");
+        }
+
+        ~TableText() { rpvg_hip_table_text_free(text); }
+
+        TableText(const TableText &) = delete;
+        TableText & operator=(const TableText &) = delete;
+
+        // row_off and one page-locked copy of the whole text; valid until the text's end
+        const rpvg_table_text_view & view() {
+
+            if (!has_view) {
+
+                HipEngine::check(rpvg_hip_table_text_view(text, &text_view), "rpvg_hip_table_text_view");
+                has_view = true;
+            }
+
+            return text_view;
+        }
+
+        // bytes [begin, end) only, for a writer that streams a text it could not hold twice
+        std::string bytes(const uint64_t begin, const uint64_t end) {
+
+            std::string out(end > begin ? end - begin : 0, '\0');
+            HipEngine::check(rpvg_hip_table_text_get(text, begin, end, out.empty() ? nullptr : &out[0]), "rpvg_hip_table_text_get");
+
+            return out;
+        }
+
+    private:
+
+        std::shared_ptr<HipEngine> hip_engine;
+        rpvg_hip_table_text * text;
+        rpvg_table_text_view text_view;
+        bool has_view;
+};
+
+// ---- the comparison line: the same rows on one host thread ----------------------------------------------------------------------
+
+struct HostLine {
+
+    std::vector<uint64_t> row_off;
+    std::string bytes;
+    uint64_t exact_cells = 0;
+};
+
+inline const uint64_t * hostPow10Table() {
+
+    static const std::vector<uint64_t> words = [] {
+
+        std::vector<uint64_t> table(rpvg_number_text::kPow10Words);
+        rpvg_number_text::buildPow10Table(table.data(), nullptr);
+        return table;
+    }();
+
+    return words.data();
+}
+
+// the descriptor of the Gibbs rows over the host view of the table
+inline rpvg_table_text::TextRows gibbsTextRows(const rpvg_gibbs_table_view & table, const rpvg_table_labels & labels, const int32_t precision) {
+
+    rpvg_table_text::TextRows rows = {};
+    rows.num_rows = table.num_paths;
+    rows.num_clusters = table.num_clusters;
+    rows.name_off = labels.name_off;
+    rows.name_bytes = labels.name_bytes;
+    rows.cluster_path_off = table.cluster_path_off;
+    rows.cluster_id = labels.cluster_id;
+    rows.run_length = table.num_gibbs_samples;
+    rows.run = table.samples;
+    rows.run_stride = table.num_gibbs_samples;
+    rows.filter = table.listed;
+    rows.precision = precision;
+    rows.pow10 = hostPow10Table();
+
+    return rows;
+}
+
+// the descriptor of the estimates rows over the host estimates and the host view of the table; member_base is filled for the
+// per-path kind and must outlive the descriptor (set i = {i} is the caller's precondition, as it is addTable()'s)
+inline rpvg_table_text::TextRows estimatesTextRows(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const rpvg_table_labels & labels, const int32_t kind, const int32_t precision, std::vector<uint64_t> * member_base) {
+
+    rpvg_table_text::TextRows rows = {};
+    rows.num_rows = table.num_paths;
+    rows.num_clusters = table.num_clusters;
+    rows.name_off = labels.name_off;
+    rows.name_bytes = labels.name_bytes;
+    rows.cluster_path_off = estimates.cluster_path_off;
+    rows.cluster_id = labels.cluster_id;
+    rows.second_u32 = labels.path_length;
+    rows.precision = precision;
+    rows.pow10 = hostPow10Table();
+    rows.fixed[0] = rpvg_table_text::DoubleColumn{estimates.path_effective_length, nullptr};
+
+    if (kind == RPVG_TEXT_PER_PATH) {
+
+        member_base->assign(table.num_clusters, 0);
+
+        for (uint32_t k = 0; k < table.num_clusters; ++k) {
+
+            (*member_base)[k] = estimates.member_off[estimates.set_off[k]];
+        }
+
+        rows.num_fixed = 3;
+        rows.fixed[1] = rpvg_table_text::DoubleColumn{estimates.abundances, estimates.abund_off};
+        rows.fixed[2] = rpvg_table_text::DoubleColumn{table.member_tpm, member_base->data()};
+
+    } else {
+
+        rows.num_fixed = 4;
+        rows.fixed[1] = rpvg_table_text::DoubleColumn{table.haplotype_prob, nullptr};
+        rows.fixed[2] = rpvg_table_text::DoubleColumn{table.read_count, nullptr};
+        rows.fixed[3] = rpvg_table_text::DoubleColumn{table.tpm, nullptr};
+    }
+
+    return rows;
+}
+
+inline HostLine hostLine(const rpvg_table_text::TextRows & rows) {
+
+    if (const char * wrong = rpvg_table_text::descriptorBad(rows)) {
+
+        throw std::runtime_error(std::string("hostLine: ") + wrong);
+    }
+
+    HostLine line;
+    line.row_off.assign(rows.num_rows + 1, 0);
+
+    for (uint64_t r = 0; r < rows.num_rows; ++r) {
+
+        line.row_off[r + 1] = line.row_off[r] + rpvg_table_text::rowBytes(rows, r, &line.exact_cells);
+    }
+
+    line.bytes.assign(line.row_off[rows.num_rows], '\0');
+
+    for (uint64_t r = 0; r < rows.num_rows; ++r) {
+
+        rpvg_table_text::rowWrite(rows, r, &line.bytes[line.row_off[r]]);
+    }
+
+    return line;
+}
+
+}
+
+#endif

@@ -1,6 +1,7 @@
 // C entry points of the harness for the two output tables of a prepared batch: the estimates table (estimates_table.hpp;
 // include/rpvg_table.h) and the Gibbs samples table (gibbs_samples_table.hpp; include/rpvg_samples.h), each beside the same file
-// or table made from the containers by the writers' own loops.  Nothing here runs a batch (runner_capi.cpp does).
+// or table made from the containers by the writers' own loops, and the text of their rows formatted on the GPU (table_text.hpp;
+// include/rpvg_text.h) beside the same rows from one host thread.  Nothing here runs a batch (runner_capi.cpp does).
 
 #include <algorithm>
 #include <chrono>
@@ -14,6 +15,7 @@
 #include "gibbs_samples_table.hpp"
 #include "io/estimates_writers.hpp"
 #include "runner_handles.hpp"
+#include "table_text.hpp"
 
 using namespace rpvg_amd;
 using namespace rpvg_amd_harness;
@@ -102,6 +104,11 @@ void writeWith(const std::string & writer, const uint32_t ploidy, const double m
         throw std::runtime_error("no such writer: " + writer);
     }
 }
+
+// addText() of the two writers that have one (writeWith hands its callback any of the three)
+void addTextTo(AbundanceEstimatesWriter & out, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
+void addTextTo(HaplotypeAbundanceEstimatesWriter & out, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
+void addTextTo(JointHaplotypeAbundanceEstimatesWriter &, const rpvg_estimates_table_view &, const rpvg_table_text_view &) { throw std::runtime_error("the joint file has no text route"); }
 
 }
 
@@ -444,6 +451,227 @@ int rpvg_amd_gibbs_from_containers(void * prepared_batch, uint32_t num_gibbs_sam
 
         return 0;
     });
+}
+
+// ---- the text of a table's rows (table_text.hpp; include/rpvg_text.h) -----------------------------------------------------------
+
+namespace {
+
+// a text and the table handle it was made from (which must outlive it)
+struct TextHandle {
+
+    std::unique_ptr<TableText> text;
+    GibbsSamplesTable * gibbs = nullptr;
+    TableHandle * estimates = nullptr;
+    int32_t kind = 0, precision = 0;
+    std::unique_ptr<HostLine> line;  // the comparison line, once it has been walked
+};
+
+}
+
+// The rows of ReadCountGibbsSamplesWriter from a table of rpvg_amd_gibbs_table_build.  seconds_out: the build of the text.
+void * rpvg_amd_table_text_gibbs(void * engine, void * gibbs_table_handle, int32_t precision, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        std::unique_ptr<TextHandle> handle(new TextHandle());
+        handle->gibbs = static_cast<GibbsSamplesTable *>(gibbs_table_handle);
+        handle->precision = precision;
+        const auto start = std::chrono::steady_clock::now();
+        handle->text.reset(new TableText(static_cast<Engine *>(engine)->hip, *handle->gibbs, precision));
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return handle.release();
+    });
+}
+
+// The rows of AbundanceEstimatesWriter (kind RPVG_TEXT_PER_PATH) or HaplotypeAbundanceEstimatesWriter (RPVG_TEXT_HAPLOTYPE) from a
+// table of rpvg_amd_estimates_table_build, after rpvg_amd_estimates_table_tpm.
+void * rpvg_amd_table_text_estimates(void * engine, void * table_handle, int32_t kind, int32_t precision, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        std::unique_ptr<TextHandle> handle(new TextHandle());
+        handle->estimates = static_cast<TableHandle *>(table_handle);
+        handle->kind = kind;
+        handle->precision = precision;
+        const auto start = std::chrono::steady_clock::now();
+        handle->text.reset(new TableText(static_cast<Engine *>(engine)->hip, *handle->estimates->table, handle->estimates->labels, kind, precision));
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return handle.release();
+    });
+}
+
+// valid until the text's end
+int rpvg_amd_table_text_view(void * text_handle, rpvg_table_text_view * view_out) {
+
+    return guardedInt([&]() -> int {
+
+        *view_out = static_cast<TextHandle *>(text_handle)->text->view();
+        return 0;
+    });
+}
+
+// The file of the text's writer through its addText(): <prefix>.txt.gz for a Gibbs text (num_gibbs_samples the writer's),
+// <prefix>.txt for an estimates text.
+int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    return guardedInt([&]() -> int {
+
+        TextHandle * handle = static_cast<TextHandle *>(text_handle);
+
+        if (handle->gibbs) {
+
+            ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+            out.addText(handle->gibbs->view(), handle->text->view());
+            out.addNoiseTranscript(unaligned_read_count);
+            out.close();
+
+        } else {
+
+            const rpvg_estimates_table_view & view = handle->estimates->table->view();
+            const std::string writer = handle->kind == RPVG_TEXT_PER_PATH ? "abundance" : "haplotype";
+
+            writeWith(writer, handle->estimates->ploidy, 0.0, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { addTextTo(out, view, handle->text->view()); });
+        }
+
+        return 0;
+    });
+}
+
+// The same rows from the host views of the table by one host thread: the row descriptors of the kernels walked with number_text.hpp.
+// The line is kept with the handle; recompute != 0 walks again.  seconds_out: the walk alone (both passes), written when it ran.
+// bytes_out [the line's bytes] and row_off_out [P + 1] may be NULL; equal_out: whether the line's bytes and offsets are the text's.
+int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * bytes_out, uint64_t * row_off_out, uint64_t * num_bytes_out, uint64_t * exact_cells_out, int32_t * equal_out, double * seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        TextHandle * handle = static_cast<TextHandle *>(text_handle);
+
+        if (!handle->line || recompute) {
+
+            std::vector<uint64_t> member_base;
+            rpvg_table_text::TextRows rows;
+            std::unique_ptr<FlatLabels> labels;
+            rpvg_estimates_flat estimates = {};
+
+            if (handle->gibbs) {
+
+                labels.reset(new FlatLabels(handle->gibbs->labels()));
+                rows = gibbsTextRows(handle->gibbs->view(), labels->view(), handle->precision);
+                rows.second_u32 = nullptr;
+
+            } else {
+
+                labels.reset(new FlatLabels(handle->estimates->labels));
+                estimates = handle->estimates->table->estimates();
+                rows = estimatesTextRows(estimates, handle->estimates->table->view(), labels->view(), handle->kind, handle->precision, &member_base);
+            }
+
+            const auto start = std::chrono::steady_clock::now();
+            handle->line.reset(new HostLine(hostLine(rows)));
+
+            if (seconds_out) {
+
+                *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+            }
+        }
+
+        const HostLine & line = *handle->line;
+
+        if (num_bytes_out) {
+
+            *num_bytes_out = line.bytes.size();
+        }
+
+        if (exact_cells_out) {
+
+            *exact_cells_out = line.exact_cells;
+        }
+
+        if (bytes_out) {
+
+            std::copy(line.bytes.begin(), line.bytes.end(), bytes_out);
+        }
+
+        if (row_off_out) {
+
+            std::copy(line.row_off.begin(), line.row_off.end(), row_off_out);
+        }
+
+        if (equal_out) {
+
+            const rpvg_table_text_view & view = handle->text->view();
+            *equal_out = view.num_bytes == line.bytes.size() && view.num_paths + 1 == line.row_off.size() && std::equal(line.row_off.begin(), line.row_off.end(), view.row_off) &&
+                         (view.num_bytes == 0 || std::equal(line.bytes.begin(), line.bytes.end(), view.bytes));
+        }
+
+        return 0;
+    });
+}
+
+// The route the text replaces, for the timing of tools/table_text_ab.py: the table's host view (view_seconds_out: the download when
+// this is the first look at it, next to nothing afterwards) and the writer's addTable() into its stream, without the file
+// (add_seconds_out).
+int rpvg_amd_table_text_parent_route(void * text_handle, uint32_t num_gibbs_samples, double * view_seconds_out, double * add_seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        TextHandle * handle = static_cast<TextHandle *>(text_handle);
+        const auto start = std::chrono::steady_clock::now();
+        auto viewed = start;
+
+        if (handle->gibbs) {
+
+            const rpvg_gibbs_table_view & view = handle->gibbs->view();
+            viewed = std::chrono::steady_clock::now();
+            ReadCountGibbsSamplesWriter out("", num_gibbs_samples);
+            out.addTable(view, handle->gibbs->labels());
+
+        } else {
+
+            const rpvg_estimates_table_view & view = handle->estimates->table->view();
+            const rpvg_estimates_flat estimates = handle->estimates->table->estimates();
+            viewed = std::chrono::steady_clock::now();
+
+            if (handle->kind == RPVG_TEXT_PER_PATH) {
+
+                AbundanceEstimatesWriter out("", view.tpm_denominator);
+                out.addTable(estimates, view, handle->estimates->labels);
+
+            } else {
+
+                HaplotypeAbundanceEstimatesWriter out("", handle->estimates->ploidy, view.tpm_denominator);
+                out.addTable(estimates, view, handle->estimates->labels);
+            }
+        }
+
+        if (view_seconds_out) {
+
+            *view_seconds_out = std::chrono::duration<double>(viewed - start).count();
+        }
+
+        if (add_seconds_out) {
+
+            *add_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - viewed).count();
+        }
+
+        return 0;
+    });
+}
+
+void rpvg_amd_table_text_free(void * text_handle) {
+
+    delete static_cast<TextHandle *>(text_handle);
 }
 
 }

@@ -1,0 +1,178 @@
+"""The rows of a result file as text, formatted on the GPU from a resident table (include/rpvg_text.h, rpvg_amd/csrc/table_text.hip):
+the rows ReadCountGibbsSamplesWriter, AbundanceEstimatesWriter and HaplotypeAbundanceEstimatesWriter print, every double as glibc's
+"%.*g" writes it, byte for byte.  The header row and the `Unknown` row stay with the host writers.
+
+  Labels      the names, lengths and ClusterIDs of a batch's paths in the flat form of rpvg_table_labels, host arrays
+  TableText   over the C ABI (a hip.Context or an engine.Engine): gibbs / estimates / view / bytes / guards_intact / free
+  HarnessTableText  over the harness entry points: the text of a HarnessGibbsTable or a HarnessTable through the host class
+              (rpvg_amd/host/table_text.hpp), the file from it by the writer's addText(), and the same rows from one host thread
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import hip
+from ._flat import FlatArrays, HandleOwner, ctx_handle
+
+PER_PATH, HAPLOTYPE = 0, 1  # RPVG_TEXT_PER_PATH, RPVG_TEXT_HAPLOTYPE
+
+
+class CTableLabels(C.Structure):
+    """rpvg_table_labels"""
+    _fields_ = [("num_clusters", C.c_uint32), ("num_paths", C.c_uint64), ("num_name_bytes", C.c_uint64), ("name_off", C.c_void_p),
+                ("name_bytes", C.c_void_p), ("path_length", C.c_void_p), ("cluster_id", C.c_void_p), ("on_device", C.c_int32)]
+
+
+class CTableTextView(C.Structure):
+    """rpvg_table_text_view"""
+    _fields_ = [("num_paths", C.c_uint64), ("num_rows", C.c_uint64), ("num_bytes", C.c_uint64), ("row_off", C.POINTER(C.c_uint64)),
+                ("bytes", C.POINTER(C.c_char))]
+
+
+_LABEL_FIELDS = (("name_off", np.uint64), ("name_bytes", np.uint8), ("path_length", np.uint32), ("cluster_id", np.uint32))
+
+
+@dataclass
+class Labels(FlatArrays):
+    """TableLabels of rpvg_amd/host/io/estimates_writers.hpp, flat.  path_length may be empty for the Gibbs file."""
+    name_off: np.ndarray
+    name_bytes: np.ndarray
+    path_length: np.ndarray
+    cluster_id: np.ndarray
+    _FIELDS, _C_STRUCT = _LABEL_FIELDS, CTableLabels
+
+    @staticmethod
+    def of(names: Sequence, cluster_ids: Sequence[int], lengths: Optional[Sequence[int]] = None) -> "Labels":
+        """names: one str or bytes per path; cluster_ids: one per cluster; lengths: one per path, or None."""
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        off = np.zeros(len(raw) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(n) for n in raw])
+        return Labels(off, np.frombuffer(b"".join(raw), dtype=np.uint8), [] if lengths is None else lengths, cluster_ids)
+
+    def sizes(self) -> dict:
+        return dict(num_clusters=len(self.cluster_id), num_paths=max(len(self.name_off) - 1, 0), num_name_bytes=len(self.name_bytes))
+
+
+class TableText(HandleOwner):
+    """A text resident on the GPU (rpvg_hip_table_text)."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    @classmethod
+    def gibbs(cls, ctx_or_engine, table, labels, precision: int = 8) -> "TableText":
+        """table: a gibbs_table.GibbsTable; labels: Labels, or a CTableLabels (host or device pointers)."""
+        handle = C.c_void_p()
+        flat = labels.as_c() if isinstance(labels, Labels) else labels
+        hip._check(hip.lib().rpvg_hip_gibbs_table_text(ctx_handle(ctx_or_engine), table.handle, C.byref(flat), C.c_int32(precision), C.byref(handle)),
+                   "rpvg_hip_gibbs_table_text")
+        return cls(handle)
+
+    @classmethod
+    def estimates(cls, ctx_or_engine, table, estimates_flat, labels, kind: int, precision: int = 8) -> "TableText":
+        """table: an estimates_table.EstimatesTable with TPMs; estimates_flat: the CEstimatesFlat it was built from."""
+        handle = C.c_void_p()
+        flat = labels.as_c() if isinstance(labels, Labels) else labels
+        hip._check(hip.lib().rpvg_hip_estimates_table_text(ctx_handle(ctx_or_engine), table.handle, C.byref(estimates_flat), C.byref(flat), C.c_int32(kind),
+                                                          C.c_int32(precision), C.byref(handle)), "rpvg_hip_estimates_table_text")
+        return cls(handle)
+
+    def view(self) -> dict:
+        """row_off [P + 1], the text as bytes (copied out of the page-locked block), num_rows (printed)."""
+        v = CTableTextView()
+        hip._check(hip.lib().rpvg_hip_table_text_view(self.handle, C.byref(v)), "rpvg_hip_table_text_view")
+        P, n = int(v.num_paths), int(v.num_bytes)
+        return dict(row_off=np.ctypeslib.as_array(v.row_off, shape=(P + 1,)).copy(), bytes=C.string_at(v.bytes, n) if n else b"", num_rows=int(v.num_rows),
+                    num_bytes=n)
+
+    def bytes(self, begin: int, end: int) -> bytes:
+        """Bytes [begin, end) of the text (rpvg_hip_table_text_get)."""
+        out = C.create_string_buffer(max(end - begin, 1))
+        hip._check(hip.lib().rpvg_hip_table_text_get(self.handle, C.c_uint64(begin), C.c_uint64(end), out), "rpvg_hip_table_text_get")
+        return out.raw[:max(end - begin, 0)]
+
+    def guards_intact(self) -> bool:
+        """Whether the 64 pattern bytes on either side of the text on the device are as they were written."""
+        intact = C.c_int32(0)
+        hip._check(hip.lib().rpvg_hip_table_text_guards(self.handle, C.byref(intact)), "rpvg_hip_table_text_guards")
+        return bool(intact.value)
+
+    def _release(self):
+        hip.lib().rpvg_hip_table_text_free(self.handle)
+
+
+# ---- the harness: the text of a prepared batch's tables, the files from it and the host line ------------------------------------
+
+def _harness():
+    from . import engine
+    L = engine.lib()
+    L.rpvg_amd_table_text_gibbs.restype = C.c_void_p
+    L.rpvg_amd_table_text_gibbs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_estimates.restype = C.c_void_p
+    L.rpvg_amd_table_text_estimates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_view.argtypes = [C.c_void_p, C.POINTER(CTableTextView)]
+    L.rpvg_amd_table_text_write.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]
+    L.rpvg_amd_table_text_host_line.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_parent_route.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_free.argtypes = [C.c_void_p]
+    return L, engine
+
+
+class HarnessTableText(HandleOwner):
+    """The text of a harness table (gibbs_table.HarnessGibbsTable or estimates_table.HarnessTable, which must outlive it)."""
+
+    def __init__(self, engine, table, kind: Optional[int] = None, precision: int = 8):
+        L, eng = _harness()
+        secs = C.c_double(0)
+        if kind is None:
+            self.handle = L.rpvg_amd_table_text_gibbs(engine.handle, table.handle, precision, C.byref(secs))
+        else:
+            self.handle = L.rpvg_amd_table_text_estimates(engine.handle, table.handle, kind, precision, C.byref(secs))
+        if not self.handle:
+            raise hip.EngineError(f"table text failed: {eng._err()}")
+        self.build_seconds, self._table = secs.value, table
+
+    def view(self, copy: bool = True) -> dict:
+        L, eng = _harness()
+        v = CTableTextView()
+        if L.rpvg_amd_table_text_view(self.handle, C.byref(v)) != 0:
+            raise hip.EngineError(f"table text view failed: {eng._err()}")
+        P, n = int(v.num_paths), int(v.num_bytes)
+        return dict(row_off=np.ctypeslib.as_array(v.row_off, shape=(P + 1,)).copy(), bytes=C.string_at(v.bytes, n) if n and copy else b"", num_rows=int(v.num_rows),
+                    num_bytes=n)
+
+    def write(self, prefix: str, num_gibbs_samples: int = 0, unaligned_read_count: int = 0):
+        """<prefix>.txt.gz (a Gibbs text) or <prefix>.txt (an estimates text) through the writer's addText()."""
+        L, eng = _harness()
+        if L.rpvg_amd_table_text_write(self.handle, num_gibbs_samples, prefix.encode(), unaligned_read_count) != 0:
+            raise hip.EngineError(f"table text write failed: {eng._err()}")
+
+    def host_line(self, num_paths: int, want_bytes: bool = True, recompute: bool = False) -> dict:
+        """The same rows from the host views of the table on one host thread: bytes, row_off, exact_cells, seconds (of the walk,
+        when this call walked), and equal: whether bytes and row_off are the device text's (compared by the harness)."""
+        L, eng = _harness()
+        n, exact, equal, secs = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_double(0)
+        row_off = np.zeros(num_paths + 1, dtype=np.uint64)
+        if L.rpvg_amd_table_text_host_line(self.handle, int(recompute), None, row_off.ctypes.data, C.byref(n), C.byref(exact), C.byref(equal), C.byref(secs)) != 0:
+            raise hip.EngineError(f"table text host line failed: {eng._err()}")
+        out = C.create_string_buffer(max(n.value, 1) if want_bytes else 1)
+        if want_bytes and L.rpvg_amd_table_text_host_line(self.handle, 0, out, None, None, None, None, None) != 0:
+            raise hip.EngineError(f"table text host line failed: {eng._err()}")
+        return dict(bytes=out.raw[:n.value] if want_bytes else b"", row_off=row_off, exact_cells=int(exact.value), seconds=secs.value, num_bytes=int(n.value),
+                    equal=bool(equal.value))
+
+    def parent_route(self, num_gibbs_samples: int = 0):
+        """(seconds of the table's host view, seconds of the writer's addTable() into its stream): the route the text replaces."""
+        L, eng = _harness()
+        viewed, added = C.c_double(0), C.c_double(0)
+        if L.rpvg_amd_table_text_parent_route(self.handle, num_gibbs_samples, C.byref(viewed), C.byref(added)) != 0:
+            raise hip.EngineError(f"table text parent route failed: {eng._err()}")
+        return viewed.value, added.value
+
+    def _release(self):
+        _harness()[0].rpvg_amd_table_text_free(self.handle)
