@@ -851,6 +851,17 @@ int rpvg_hip_gibbs_table_build_resident(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs
  *                                 Both refuse, before anything is queued, a precision outside 1 .. 17 and labels whose sizes are not
  *                                 the table's; a name_off that is not a non-decreasing sequence of offsets from 0 to num_name_bytes
  *                                 is refused by a kernel before any text kernel runs (last_error names the smallest offending path).
+ *   rpvg_hip_estimates_set_text    the rows whose unit is a path group set (rpvg_text.h): RPVG_TEXT_JOINT, the rows of
+ *                                 JointHaplotypeAbundanceEstimatesWriter (src/threaded_output_writer.cpp:434-546), from a table with its
+ *                                 TPMs that was built for `ploidy`; RPVG_TEXT_POSTERIOR, the rows of JointHaplotypeEstimatesWriter
+ *                                 (:233-280), which reads neither abundances nor TPMs.  A set is printed iff
+ *                                 !(posterior < min_posterior).  Refused before anything is queued: a precision outside 1 .. 17, a
+ *                                 ploidy outside 1 .. 8, a joint text from a table without TPMs or of another ploidy, labels whose
+ *                                 sizes are not the table's.  Refused by a kernel before any text kernel runs: offsets that do not
+ *                                 run from 0 to their totals, a set whose size is not in 1 .. ploidy, a member that is no path of its
+ *                                 cluster and, for the joint kind, a cluster without one abundance per member (last_error names the
+ *                                 smallest offending path, else the smallest offending cluster).  The handle is that of the other
+ *                                 texts: in its view num_paths is the number of sets S and row_off has S + 1 entries.
  *   rpvg_hip_table_text_view       row_off and ONE copy of the whole text into page-locked memory of the library's pool.
  *   rpvg_hip_table_text_get        bytes [byte_begin, byte_end) of the text to host memory: a writer streams a text of gigabytes in pieces.
  *   rpvg_hip_table_text_guards     test hook: the text lies in a device block between two runs of 64 pattern bytes; *intact_out says
@@ -859,6 +870,9 @@ int rpvg_hip_gibbs_table_text(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs_table * t
                               rpvg_hip_table_text ** text_out);
 int rpvg_hip_estimates_table_text(rpvg_hip_ctx * ctx, const rpvg_hip_estimates_table * table, const rpvg_estimates_flat * estimates,
                                   const rpvg_table_labels * labels, int32_t kind, int32_t precision, rpvg_hip_table_text ** text_out);
+int rpvg_hip_estimates_set_text(rpvg_hip_ctx * ctx, const rpvg_hip_estimates_table * table, const rpvg_estimates_flat * estimates,
+                                const rpvg_table_labels * labels, int32_t kind, uint32_t ploidy, double min_posterior, int32_t precision,
+                                rpvg_hip_table_text ** text_out);
 int rpvg_hip_table_text_view(rpvg_hip_table_text * text, rpvg_table_text_view * view_out);
 int rpvg_hip_table_text_get(rpvg_hip_table_text * text, uint64_t byte_begin, uint64_t byte_end, char * dst);
 int rpvg_hip_table_text_guards(rpvg_hip_table_text * text, int32_t * intact_out);
@@ -964,7 +978,7 @@ typedef struct rpvg_hip_kernel_stats {
     /* rpvg_hip_min_path_cover_any: clusters that took the whole-GPU route (path_cover_grid.hip) and the paths their greedy rounds chose */
     uint64_t cover_grid_problems;
     uint64_t cover_grid_rounds;
-    /* rpvg_hip_gibbs_table_text, rpvg_hip_estimates_table_text: cells whose rounding was decided by the exact multiword comparison
+    /* rpvg_hip_gibbs_table_text, rpvg_hip_estimates_table_text, rpvg_hip_estimates_set_text: cells whose rounding was decided by the exact multiword comparison
      * (exact ties and doubles within 2^-60 relative of one; rpvg_amd/csrc/number_text.hpp) */
     uint64_t text_exact_cells;
     /* rpvg_hip_nested_full_subset_em: calls that returned RPVG_HIP_OK with at least one matrix, the sets they enumerated and the

@@ -40,8 +40,15 @@ typedef struct rpvg_table_labels {
 #define RPVG_TEXT_PER_PATH 0  /* name, ClusterID, Length, EffectiveLength, abundance, member_tpm  (AbundanceEstimatesWriter) */
 #define RPVG_TEXT_HAPLOTYPE 1 /* name, ClusterID, Length, EffectiveLength, haplotype_prob, read_count, tpm  (HaplotypeAbundanceEstimatesWriter) */
 
+/* The rows of a set text (rpvg_hip_estimates_set_text): one per path group set s of cluster k, n = its number of members (1 .. ploidy),
+ *   ( name(member) '\t' ){n} ( '.' '\t' ){ploidy - n}  ClusterID '\t' posterior  [ joint: ( '\t' abundance '\t' member_tpm ){n} ( "\t0\t0" ){ploidy - n} ]  '\n'
+ * printed iff !(posterior < min_posterior): a posterior equal to min_posterior and a NaN posterior are printed. */
+#define RPVG_TEXT_JOINT 2     /* JointHaplotypeAbundanceEstimatesWriter (src/threaded_output_writer.cpp:434-546): needs the table's TPMs and one abundance per member */
+#define RPVG_TEXT_POSTERIOR 3 /* JointHaplotypeEstimatesWriter (src/threaded_output_writer.cpp:233-280): no pairs; needs neither abundances nor TPMs */
+
 /* Host copies of a text (valid until the text is freed).  Row g lies in bytes [row_off[g], row_off[g + 1]); a path that is not
- * printed has an empty range. */
+ * printed has an empty range.  In the view of a set text the rows are the sets: num_paths is the number of sets S, row_off has
+ * S + 1 entries, and a set that is not printed has an empty range. */
 typedef struct rpvg_table_text_view {
     uint64_t num_paths;
     uint64_t num_rows;                  /* printed */

@@ -398,7 +398,7 @@ const char * const kReasons[] = {"",
 // for table_text.hip
 rpvg_hip_detail::EstimatesTableResident rpvg_hip_detail::residentOf(const rpvg_hip_estimates_table * table) {
     return EstimatesTableResident{table->num_clusters, table->num_paths, table->num_members, table->has_tpm, table->haplotype_prob.ptr,
-                                  table->read_count.ptr, table->tpm.ptr, table->member_tpm.ptr};
+                                  table->read_count.ptr, table->tpm.ptr, table->member_tpm.ptr, table->ploidy};
 }
 
 extern "C" {

@@ -1,6 +1,6 @@
-// What every device table needs (align_index.hip, path_table.hip, estimates_table.hip, gibbs_table.hip, table_text.hip): one validated flat input,
+// What every device table needs (align_index.hip, path_table.hip, estimates_table.hip, gibbs_table.hip, table_text.hip, set_text.hip): one validated flat input,
 // one build call, one resident handle, one host view.  Nothing here knows a particular table; a helper is here because at least two
-// of the five files call it.
+// of the six files call it.
 //
 // The first part is pure computation in plain C++17 under the RPVG_PLAN_FN convention of the *_plan.hpp files, so a CPU program
 // reaches it (tests/cpp/table_kit_check.cpp); the second part, under hipcc only, needs common.hpp.

@@ -24,6 +24,7 @@ struct EstimatesTableResident {
     bool has_tpm;
     const double * haplotype_prob, * read_count, * tpm;  // device [P]
     const double * member_tpm;                           // device [M]
+    uint32_t ploidy;                                     // the table was built for
 };
 
 GibbsTableResident residentOf(const rpvg_hip_gibbs_table * table);

@@ -25,36 +25,22 @@
 //              the first steps (a piece of kMaxCellBytes bytes per lane), the integer columns the first cells.
 //              The write pass formats again instead of reading lengths the measure pass would have kept (a byte per cell).
 // The text lies between two guards of 64 pattern bytes (rpvg_hip_table_text_guards).
+// The handle, the guards, the staging block's flush and the wave sum are in table_text_device.hpp, shared with set_text.hip (the rows
+// whose unit is a path group set), whose texts _view, _get, _guards and _free below serve as they serve the ones built here.
 
 #include <mutex>
 
 #include "device_algos.hpp"
 #include "table_kit.hpp"
 #include "table_residents.hpp"
+#include "table_text_device.hpp"
 #include "table_text_plan.hpp"
 #include "../../include/rpvg_text.h"
 
 using namespace rpvg_hip_detail;
 using namespace rpvg_table_text;
 
-struct rpvg_hip_table_text {
-    rpvg_hip_ctx * ctx = nullptr;
-    uint64_t num_paths = 0, num_rows = 0, num_bytes = 0;
-    DeviceBuffer<char> block;  // guard, text, guard
-    std::vector<uint64_t> h_row_off;
-    void * pinned = nullptr;   // the host copy of the text
-    ~rpvg_hip_table_text() {
-        if (pinned) pinnedFree(pinned);
-    }
-    char * text() const { return block.ptr + 64; }
-};
-
 namespace {
-
-constexpr int kBlock = 256;
-constexpr uint64_t kGuardBytes = 64;
-constexpr unsigned char kGuardPattern = 0xa5;
-constexpr uint32_t kMaxWriteBlocks = 1u << 20;
 
 // bad = min over the offending paths and clusters (table_kit.hpp: a cluster is the second kind, so a path comes before every cluster)
 enum TextBad { kBadNameOff = 1, kBadPathOff = 2, kBadSetOff = 3, kBadAbundOff = 4, kBadSetCount = 5, kBadNotSingleton = 6 };
@@ -107,11 +93,6 @@ __global__ __launch_bounds__(kBlock) void describeKernel(const TextRows t, const
     }
 }
 
-__device__ __forceinline__ uint64_t waveSum(uint64_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(static_cast<unsigned long long>(v), d, 64);
-    return __shfl(static_cast<unsigned long long>(v), 0, 64);
-}
-
 // row_len [P+1]: the bytes of every row and a trailing 0
 template <bool kWavefront>
 __global__ __launch_bounds__(kBlock) void measureKernel(const TextRows t, uint64_t * __restrict__ row_len, word64 * exact_cells) {
@@ -139,30 +120,6 @@ __global__ __launch_bounds__(kBlock) void measureKernel(const TextRows t, uint64
     }
     exact = waveSum(exact);
     if (lane == 0 && exact) atomicAdd(exact_cells, static_cast<word64>(exact));
-}
-
-// the wavefront's staging block leaves (table_text_plan.hpp); [lo, hi) and base are uniform
-__device__ __forceinline__ void flush(char * stage, char * text, uint64_t & base, uint32_t & lo, uint32_t & hi, const bool last, const uint32_t lane) {
-    __syncthreads();  // the step's stores into the block
-    const FlushPlan p = flushPlan(lo, hi);
-    char * out = text + base;
-    if (lane >= lo && lane < p.head_end) out[lane] = stage[lane];
-    const uint32_t * words = reinterpret_cast<const uint32_t *>(stage);
-    uint32_t * out_words = reinterpret_cast<uint32_t *>(out);
-    for (uint32_t w = p.first_word + lane; w < p.end_word; w += 64) out_words[w] = words[w];
-    const uint32_t behind = hi - p.tail_begin;  // at most 3
-    if (last) {
-        if (lane < behind) out[p.tail_begin + lane] = stage[p.tail_begin + lane];
-        __syncthreads();  // the block is free for the next row
-        return;
-    }
-    char carried = 0;
-    if (lane < behind) carried = stage[p.tail_begin + lane];
-    __syncthreads();
-    if (lane < behind) stage[p.next_lo + lane] = carried;
-    base += p.advance;
-    lo = p.next_lo;
-    hi = p.next_hi;
 }
 
 // a workgroup of one wavefront per row (the rows in a grid-stride loop)
@@ -201,18 +158,6 @@ __global__ __launch_bounds__(64) void writeKernel(const TextRows t, const uint64
             flush(stage, text, base, lo, hi, c0 + kStepCells >= cells, lane);
         }
     }
-}
-
-__global__ __launch_bounds__(128) void guardKernel(char * block, const uint64_t num_bytes) {
-    const uint32_t i = threadIdx.x;
-    block[i < kGuardBytes ? i : num_bytes + i] = static_cast<char>(kGuardPattern);
-}
-
-const uint64_t * pow10Table() {
-    static uint64_t words[rpvg_number_text::kPow10Words];
-    static std::once_flag once;
-    std::call_once(once, [] { rpvg_number_text::buildPow10Table(words, nullptr); });
-    return words;
 }
 
 // what an entry point hands over: the descriptor with the table's device pointers in place, the labels and what came with the call

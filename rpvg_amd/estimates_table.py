@@ -150,6 +150,7 @@ class EstimatesTable(HandleOwner):
 # ---- the harness: the table of a prepared batch's estimates and the result files from it -----------------------------------------
 
 WRITERS = ("abundance", "haplotype", "joint")  # <prefix>.txt, <prefix>.txt, <prefix>_joint.txt
+POSTERIOR_WRITER = "posterior"                 # <prefix>.txt of a `haplotypes` result: no TPMs, no `Unknown` row, no transcript count
 
 
 def _harness():

@@ -460,6 +460,32 @@ void JointHaplotypeAbundanceEstimatesWriter::addTable(const rpvg_estimates_flat 
     }
 }
 
+void JointHaplotypeAbundanceEstimatesWriter::addText(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) {
+
+    if (!table.has_tpm) {
+
+        throw EngineError("JointHaplotypeAbundanceEstimatesWriter::addText: the table has no TPMs yet (EstimatesTable::tpm)");
+    }
+
+    if (table.ploidy != ploidy) {
+
+        throw EngineError("JointHaplotypeAbundanceEstimatesWriter::addText: the table was built for ploidy " + std::to_string(table.ploidy) + ", the writer for " + std::to_string(ploidy));
+    }
+
+    if (text.num_paths != estimates.num_sets || estimates.num_members != table.num_members || (text.num_bytes > 0 && !text.bytes)) {
+
+        throw EngineError("JointHaplotypeAbundanceEstimatesWriter::addText: the text is not that of the table's sets");
+    }
+
+    out << std::setprecision(out_precision_digits);
+    out.write(text.bytes, text.num_bytes);
+
+    for (auto & noise_count: noise_counts) {
+
+        noise_count += table.noise_count_share_total;
+    }
+}
+
 JointHaplotypeEstimatesWriter::JointHaplotypeEstimatesWriter(const std::string filename_prefix, const uint32_t ploidy_in, const double min_posterior_in) : EstimatesWriter(filename_prefix + ".txt"), ploidy(ploidy_in), min_posterior(min_posterior_in) {
 
     for (uint32_t i = 0; i < ploidy; ++i) {
@@ -502,6 +528,83 @@ void JointHaplotypeEstimatesWriter::addEstimates(const ClusterEstimatesList & pa
             out << cur_estimates.first << "\t" << estimates.posteriors.at(i) << std::endl;
         }
     }
+}
+
+void JointHaplotypeEstimatesWriter::addTable(const rpvg_estimates_flat & estimates, const TableLabels & labels) {
+
+    if (estimates.on_device) {
+
+        throw EngineError("JointHaplotypeEstimatesWriter::addTable: the estimates are device memory");
+    }
+
+    if (labels.names.size() != estimates.num_paths || labels.cluster_ids.size() != estimates.num_clusters) {
+
+        throw EngineError("JointHaplotypeEstimatesWriter::addTable: one name per path and one ClusterID per cluster");
+    }
+
+    // every cluster is checked before a row is written
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        const uint64_t num_paths = estimates.cluster_path_off[k + 1] - estimates.cluster_path_off[k];
+
+        for (uint64_t s = estimates.set_off[k]; s < estimates.set_off[k + 1]; ++s) {
+
+            const uint64_t set_size = estimates.member_off[s + 1] - estimates.member_off[s];
+
+            if (set_size == 0 || set_size > ploidy) {
+
+                throw EngineError("JointHaplotypeEstimatesWriter::addTable: cluster " + std::to_string(k) + " has a set of " + std::to_string(set_size) + " paths");
+            }
+
+            for (uint64_t m = estimates.member_off[s]; m < estimates.member_off[s + 1]; ++m) {
+
+                if (estimates.members[m] >= num_paths) {
+
+                    throw EngineError("JointHaplotypeEstimatesWriter::addTable: cluster " + std::to_string(k) + " has a set member that is not one of its paths");
+                }
+            }
+        }
+    }
+
+    out << std::setprecision(out_precision_digits);
+
+    for (uint32_t k = 0; k < estimates.num_clusters; ++k) {
+
+        const uint64_t first_path = estimates.cluster_path_off[k];
+
+        for (uint64_t s = estimates.set_off[k]; s < estimates.set_off[k + 1]; ++s) {
+
+            if (estimates.posteriors[s] < min_posterior) {
+
+                continue;
+            }
+
+            const uint64_t set_begin = estimates.member_off[s], set_end = estimates.member_off[s + 1];
+
+            for (uint64_t m = set_begin; m < set_end; ++m) {
+
+                out << labels.names[first_path + estimates.members[m]] << "\t";
+            }
+
+            for (uint64_t j = set_end - set_begin; j < ploidy; ++j) {
+
+                out << ".\t";
+            }
+
+            out << labels.cluster_ids[k] << "\t" << estimates.posteriors[s] << std::endl;
+        }
+    }
+}
+
+void JointHaplotypeEstimatesWriter::addText(const rpvg_estimates_flat & estimates, const rpvg_table_text_view & text) {
+
+    if (text.num_paths != estimates.num_sets || (text.num_bytes > 0 && !text.bytes)) {
+
+        throw EngineError("JointHaplotypeEstimatesWriter::addText: the text is not that of the estimates' sets");
+    }
+
+    out << std::setprecision(out_precision_digits);
+    out.write(text.bytes, text.num_bytes);
 }
 
 ReadCountGibbsSamplesWriter::ReadCountGibbsSamplesWriter(const std::string filename_prefix, const uint32_t num_gibbs_samples_in) : EstimatesWriter(filename_prefix + ".txt.gz"), num_gibbs_samples(num_gibbs_samples_in), noise_counts(num_gibbs_samples_in, 0) {

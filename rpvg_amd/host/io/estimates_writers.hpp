@@ -132,6 +132,12 @@ class JointHaplotypeAbundanceEstimatesWriter : public EstimatesWriter {
         // another ploidy (its noise share is noise_count / ploidy).
         void addTable(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels);
 
+        // The rows as text the GPU formatted from the table (TableText::sets with RPVG_TEXT_JOINT, this writer's ploidy and
+        // min_posterior; rpvg_amd/host/table_text.hpp): the writer's noise shares move on exactly as in addTable(), then the block is
+        // appended to the stream as it is.  Throws EngineError for a table without TPMs or of another ploidy and for a text of
+        // another number of sets than the estimates'.
+        void addText(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text);
+
     private:
 
         const uint32_t ploidy;
@@ -147,6 +153,16 @@ class JointHaplotypeEstimatesWriter : public EstimatesWriter {
         JointHaplotypeEstimatesWriter(const std::string filename_prefix, const uint32_t ploidy_in, const double min_posterior_in);
 
         void addEstimates(const ClusterEstimatesList & path_cluster_estimates);
+
+        // The same rows from the flat estimates of a batch (host memory) and its labels: the text is what addEstimates() writes
+        // from the containers, byte for byte.  A `haplotypes` result has neither abundances nor TPMs and none are read.  Throws
+        // EngineError for labels of another size, a set whose size is not in 1 .. ploidy (what addEstimates() asserts) and a set
+        // member that is not a path of its cluster.
+        void addTable(const rpvg_estimates_flat & estimates, const TableLabels & labels);
+
+        // The rows as text the GPU formatted (TableText::sets with RPVG_TEXT_POSTERIOR, this writer's ploidy and min_posterior):
+        // the block is appended to the stream as it is.  Throws EngineError for a text of another number of sets than the estimates'.
+        void addText(const rpvg_estimates_flat & estimates, const rpvg_table_text_view & text);
 
     private:
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/rpvg_text.h"
+#include "../csrc/set_text_plan.hpp"
 #include "../csrc/table_text_plan.hpp"
 #include "estimates_table.hpp"
 #include "gibbs_samples_table.hpp"
@@ -77,6 +78,20 @@ class TableText {
             HipEngine::check(rpvg_hip_estimates_table_text(hip_engine->ctx(), table.handle(), &estimates, &flat, kind, precision, &text), "rpvg_hip_estimates_table_text");
         }
 
+        // The rows whose unit is a path group set.  kind RPVG_TEXT_JOINT: the rows of JointHaplotypeAbundanceEstimatesWriter::addTable,
+        // after EstimatesTable::tpm(), from a table built for `ploidy`; RPVG_TEXT_POSTERIOR: the rows of
+        // JointHaplotypeEstimatesWriter::addTable, which need neither abundances nor TPMs.  In the view num_paths is the number of sets.
+        static std::unique_ptr<TableText> sets(std::shared_ptr<HipEngine> engine_in, EstimatesTable & table, const TableLabels & table_labels, const int32_t kind, const uint32_t ploidy, const double min_posterior, const int32_t precision) {
+
+            std::unique_ptr<TableText> out(new TableText(std::move(engine_in)));
+            const FlatLabels labels(table_labels);
+            const rpvg_table_labels flat = labels.view();
+            const rpvg_estimates_flat estimates = table.estimates();
+            HipEngine::check(rpvg_hip_estimates_set_text(out->hip_engine->ctx(), table.handle(), &estimates, &flat, kind, ploidy, min_posterior, precision, &out->text), "rpvg_hip_estimates_set_text");
+
+            return out;
+        }
+
         ~TableText() { rpvg_hip_table_text_free(text); }
 
         TableText(const TableText &) = delete;
@@ -104,6 +119,8 @@ class TableText {
         }
 
     private:
+
+        explicit TableText(std::shared_ptr<HipEngine> engine_in) : hip_engine(std::move(engine_in)), text(nullptr), text_view(), has_view(false) {}
 
         std::shared_ptr<HipEngine> hip_engine;
         rpvg_hip_table_text * text;
@@ -212,6 +229,60 @@ inline HostLine hostLine(const rpvg_table_text::TextRows & rows) {
     for (uint64_t r = 0; r < rows.num_rows; ++r) {
 
         rpvg_table_text::rowWrite(rows, r, &line.bytes[line.row_off[r]]);
+    }
+
+    return line;
+}
+
+// the descriptor of the set rows over the host estimates and the host view of the table (which the posterior kind does not read)
+inline rpvg_set_text::SetRows setsTextRows(const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const rpvg_table_labels & labels, const int32_t kind, const uint32_t ploidy, const double min_posterior, const int32_t precision) {
+
+    const bool joint = kind == RPVG_TEXT_JOINT;
+
+    rpvg_set_text::SetRows rows = {};
+    rows.num_sets = estimates.num_sets;
+    rows.num_clusters = estimates.num_clusters;
+    rows.ploidy = ploidy;
+    rows.joint = joint;
+    rows.name_off = labels.name_off;
+    rows.name_bytes = labels.name_bytes;
+    rows.cluster_path_off = estimates.cluster_path_off;
+    rows.cluster_id = labels.cluster_id;
+    rows.set_off = estimates.set_off;
+    rows.member_off = estimates.member_off;
+    rows.members = estimates.members;
+    rows.posteriors = estimates.posteriors;
+    rows.abund_off = joint ? estimates.abund_off : nullptr;
+    rows.abundances = joint ? estimates.abundances : nullptr;
+    rows.member_tpm = joint ? table.member_tpm : nullptr;
+    rows.min_posterior = min_posterior;
+    rows.precision = precision;
+    rows.pow10 = hostPow10Table();
+
+    return rows;
+}
+
+// the comparison line of the set rows (valid sets are the caller's precondition, as they are addTable()'s)
+inline HostLine hostLineSets(const rpvg_set_text::SetRows & rows) {
+
+    if (const char * wrong = rpvg_set_text::descriptorBad(rows)) {
+
+        throw std::runtime_error(std::string("hostLineSets: ") + wrong);
+    }
+
+    HostLine line;
+    line.row_off.assign(rows.num_sets + 1, 0);
+
+    for (uint64_t s = 0; s < rows.num_sets; ++s) {
+
+        line.row_off[s + 1] = line.row_off[s] + rpvg_set_text::rowBytes(rows, s, &line.exact_cells);
+    }
+
+    line.bytes.assign(line.row_off[rows.num_sets], '\0');
+
+    for (uint64_t s = 0; s < rows.num_sets; ++s) {
+
+        rpvg_set_text::rowWrite(rows, s, &line.bytes[line.row_off[s]]);
     }
 
     return line;

@@ -74,7 +74,8 @@ ClusterEstimatesList labelledListOf(const Prepared & prepared) {
 }
 
 // "abundance": <prefix>.txt of AbundanceEstimatesWriter; "haplotype": <prefix>.txt of HaplotypeAbundanceEstimatesWriter; "joint":
-// <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter.  add(writer) adds the rows.
+// <prefix>_joint.txt of JointHaplotypeAbundanceEstimatesWriter; "posterior": <prefix>.txt of JointHaplotypeEstimatesWriter, which has no
+// `Unknown` row.  add(writer) adds the rows.
 template <typename AddRows>
 void writeWith(const std::string & writer, const uint32_t ploidy, const double min_posterior, const double denominator, const std::string & prefix, const uint32_t unaligned_read_count, AddRows add) {
 
@@ -99,16 +100,27 @@ void writeWith(const std::string & writer, const uint32_t ploidy, const double m
         out.addNoiseTranscript(unaligned_read_count);
         out.close();
 
+    } else if (writer == "posterior") {
+
+        JointHaplotypeEstimatesWriter out(prefix, ploidy, min_posterior);
+        add(out);
+        out.close();
+
     } else {
 
         throw std::runtime_error("no such writer: " + writer);
     }
 }
 
-// addText() of the two writers that have one (writeWith hands its callback any of the three)
-void addTextTo(AbundanceEstimatesWriter & out, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
-void addTextTo(HaplotypeAbundanceEstimatesWriter & out, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
-void addTextTo(JointHaplotypeAbundanceEstimatesWriter &, const rpvg_estimates_table_view &, const rpvg_table_text_view &) { throw std::runtime_error("the joint file has no text route"); }
+// addText() and addTable() of the four writers behind one signature (writeWith hands its callback any of them)
+void addTextTo(AbundanceEstimatesWriter & out, const rpvg_estimates_flat &, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
+void addTextTo(HaplotypeAbundanceEstimatesWriter & out, const rpvg_estimates_flat &, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(table, text); }
+void addTextTo(JointHaplotypeAbundanceEstimatesWriter & out, const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const rpvg_table_text_view & text) { out.addText(estimates, table, text); }
+void addTextTo(JointHaplotypeEstimatesWriter & out, const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view &, const rpvg_table_text_view & text) { out.addText(estimates, text); }
+
+template <typename Writer>
+void addTableTo(Writer & out, const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view & table, const TableLabels & labels) { out.addTable(estimates, table, labels); }
+void addTableTo(JointHaplotypeEstimatesWriter & out, const rpvg_estimates_flat & estimates, const rpvg_estimates_table_view &, const TableLabels & labels) { out.addTable(estimates, labels); }
 
 }
 
@@ -198,7 +210,8 @@ int rpvg_amd_estimates_table_view(void * table_handle, rpvg_estimates_table_view
     });
 }
 
-// One of the three files from the table (after rpvg_amd_estimates_table_tpm): writer = "abundance", "haplotype" or "joint".
+// One of the four files from the table (after rpvg_amd_estimates_table_tpm, which "posterior" does not need): writer = "abundance",
+// "haplotype", "joint" or "posterior".
 int rpvg_amd_estimates_table_write(void * table_handle, const char * writer, double min_posterior, const char * output_prefix, uint32_t unaligned_read_count) {
 
     return guardedInt([&]() -> int {
@@ -207,7 +220,7 @@ int rpvg_amd_estimates_table_write(void * table_handle, const char * writer, dou
         const rpvg_estimates_flat estimates = handle->table->estimates();
         const rpvg_estimates_table_view & view = handle->table->view();
 
-        writeWith(writer, handle->ploidy, min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { out.addTable(estimates, view, handle->labels); });
+        writeWith(writer, handle->ploidy, min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { addTableTo(out, estimates, view, handle->labels); });
         return 0;
     });
 }
@@ -233,8 +246,10 @@ int rpvg_amd_estimates_write_from_containers(void * prepared_batch, const char *
 
         const ClusterEstimatesList list = labelledListOf(*prepared);
 
+        // (a `haplotypes` result has no abundances to sum: the "posterior" writer takes no denominator)
+        const bool has_total = !(writer && std::string(writer) == "posterior");
         const auto start = std::chrono::steady_clock::now();
-        const double total = totalTranscriptCount(list);
+        const double total = has_total ? totalTranscriptCount(list) : 0.0;
         const auto stop = std::chrono::steady_clock::now();
 
         if (total_transcript_count_out) {
@@ -464,6 +479,9 @@ struct TextHandle {
     GibbsSamplesTable * gibbs = nullptr;
     TableHandle * estimates = nullptr;
     int32_t kind = 0, precision = 0;
+    bool sets = false;               // a set text: kind RPVG_TEXT_JOINT or RPVG_TEXT_POSTERIOR
+    uint32_t ploidy = 0;
+    double min_posterior = 0;
     std::unique_ptr<HostLine> line;  // the comparison line, once it has been walked
 };
 
@@ -511,6 +529,31 @@ void * rpvg_amd_table_text_estimates(void * engine, void * table_handle, int32_t
     });
 }
 
+// The rows of JointHaplotypeAbundanceEstimatesWriter (kind RPVG_TEXT_JOINT, after rpvg_amd_estimates_table_tpm) or of
+// JointHaplotypeEstimatesWriter (RPVG_TEXT_POSTERIOR) from a table of rpvg_amd_estimates_table_build: a row per path group set.
+void * rpvg_amd_table_text_sets(void * engine, void * table_handle, int32_t kind, uint32_t ploidy, double min_posterior, int32_t precision, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        std::unique_ptr<TextHandle> handle(new TextHandle());
+        handle->estimates = static_cast<TableHandle *>(table_handle);
+        handle->kind = kind;
+        handle->precision = precision;
+        handle->sets = true;
+        handle->ploidy = ploidy;
+        handle->min_posterior = min_posterior;
+        const auto start = std::chrono::steady_clock::now();
+        handle->text = TableText::sets(static_cast<Engine *>(engine)->hip, *handle->estimates->table, handle->estimates->labels, kind, ploidy, min_posterior, precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return handle.release();
+    });
+}
+
 // valid until the text's end
 int rpvg_amd_table_text_view(void * text_handle, rpvg_table_text_view * view_out) {
 
@@ -522,7 +565,7 @@ int rpvg_amd_table_text_view(void * text_handle, rpvg_table_text_view * view_out
 }
 
 // The file of the text's writer through its addText(): <prefix>.txt.gz for a Gibbs text (num_gibbs_samples the writer's),
-// <prefix>.txt for an estimates text.
+// <prefix>.txt for an estimates text (<prefix>_joint.txt for the joint set text).
 int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
 
     return guardedInt([&]() -> int {
@@ -539,9 +582,10 @@ int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, co
         } else {
 
             const rpvg_estimates_table_view & view = handle->estimates->table->view();
-            const std::string writer = handle->kind == RPVG_TEXT_PER_PATH ? "abundance" : "haplotype";
+            const rpvg_estimates_flat estimates = handle->estimates->table->estimates();
+            const std::string writer = handle->sets ? (handle->kind == RPVG_TEXT_JOINT ? "joint" : "posterior") : (handle->kind == RPVG_TEXT_PER_PATH ? "abundance" : "haplotype");
 
-            writeWith(writer, handle->estimates->ploidy, 0.0, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { addTextTo(out, view, handle->text->view()); });
+            writeWith(writer, handle->sets ? handle->ploidy : handle->estimates->ploidy, handle->min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { addTextTo(out, estimates, view, handle->text->view()); });
         }
 
         return 0;
@@ -550,7 +594,7 @@ int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, co
 
 // The same rows from the host views of the table by one host thread: the row descriptors of the kernels walked with number_text.hpp.
 // The line is kept with the handle; recompute != 0 walks again.  seconds_out: the walk alone (both passes), written when it ran.
-// bytes_out [the line's bytes] and row_off_out [P + 1] may be NULL; equal_out: whether the line's bytes and offsets are the text's.
+// For a set text the line is hostLineSets() and the rows are the sets.  bytes_out [the line's bytes] and row_off_out [P + 1] may be NULL; equal_out: whether the line's bytes and offsets are the text's.
 int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * bytes_out, uint64_t * row_off_out, uint64_t * num_bytes_out, uint64_t * exact_cells_out, int32_t * equal_out, double * seconds_out) {
 
     return guardedInt([&]() -> int {
@@ -560,7 +604,8 @@ int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * 
         if (!handle->line || recompute) {
 
             std::vector<uint64_t> member_base;
-            rpvg_table_text::TextRows rows;
+            rpvg_table_text::TextRows rows = {};
+            rpvg_set_text::SetRows set_rows = {};
             std::unique_ptr<FlatLabels> labels;
             rpvg_estimates_flat estimates = {};
 
@@ -570,6 +615,12 @@ int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * 
                 rows = gibbsTextRows(handle->gibbs->view(), labels->view(), handle->precision);
                 rows.second_u32 = nullptr;
 
+            } else if (handle->sets) {
+
+                labels.reset(new FlatLabels(handle->estimates->labels));
+                estimates = handle->estimates->table->estimates();
+                set_rows = setsTextRows(estimates, handle->estimates->table->view(), labels->view(), handle->kind, handle->ploidy, handle->min_posterior, handle->precision);
+
             } else {
 
                 labels.reset(new FlatLabels(handle->estimates->labels));
@@ -578,7 +629,7 @@ int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * 
             }
 
             const auto start = std::chrono::steady_clock::now();
-            handle->line.reset(new HostLine(hostLine(rows)));
+            handle->line.reset(new HostLine(handle->sets ? hostLineSets(set_rows) : hostLine(rows)));
 
             if (seconds_out) {
 
@@ -643,7 +694,17 @@ int rpvg_amd_table_text_parent_route(void * text_handle, uint32_t num_gibbs_samp
             const rpvg_estimates_flat estimates = handle->estimates->table->estimates();
             viewed = std::chrono::steady_clock::now();
 
-            if (handle->kind == RPVG_TEXT_PER_PATH) {
+            if (handle->sets && handle->kind == RPVG_TEXT_JOINT) {
+
+                JointHaplotypeAbundanceEstimatesWriter out("", handle->ploidy, handle->min_posterior, view.tpm_denominator);
+                out.addTable(estimates, view, handle->estimates->labels);
+
+            } else if (handle->sets) {
+
+                JointHaplotypeEstimatesWriter out("", handle->ploidy, handle->min_posterior);
+                out.addTable(estimates, handle->estimates->labels);
+
+            } else if (handle->kind == RPVG_TEXT_PER_PATH) {
 
                 AbundanceEstimatesWriter out("", view.tpm_denominator);
                 out.addTable(estimates, view, handle->estimates->labels);

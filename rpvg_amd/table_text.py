@@ -19,6 +19,7 @@ from . import hip
 from ._flat import FlatArrays, HandleOwner, ctx_handle
 
 PER_PATH, HAPLOTYPE = 0, 1  # RPVG_TEXT_PER_PATH, RPVG_TEXT_HAPLOTYPE
+JOINT, POSTERIOR = 2, 3     # RPVG_TEXT_JOINT, RPVG_TEXT_POSTERIOR: a row per path group set (TableText.sets)
 
 
 class CTableLabels(C.Structure):
@@ -81,6 +82,18 @@ class TableText(HandleOwner):
                                                           C.c_int32(precision), C.byref(handle)), "rpvg_hip_estimates_table_text")
         return cls(handle)
 
+    @classmethod
+    def sets(cls, ctx_or_engine, table, estimates_flat, labels, kind: int, ploidy: int, min_posterior: float, precision: int = 8) -> "TableText":
+        """A row per path group set.  JOINT: the rows of JointHaplotypeAbundanceEstimatesWriter, from a table with TPMs built for
+        `ploidy`; POSTERIOR: those of JointHaplotypeEstimatesWriter, which read neither abundances nor TPMs.  A set is printed iff
+        not (posterior < min_posterior).  In the view the rows are the sets: row_off has num_sets + 1 entries."""
+        handle = C.c_void_p()
+        flat = labels.as_c() if isinstance(labels, Labels) else labels
+        hip._check(hip.lib().rpvg_hip_estimates_set_text(ctx_handle(ctx_or_engine), table.handle, C.byref(estimates_flat), C.byref(flat), C.c_int32(kind),
+                                                        C.c_uint32(ploidy), C.c_double(min_posterior), C.c_int32(precision), C.byref(handle)),
+                   "rpvg_hip_estimates_set_text")
+        return cls(handle)
+
     def view(self) -> dict:
         """row_off [P + 1], the text as bytes (copied out of the page-locked block), num_rows (printed)."""
         v = CTableTextView()
@@ -114,6 +127,8 @@ def _harness():
     L.rpvg_amd_table_text_gibbs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_estimates.restype = C.c_void_p
     L.rpvg_amd_table_text_estimates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_sets.restype = C.c_void_p
+    L.rpvg_amd_table_text_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_double, C.c_int32, C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_view.argtypes = [C.c_void_p, C.POINTER(CTableTextView)]
     L.rpvg_amd_table_text_write.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]
     L.rpvg_amd_table_text_host_line.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
@@ -126,11 +141,15 @@ def _harness():
 class HarnessTableText(HandleOwner):
     """The text of a harness table (gibbs_table.HarnessGibbsTable or estimates_table.HarnessTable, which must outlive it)."""
 
-    def __init__(self, engine, table, kind: Optional[int] = None, precision: int = 8):
+    def __init__(self, engine, table, kind: Optional[int] = None, precision: int = 8, ploidy: int = 0, min_posterior: float = 0.0):
+        """kind None: the Gibbs text; PER_PATH, HAPLOTYPE: a row per path; JOINT, POSTERIOR: a row per path group set, for a writer of
+        `ploidy` and `min_posterior` (in view() and host_line() the rows are then the sets)."""
         L, eng = _harness()
         secs = C.c_double(0)
         if kind is None:
             self.handle = L.rpvg_amd_table_text_gibbs(engine.handle, table.handle, precision, C.byref(secs))
+        elif kind in (JOINT, POSTERIOR):
+            self.handle = L.rpvg_amd_table_text_sets(engine.handle, table.handle, kind, ploidy, min_posterior, precision, C.byref(secs))
         else:
             self.handle = L.rpvg_amd_table_text_estimates(engine.handle, table.handle, kind, precision, C.byref(secs))
         if not self.handle:
