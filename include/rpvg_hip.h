@@ -873,6 +873,23 @@ int rpvg_hip_estimates_table_text(rpvg_hip_ctx * ctx, const rpvg_hip_estimates_t
 int rpvg_hip_estimates_set_text(rpvg_hip_ctx * ctx, const rpvg_hip_estimates_table * table, const rpvg_estimates_flat * estimates,
                                 const rpvg_table_labels * labels, int32_t kind, uint32_t ploidy, double min_posterior, int32_t precision,
                                 rpvg_hip_table_text ** text_out);
+/*   rpvg_hip_rows_text             the --write-probs dump (rpvg_text.h; rpvg_amd/csrc/rows_text.hip) from host or device arrays: marker,
+ *                                 path line and row lines of every cluster that has paths and rows.  labels: the names and
+ *                                 path_length of the P paths (cluster_id is not read).  Refused before anything is queued: a
+ *                                 prob_precision outside (0, 1) or one that asks for more than 17 digits, one rank-key array without
+ *                                 the other, labels whose sizes are not the input's or without path_length, 2^31 - 1 or more lines
+ *                                 (2 K + R) or cells (3 K + 3 P + 2 R + G + M).  Refused by a kernel before any text kernel runs:
+ *                                 offsets that do not run from 0 to their totals and a path_idx that is not below its cluster's path
+ *                                 count (last_error names the array and the smallest offending position).  The handle is that of the
+ *                                 other texts: in its view num_paths is the number of lines and row_off has 2 K + R + 1 entries.
+ *   rpvg_hip_read_rows_text        the same from resident rows (rpvg_hip_read_rows_build), read where they lie: nothing is downloaded
+ *                                 and the rows stay usable.  labels: those of the rows' columns (the name groups of a collapsed
+ *                                 build); path_effective_length [P] host; num_align_lists and cluster_index [K] host, both or NULL. */
+int rpvg_hip_rows_text(rpvg_hip_ctx * ctx, const rpvg_rows_text_input * input, const rpvg_table_labels * labels, double prob_precision,
+                       rpvg_hip_table_text ** text_out);
+int rpvg_hip_read_rows_text(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows, const rpvg_table_labels * labels,
+                            const double * path_effective_length, const uint64_t * num_align_lists, const uint64_t * cluster_index,
+                            double prob_precision, rpvg_hip_table_text ** text_out);
 int rpvg_hip_table_text_view(rpvg_hip_table_text * text, rpvg_table_text_view * view_out);
 int rpvg_hip_table_text_get(rpvg_hip_table_text * text, uint64_t byte_begin, uint64_t byte_end, char * dst);
 int rpvg_hip_table_text_guards(rpvg_hip_table_text * text, int32_t * intact_out);
@@ -978,7 +995,7 @@ typedef struct rpvg_hip_kernel_stats {
     /* rpvg_hip_min_path_cover_any: clusters that took the whole-GPU route (path_cover_grid.hip) and the paths their greedy rounds chose */
     uint64_t cover_grid_problems;
     uint64_t cover_grid_rounds;
-    /* rpvg_hip_gibbs_table_text, rpvg_hip_estimates_table_text, rpvg_hip_estimates_set_text: cells whose rounding was decided by the exact multiword comparison
+    /* rpvg_hip_gibbs_table_text, rpvg_hip_estimates_table_text, rpvg_hip_estimates_set_text, rpvg_hip_rows_text, rpvg_hip_read_rows_text: cells whose rounding was decided by the exact multiword comparison
      * (exact ties and doubles within 2^-60 relative of one; rpvg_amd/csrc/number_text.hpp) */
     uint64_t text_exact_cells;
     /* rpvg_hip_nested_full_subset_em: calls that returned RPVG_HIP_OK with at least one matrix, the sets they enumerated and the

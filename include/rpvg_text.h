@@ -59,6 +59,37 @@ typedef struct rpvg_table_text_view {
 
 typedef struct rpvg_hip_table_text rpvg_hip_table_text;
 
+/* The --write-probs dump (rpvg_hip_rows_text, rpvg_hip_read_rows_text; rpvg_amd/csrc/rows_text.hip): the file of
+ * ProbabilityClusterWriter::addCluster (src/threaded_output_writer.cpp:40-95).  For cluster k with at least one path and one row
+ *   "#\n"                                   or, with rank keys,   "# " num_align_lists[k] " " cluster_index[k] "\n"
+ *   name(p) "," path_length[p] "," path_effective_length[p]      for every path of the cluster, a ' ' between paths, then "\n"
+ *   row_count[r] " " row_noise[r] ( " " grp_prob[g] ":" idx "," idx ... ){groups of r} "\n"                 for every row
+ * with the effective length at 8 digits and row_noise and grp_prob at max(8, ceil(-log10(prob_precision))) digits; any other
+ * cluster has no bytes.  The rows of the text's view are its LINES: num_paths is L = 2 K + R, line 2 k + cluster_row_off[k] is the
+ * marker of cluster k, the next its path line and line 2 (k + 1) + r row r of cluster k; a skipped cluster's lines are empty.
+ *
+ * The input: the row fields of rpvg_cluster_batch (rpvg_batch.h) in their 64-bit-offset form with their sizes beside them, and the
+ * path side the dump prints.  on_device = 0: host pointers, copied by the call; 1: device pointers of the context's GPU. */
+typedef struct rpvg_rows_text_input {
+    uint32_t num_clusters;                 /* K */
+    uint64_t num_rows;                     /* R */
+    uint64_t num_groups;                   /* G */
+    uint64_t num_entries;                  /* M */
+    uint64_t num_paths;                    /* P */
+    const uint64_t * cluster_row_off;      /* [K+1] from 0 to R */
+    const uint64_t * cluster_path_off;     /* [K+1] from 0 to P */
+    const uint32_t * row_count;            /* [R] */
+    const double * row_noise;              /* [R] */
+    const uint64_t * row_grp_off;          /* [R+1] from 0 to G */
+    const double * grp_prob;               /* [G] */
+    const uint64_t * grp_idx_off;          /* [G+1] from 0 to M */
+    const uint32_t * path_idx;             /* [M] cluster-local: below the path count of the row's cluster */
+    const double * path_effective_length;  /* [P] */
+    const uint64_t * num_align_lists;      /* [K] or NULL: bare "#" markers */
+    const uint64_t * cluster_index;        /* [K], given iff num_align_lists is */
+    int32_t on_device;
+} rpvg_rows_text_input;
+
 #ifdef __cplusplus
 }
 #endif

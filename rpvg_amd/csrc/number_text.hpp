@@ -339,6 +339,34 @@ RPVG_PLAN_FN int formatU32(const uint32_t x, char * out) {
     return n;
 }
 
+RPVG_PLAN_FN int decimalDigits64(const uint64_t x) {
+    if (x <= 0xffffffffull) return decimalDigits(static_cast<uint32_t>(x));
+    int n = 10;
+    uint64_t power = 10000000000ull;  // 10^10 .. 10^19 < 2^64
+    for (int i = 10; i <= 19; ++i) {
+        if (x >= power) n = i + 1;
+        if (i < 19) power *= 10u;
+    }
+    return n;
+}
+
+// x in decimal: at most 20 bytes, no terminator; returns their number
+RPVG_PLAN_FN int formatU64(const uint64_t x, char * out) {
+    const int n = decimalDigits64(x), skipped = 20 - n;
+    const uint32_t high = static_cast<uint32_t>(x / 10000000000000000ull);  // four digits
+    const uint64_t rest = x % 10000000000000000ull;
+    const auto put = [&](const int j, const uint32_t digit) {
+        if (j >= skipped) out[j - skipped] = static_cast<char>('0' + digit);
+    };
+    put(0, high / 1000u);
+    put(1, high / 100u % 10u);
+    put(2, high / 10u % 10u);
+    put(3, high % 10u);
+    eightDigits(static_cast<uint32_t>(rest / 100000000ull), 4, put);
+    eightDigits(static_cast<uint32_t>(rest % 100000000ull), 12, put);
+    return n;
+}
+
 // ---- the table of powers of ten (host) ----------------------------------------------------------------------------------------
 
 namespace big {

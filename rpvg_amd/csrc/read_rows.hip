@@ -35,6 +35,7 @@
 #include "frag_length.hpp"
 #include "read_rows.hpp"
 #include "rows_plan.hpp"
+#include "rows_residents.hpp"
 #include "table_kit.hpp"
 
 using namespace rpvg_hip_detail;
@@ -891,6 +892,13 @@ extern "C" int rpvg_hip_read_rows_sizes(rpvg_hip_ctx * ctx, const rpvg_hip_read_
     view->cluster_row_off = rows->h_cluster_row_off.data();
     view->cluster_path_off = rows->h_cluster_path_off.data();
     return RPVG_HIP_OK;
+}
+
+// the device arrays of the rows where they lie (rows_residents.hpp: rows_text.hip formats the --write-probs dump from them)
+ReadRowsResident rpvg_hip_detail::residentOf(const rpvg_hip_read_rows * rows) {
+    return ReadRowsResident{rows->num_clusters,       rows->num_rows,        rows->num_groups,      rows->num_members,   rows->h_cluster_row_off.data(),
+                            rows->h_cluster_path_off.data(), rows->cluster_row_off.ptr, rows->row_grp_off.ptr, rows->grp_idx_off.ptr, rows->row_count.ptr,
+                            rows->path_idx.ptr,       rows->row_noise.ptr,   rows->grp_prob.ptr};
 }
 
 // rows -> the device-resident batch the estimators take, without leaving the GPU: the shell and the routine of the upload

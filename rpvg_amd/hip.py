@@ -49,7 +49,7 @@ EXPORTS = [
     "rpvg_hip_gibbs_table_build", "rpvg_hip_gibbs_table_view", "rpvg_hip_gibbs_table_rows", "rpvg_hip_gibbs_table_limits", "rpvg_hip_gibbs_table_free",
     "rpvg_hip_gibbs_read_counts_resident", "rpvg_hip_gibbs_samples_get", "rpvg_hip_gibbs_samples_free", "rpvg_hip_gibbs_table_build_resident",
     "rpvg_hip_gibbs_table_text", "rpvg_hip_estimates_table_text", "rpvg_hip_table_text_view", "rpvg_hip_table_text_get", "rpvg_hip_table_text_guards",
-    "rpvg_hip_table_text_free", "rpvg_hip_estimates_set_text",
+    "rpvg_hip_table_text_free", "rpvg_hip_estimates_set_text", "rpvg_hip_rows_text", "rpvg_hip_read_rows_text",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
     "rpvg_hip_segment_sort_words",
@@ -430,6 +430,13 @@ class DeviceRows:
         _check(lib().rpvg_hip_read_rows_to_batch_with_paths(self.ctx.handle, self.handle, index.handle, table.handle, C.byref(h)),
                "rpvg_hip_read_rows_to_batch_with_paths")
         return DeviceBatch.from_handle(self.ctx, h, K, P)
+
+    def text(self, labels, effective_lengths, prob_precision: float = 1e-8, num_align_lists=None, cluster_index=None):
+        """The --write-probs dump of the rows as a table_text.TableText, formatted on the GPU from the resident arrays: nothing is
+        downloaded and the rows stay usable.  labels: table_text.Labels of the rows' columns with path_length (the name groups of a
+        collapsed build); effective_lengths: one per column; num_align_lists and cluster_index: both or neither, one per cluster."""
+        from . import table_text
+        return table_text.TableText.resident_rows(self.ctx, self.handle, labels, effective_lengths, prob_precision, num_align_lists, cluster_index)
 
     def free(self):
         if self.handle:

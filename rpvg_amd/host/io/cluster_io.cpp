@@ -8,6 +8,8 @@
 
 #include <zlib.h>
 
+#include "../../csrc/rows_text_plan.hpp"
+
 namespace rpvg_amd {
 
 namespace {
@@ -52,7 +54,20 @@ std::string readTextFile(const std::string & filename) {
     return text;
 }
 
+namespace {
+
+void writeBytes(const std::string & filename, const char * data, const size_t size);
+
+}
+
 void writeTextFile(const std::string & filename, const std::string & text) {
+
+    writeBytes(filename, text.data(), text.size());
+}
+
+namespace {
+
+void writeBytes(const std::string & filename, const char * data, const size_t size) {
 
     const bool gzip = filename.size() > 3 && filename.compare(filename.size() - 3, 3, ".gz") == 0;
 
@@ -66,9 +81,9 @@ void writeTextFile(const std::string & filename, const std::string & text) {
 
     size_t written = 0;
 
-    while (written < text.size()) {
+    while (written < size) {
 
-        const int chunk = gzwrite(file, text.data() + written, std::min<size_t>(text.size() - written, 1 << 30));
+        const int chunk = gzwrite(file, data + written, std::min<size_t>(size - written, 1 << 30));
 
         if (chunk <= 0) {
 
@@ -81,8 +96,6 @@ void writeTextFile(const std::string & filename, const std::string & text) {
 
     gzclose(file);
 }
-
-namespace {
 
 std::vector<std::string> splitString(const std::string & text, const char delim) {
 
@@ -218,10 +231,11 @@ std::vector<ProbabilityCluster> readProbabilityClusters(const std::string & file
     return clusters;
 }
 
-void writeProbabilityClusters(const std::string & filename, const std::vector<ProbabilityCluster> & clusters, const double prob_precision) {
+std::string formatProbabilityClusters(const std::vector<ProbabilityCluster> & clusters, const double prob_precision) {
 
-    // digits as the reference chooses them (src/threaded_output_writer.cpp:40)
-    const uint32_t prob_precision_digits = std::max(out_precision_digits, static_cast<uint32_t>(std::ceil(-1 * std::log10(prob_precision))));
+    // digits as the reference chooses them (src/threaded_output_writer.cpp:40): the one expression of the device text too
+    static_assert(out_precision_digits == rpvg_rows_text::kPathDigits, "the path line's digits");
+    const uint32_t prob_precision_digits = rpvg_rows_text::probPrecisionDigits(prob_precision);
 
     std::stringstream out;
 
@@ -269,7 +283,17 @@ void writeProbabilityClusters(const std::string & filename, const std::vector<Pr
         }
     }
 
-    writeTextFile(filename, out.str());
+    return out.str();
+}
+
+void writeProbabilityClusters(const std::string & filename, const std::vector<ProbabilityCluster> & clusters, const double prob_precision) {
+
+    writeTextFile(filename, formatProbabilityClusters(clusters, prob_precision));
+}
+
+void writeProbabilityClustersText(const std::string & filename, const rpvg_table_text_view & text) {
+
+    writeBytes(filename, text.bytes, text.num_bytes);
 }
 
 std::unordered_map<std::string, PathInfo> parseHaplotypeTranscriptInfo(const std::string & filename, const bool parse_haplotype_ids, const bool use_transcript_names) {

@@ -11,6 +11,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../../include/rpvg_text.h"
 #include "../path_cluster_estimates.hpp"
 #include "../read_path_probabilities.hpp"
 
@@ -41,6 +42,12 @@ std::vector<ProbabilityCluster> readProbabilityClusters(const std::string & file
 // Same format as the reference's writer (a block whose cluster has a rank key gets the extended marker line); gzip when the
 // name ends in ".gz".
 void writeProbabilityClusters(const std::string & filename, const std::vector<ProbabilityCluster> & clusters, const double prob_precision);
+
+// ... its text, without the file
+std::string formatProbabilityClusters(const std::vector<ProbabilityCluster> & clusters, const double prob_precision);
+
+// The same file from a text formatted on the GPU (TableText::rows, table_text.hpp): the block goes into the file as it is.
+void writeProbabilityClustersText(const std::string & filename, const rpvg_table_text_view & text);
 
 // Path name -> PathInfo with group_id (dense transcript ids in first-seen order), source_count and — when
 // parse_haplotype_ids — source_ids (dense haplotype ids in first-seen order); use_transcript_names

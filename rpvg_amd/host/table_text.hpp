@@ -14,11 +14,13 @@
 #include <vector>
 
 #include "../../include/rpvg_text.h"
+#include "../csrc/rows_text_plan.hpp"
 #include "../csrc/set_text_plan.hpp"
 #include "../csrc/table_text_plan.hpp"
 #include "estimates_table.hpp"
 #include "gibbs_samples_table.hpp"
 #include "hip_engine.hpp"
+#include "io/cluster_io.hpp"
 #include "io/estimates_writers.hpp"
 
 namespace rpvg_amd {
@@ -56,6 +58,123 @@ struct FlatLabels {
     }
 };
 
+// The rows and paths of a --write-probs dump in the flat form of rpvg_rows_text_input and rpvg_table_labels (host memory): a copy of
+// such arrays, or the clusters of the writer (io/cluster_io.hpp) flattened.
+struct FlatRows {
+
+    std::vector<uint64_t> cluster_row_off, cluster_path_off, row_grp_off, grp_idx_off, num_align_lists, cluster_index, name_off;
+    std::vector<uint32_t> row_count, path_idx, path_length;
+    std::vector<double> row_noise, grp_prob, path_effective_length;
+    std::string name_bytes;
+
+    // host pointers; the sizes are the input's
+    FlatRows(const rpvg_rows_text_input & in, const rpvg_table_labels & labels) {
+
+        const size_t K = in.num_clusters, R = in.num_rows, G = in.num_groups, M = in.num_entries, P = in.num_paths;
+
+        if (in.on_device || labels.on_device || labels.num_paths != P || (P && !labels.path_length)) {
+
+            throw std::runtime_error("FlatRows: host arrays and labels with path_length of the input's paths");
+        }
+
+        const auto copy = [](auto & into, const auto * from, const size_t n) { if (from) into.assign(from, from + n); };
+        copy(cluster_row_off, in.cluster_row_off, K + 1);
+        copy(cluster_path_off, in.cluster_path_off, K + 1);
+        copy(row_count, in.row_count, R);
+        copy(row_noise, in.row_noise, R);
+        copy(row_grp_off, in.row_grp_off, R + 1);
+        copy(grp_prob, in.grp_prob, G);
+        copy(grp_idx_off, in.grp_idx_off, G + 1);
+        copy(path_idx, in.path_idx, M);
+        copy(path_effective_length, in.path_effective_length, P);
+        copy(num_align_lists, in.num_align_lists, K);
+        copy(cluster_index, in.cluster_index, K);
+        copy(name_off, labels.name_off, P + 1);
+        copy(path_length, labels.path_length, P);
+        copy(name_bytes, labels.name_bytes, labels.num_name_bytes);
+        has_rank_keys = in.num_align_lists && in.cluster_index;
+    }
+
+    // rank keys in the markers iff every cluster has one (an empty list: none)
+    explicit FlatRows(const std::vector<ProbabilityCluster> & clusters) : cluster_row_off(1, 0), cluster_path_off(1, 0), row_grp_off(1, 0), grp_idx_off(1, 0), name_off(1, 0) {
+
+        has_rank_keys = !clusters.empty();
+
+        for (auto & cluster: clusters) {
+
+            has_rank_keys = has_rank_keys && cluster.has_rank_key;
+            num_align_lists.emplace_back(cluster.num_align_lists);
+            cluster_index.emplace_back(cluster.cluster_index);
+
+            for (auto & path: cluster.paths) {
+
+                name_bytes += path.name;
+                name_off.emplace_back(name_bytes.size());
+                path_length.emplace_back(path.length);
+                path_effective_length.emplace_back(path.effective_length);
+            }
+
+            for (auto & read_path_probs: cluster.cluster_probs) {
+
+                row_count.emplace_back(read_path_probs.readCount());
+                row_noise.emplace_back(read_path_probs.noiseProb());
+
+                for (auto & path_probs: read_path_probs.pathProbs()) {
+
+                    grp_prob.emplace_back(path_probs.first);
+                    path_idx.insert(path_idx.end(), path_probs.second.begin(), path_probs.second.end());
+                    grp_idx_off.emplace_back(path_idx.size());
+                }
+
+                row_grp_off.emplace_back(grp_prob.size());
+            }
+
+            cluster_row_off.emplace_back(row_count.size());
+            cluster_path_off.emplace_back(path_length.size());
+        }
+    }
+
+    // valid while this lives
+    rpvg_rows_text_input input() const {
+
+        rpvg_rows_text_input in = {};
+        in.num_clusters = cluster_row_off.empty() ? 0 : cluster_row_off.size() - 1;
+        in.num_rows = row_count.size();
+        in.num_groups = grp_prob.size();
+        in.num_entries = path_idx.size();
+        in.num_paths = path_length.size();
+        in.cluster_row_off = cluster_row_off.data();
+        in.cluster_path_off = cluster_path_off.data();
+        in.row_count = row_count.data();
+        in.row_noise = row_noise.data();
+        in.row_grp_off = row_grp_off.data();
+        in.grp_prob = grp_prob.data();
+        in.grp_idx_off = grp_idx_off.data();
+        in.path_idx = path_idx.data();
+        in.path_effective_length = path_effective_length.data();
+        in.num_align_lists = has_rank_keys ? num_align_lists.data() : nullptr;
+        in.cluster_index = has_rank_keys ? cluster_index.data() : nullptr;
+
+        return in;
+    }
+
+    // (cluster_id is not read by the dump)
+    rpvg_table_labels labels() const {
+
+        rpvg_table_labels flat = {};
+        flat.num_clusters = cluster_row_off.empty() ? 0 : cluster_row_off.size() - 1;
+        flat.num_paths = path_length.size();
+        flat.num_name_bytes = name_bytes.size();
+        flat.name_off = name_off.data();
+        flat.name_bytes = name_bytes.data();
+        flat.path_length = path_length.data();
+
+        return flat;
+    }
+
+    bool has_rank_keys = false;
+};
+
 class TableText {
 
     public:
@@ -88,6 +207,34 @@ class TableText {
             const rpvg_table_labels flat = labels.view();
             const rpvg_estimates_flat estimates = table.estimates();
             HipEngine::check(rpvg_hip_estimates_set_text(out->hip_engine->ctx(), table.handle(), &estimates, &flat, kind, ploidy, min_posterior, precision, &out->text), "rpvg_hip_estimates_set_text");
+
+            return out;
+        }
+
+        // The --write-probs dump (ProbabilityClusterWriter::addCluster, src/threaded_output_writer.cpp:40-95) of flat rows, host or
+        // device arrays: in the view the rows are the 2 K + R lines of the text.  writeProbabilityClustersText (io/cluster_io.hpp)
+        // puts the view into the file.
+        static std::unique_ptr<TableText> rows(std::shared_ptr<HipEngine> engine_in, const rpvg_rows_text_input & input, const rpvg_table_labels & labels, const double prob_precision) {
+
+            std::unique_ptr<TableText> out(new TableText(std::move(engine_in)));
+            HipEngine::check(rpvg_hip_rows_text(out->hip_engine->ctx(), &input, &labels, prob_precision, &out->text), "rpvg_hip_rows_text");
+
+            return out;
+        }
+
+        // ... of the writer's clusters, flattened
+        static std::unique_ptr<TableText> rows(std::shared_ptr<HipEngine> engine_in, const std::vector<ProbabilityCluster> & clusters, const double prob_precision) {
+
+            const FlatRows flat(clusters);
+
+            return rows(std::move(engine_in), flat.input(), flat.labels(), prob_precision);
+        }
+
+        // ... of resident rows (rpvg_hip_read_rows_build), read where they lie; labels and effective lengths of the rows' columns
+        static std::unique_ptr<TableText> rows(std::shared_ptr<HipEngine> engine_in, const rpvg_hip_read_rows * resident, const rpvg_table_labels & labels, const double * path_effective_length, const uint64_t * num_align_lists, const uint64_t * cluster_index, const double prob_precision) {
+
+            std::unique_ptr<TableText> out(new TableText(std::move(engine_in)));
+            HipEngine::check(rpvg_hip_read_rows_text(out->hip_engine->ctx(), resident, &labels, path_effective_length, num_align_lists, cluster_index, prob_precision, &out->text), "rpvg_hip_read_rows_text");
 
             return out;
         }
@@ -283,6 +430,68 @@ inline HostLine hostLineSets(const rpvg_set_text::SetRows & rows) {
     for (uint64_t s = 0; s < rows.num_sets; ++s) {
 
         rpvg_set_text::rowWrite(rows, s, &line.bytes[line.row_off[s]]);
+    }
+
+    return line;
+}
+
+// the descriptor of the dump over host arrays (prob_precision in (0, 1) and at most 17 digits are the caller's precondition)
+inline rpvg_rows_text::DumpRows dumpTextRows(const rpvg_rows_text_input & input, const rpvg_table_labels & labels, const double prob_precision) {
+
+    if (const char * wrong = rpvg_rows_text::probPrecisionBad(prob_precision)) {
+
+        throw std::runtime_error(std::string("dumpTextRows: ") + wrong);
+    }
+
+    rpvg_rows_text::DumpRows rows = {};
+    rows.num_clusters = input.num_clusters;
+    rows.num_rows = input.num_rows;
+    rows.num_groups = input.num_groups;
+    rows.num_entries = input.num_entries;
+    rows.num_paths = input.num_paths;
+    rows.cluster_row_off = input.cluster_row_off;
+    rows.cluster_path_off = input.cluster_path_off;
+    rows.row_count = input.row_count;
+    rows.row_noise = input.row_noise;
+    rows.row_grp_off = input.row_grp_off;
+    rows.grp_prob = input.grp_prob;
+    rows.grp_idx_off = input.grp_idx_off;
+    rows.path_idx = input.path_idx;
+    rows.name_off = labels.name_off;
+    rows.name_bytes = labels.name_bytes;
+    rows.path_length = labels.path_length;
+    rows.path_effective_length = input.path_effective_length;
+    rows.num_align_lists = input.num_align_lists;
+    rows.cluster_index = input.cluster_index;
+    rows.digits = rpvg_rows_text::probPrecisionDigits(prob_precision);
+    rows.pow10 = hostPow10Table();
+
+    return rows;
+}
+
+// the comparison line of the dump: rowWrite walked on one thread (valid offsets and indices are the caller's precondition); the rows
+// of the line are the 2 K + R lines of the text
+inline HostLine hostLineRows(const rpvg_rows_text::DumpRows & rows) {
+
+    if (const char * wrong = rpvg_rows_text::descriptorBad(rows)) {
+
+        throw std::runtime_error(std::string("hostLineRows: ") + wrong);
+    }
+
+    const uint64_t num_lines = rpvg_rows_text::numLines(rows);
+    HostLine line;
+    line.row_off.assign(num_lines + 1, 0);
+
+    for (uint64_t j = 0; j < num_lines; ++j) {
+
+        line.row_off[j + 1] = line.row_off[j] + rpvg_rows_text::rowBytes(rows, j, &line.exact_cells);
+    }
+
+    line.bytes.assign(line.row_off[num_lines], '\0');
+
+    for (uint64_t j = 0; j < num_lines; ++j) {
+
+        rpvg_rows_text::rowWrite(rows, j, &line.bytes[line.row_off[j]]);
     }
 
     return line;

@@ -483,7 +483,93 @@ struct TextHandle {
     uint32_t ploidy = 0;
     double min_posterior = 0;
     std::unique_ptr<HostLine> line;  // the comparison line, once it has been walked
+    // a rows text (the --write-probs dump): a host copy of its arrays, made at the build from arrays and on demand from resident rows
+    bool rows = false;
+    Engine * engine = nullptr;
+    std::unique_ptr<FlatRows> flat;
+    rpvg_hip_read_rows * resident = nullptr;
+    std::vector<double> effective_lengths;
+    std::vector<uint64_t> num_align_lists, cluster_index;
+    std::unique_ptr<FlatLabels> resident_labels;
+    std::vector<uint32_t> resident_lengths;
+    double prob_precision = 0;
 };
+
+// the host arrays of a rows text; for resident rows their view (seconds_out: that download, when this is the first look at them)
+const FlatRows & flatRowsOf(TextHandle * handle, double * view_seconds_out) {
+
+    const auto start = std::chrono::steady_clock::now();
+
+    if (!handle->flat) {
+
+        rpvg_cluster_batch view = {};
+        HipEngine::check(rpvg_hip_read_rows_view(handle->engine->hip->ctx(), handle->resident, &view, nullptr, nullptr), "rpvg_hip_read_rows_view");
+
+        if (view_seconds_out) {
+
+            *view_seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        const uint32_t K = view.num_clusters;
+        rpvg_rows_text_input input = {};
+        input.num_clusters = K;
+        input.num_rows = K ? view.cluster_row_off[K] : 0;
+        input.num_groups = input.num_rows ? view.row_grp_off[input.num_rows] : 0;
+        input.num_entries = input.num_groups ? view.grp_idx_off[input.num_groups] : 0;
+        input.num_paths = K ? view.cluster_path_off[K] : 0;
+        input.cluster_row_off = view.cluster_row_off;
+        input.cluster_path_off = view.cluster_path_off;
+        input.row_count = view.row_count;
+        input.row_noise = view.row_noise;
+        input.row_grp_off = view.row_grp_off;
+        input.grp_prob = view.grp_prob;
+        input.grp_idx_off = view.grp_idx_off;
+        input.path_idx = view.path_idx;
+        input.path_effective_length = handle->effective_lengths.data();
+        input.num_align_lists = handle->num_align_lists.empty() ? nullptr : handle->num_align_lists.data();
+        input.cluster_index = handle->cluster_index.empty() ? nullptr : handle->cluster_index.data();
+        rpvg_table_labels labels = handle->resident_labels->view();
+        labels.path_length = handle->resident_lengths.data();
+        handle->flat.reset(new FlatRows(input, labels));
+    }
+
+    return *handle->flat;
+}
+
+// the writer's clusters of flat rows, as io_capi.cpp's clustersFromBatch builds them: one ReadPathProbabilities per row
+std::vector<ProbabilityCluster> clustersOf(const FlatRows & flat, const double prob_precision) {
+
+    std::vector<ProbabilityCluster> clusters(flat.cluster_row_off.size() - 1);
+
+    for (size_t k = 0; k < clusters.size(); ++k) {
+
+        for (uint64_t p = flat.cluster_path_off[k]; p < flat.cluster_path_off[k + 1]; ++p) {
+
+            PathInfo path(flat.name_bytes.substr(flat.name_off[p], flat.name_off[p + 1] - flat.name_off[p]));
+            path.length = flat.path_length[p];
+            path.effective_length = flat.path_effective_length[p];
+            clusters[k].paths.emplace_back(std::move(path));
+        }
+
+        for (uint64_t r = flat.cluster_row_off[k]; r < flat.cluster_row_off[k + 1]; ++r) {
+
+            ReadPathProbabilities::PathProbs path_probs;
+
+            for (uint64_t g = flat.row_grp_off[r]; g < flat.row_grp_off[r + 1]; ++g) {
+
+                path_probs.emplace_back(flat.grp_prob[g], std::vector<uint32_t>(flat.path_idx.begin() + flat.grp_idx_off[g], flat.path_idx.begin() + flat.grp_idx_off[g + 1]));
+            }
+
+            clusters[k].cluster_probs.emplace_back(flat.row_count[r], flat.row_noise[r], path_probs, prob_precision);
+        }
+
+        clusters[k].has_rank_key = flat.has_rank_keys;
+        clusters[k].num_align_lists = flat.has_rank_keys ? flat.num_align_lists[k] : 0;
+        clusters[k].cluster_index = flat.has_rank_keys ? flat.cluster_index[k] : 0;
+    }
+
+    return clusters;
+}
 
 }
 
@@ -554,6 +640,114 @@ void * rpvg_amd_table_text_sets(void * engine, void * table_handle, int32_t kind
     });
 }
 
+// The --write-probs dump of flat rows in host memory (TableText::rows): in view() and host_line() the rows are the 2 K + R lines.
+void * rpvg_amd_table_text_rows(void * engine, const rpvg_rows_text_input * input, const rpvg_table_labels * labels, double prob_precision, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        std::unique_ptr<TextHandle> handle(new TextHandle());
+        handle->rows = true;
+        handle->engine = static_cast<Engine *>(engine);
+        handle->prob_precision = prob_precision;
+        handle->flat.reset(new FlatRows(*input, *labels));
+        const auto start = std::chrono::steady_clock::now();
+        handle->text = TableText::rows(handle->engine->hip, *input, *labels, prob_precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return handle.release();
+    });
+}
+
+// ... of rows resident on the engine's GPU (a rpvg_hip_read_rows of the engine's context, which must outlive the text): host labels
+// with path_length, effective lengths [P] and rank keys [K] (both or NULL) of the rows' columns.
+void * rpvg_amd_table_text_resident_rows(void * engine, void * read_rows, const rpvg_table_labels * labels, const double * path_effective_length, const uint64_t * num_align_lists, const uint64_t * cluster_index, double prob_precision, double * seconds_out) {
+
+    return guardedHandle([&]() -> void * {
+
+        std::unique_ptr<TextHandle> handle(new TextHandle());
+        handle->rows = true;
+        handle->engine = static_cast<Engine *>(engine);
+        handle->prob_precision = prob_precision;
+        handle->resident = static_cast<rpvg_hip_read_rows *>(read_rows);
+
+        if (labels->on_device || (labels->num_paths && !(labels->path_length && path_effective_length))) {
+
+            throw std::runtime_error("host labels with path_length and effective lengths");
+        }
+
+        TableLabels kept;
+
+        for (uint64_t p = 0; p < labels->num_paths; ++p) {
+
+            kept.names.emplace_back(labels->name_bytes + labels->name_off[p], labels->name_bytes + labels->name_off[p + 1]);
+        }
+
+        kept.cluster_ids.assign(labels->num_clusters, 0);
+        handle->resident_labels.reset(new FlatLabels(kept));
+        handle->resident_lengths.assign(labels->path_length, labels->path_length + labels->num_paths);
+        handle->effective_lengths.assign(path_effective_length, path_effective_length + labels->num_paths);
+
+        if (num_align_lists && cluster_index) {
+
+            handle->num_align_lists.assign(num_align_lists, num_align_lists + labels->num_clusters);
+            handle->cluster_index.assign(cluster_index, cluster_index + labels->num_clusters);
+        }
+
+        const auto start = std::chrono::steady_clock::now();
+        handle->text = TableText::rows(handle->engine->hip, handle->resident, *labels, path_effective_length, num_align_lists, cluster_index, prob_precision);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        return handle.release();
+    });
+}
+
+// The comparison line of the dump without a GPU: hostLineRows() over host arrays (valid offsets and indices are the caller's
+// precondition).  bytes_out [the line's bytes] and row_off_out [2 K + R + 1] may be NULL: a first call asks for num_bytes_out.
+int rpvg_amd_rows_text_host_line(const rpvg_rows_text_input * input, const rpvg_table_labels * labels, double prob_precision, char * bytes_out, uint64_t * row_off_out, uint64_t * num_bytes_out, uint64_t * exact_cells_out, double * seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        const rpvg_rows_text::DumpRows rows = dumpTextRows(*input, *labels, prob_precision);
+        const auto start = std::chrono::steady_clock::now();
+        const HostLine line = hostLineRows(rows);
+
+        if (seconds_out) {
+
+            *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        }
+
+        if (num_bytes_out) {
+
+            *num_bytes_out = line.bytes.size();
+        }
+
+        if (exact_cells_out) {
+
+            *exact_cells_out = line.exact_cells;
+        }
+
+        if (bytes_out) {
+
+            std::copy(line.bytes.begin(), line.bytes.end(), bytes_out);
+        }
+
+        if (row_off_out) {
+
+            std::copy(line.row_off.begin(), line.row_off.end(), row_off_out);
+        }
+
+        return 0;
+    });
+}
+
 // valid until the text's end
 int rpvg_amd_table_text_view(void * text_handle, rpvg_table_text_view * view_out) {
 
@@ -572,7 +766,11 @@ int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, co
 
         TextHandle * handle = static_cast<TextHandle *>(text_handle);
 
-        if (handle->gibbs) {
+        if (handle->rows) {  // the dump: output_prefix is the file's name (gzip when it ends in ".gz")
+
+            writeProbabilityClustersText(output_prefix, handle->text->view());
+
+        } else if (handle->gibbs) {
 
             ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
             out.addText(handle->gibbs->view(), handle->text->view());
@@ -608,8 +806,18 @@ int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * 
             rpvg_set_text::SetRows set_rows = {};
             std::unique_ptr<FlatLabels> labels;
             rpvg_estimates_flat estimates = {};
+            rpvg_rows_text::DumpRows dump_rows = {};
+            rpvg_rows_text_input dump_input = {};
+            rpvg_table_labels dump_labels = {};
 
-            if (handle->gibbs) {
+            if (handle->rows) {
+
+                const FlatRows & flat = flatRowsOf(handle, nullptr);
+                dump_input = flat.input();
+                dump_labels = flat.labels();
+                dump_rows = dumpTextRows(dump_input, dump_labels, handle->prob_precision);
+
+            } else if (handle->gibbs) {
 
                 labels.reset(new FlatLabels(handle->gibbs->labels()));
                 rows = gibbsTextRows(handle->gibbs->view(), labels->view(), handle->precision);
@@ -629,7 +837,7 @@ int rpvg_amd_table_text_host_line(void * text_handle, int32_t recompute, char * 
             }
 
             const auto start = std::chrono::steady_clock::now();
-            handle->line.reset(new HostLine(handle->sets ? hostLineSets(set_rows) : hostLine(rows)));
+            handle->line.reset(new HostLine(handle->rows ? hostLineRows(dump_rows) : (handle->sets ? hostLineSets(set_rows) : hostLine(rows))));
 
             if (seconds_out) {
 
@@ -681,7 +889,18 @@ int rpvg_amd_table_text_parent_route(void * text_handle, uint32_t num_gibbs_samp
         const auto start = std::chrono::steady_clock::now();
         auto viewed = start;
 
-        if (handle->gibbs) {
+        if (handle->rows) {  // rpvg_hip_read_rows_view, one ReadPathProbabilities per row, writeProbabilityClusters into its stream
+
+            const FlatRows & flat = flatRowsOf(handle, nullptr);
+            viewed = std::chrono::steady_clock::now();
+            const std::string text = formatProbabilityClusters(clustersOf(flat, handle->prob_precision), handle->prob_precision);
+
+            if (text.size() != handle->text->view().num_bytes) {
+
+                throw std::runtime_error("writeProbabilityClusters wrote a text of another length");
+            }
+
+        } else if (handle->gibbs) {
 
             const rpvg_gibbs_table_view & view = handle->gibbs->view();
             viewed = std::chrono::steady_clock::now();

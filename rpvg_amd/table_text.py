@@ -3,7 +3,9 @@ the rows ReadCountGibbsSamplesWriter, AbundanceEstimatesWriter and HaplotypeAbun
 "%.*g" writes it, byte for byte.  The header row and the `Unknown` row stay with the host writers.
 
   Labels      the names, lengths and ClusterIDs of a batch's paths in the flat form of rpvg_table_labels, host arrays
-  TableText   over the C ABI (a hip.Context or an engine.Engine): gibbs / estimates / view / bytes / guards_intact / free
+  RowsInput   the rows of a batch and the path side of the --write-probs dump in the flat form of rpvg_rows_text_input
+  TableText   over the C ABI (a hip.Context or an engine.Engine): gibbs / estimates / sets / rows / resident_rows / view / bytes /
+              guards_intact / free; rows: the --write-probs dump (rpvg_amd/csrc/rows_text.hip), whose rows are the lines of the file
   HarnessTableText  over the harness entry points: the text of a HarnessGibbsTable or a HarnessTable through the host class
               (rpvg_amd/host/table_text.hpp), the file from it by the writer's addText(), and the same rows from one host thread
 """
@@ -20,6 +22,7 @@ from ._flat import FlatArrays, HandleOwner, ctx_handle
 
 PER_PATH, HAPLOTYPE = 0, 1  # RPVG_TEXT_PER_PATH, RPVG_TEXT_HAPLOTYPE
 JOINT, POSTERIOR = 2, 3     # RPVG_TEXT_JOINT, RPVG_TEXT_POSTERIOR: a row per path group set (TableText.sets)
+ROWS = 4                    # HarnessTableText only: the --write-probs dump of a prepared batch's rows (TableText.rows)
 
 
 class CTableLabels(C.Structure):
@@ -32,6 +35,14 @@ class CTableTextView(C.Structure):
     """rpvg_table_text_view"""
     _fields_ = [("num_paths", C.c_uint64), ("num_rows", C.c_uint64), ("num_bytes", C.c_uint64), ("row_off", C.POINTER(C.c_uint64)),
                 ("bytes", C.POINTER(C.c_char))]
+
+
+class CRowsTextInput(C.Structure):
+    """rpvg_rows_text_input"""
+    _fields_ = [("num_clusters", C.c_uint32), ("num_rows", C.c_uint64), ("num_groups", C.c_uint64), ("num_entries", C.c_uint64), ("num_paths", C.c_uint64),
+                ("cluster_row_off", C.c_void_p), ("cluster_path_off", C.c_void_p), ("row_count", C.c_void_p), ("row_noise", C.c_void_p),
+                ("row_grp_off", C.c_void_p), ("grp_prob", C.c_void_p), ("grp_idx_off", C.c_void_p), ("path_idx", C.c_void_p),
+                ("path_effective_length", C.c_void_p), ("num_align_lists", C.c_void_p), ("cluster_index", C.c_void_p), ("on_device", C.c_int32)]
 
 
 _LABEL_FIELDS = (("name_off", np.uint64), ("name_bytes", np.uint8), ("path_length", np.uint32), ("cluster_id", np.uint32))
@@ -56,6 +67,40 @@ class Labels(FlatArrays):
 
     def sizes(self) -> dict:
         return dict(num_clusters=len(self.cluster_id), num_paths=max(len(self.name_off) - 1, 0), num_name_bytes=len(self.name_bytes))
+
+
+_ROWS_FIELDS = (("cluster_row_off", np.uint64), ("cluster_path_off", np.uint64), ("row_count", np.uint32), ("row_noise", np.float64),
+                ("row_grp_off", np.uint64), ("grp_prob", np.float64), ("grp_idx_off", np.uint64), ("path_idx", np.uint32),
+                ("path_effective_length", np.float64), ("num_align_lists", np.uint64), ("cluster_index", np.uint64))
+
+
+@dataclass
+class RowsInput(FlatArrays):
+    """rpvg_rows_text_input: the row fields of a ClusterBatch with 64-bit offsets, the effective lengths of the paths and the rank
+    keys of the clusters (both empty: bare "#" markers)."""
+    cluster_row_off: np.ndarray
+    cluster_path_off: np.ndarray
+    row_count: np.ndarray
+    row_noise: np.ndarray
+    row_grp_off: np.ndarray
+    grp_prob: np.ndarray
+    grp_idx_off: np.ndarray
+    path_idx: np.ndarray
+    path_effective_length: np.ndarray
+    num_align_lists: np.ndarray
+    cluster_index: np.ndarray
+    _FIELDS, _C_STRUCT = _ROWS_FIELDS, CRowsTextInput
+
+    @staticmethod
+    def of(batch, effective_lengths, num_align_lists=None, cluster_index=None) -> "RowsInput":
+        """batch: anything with the row arrays of a ClusterBatch as attributes or keys."""
+        get = (lambda n: batch[n]) if isinstance(batch, dict) else (lambda n: getattr(batch, n))
+        return RowsInput(*[get(n) for n, _ in _ROWS_FIELDS[:8]], effective_lengths, [] if num_align_lists is None else num_align_lists,
+                         [] if cluster_index is None else cluster_index)
+
+    def sizes(self) -> dict:
+        return dict(num_clusters=max(len(self.cluster_row_off) - 1, 0), num_rows=len(self.row_count), num_groups=len(self.grp_prob),
+                    num_entries=len(self.path_idx), num_paths=len(self.path_effective_length))
 
 
 class TableText(HandleOwner):
@@ -94,6 +139,31 @@ class TableText(HandleOwner):
                    "rpvg_hip_estimates_set_text")
         return cls(handle)
 
+    @classmethod
+    def rows(cls, ctx_or_engine, rows_input, labels, prob_precision: float = 1e-8) -> "TableText":
+        """The --write-probs dump: marker, path line and row lines of every cluster that has paths and rows.  rows_input: a RowsInput,
+        or a CRowsTextInput (host or device pointers); labels need path_length.  In the view the rows are the LINES of the text:
+        row_off has 2 K + R + 1 entries."""
+        handle = C.c_void_p()
+        flat = labels.as_c() if isinstance(labels, Labels) else labels
+        inp = rows_input.as_c() if isinstance(rows_input, RowsInput) else rows_input
+        hip._check(hip.lib().rpvg_hip_rows_text(ctx_handle(ctx_or_engine), C.byref(inp), C.byref(flat), C.c_double(prob_precision), C.byref(handle)),
+                   "rpvg_hip_rows_text")
+        return cls(handle)
+
+    @classmethod
+    def resident_rows(cls, ctx_or_engine, rows_handle, labels, effective_lengths, prob_precision: float = 1e-8, num_align_lists=None,
+                      cluster_index=None) -> "TableText":
+        """The same from a rpvg_hip_read_rows handle, read where it lies (hip.DeviceRows.text)."""
+        handle = C.c_void_p()
+        flat = labels.as_c() if isinstance(labels, Labels) else labels
+        eff = np.ascontiguousarray(effective_lengths, dtype=np.float64)
+        keys = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64) for a in (num_align_lists, cluster_index)]
+        pointers = [C.c_void_p(a.ctypes.data if a is not None and a.size else None) for a in [eff] + keys]
+        hip._check(hip.lib().rpvg_hip_read_rows_text(ctx_handle(ctx_or_engine), rows_handle, C.byref(flat), *pointers, C.c_double(prob_precision),
+                                                    C.byref(handle)), "rpvg_hip_read_rows_text")
+        return cls(handle)
+
     def view(self) -> dict:
         """row_off [P + 1], the text as bytes (copied out of the page-locked block), num_rows (printed)."""
         v = CTableTextView()
@@ -129,6 +199,10 @@ def _harness():
     L.rpvg_amd_table_text_estimates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_sets.restype = C.c_void_p
     L.rpvg_amd_table_text_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_double, C.c_int32, C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_rows.restype = C.c_void_p
+    L.rpvg_amd_table_text_rows.argtypes = [C.c_void_p, C.POINTER(CRowsTextInput), C.POINTER(CTableLabels), C.c_double, C.POINTER(C.c_double)]
+    L.rpvg_amd_table_text_resident_rows.restype = C.c_void_p
+    L.rpvg_amd_table_text_resident_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CTableLabels), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_view.argtypes = [C.c_void_p, C.POINTER(CTableTextView)]
     L.rpvg_amd_table_text_write.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]
     L.rpvg_amd_table_text_host_line.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
@@ -141,12 +215,25 @@ def _harness():
 class HarnessTableText(HandleOwner):
     """The text of a harness table (gibbs_table.HarnessGibbsTable or estimates_table.HarnessTable, which must outlive it)."""
 
-    def __init__(self, engine, table, kind: Optional[int] = None, precision: int = 8, ploidy: int = 0, min_posterior: float = 0.0):
+    def __init__(self, engine, table, kind: Optional[int] = None, precision: int = 8, ploidy: int = 0, min_posterior: float = 0.0, labels: Optional[Labels] = None,
+                 prob_precision: float = 1e-8, effective_lengths=None, num_align_lists=None, cluster_index=None):
         """kind None: the Gibbs text; PER_PATH, HAPLOTYPE: a row per path; JOINT, POSTERIOR: a row per path group set, for a writer of
-        `ploidy` and `min_posterior` (in view() and host_line() the rows are then the sets)."""
+        `ploidy` and `min_posterior` (in view() and host_line() the rows are then the sets).  ROWS: the --write-probs dump at
+        `prob_precision` with `labels` (with path_length); `table` is a RowsInput, or the handle of resident rows built on the
+        engine's context (engine._ctx()), which takes effective_lengths and the rank keys beside it.  The rows of view() and
+        host_line() are then the 2 K + R lines, and write(name) writes the file `name`."""
         L, eng = _harness()
         secs = C.c_double(0)
-        if kind is None:
+        if kind == ROWS:
+            self._keep = [labels.as_c()]
+            if isinstance(table, RowsInput):
+                self._keep.append(table.as_c())
+                self.handle = L.rpvg_amd_table_text_rows(engine.handle, C.byref(self._keep[1]), C.byref(self._keep[0]), prob_precision, C.byref(secs))
+            else:
+                arrays = [np.ascontiguousarray(effective_lengths, dtype=np.float64)] + [None if a is None else np.ascontiguousarray(a, dtype=np.uint64) for a in (num_align_lists, cluster_index)]
+                pointers = [C.c_void_p(a.ctypes.data if a is not None and a.size else None) for a in arrays]
+                self.handle = L.rpvg_amd_table_text_resident_rows(engine.handle, table, C.byref(self._keep[0]), *pointers, prob_precision, C.byref(secs))
+        elif kind is None:
             self.handle = L.rpvg_amd_table_text_gibbs(engine.handle, table.handle, precision, C.byref(secs))
         elif kind in (JOINT, POSTERIOR):
             self.handle = L.rpvg_amd_table_text_sets(engine.handle, table.handle, kind, ploidy, min_posterior, precision, C.byref(secs))
@@ -195,3 +282,21 @@ class HarnessTableText(HandleOwner):
 
     def _release(self):
         _harness()[0].rpvg_amd_table_text_free(self.handle)
+
+
+def host_line_rows(rows_input: RowsInput, labels: Labels, prob_precision: float = 1e-8) -> dict:
+    """The --write-probs dump of host arrays from one host thread, without a GPU (rpvg_amd/host/table_text.hpp: hostLineRows over the
+    plan's rowBytes and rowWrite): bytes, row_off [2 K + R + 1], exact_cells and the seconds of the walk."""
+    from . import engine
+    L = engine.lib()
+    L.rpvg_amd_rows_text_host_line.argtypes = [C.POINTER(CRowsTextInput), C.POINTER(CTableLabels), C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    inp, flat = rows_input.as_c(), labels.as_c()
+    n, exact, secs = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+    row_off = np.zeros(2 * inp.num_clusters + inp.num_rows + 1, dtype=np.uint64)
+    if L.rpvg_amd_rows_text_host_line(C.byref(inp), C.byref(flat), prob_precision, None, row_off.ctypes.data, C.byref(n), C.byref(exact), C.byref(secs)) != 0:
+        raise hip.EngineError(f"rows text host line failed: {engine._err()}")
+    out = C.create_string_buffer(max(n.value, 1))
+    if L.rpvg_amd_rows_text_host_line(C.byref(inp), C.byref(flat), prob_precision, out, None, None, None, None) != 0:
+        raise hip.EngineError(f"rows text host line failed: {engine._err()}")
+    return dict(bytes=out.raw[:n.value], row_off=row_off, exact_cells=int(exact.value), seconds=secs.value, num_bytes=int(n.value))
