@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "subset_pack.hpp"
+#include "subset_select_plan.hpp"
 
 #include <cmath>
 #include <memory>
@@ -102,37 +103,69 @@ struct SelectArgs {
 
 // ---- selectPathSubsetIndices (src/path_abundance_estimator.cpp:569-606) + the retained subsets in order ----------
 // Two launches: one wavefront per matrix for the matrices the search left at most kSmallSelected pairs (nearly all: a bench
-// batch keeps eight per matrix), and a few 256-thread workgroups that walk the list of the others (a matrix with a flat
-// posterior keeps hundreds: one wave over global scratch spent 3 ms on one of them).  Both copy the path lists of the
-// matrix's columns into LDS first when they fit — every comparison of two subsets walks four of them — and both order
-// the retained subsets by a bitonic network over their indices (rank by counting is quadratic in list walks).
+// batch keeps four per matrix), and a few 256-thread workgroups that walk the list of the others (a matrix with a flat
+// posterior keeps hundreds to a thousand).  Both copy the path lists of the matrix's columns into LDS when they fit, and both
+// bring everything a selected diplotype is asked for more than once into LDS first — its posterior, where its two column lists
+// begin and how long they are, and from ONE walk of its merged list the hash, the length and the distinct paths — so that
+// nothing behind the staging waits for device memory.  The index logic is subset_select_plan.hpp (groups by one sort of the
+// indices, leaders, members in pair order, rank by a key of the leading elements): tests/cpp/subset_select_check.cpp runs the
+// same functions on the host.
 constexpr uint32_t kSmallSelected = 64;
 constexpr uint32_t kSmallCachedPaths = 1024, kWideCachedPaths = 6144;  // column path lists cached in LDS (entries)
 
-struct CachedColumns {  // the columns of one matrix as path lists, in LDS when they fit
-    const uint64_t * group_path_off;  // global offsets (relative to all matrices)
-    const uint32_t * paths;           // LDS copy (offsets relative to `first_offset`) or the global array
-    uint64_t first_column, base;      // base: what to subtract from a global offset to index `paths`
-    __device__ __forceinline__ MergedList list(const uint32_t first, const uint32_t second) const {
-        const uint64_t a0 = group_path_off[first_column + first], a1 = group_path_off[first_column + first + 1];
-        const uint64_t b0 = group_path_off[first_column + second], b1 = group_path_off[first_column + second + 1];
-        return MergedList(paths + (a0 - base), static_cast<uint32_t>(a1 - a0), paths + (b0 - base), static_cast<uint32_t>(b1 - b0));
+template <uint32_t CAP, uint32_t CACHE>
+struct SelectLds {
+    union {
+        unsigned long long hash[CAP];  // of a selected diplotype's list, until the leaders are known ...
+        double weight[CAP];            // ... then the weight of a leader's subset
+    };
+    union {
+        double value[CAP];             // posterior of a selected diplotype, until the weights are known ...
+        unsigned long long key[CAP];   // ... then the leading elements of a retained subset's list
+    };
+    uint32_t sel[CAP];                 // selected pair -> index among the matrix's kept pairs
+    uint32_t a_off[CAP], b_off[CAP];   // where the lists of its two columns begin (entries behind the matrix's first)
+    uint32_t b_len[CAP], length[CAP];  // entries of the second column's list, and of both
+    uint32_t distinct[CAP];            // distinct paths of the merged list
+    uint32_t sorted[CAP];              // the selected by (hash, length, index)
+    uint32_t head[CAP];                // position in `sorted` at which the run of equal (hash, length) begins
+    uint32_t leader[CAP];              // first selected pair with the identical path list
+    uint32_t order[CAP];               // retained subsets, then sorted by their path lists
+    uint32_t cached_paths[CACHE];
+    unsigned long long red[3];
+    double sum_posterior;
+    uint32_t scratch[4];
+    uint32_t n_retained;
+    uint32_t max_path;                 // largest entry of the matrix's column lists
+};
+constexpr size_t kWideSelectLds = sizeof(SelectLds<kMaxSelected, kWideCachedPaths>);  // 80 KB: dynamic, behind hipFuncSetAttribute
+
+// the merged lists of the selected diplotypes of one matrix, from what the staging left in LDS
+struct StagedLists {
+    const uint32_t * paths;  // the LDS copy of the matrix's lists, or the global array at the matrix's first entry
+    const uint32_t * a_off;
+    const uint32_t * b_off;
+    const uint32_t * b_len;
+    const uint32_t * length;
+    __device__ __forceinline__ MergedList list(const uint32_t s) const {
+        return MergedList(paths + a_off[s], length[s] - b_len[s], paths + b_off[s], b_len[s]);
     }
 };
 
+// the bitonic network of subset_select_plan.hpp over order[0 .. padded): every thread takes pairs, a barrier behind every stage
+template <int BLOCK, class Before>
+__device__ __forceinline__ void sortIndices(uint32_t * order, const uint32_t padded, Before before) {
+    for (uint32_t size = 2; size <= padded; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t p = threadIdx.x; p < rpvg_select::sortStagePairs(padded); p += BLOCK) rpvg_select::compareExchange(order, p, size, stride, before);
+            __syncthreads();
+        }
+    }
+}
+
 template <uint32_t CAP, uint32_t CACHE, int BLOCK>
-__device__ __forceinline__ void selectSubsetsOfMatrix(const SelectArgs & args, const uint32_t m) {
-    __shared__ uint32_t sel[CAP];          // selected pair -> index among the matrix's kept pairs
-    __shared__ unsigned long long hash[CAP];
-    __shared__ uint32_t length[CAP];
-    __shared__ uint32_t leader[CAP];       // first selected pair with the identical path list
-    __shared__ double weight[CAP];
-    __shared__ uint32_t order[CAP];        // retained subsets, then sorted by their path lists
-    __shared__ uint32_t cached_paths[CACHE];
-    __shared__ uint32_t scratch[BLOCK / 64];
-    __shared__ double sum_posterior;
-    __shared__ unsigned long long red[3];
-    __shared__ uint32_t n_retained;
+__device__ __forceinline__ void selectSubsetsOfMatrix(const SelectArgs & args, const uint32_t m, SelectLds<CAP, CACHE> & lds) {
+    constexpr uint32_t ITEMS = (CAP + BLOCK - 1) / BLOCK;  // selected diplotypes a thread looks after
     const uint32_t n_pairs = args.pair_count[m];
     const uint64_t base = args.pair_cap_off[m];
     const uint32_t * first = args.pair_first + base;
@@ -140,14 +173,20 @@ __device__ __forceinline__ void selectSubsetsOfMatrix(const SelectArgs & args, c
     const double * value = args.pair_value + base;
     const uint32_t k = args.cluster[m];
     MatrixTotals * out_totals = args.totals + m;
-    // the path lists of the matrix's columns
+    // the path lists of the matrix's columns (far below 2^32 entries: the offsets into them are 32-bit from here on)
     const uint64_t col0 = args.group_off[m], col1 = args.group_off[m + 1];
     const uint64_t path0 = args.group_path_off[col0], path1 = args.group_path_off[col1];
     const bool cached = path1 - path0 <= CACHE;
-    if (cached) {
-        for (uint32_t i = threadIdx.x; i < path1 - path0; i += BLOCK) cached_paths[i] = args.group_path[path0 + i];
+    if (threadIdx.x == 0) lds.max_path = 0;
+    __syncthreads();
+    uint32_t my_max_path = 0;  // (how many bits an element of the rank's key takes)
+    for (uint64_t i = threadIdx.x; i < path1 - path0; i += BLOCK) {
+        const uint32_t path = args.group_path[path0 + i];
+        if (cached) lds.cached_paths[i] = path;
+        my_max_path = path > my_max_path ? path : my_max_path;
     }
-    const CachedColumns columns{args.group_path_off, cached ? cached_paths : args.group_path, col0, cached ? path0 : 0};
+    if (my_max_path) atomicMax(&lds.max_path, my_max_path);
+    const StagedLists lists{cached ? lds.cached_paths : args.group_path + path0, lds.a_off, lds.b_off, lds.b_len, lds.length};
 
     // the selected diplotypes, in the order the search kept them (:574-576)
     uint32_t n_sel = 0;
@@ -155,8 +194,8 @@ __device__ __forceinline__ void selectSubsetsOfMatrix(const SelectArgs & args, c
         const uint32_t i = c + threadIdx.x;
         const uint32_t take = (i < n_pairs && value[i] >= args.min_hap_prob) ? 1u : 0u;
         uint32_t total;
-        const uint32_t at = n_sel + blockExclusiveScan<BLOCK>(take, total, scratch);
-        if (take && at < CAP) sel[at] = i;
+        const uint32_t at = n_sel + blockExclusiveScan<BLOCK>(take, total, lds.scratch);
+        if (take && at < CAP) lds.sel[at] = i;
         n_sel += total;
     }
     if (n_sel > CAP) {  // (a threshold below 1 / kMaxSelected: the caller takes the host-driven path)
@@ -167,128 +206,177 @@ __device__ __forceinline__ void selectSubsetsOfMatrix(const SelectArgs & args, c
         return;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double sum = 0;  // in pair order, as the reference adds it up (:598)
-        for (uint32_t s = 0; s < n_sel; ++s) sum += value[sel[s]];
-        sum_posterior = sum;
-        red[0] = red[1] = red[2] = 0;
-        n_retained = 0;
-    }
-    // every selected diplotype's path list: length and a hash (FNV-1a over the merged walk)
-    for (uint32_t s = threadIdx.x; s < n_sel; s += BLOCK) {
-        MergedList list = columns.list(first[sel[s]], second[sel[s]]);
-        unsigned long long h = 1469598103934665603ull;
-        uint32_t n = 0;
-        while (!list.done()) {
-            h = (h ^ list.next()) * 1099511628211ull;
-            ++n;
+    // staging: the posterior, the two column lists, and one walk of the merged list — hash (FNV-1a), length, distinct paths
+    const uint32_t padded_sel = rpvg_select::paddedSize(n_sel);
+    {
+        uint32_t pair[ITEMS] = {}, col_a[ITEMS] = {}, col_b[ITEMS] = {};  // (every round of loads for all of a thread's diplotypes at once)
+        uint64_t a0[ITEMS] = {}, a1[ITEMS] = {}, b0[ITEMS] = {}, b1[ITEMS] = {};
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t s = threadIdx.x + e * BLOCK;
+            pair[e] = s < n_sel ? lds.sel[s] : 0u;
         }
-        hash[s] = h;
-        length[s] = n;
-    }
-    __syncthreads();
-    // identical lists: the first of them leads (:595, emplace finds the existing key)
-    for (uint32_t s = threadIdx.x; s < n_sel; s += BLOCK) {
-        uint32_t lead = s;
-        for (uint32_t t = 0; t < s; ++t) {
-            if (hash[t] == hash[s] && length[t] == length[s] &&
-                compareLists(columns.list(first[sel[t]], second[sel[t]]), columns.list(first[sel[s]], second[sel[s]])) == 0) {
-                lead = t;
-                break;
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t s = threadIdx.x + e * BLOCK;
+            if (s < n_sel) {
+                lds.value[s] = value[pair[e]];
+                col_a[e] = first[pair[e]];
+                col_b[e] = second[pair[e]];
             }
         }
-        leader[s] = lead;
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t s = threadIdx.x + e * BLOCK;
+            if (s < n_sel) {
+                a0[e] = args.group_path_off[col0 + col_a[e]];
+                a1[e] = args.group_path_off[col0 + col_a[e] + 1];
+                b0[e] = args.group_path_off[col0 + col_b[e]];
+                b1[e] = args.group_path_off[col0 + col_b[e] + 1];
+            }
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t s = threadIdx.x + e * BLOCK;
+            if (s >= n_sel) {
+                if (s < padded_sel) lds.sorted[s] = rpvg_select::kPadding;
+                continue;
+            }
+            lds.a_off[s] = static_cast<uint32_t>(a0[e] - path0);
+            lds.b_off[s] = static_cast<uint32_t>(b0[e] - path0);
+            lds.b_len[s] = static_cast<uint32_t>(b1[e] - b0[e]);
+            lds.length[s] = static_cast<uint32_t>(a1[e] - a0[e]) + static_cast<uint32_t>(b1[e] - b0[e]);
+            MergedList walk(lists.paths + (a0[e] - path0), static_cast<uint32_t>(a1[e] - a0[e]), lists.paths + (b0[e] - path0), static_cast<uint32_t>(b1[e] - b0[e]));
+            unsigned long long h = 1469598103934665603ull;
+            uint32_t distinct = 0, previous = 0xffffffffu;
+            while (!walk.done()) {
+                const uint32_t path = walk.next();
+                h = (h ^ path) * 1099511628211ull;
+                distinct += (path != previous) ? 1u : 0u;
+                previous = path;
+            }
+            lds.hash[s] = h;
+            lds.distinct[s] = distinct;
+            lds.sorted[s] = s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0;  // in pair order, as the reference adds it up (:598); eight reads in flight in front of eight additions
+        uint32_t s = 0;
+        for (; s + 8 <= n_sel; s += 8) {
+            double v[8];
+#pragma unroll
+            for (uint32_t j = 0; j < 8; ++j) v[j] = lds.value[s + j];
+#pragma unroll
+            for (uint32_t j = 0; j < 8; ++j) sum += v[j];
+        }
+        for (; s < n_sel; ++s) sum += lds.value[s];
+        lds.sum_posterior = sum;
+        lds.red[0] = lds.red[1] = lds.red[2] = 0;
+        lds.n_retained = 0;
+    }
+    // identical lists: the candidates side by side and in pair order, the runs' first positions, then the first of the run
+    // with the identical list leads (:595, emplace finds the existing key)
+    sortIndices<BLOCK>(lds.sorted, padded_sel, [&](const uint32_t x, const uint32_t y) { return rpvg_select::groupBefore(lds.hash, lds.length, x, y); });
+    for (uint32_t p = threadIdx.x; p < n_sel; p += BLOCK) lds.head[p] = rpvg_select::isRunHead(lds.sorted, lds.hash, lds.length, p) ? p : 0u;
+    __syncthreads();
+    for (uint32_t d = 1; d < n_sel; d <<= 1) {
+        uint32_t next[ITEMS];
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t p = threadIdx.x + e * BLOCK;
+            next[e] = p < n_sel ? rpvg_select::scanStep(lds.head, p, d) : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t e = 0; e < ITEMS; ++e) {
+            const uint32_t p = threadIdx.x + e * BLOCK;
+            if (p < n_sel) lds.head[p] = next[e];
+        }
+        __syncthreads();
+    }
+    for (uint32_t p = threadIdx.x; p < n_sel; p += BLOCK) {
+        lds.leader[lds.sorted[p]] = rpvg_select::leaderAt(lds.sorted, lds.head, p, [&](const uint32_t t, const uint32_t s) { return compareLists(lists.list(t), lists.list(s)) == 0; });
     }
     __syncthreads();
     // weight of a subset: the posteriors of its diplotypes added in pair order (:596), over the sum of all selected
     // (:602-605); the retained ones (:627-630: subsets below the threshold are skipped), in any order for now
-    for (uint32_t s = threadIdx.x; s < n_sel; s += BLOCK) {
-        double w = 0;
-        if (leader[s] == s) {
-            for (uint32_t t = s; t < n_sel; ++t) {
-                if (leader[t] == s) w += value[sel[t]];
-            }
-            w /= sum_posterior;
-            if (w >= args.min_hap_prob) order[atomicAdd(&n_retained, 1u)] = s;
-        }
-        weight[s] = w;
+    for (uint32_t p = threadIdx.x; p < n_sel; p += BLOCK) {
+        const uint32_t s = lds.sorted[p];
+        if (lds.leader[s] != s) continue;
+        const double w = rpvg_select::memberSum(lds.sorted, lds.head, lds.leader, lds.value, p, n_sel) / lds.sum_posterior;
+        lds.weight[s] = w;  // (in place of the hash: nothing reads that any more)
+        if (w >= args.min_hap_prob) lds.order[atomicAdd(&lds.n_retained, 1u)] = s;
     }
     __syncthreads();
-    // ... then in lexicographic order of their path lists: a bitonic network over `order` (padding sorts last)
-    const uint32_t n_ret = n_retained;
-    uint32_t padded = 1;
-    while (padded < n_ret) padded <<= 1;
-    for (uint32_t i = n_ret + threadIdx.x; i < padded; i += BLOCK) order[i] = 0xffffffffu;
-    __syncthreads();
-    auto before = [&](const uint32_t x, const uint32_t y) {  // subset x sorts before subset y
-        if (x == 0xffffffffu) return false;
-        if (y == 0xffffffffu) return true;
-        return compareLists(columns.list(first[sel[x]], second[sel[x]]), columns.list(first[sel[y]], second[sel[y]])) < 0;
-    };
-    for (uint32_t size = 2; size <= padded; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t i = threadIdx.x; i < padded; i += BLOCK) {
-                const uint32_t partner = i ^ stride;
-                if (partner > i) {
-                    const bool ascending = (i & size) == 0;
-                    const uint32_t x = order[i], y = order[partner];
-                    if (before(y, x) == ascending) {
-                        order[i] = y;
-                        order[partner] = x;
-                    }
-                }
-            }
-            __syncthreads();
+    // ... then in lexicographic order of their path lists: the leading elements as a key (in place of the posteriors; ten of
+    // them where the cluster has 40 paths), the lists themselves between equal keys only
+    const uint32_t n_ret = lds.n_retained;
+    const uint32_t padded_ret = rpvg_select::paddedSize(n_ret);
+    const uint32_t key_bits = rpvg_select::keyElementBits(lds.max_path), key_elements = rpvg_select::keyElements(key_bits);
+    for (uint32_t r = threadIdx.x; r < padded_ret; r += BLOCK) {
+        if (r >= n_ret) {
+            lds.order[r] = rpvg_select::kPadding;
+            continue;
         }
+        const uint32_t s = lds.order[r];
+        MergedList walk = lists.list(s);
+        unsigned long long key = 0;
+        for (uint32_t i = 0; i < key_elements; ++i) {
+            const bool present = !walk.done();
+            key = rpvg_select::keyAppend(key, key_bits, present, present ? walk.next() : 0u);
+        }
+        lds.key[s] = key;
     }
+    __syncthreads();
+    sortIndices<BLOCK>(lds.order, padded_ret, [&](const uint32_t x, const uint32_t y) {
+        return rpvg_select::rankBefore(lds.key, x, y, [&](const uint32_t u, const uint32_t v) { return compareLists(lists.list(u), lists.list(v)) < 0; });
+    });
     // their slots
     const uint64_t slot0 = args.slot_off[m];
     unsigned long long my_subsets = 0, my_length = 0, my_columns = 0;
     for (uint32_t rank = threadIdx.x; rank < n_ret; rank += BLOCK) {
-        const uint32_t s = order[rank];
-        uint32_t distinct = 0, previous = 0xffffffffu;
-        MergedList walk = columns.list(first[sel[s]], second[sel[s]]);
-        while (!walk.done()) {
-            const uint32_t path = walk.next();
-            distinct += (path != previous) ? 1u : 0u;
-            previous = path;
-        }
-        args.slot_first[slot0 + rank] = first[sel[s]];
-        args.slot_second[slot0 + rank] = second[sel[s]];
-        args.slot_weight[slot0 + rank] = weight[s];
-        args.slot_length[slot0 + rank] = length[s];
-        args.slot_columns[slot0 + rank] = distinct;
+        const uint32_t s = lds.order[rank];
+        args.slot_first[slot0 + rank] = first[lds.sel[s]];
+        args.slot_second[slot0 + rank] = second[lds.sel[s]];
+        args.slot_weight[slot0 + rank] = lds.weight[s];
+        args.slot_length[slot0 + rank] = lds.length[s];
+        args.slot_columns[slot0 + rank] = lds.distinct[s];
         my_subsets += 1;
-        my_length += length[s];
-        my_columns += distinct;
+        my_length += lds.length[s];
+        my_columns += lds.distinct[s];
     }
     if (my_subsets) {
-        atomicAdd(&red[0], my_subsets);
-        atomicAdd(&red[1], my_length);
-        atomicAdd(&red[2], my_columns);
+        atomicAdd(&lds.red[0], my_subsets);
+        atomicAdd(&lds.red[1], my_length);
+        atomicAdd(&lds.red[2], my_columns);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint64_t r0 = args.cluster_row_off[k], r1 = args.cluster_row_off[k + 1];
         const unsigned long long rows = r1 - r0, entries = args.row_ent_off[r1] - args.row_ent_off[r0];
-        *out_totals = MatrixTotals{red[0], red[1], red[2], red[0] * rows, red[0] * entries, red[0] * ((rows + args.segment_rows - 1) / args.segment_rows)};
+        *out_totals = MatrixTotals{lds.red[0], lds.red[1], lds.red[2], lds.red[0] * rows, lds.red[0] * entries, lds.red[0] * ((rows + args.segment_rows - 1) / args.segment_rows)};
     }
 }
 
 __global__ __launch_bounds__(64) void subsetSelectSmallKernel(const SelectArgs args) {
+    __shared__ SelectLds<kSmallSelected, kSmallCachedPaths> lds;
     const uint32_t m = blockIdx.x;
     if (m >= args.num_matrices) return;
     if (args.pair_count[m] > kSmallSelected) {  // left to the wide launch: a few workgroups that walk this list
         if (threadIdx.x == 0) args.big_matrices[atomicAdd(&args.header->big_count, 1u)] = m;
         return;
     }
-    selectSubsetsOfMatrix<kSmallSelected, kSmallCachedPaths, 64>(args, m);
+    selectSubsetsOfMatrix<kSmallSelected, kSmallCachedPaths, 64>(args, m, lds);
 }
 
 __global__ __launch_bounds__(256) void subsetSelectWideKernel(const SelectArgs args) {
+    extern __shared__ __align__(16) unsigned char wide_select_lds[];  // kWideSelectLds bytes
+    SelectLds<kMaxSelected, kWideCachedPaths> & lds = *reinterpret_cast<SelectLds<kMaxSelected, kWideCachedPaths> *>(wide_select_lds);
     const uint32_t count = args.header->big_count;
     for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
-        selectSubsetsOfMatrix<kMaxSelected, kWideCachedPaths, 256>(args, args.big_matrices[item]);
+        selectSubsetsOfMatrix<kMaxSelected, kWideCachedPaths, 256>(args, args.big_matrices[item], lds);
         __syncthreads();  // the LDS is reused
     }
 }
@@ -750,7 +838,9 @@ static int nestedSubsetEmAttempt(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batc
     sa.header = header;
     sa.big_matrices = d_big_matrices.ptr;
     subsetSelectSmallKernel<<<dim3(M), dim3(64), 0, st>>>(sa);
-    subsetSelectWideKernel<<<dim3(std::min<uint32_t>(M, 128)), dim3(256), 0, st>>>(sa);
+    // (80 KB of LDS for the wide one: only a few of its workgroups find work, a CU has 160 KB)
+    ok(hipFuncSetAttribute(reinterpret_cast<const void *>(&subsetSelectWideKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kWideSelectLds)));
+    subsetSelectWideKernel<<<dim3(std::min<uint32_t>(M, 128)), dim3(256), kWideSelectLds, st>>>(sa);
     const bool check_build = !groups->build_checked && groups->build_error_flag.ptr;
     OffsetsArgs oa;
     oa.pair_count = search.d_tail.ptr;
