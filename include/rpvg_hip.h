@@ -863,6 +863,9 @@ int rpvg_hip_gibbs_table_build_resident(rpvg_hip_ctx * ctx, const rpvg_hip_gibbs
  *                                 smallest offending path, else the smallest offending cluster).  The handle is that of the other
  *                                 texts: in its view num_paths is the number of sets S and row_off has S + 1 entries.
  *   rpvg_hip_table_text_view       row_off and ONE copy of the whole text into page-locked memory of the library's pool.
+ *   rpvg_hip_table_text_sizes      the view without the copy: the sizes and row_off, which the host holds since the build; bytes is NULL
+ *                                 unless rpvg_hip_table_text_view has run.  For a caller that takes the text as BGZF members and never
+ *                                 downloads it.
  *   rpvg_hip_table_text_get        bytes [byte_begin, byte_end) of the text to host memory: a writer streams a text of gigabytes in pieces.
  *   rpvg_hip_table_text_guards     test hook: the text lies in a device block between two runs of 64 pattern bytes; *intact_out says
  *                                 whether both still hold the pattern. */
@@ -891,9 +894,23 @@ int rpvg_hip_read_rows_text(rpvg_hip_ctx * ctx, const rpvg_hip_read_rows * rows,
                             const double * path_effective_length, const uint64_t * num_align_lists, const uint64_t * cluster_index,
                             double prob_precision, rpvg_hip_table_text ** text_out);
 int rpvg_hip_table_text_view(rpvg_hip_table_text * text, rpvg_table_text_view * view_out);
+int rpvg_hip_table_text_sizes(rpvg_hip_table_text * text, rpvg_table_text_view * view_out);
 int rpvg_hip_table_text_get(rpvg_hip_table_text * text, uint64_t byte_begin, uint64_t byte_end, char * dst);
 int rpvg_hip_table_text_guards(rpvg_hip_table_text * text, int32_t * intact_out);
 void rpvg_hip_table_text_free(rpvg_hip_table_text * text);
+/*   rpvg_hip_table_text_bgzf       a resident text of any of the builders above as BGZF members (rpvg_text.h; rpvg_amd/csrc/text_deflate.hip),
+ *                                 deflated on the GPU: only the compressed bytes are left to download.  The text stays as it is.
+ *   rpvg_hip_bytes_bgzf            the same for any n bytes, host memory (on_device = 0) or device memory of the context's GPU, copied by
+ *                                 the call.  Refused: n > 0 with a NULL pointer.  No bytes: no members, no error.
+ *   rpvg_hip_text_bgzf_view        the sizes, member_off and ONE copy of the members into page-locked memory of the library's pool.
+ *   rpvg_hip_text_bgzf_get         bytes [byte_begin, byte_end) of the members to host memory; a range outside them or reversed is refused.
+ *   rpvg_hip_text_bgzf_guards      test hook: the members lie in a device block between two runs of 64 pattern bytes. */
+int rpvg_hip_table_text_bgzf(rpvg_hip_table_text * text, rpvg_hip_text_bgzf ** bgzf_out);
+int rpvg_hip_bytes_bgzf(rpvg_hip_ctx * ctx, const char * bytes, uint64_t n, int32_t on_device, rpvg_hip_text_bgzf ** bgzf_out);
+int rpvg_hip_text_bgzf_view(rpvg_hip_text_bgzf * bgzf, rpvg_text_bgzf_view * view_out);
+int rpvg_hip_text_bgzf_get(rpvg_hip_text_bgzf * bgzf, uint64_t byte_begin, uint64_t byte_end, char * dst);
+int rpvg_hip_text_bgzf_guards(rpvg_hip_text_bgzf * bgzf, int32_t * intact_out);
+void rpvg_hip_text_bgzf_free(rpvg_hip_text_bgzf * bgzf);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the

@@ -90,6 +90,26 @@ typedef struct rpvg_rows_text_input {
     int32_t on_device;
 } rpvg_rows_text_input;
 
+/* ---- a text as the bytes of a .gz file (rpvg_hip_table_text_bgzf, rpvg_hip_bytes_bgzf; rpvg_amd/csrc/text_deflate.hip) -------------
+ * BGZF, the blocked gzip of bgzip and htslib: the text is cut at byte positions into chunks of 65 280 bytes (the last one shorter,
+ * an empty text has none), and chunk i becomes gzip member i: 18 header bytes (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C'
+ * 02 00, BSIZE = member size - 1), one raw DEFLATE block with BFINAL set — dynamic Huffman codes over literals and matches inside
+ * the chunk, or the stored form when that is not larger, so a member is at most its chunk + 31 bytes —, CRC-32 and ISIZE of the
+ * chunk.  The members are a function of the text's bytes alone.  The file's last 28 bytes, BGZF's empty end-of-file member, are the
+ * writer's to append (rpvg_amd/csrc/text_deflate_plan.hpp: eofBlock).  What src/threaded_output_writer.cpp:8-40 leaves to htslib's
+ * writer thread (mode "wg"). */
+typedef struct rpvg_text_bgzf_view {
+    uint64_t num_members;
+    uint64_t num_text_bytes;            /* of the text the members hold */
+    uint64_t num_bytes;                 /* of the members */
+    uint64_t num_stored_members;        /* members whose block is the stored form */
+    const uint64_t * member_off;        /* [num_members + 1]: member i lies in bytes [member_off[i], member_off[i + 1]) and holds the
+                                           text from byte i * 65280: what a .gzi index lists */
+    const char * bytes;                 /* page-locked memory of the library's pool; NULL without members */
+} rpvg_text_bgzf_view;
+
+typedef struct rpvg_hip_text_bgzf rpvg_hip_text_bgzf;
+
 #ifdef __cplusplus
 }
 #endif

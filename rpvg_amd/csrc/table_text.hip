@@ -400,6 +400,17 @@ int rpvg_hip_table_text_view(rpvg_hip_table_text * text, rpvg_table_text_view * 
     return RPVG_HIP_OK;
 }
 
+int rpvg_hip_table_text_sizes(rpvg_hip_table_text * text, rpvg_table_text_view * view_out) {
+    RPVG_REQUIRE(text && view_out, "rpvg_hip_table_text_sizes: NULL argument");
+    std::lock_guard<std::mutex> lock(text->ctx->mutex);
+    view_out->num_paths = text->num_paths;
+    view_out->num_rows = text->num_rows;
+    view_out->num_bytes = text->num_bytes;
+    view_out->row_off = text->h_row_off.data();
+    view_out->bytes = static_cast<const char *>(text->pinned);  // NULL until rpvg_hip_table_text_view has copied the text
+    return RPVG_HIP_OK;
+}
+
 int rpvg_hip_table_text_get(rpvg_hip_table_text * text, uint64_t byte_begin, uint64_t byte_end, char * dst) {
     RPVG_REQUIRE(text, "rpvg_hip_table_text_get: NULL argument");
     RPVG_REQUIRE(byte_begin <= byte_end && byte_end <= text->num_bytes, "rpvg_hip_table_text_get: bytes %llu to %llu of %llu", static_cast<unsigned long long>(byte_begin),

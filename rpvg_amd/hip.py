@@ -50,6 +50,7 @@ EXPORTS = [
     "rpvg_hip_gibbs_read_counts_resident", "rpvg_hip_gibbs_samples_get", "rpvg_hip_gibbs_samples_free", "rpvg_hip_gibbs_table_build_resident",
     "rpvg_hip_gibbs_table_text", "rpvg_hip_estimates_table_text", "rpvg_hip_table_text_view", "rpvg_hip_table_text_get", "rpvg_hip_table_text_guards",
     "rpvg_hip_table_text_free", "rpvg_hip_estimates_set_text", "rpvg_hip_rows_text", "rpvg_hip_read_rows_text",
+    "rpvg_hip_table_text_sizes", "rpvg_hip_table_text_bgzf", "rpvg_hip_bytes_bgzf", "rpvg_hip_text_bgzf_view", "rpvg_hip_text_bgzf_get", "rpvg_hip_text_bgzf_guards", "rpvg_hip_text_bgzf_free",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
     "rpvg_hip_segment_sort_words",

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <iomanip>
 #include <sstream>
 #include <stdexcept>
@@ -9,6 +10,7 @@
 #include <zlib.h>
 
 #include "../../csrc/rows_text_plan.hpp"
+#include "../../csrc/text_deflate_plan.hpp"
 
 namespace rpvg_amd {
 
@@ -63,6 +65,23 @@ void writeBytes(const std::string & filename, const char * data, const size_t si
 void writeTextFile(const std::string & filename, const std::string & text) {
 
     writeBytes(filename, text.data(), text.size());
+}
+
+void writeRawFile(const std::string & filename, const char * data, const size_t size) {
+
+    std::FILE * file = std::fopen(filename.c_str(), "wb");
+
+    if (!file) {
+
+        throw std::runtime_error("cannot open " + filename + " for writing");
+    }
+
+    const bool written = size == 0 || std::fwrite(data, 1, size, file) == size;
+
+    if (std::fclose(file) != 0 || !written) {
+
+        throw std::runtime_error("cannot write " + filename);
+    }
 }
 
 namespace {
@@ -294,6 +313,13 @@ void writeProbabilityClusters(const std::string & filename, const std::vector<Pr
 void writeProbabilityClustersText(const std::string & filename, const rpvg_table_text_view & text) {
 
     writeBytes(filename, text.bytes, text.num_bytes);
+}
+
+void writeProbabilityClustersBgzf(const std::string & filename, const rpvg_text_bgzf_view & members) {
+
+    std::string file(members.num_bytes ? members.bytes : "", members.num_bytes);
+    rpvg_text_deflate::appendEof(file);
+    writeRawFile(filename, file.data(), file.size());
 }
 
 std::unordered_map<std::string, PathInfo> parseHaplotypeTranscriptInfo(const std::string & filename, const bool parse_haplotype_ids, const bool use_transcript_names) {

@@ -37,6 +37,9 @@ struct ProbabilityCluster {
 std::string readTextFile(const std::string & filename);
 void writeTextFile(const std::string & filename, const std::string & text);
 
+// bytes that are a file already (BGZF members): no gzip, whatever the name ends in
+void writeRawFile(const std::string & filename, const char * data, const size_t size);
+
 std::vector<ProbabilityCluster> readProbabilityClusters(const std::string & filename, const double prob_precision);
 
 // Same format as the reference's writer (a block whose cluster has a rank key gets the extended marker line); gzip when the
@@ -48,6 +51,10 @@ std::string formatProbabilityClusters(const std::vector<ProbabilityCluster> & cl
 
 // The same file from a text formatted on the GPU (TableText::rows, table_text.hpp): the block goes into the file as it is.
 void writeProbabilityClustersText(const std::string & filename, const rpvg_table_text_view & text);
+
+// The same file from the BGZF members the GPU deflated that text into (TableText::bgzf): the members as they are, then BGZF's
+// end-of-file block.  A gzip reader gives the bytes of the text.
+void writeProbabilityClustersBgzf(const std::string & filename, const rpvg_text_bgzf_view & members);
 
 // Path name -> PathInfo with group_id (dense transcript ids in first-seen order), source_count and — when
 // parse_haplotype_ids — source_ids (dense haplotype ids in first-seen order); use_transcript_names

@@ -7,6 +7,7 @@
 
 #include "../hip_engine.hpp"
 #include "cluster_io.hpp"
+#include "../../csrc/text_deflate_plan.hpp"
 
 namespace rpvg_amd {
 
@@ -46,7 +47,33 @@ EstimatesWriter::EstimatesWriter(const std::string & filename_in) : filename(fil
 
 void EstimatesWriter::close() {
 
-    writeTextFile(filename, out.str());
+    if (!has_members) {
+
+        writeTextFile(filename, out.str());
+        return;
+    }
+
+    frameStream();
+    rpvg_text_deflate::appendEof(framed);
+    writeRawFile(filename, framed.data(), framed.size());
+}
+
+void EstimatesWriter::frameStream() {
+
+    const std::string text = out.str();
+    rpvg_text_deflate::frameMembers(text.data(), text.size(), framed);
+    out.str(std::string());
+}
+
+void EstimatesWriter::appendMembers(const rpvg_text_bgzf_view & members) {
+
+    frameStream();
+    has_members = true;
+
+    if (members.num_bytes) {
+
+        framed.append(members.bytes, members.num_bytes);
+    }
 }
 
 AbundanceEstimatesWriter::AbundanceEstimatesWriter(const std::string filename_prefix, const double total_transcript_count_in) : EstimatesWriter(filename_prefix + ".txt"), total_transcript_count(total_transcript_count_in), noise_count(0) {
@@ -778,6 +805,31 @@ void ReadCountGibbsSamplesWriter::addText(const rpvg_gibbs_table_view & table, c
 
     out << std::setprecision(out_precision_digits);
     out.write(text.bytes, text.num_bytes);
+}
+
+void ReadCountGibbsSamplesWriter::addCompressedText(const rpvg_gibbs_table_view & table, const rpvg_table_text_view & text, const rpvg_text_bgzf_view & members) {
+
+    if (table.num_gibbs_samples != num_gibbs_samples) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addCompressedText: the table has " + std::to_string(table.num_gibbs_samples) + " samples per path, the writer " + std::to_string(num_gibbs_samples));
+    }
+
+    if (text.num_paths != table.num_paths) {  // (the text's bytes are not read: a view of its sizes alone will do)
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addCompressedText: the text is not that of the table");
+    }
+
+    if (members.num_text_bytes != text.num_bytes || (members.num_bytes > 0 && !members.bytes)) {
+
+        throw EngineError("ReadCountGibbsSamplesWriter::addCompressedText: the members are not those of the text");
+    }
+
+    for (uint32_t idx = 0; idx < num_gibbs_samples; ++idx) {
+
+        noise_counts.at(idx) += table.noise_counts[idx];
+    }
+
+    appendMembers(members);
 }
 
 void ReadCountGibbsSamplesWriter::addNoiseTranscript(const uint32_t unaligned_read_count) {

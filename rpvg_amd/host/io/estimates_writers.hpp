@@ -9,7 +9,7 @@
 //   ReadCountGibbsSamplesWriter              <prefix>_gibbs.txt.gz  -n > 0                     :98-230
 //
 // The reference streams string buffers to a BGZF writer thread; these writers collect the text and write
-// the file on close() (plain text, gzip for the ".gz" one).  Row order across clusters follows the order
+// the file on close() (plain text, gzip for the ".gz" one; BGZF members from the GPU as they are).  Row order across clusters follows the order
 // of the addEstimates() calls (the reference's order depends on its OpenMP schedule).
 #ifndef RPVG_AMD_ESTIMATES_WRITERS_HPP
 #define RPVG_AMD_ESTIMATES_WRITERS_HPP
@@ -54,9 +54,18 @@ class EstimatesWriter {
 
         std::stringstream out;
 
+        // A writer that took members the GPU deflated (rpvg_amd/csrc/text_deflate.hip): what the stream holds so far becomes members
+        // framed on the host (rpvg_amd/csrc/text_deflate_plan.hpp), the device's members follow as they are.  close() then frames
+        // the rest of the stream, appends BGZF's end-of-file block and writes the bytes as they are.
+        void appendMembers(const rpvg_text_bgzf_view & members);
+
     private:
 
+        void frameStream();
+
         const std::string filename;
+        std::string framed;
+        bool has_members = false;
 };
 
 class AbundanceEstimatesWriter : public EstimatesWriter {
@@ -192,6 +201,11 @@ class ReadCountGibbsSamplesWriter : public EstimatesWriter {
         // exactly as in addTable(), then the block is appended to the stream as it is.  Throws EngineError for a view of another
         // number of samples or a text of another number of paths.
         void addText(const rpvg_gibbs_table_view & table, const rpvg_table_text_view & text);
+
+        // The same text as BGZF members the GPU deflated (TableText::bgzf): addText()'s checks, and the members must be those of the
+        // text (num_text_bytes).  The text's bytes are not read, so TableText::sizes() serves and the plain text stays on the GPU.  The file is then the header row as a member framed here, the device's members, the `Unknown` row
+        // as a member framed here and the end-of-file block: gzip readers give the bytes of the file addText() leads to.
+        void addCompressedText(const rpvg_gibbs_table_view & table, const rpvg_table_text_view & text, const rpvg_text_bgzf_view & members);
 
     private:
 

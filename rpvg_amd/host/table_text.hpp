@@ -239,7 +239,11 @@ class TableText {
             return out;
         }
 
-        ~TableText() { rpvg_hip_table_text_free(text); }
+        ~TableText() {
+
+            rpvg_hip_text_bgzf_free(members);
+            rpvg_hip_table_text_free(text);
+        }
 
         TableText(const TableText &) = delete;
         TableText & operator=(const TableText &) = delete;
@@ -256,6 +260,15 @@ class TableText {
             return text_view;
         }
 
+        // the sizes and row_off without the copy of the text (bytes is NULL unless view() has run): for a writer that takes bgzf()
+        rpvg_table_text_view sizes() {
+
+            rpvg_table_text_view out = {};
+            HipEngine::check(rpvg_hip_table_text_sizes(text, &out), "rpvg_hip_table_text_sizes");
+
+            return out;
+        }
+
         // bytes [begin, end) only, for a writer that streams a text it could not hold twice
         std::string bytes(const uint64_t begin, const uint64_t end) {
 
@@ -263,6 +276,31 @@ class TableText {
             HipEngine::check(rpvg_hip_table_text_get(text, begin, end, out.empty() ? nullptr : &out[0]), "rpvg_hip_table_text_get");
 
             return out;
+        }
+
+        // The text as BGZF members, deflated on the GPU on the first call (rpvg_amd/csrc/text_deflate.hip): the sizes, member_off and
+        // one page-locked copy of the compressed bytes, which ReadCountGibbsSamplesWriter::addCompressedText and
+        // writeProbabilityClustersBgzf put into the .gz file.  The plain text need not be downloaded for it.  Valid until the text's end.
+        const rpvg_text_bgzf_view & bgzf() {
+
+            deflate();
+
+            if (!has_members_view) {
+
+                HipEngine::check(rpvg_hip_text_bgzf_view(members, &members_view), "rpvg_hip_text_bgzf_view");
+                has_members_view = true;
+            }
+
+            return members_view;
+        }
+
+        // the first half of bgzf() alone: the members are made and stay on the GPU
+        void deflate() {
+
+            if (!members) {
+
+                HipEngine::check(rpvg_hip_table_text_bgzf(text, &members), "rpvg_hip_table_text_bgzf");
+            }
         }
 
     private:
@@ -273,6 +311,9 @@ class TableText {
         rpvg_hip_table_text * text;
         rpvg_table_text_view text_view;
         bool has_view;
+        rpvg_hip_text_bgzf * members = nullptr;
+        rpvg_text_bgzf_view members_view = {};
+        bool has_members_view = false;
 };
 
 // ---- the comparison line: the same rows on one host thread ----------------------------------------------------------------------

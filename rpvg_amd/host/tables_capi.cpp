@@ -16,6 +16,7 @@
 #include "io/estimates_writers.hpp"
 #include "runner_handles.hpp"
 #include "table_text.hpp"
+#include "../csrc/text_deflate_plan.hpp"
 
 using namespace rpvg_amd;
 using namespace rpvg_amd_harness;
@@ -784,6 +785,86 @@ int rpvg_amd_table_text_write(void * text_handle, uint32_t num_gibbs_samples, co
             const std::string writer = handle->sets ? (handle->kind == RPVG_TEXT_JOINT ? "joint" : "posterior") : (handle->kind == RPVG_TEXT_PER_PATH ? "abundance" : "haplotype");
 
             writeWith(writer, handle->sets ? handle->ploidy : handle->estimates->ploidy, handle->min_posterior, view.tpm_denominator, output_prefix, unaligned_read_count, [&](auto & out) { addTextTo(out, estimates, view, handle->text->view()); });
+        }
+
+        return 0;
+    });
+}
+
+// The text as BGZF members deflated on the GPU (TableText::bgzf); valid until the text's end.  seconds_out [2], or NULL: the
+// compression and the download of the members, each 0 when an earlier call had done it.
+int rpvg_amd_table_text_bgzf(void * text_handle, rpvg_text_bgzf_view * view_out, double * seconds_out) {
+
+    return guardedInt([&]() -> int {
+
+        TableText & text = *static_cast<TextHandle *>(text_handle)->text;
+        const auto start = std::chrono::steady_clock::now();
+        text.deflate();
+        const auto deflated = std::chrono::steady_clock::now();
+        *view_out = text.bgzf();
+
+        if (seconds_out) {
+
+            seconds_out[0] = std::chrono::duration<double>(deflated - start).count();
+            seconds_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - deflated).count();
+        }
+
+        return 0;
+    });
+}
+
+// rpvg_amd_table_text_write with the rows as the members the GPU deflated: <prefix>.txt.gz of a Gibbs text through the writer's
+// addCompressedText(), the file `output_prefix` of the dump through writeProbabilityClustersBgzf.  The estimates files are plain text
+// in the reference and have no such route.
+int rpvg_amd_table_text_write_compressed(void * text_handle, uint32_t num_gibbs_samples, const char * output_prefix, uint32_t unaligned_read_count) {
+
+    return guardedInt([&]() -> int {
+
+        TextHandle * handle = static_cast<TextHandle *>(text_handle);
+
+        if (handle->rows) {
+
+            writeProbabilityClustersBgzf(output_prefix, handle->text->bgzf());
+
+        } else if (handle->gibbs) {
+
+            ReadCountGibbsSamplesWriter out(output_prefix, num_gibbs_samples);
+            out.addCompressedText(handle->gibbs->view(), handle->text->sizes(), handle->text->bgzf());  // (the plain text is not downloaded)
+            out.addNoiseTranscript(unaligned_read_count);
+            out.close();
+
+        } else {
+
+            throw std::runtime_error("the estimates files are plain text: only the Gibbs file and the dump are written compressed");
+        }
+
+        return 0;
+    });
+}
+
+// The members of any bytes by the host's model of the device's member (rpvg_amd/csrc/text_deflate_plan.hpp: modelMembers), without a
+// GPU.  bytes_out may be NULL: a first call asks for num_bytes_out.
+int rpvg_amd_bytes_bgzf_model(const char * bytes, uint64_t n, char * bytes_out, uint64_t * num_bytes_out, uint64_t * num_stored_out) {
+
+    return guardedInt([&]() -> int {
+
+        std::string members;
+        uint64_t stored = 0;
+        rpvg_text_deflate::modelMembers(bytes, n, members, &stored);
+
+        if (num_bytes_out) {
+
+            *num_bytes_out = members.size();
+        }
+
+        if (num_stored_out) {
+
+            *num_stored_out = stored;
+        }
+
+        if (bytes_out) {
+
+            std::copy(members.begin(), members.end(), bytes_out);
         }
 
         return 0;

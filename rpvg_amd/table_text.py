@@ -5,7 +5,10 @@ the rows ReadCountGibbsSamplesWriter, AbundanceEstimatesWriter and HaplotypeAbun
   Labels      the names, lengths and ClusterIDs of a batch's paths in the flat form of rpvg_table_labels, host arrays
   RowsInput   the rows of a batch and the path side of the --write-probs dump in the flat form of rpvg_rows_text_input
   TableText   over the C ABI (a hip.Context or an engine.Engine): gibbs / estimates / sets / rows / resident_rows / view / bytes /
-              guards_intact / free; rows: the --write-probs dump (rpvg_amd/csrc/rows_text.hip), whose rows are the lines of the file
+              guards_intact / free; rows: the --write-probs dump (rpvg_amd/csrc/rows_text.hip), whose rows are the lines of the file;
+              bgzf: the text as the members of a .gz file, deflated on the GPU (rpvg_amd/csrc/text_deflate.hip)
+  BgzfText    BGZF members resident on the GPU (rpvg_hip_text_bgzf): view / bytes / guards_intact / free; bgzf_bytes(ctx, data)
+              makes one of any bytes, bgzf_model(data) the same members on the host without a GPU
   HarnessTableText  over the harness entry points: the text of a HarnessGibbsTable or a HarnessTable through the host class
               (rpvg_amd/host/table_text.hpp), the file from it by the writer's addText(), and the same rows from one host thread
 """
@@ -35,6 +38,21 @@ class CTableTextView(C.Structure):
     """rpvg_table_text_view"""
     _fields_ = [("num_paths", C.c_uint64), ("num_rows", C.c_uint64), ("num_bytes", C.c_uint64), ("row_off", C.POINTER(C.c_uint64)),
                 ("bytes", C.POINTER(C.c_char))]
+
+
+class CTextBgzfView(C.Structure):
+    """rpvg_text_bgzf_view"""
+    _fields_ = [("num_members", C.c_uint64), ("num_text_bytes", C.c_uint64), ("num_bytes", C.c_uint64), ("num_stored_members", C.c_uint64),
+                ("member_off", C.POINTER(C.c_uint64)), ("bytes", C.POINTER(C.c_char))]
+
+
+CHUNK_BYTES = 65280  # the text of member i starts at byte i * CHUNK_BYTES
+
+
+def _bgzf_view_dict(v) -> dict:
+    M, n = int(v.num_members), int(v.num_bytes)
+    return dict(num_members=M, num_text_bytes=int(v.num_text_bytes), num_bytes=n, num_stored_members=int(v.num_stored_members),
+                member_off=np.ctypeslib.as_array(v.member_off, shape=(M + 1,)).copy(), bytes=C.string_at(v.bytes, n) if n else b"")
 
 
 class CRowsTextInput(C.Structure):
@@ -184,8 +202,71 @@ class TableText(HandleOwner):
         hip._check(hip.lib().rpvg_hip_table_text_guards(self.handle, C.byref(intact)), "rpvg_hip_table_text_guards")
         return bool(intact.value)
 
+    def bgzf(self) -> "BgzfText":
+        """The text as BGZF members, deflated on the GPU (rpvg_hip_table_text_bgzf).  The text stays as it is."""
+        handle = C.c_void_p()
+        hip._check(hip.lib().rpvg_hip_table_text_bgzf(self.handle, C.byref(handle)), "rpvg_hip_table_text_bgzf")
+        return BgzfText(handle)
+
     def _release(self):
         hip.lib().rpvg_hip_table_text_free(self.handle)
+
+
+class BgzfText(HandleOwner):
+    """BGZF members resident on the GPU (rpvg_hip_text_bgzf): the bytes of a .gz file but for the end-of-file block."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def view(self) -> dict:
+        """num_members, num_text_bytes, num_bytes, num_stored_members, member_off [num_members + 1] and the members as bytes."""
+        v = CTextBgzfView()
+        hip._check(hip.lib().rpvg_hip_text_bgzf_view(self.handle, C.byref(v)), "rpvg_hip_text_bgzf_view")
+        return _bgzf_view_dict(v)
+
+    def bytes(self, begin: int, end: int) -> bytes:
+        """Bytes [begin, end) of the members (rpvg_hip_text_bgzf_get)."""
+        out = C.create_string_buffer(max(end - begin, 1))
+        hip._check(hip.lib().rpvg_hip_text_bgzf_get(self.handle, C.c_uint64(begin), C.c_uint64(end), out), "rpvg_hip_text_bgzf_get")
+        return out.raw[:max(end - begin, 0)]
+
+    def guards_intact(self) -> bool:
+        intact = C.c_int32(0)
+        hip._check(hip.lib().rpvg_hip_text_bgzf_guards(self.handle, C.byref(intact)), "rpvg_hip_text_bgzf_guards")
+        return bool(intact.value)
+
+    def _release(self):
+        hip.lib().rpvg_hip_text_bgzf_free(self.handle)
+
+
+def bgzf_bytes(ctx_or_engine, data, device_pointer=None, num_bytes: Optional[int] = None) -> BgzfText:
+    """Any bytes as BGZF members (rpvg_hip_bytes_bgzf): data is a bytes-like object in host memory, or None with device_pointer
+    and num_bytes for bytes that lie in the memory of the context's GPU."""
+    handle = C.c_void_p()
+    if device_pointer is not None:
+        pointer, n, on_device = C.c_void_p(device_pointer), int(num_bytes), 1
+    else:
+        raw = bytes(data) if data is not None else b""
+        n = len(raw) if num_bytes is None else int(num_bytes)
+        pointer, on_device = C.cast(C.c_char_p(raw), C.c_void_p) if data is not None else C.c_void_p(None), 0
+    hip._check(hip.lib().rpvg_hip_bytes_bgzf(ctx_handle(ctx_or_engine), pointer, C.c_uint64(n), C.c_int32(on_device), C.byref(handle)), "rpvg_hip_bytes_bgzf")
+    return BgzfText(handle)
+
+
+def bgzf_model(data) -> dict:
+    """The members the GPU makes of these bytes, from the host's model of its kernel (rpvg_amd/csrc/text_deflate_plan.hpp:
+    modelMembers), without a GPU: bytes and num_stored_members."""
+    from . import engine
+    L = engine.lib()
+    L.rpvg_amd_bytes_bgzf_model.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    raw = bytes(data)
+    n, stored = C.c_uint64(0), C.c_uint64(0)
+    if L.rpvg_amd_bytes_bgzf_model(raw, len(raw), None, C.byref(n), C.byref(stored)) != 0:
+        raise hip.EngineError(f"bgzf model failed: {engine._err()}")
+    out = C.create_string_buffer(max(n.value, 1))
+    if L.rpvg_amd_bytes_bgzf_model(raw, len(raw), out, None, None) != 0:
+        raise hip.EngineError(f"bgzf model failed: {engine._err()}")
+    return dict(bytes=out.raw[:n.value], num_stored_members=int(stored.value))
 
 
 # ---- the harness: the text of a prepared batch's tables, the files from it and the host line ------------------------------------
@@ -205,6 +286,8 @@ def _harness():
     L.rpvg_amd_table_text_resident_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CTableLabels), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_view.argtypes = [C.c_void_p, C.POINTER(CTableTextView)]
     L.rpvg_amd_table_text_write.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]
+    L.rpvg_amd_table_text_write_compressed.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]
+    L.rpvg_amd_table_text_bgzf.argtypes = [C.c_void_p, C.POINTER(CTextBgzfView), C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_host_line.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_double)]
     L.rpvg_amd_table_text_parent_route.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -252,11 +335,29 @@ class HarnessTableText(HandleOwner):
         return dict(row_off=np.ctypeslib.as_array(v.row_off, shape=(P + 1,)).copy(), bytes=C.string_at(v.bytes, n) if n and copy else b"", num_rows=int(v.num_rows),
                     num_bytes=n)
 
-    def write(self, prefix: str, num_gibbs_samples: int = 0, unaligned_read_count: int = 0):
-        """<prefix>.txt.gz (a Gibbs text) or <prefix>.txt (an estimates text) through the writer's addText()."""
+    def write(self, prefix: str, num_gibbs_samples: int = 0, unaligned_read_count: int = 0, compressed: bool = False):
+        """<prefix>.txt.gz (a Gibbs text) or <prefix>.txt (an estimates text) through the writer's addText().  compressed: the rows
+        go into the file as the BGZF members the GPU deflated (the Gibbs file through addCompressedText(), the dump through
+        writeProbabilityClustersBgzf); the estimates files are plain text and refuse it."""
         L, eng = _harness()
-        if L.rpvg_amd_table_text_write(self.handle, num_gibbs_samples, prefix.encode(), unaligned_read_count) != 0:
+        write = L.rpvg_amd_table_text_write_compressed if compressed else L.rpvg_amd_table_text_write
+        if write(self.handle, num_gibbs_samples, prefix.encode(), unaligned_read_count) != 0:
             raise hip.EngineError(f"table text write failed: {eng._err()}")
+
+    def bgzf(self, copy: bool = True) -> dict:
+        """The text as BGZF members deflated on the GPU (the host class's TableText::bgzf): the dict of BgzfText.view(), and the
+        seconds the compression and the download of the members took in this call (0 when an earlier call had done them)."""
+        L, eng = _harness()
+        v = CTextBgzfView()
+        seconds = (C.c_double * 2)()
+        if L.rpvg_amd_table_text_bgzf(self.handle, C.byref(v), seconds) != 0:
+            raise hip.EngineError(f"table text bgzf failed: {eng._err()}")
+        if not copy:
+            v.num_bytes, n = 0, int(v.num_bytes)
+        out = _bgzf_view_dict(v)
+        if not copy:
+            out["num_bytes"] = n
+        return dict(out, compress_seconds=seconds[0], download_seconds=seconds[1])
 
     def host_line(self, num_paths: int, want_bytes: bool = True, recompute: bool = False) -> dict:
         """The same rows from the host views of the table on one host thread: bytes, row_off, exact_cells, seconds (of the walk,
