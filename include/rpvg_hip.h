@@ -278,10 +278,18 @@ int rpvg_hip_groups_build_single_paths(rpvg_hip_ctx * ctx, const rpvg_hip_batch 
 void rpvg_hip_groups_free(rpvg_hip_ctx * ctx, rpvg_hip_groups * groups);
 /* What the row collapse of these matrices did (waits for their build; any output may be NULL): matrices that held
  * rows within collapse_precision of each other but not equal up to rounding, whose runs were therefore replayed as
- * the reference forms them; rows that took the values of their run head; matrices that were sorted as a whole
+ * the reference forms them; rows that took the values of their run head and were changed by it (a bit-for-bit copy of
+ * its head is not counted); matrices that were sorted as a whole
  * (otherwise only the rows close to such a pair are); rows that took part in a replay. */
 int rpvg_hip_groups_collapse_info(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t * matrices_replayed,
                                   uint32_t * rows_replaced, uint32_t * matrices_sorted_whole, uint32_t * active_rows);
+/* A test entry, not part of the estimators' path: matrix `matrix` as its readers see it, copied to the host — values_out [R * G]
+ * column-major (column g at values_out + g * R), noise_out, rowmax_out and count_out [R], the rows in the matrix's own order (a
+ * permutation of its cluster's rows that does not depend on collapse_precision).  It waits for the row collapse like every
+ * reader, so a last stage that was held back for the search is queued first and the rows of every run hold their head's
+ * values.  RPVG_HIP_ERR_INVALID for a NULL argument (outputs of a matrix without rows may be NULL) or a matrix out of range. */
+int rpvg_hip_groups_rows(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t matrix, double * values_out, double * noise_out,
+                         double * rowmax_out, double * count_out);
 /* A test entry, not part of the estimators' path: the segment sort at the head of the row collapse on caller-supplied words, so
  * that its network is testable without a whole collapse.  Segment s is words[segment_off[s] .. segment_off[s + 1])
  * (segment_off[0] = 0, ascending, num_segments + 1 entries, fewer than 2^31 words in all); out receives every segment's words

@@ -1223,6 +1223,35 @@ int rpvg_hip_groups::buildError(hipStream_t stream) const {
     return RPVG_HIP_OK;
 }
 
+// One built matrix row by row, for the tests of the row collapse (include/rpvg_hip.h): behind waitCollapse, so with the rows of
+// every run rewritten — a held-back last stage is queued first.  The matrix's places come from the device's own offset arrays.
+extern "C" int rpvg_hip_groups_rows(rpvg_hip_ctx * ctx, const rpvg_hip_groups * groups, uint32_t matrix, double * values_out, double * noise_out,
+                                    double * rowmax_out, double * count_out) {
+    RPVG_REQUIRE(ctx && groups, "rpvg_hip_groups_rows: NULL argument");
+    RPVG_REQUIRE(matrix < groups->num_matrices, "rpvg_hip_groups_rows: matrix %u of %u", matrix, groups->num_matrices);
+    const uint64_t R = groups->h_num_rows[matrix], G = groups->h_num_cols[matrix];
+    RPVG_REQUIRE(R == 0 || (noise_out && rowmax_out && count_out && (values_out || G == 0)), "rpvg_hip_groups_rows: NULL output");
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    RPVG_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    RPVG_HIP_CHECK(groups->waitCollapse(st));
+    uint64_t val_off = 0, row_off = 0;
+    RPVG_HIP_CHECK(hipMemcpyAsync(&val_off, groups->mat_val_off.ptr + matrix, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(hipMemcpyAsync(&row_off, groups->mat_row_off.ptr + matrix, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RPVG_HIP_CHECK(waitStream(st));
+    RPVG_REQUIRE(val_off + R * G <= groups->values.count && row_off + R <= groups->rowmax.count && row_off + R <= groups->row_count.count &&
+                     row_off + R <= groups->row_noise.count,
+                 "rpvg_hip_groups_rows: matrix %u lies outside the buffers", matrix);
+    if (R * G) RPVG_HIP_CHECK(hipMemcpyAsync(values_out, groups->values.ptr + val_off, R * G * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (R) {
+        RPVG_HIP_CHECK(hipMemcpyAsync(noise_out, groups->row_noise.ptr + row_off, R * sizeof(double), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(rowmax_out, groups->rowmax.ptr + row_off, R * sizeof(double), hipMemcpyDeviceToHost, st));
+        RPVG_HIP_CHECK(hipMemcpyAsync(count_out, groups->row_count.ptr + row_off, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    RPVG_HIP_CHECK(waitStream(st));
+    return groups->buildError(st);  // the matrices were built without a host sync
+}
+
 extern "C" void rpvg_hip_groups_free(rpvg_hip_ctx * ctx, rpvg_hip_groups * groups) {
     if (!groups) return;
     if (ctx) {

@@ -1021,26 +1021,32 @@ __device__ __forceinline__ void finishRuns(const ReplayArgs<MatrixArrays> & a, c
         const uint32_t h = head_of[q];
         if (h == q) continue;
         const uint32_t dst = order[q], src = order[h];
+        // a copy of its head (the rows of a stretch join their runs together) takes its head's values and keeps its own: only
+        // the rows whose values CHANGE count as replaced
+        bool changed = nz[dst] != nz[src];
         // (a column is a cache line of its own, in either row: eight loads in flight per lane — one at a time, a merged row of a
         // 2 000-column matrix took a wave 60 us)
         for (uint32_t c0 = lane; c0 < mv.G; c0 += 64 * 8) {
-            double v[8];
+            double v[8], old[8];
 #pragma unroll
             for (uint32_t k = 0; k < 8; ++k) {
                 const uint32_t c = c0 + 64 * k;
                 v[k] = c < mv.G ? __builtin_nontemporal_load(&M[static_cast<uint64_t>(c) * R + src]) : 0.0;
+                old[k] = c < mv.G ? __builtin_nontemporal_load(&M[static_cast<uint64_t>(c) * R + dst]) : 0.0;
             }
 #pragma unroll
             for (uint32_t k = 0; k < 8; ++k) {
                 const uint32_t c = c0 + 64 * k;
+                changed = changed || old[k] != v[k];
                 if (c < mv.G) M[static_cast<uint64_t>(c) * R + dst] = v[k];
             }
         }
+        changed = __any(changed) != 0;  // (a wave per row: uniform)
         if (lane == 0) {
             const double noise = nz[src];
             nz[dst] = noise;
             rm[dst] = rm[src];
-            ++replaced;
+            if (changed) ++replaced;
             // a product-path row (LogProduct, common.hpp) needs noise >= kProductMinNoise: if the head's is below,
             // the whole matrix takes the logarithm path
             if (dst < fast_mid_end && !(noise >= kProductMinNoise)) *demote = 1;

@@ -53,7 +53,7 @@ EXPORTS = [
     "rpvg_hip_table_text_sizes", "rpvg_hip_table_text_bgzf", "rpvg_hip_bytes_bgzf", "rpvg_hip_text_bgzf_view", "rpvg_hip_text_bgzf_get", "rpvg_hip_text_bgzf_guards", "rpvg_hip_text_bgzf_free",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
-    "rpvg_hip_segment_sort_words",
+    "rpvg_hip_segment_sort_words", "rpvg_hip_groups_rows",
 ]
 
 COMM_ID_BYTES = 128  # RPVG_HIP_COMM_ID_BYTES
@@ -572,12 +572,16 @@ class DeviceGroups:
         self.ctx = ctx
         self.batch = batch
         cl = np.ascontiguousarray(clusters, dtype=np.uint32)
+        host = batch.host  # (None: a batch made on the device — rows() needs the host's sizes)
+        self._rows = [int(host.cluster_row_off[k + 1] - host.cluster_row_off[k]) for k in cl] if host is not None else None
         if groups is None:  # column c of a matrix = path c of its cluster alone: rpvg_hip_groups_build_single_paths
+            self._cols = [int(host.cluster_path_off[k + 1] - host.cluster_path_off[k]) for k in cl] if host is not None else None
             self.handle = C.c_void_p()
             _check(lib().rpvg_hip_groups_build_single_paths(ctx.handle, batch.handle, C.c_uint32(len(cl)), C.c_void_p(cl.ctypes.data),
                                                             C.c_int32(1 if normalise else 0), C.c_double(float(collapse_precision)),
                                                             C.byref(self.handle)), "rpvg_hip_groups_build_single_paths")
             return
+        self._cols = [len(cols) for cols in groups]
         goff, gpoff, gp = [0], [0], []
         for cols in groups:
             for paths in cols:
@@ -592,6 +596,35 @@ class DeviceGroups:
         self.handle = C.c_void_p()
         _check(lib().rpvg_hip_groups_build(ctx.handle, batch.handle, C.byref(spec), C.byref(self.handle)),
                "rpvg_hip_groups_build")
+
+    @classmethod
+    def from_sources(cls, ctx: "Context", batch: DeviceBatch, clusters: Sequence[int], normalise: bool, collapse_precision: float = 0.0) -> "DeviceGroups":
+        """rpvg_hip_groups_build_from_sources: the columns of matrix m are the haplotype columns the upload formed for clusters[m]
+        (DeviceBatch.source_columns); their multiplicities stay on the device (bounded_pair_posteriors(None, ...)).  With a
+        collapse_precision the last stage of the collapse is held back for the diploid search."""
+        self = cls.__new__(cls)
+        self.ctx, self.batch = ctx, batch
+        cl = np.ascontiguousarray(clusters, dtype=np.uint32)
+        self._rows = [int(batch.host.cluster_row_off[k + 1] - batch.host.cluster_row_off[k]) for k in cl]
+        self._cols = [len(batch.source_columns(int(k))[0]) for k in cl]
+        self.handle = C.c_void_p()
+        _check(lib().rpvg_hip_groups_build_from_sources(ctx.handle, batch.handle, C.c_uint32(len(cl)), C.c_void_p(cl.ctypes.data),
+                                                        C.c_int32(1 if normalise else 0), C.c_double(float(collapse_precision)),
+                                                        C.byref(self.handle)), "rpvg_hip_groups_build_from_sources")
+        return self
+
+    def rows(self, m: int):
+        """rpvg_hip_groups_rows (a test entry): matrix m as its readers see it behind the row collapse — (values [R, G], noise [R],
+        row maxima [R], counts [R]), rows in the matrix's own order."""
+        if self._rows is None or self._cols is None:
+            raise EngineError("DeviceGroups.rows: the batch has no host copy to take the matrix's sizes from")
+        R, G = self._rows[m], self._cols[m]
+        values = np.zeros((G, R), dtype=np.float64)  # column-major on the device
+        noise, rowmax, count = (np.zeros(R, dtype=np.float64) for _ in range(3))
+        _check(lib().rpvg_hip_groups_rows(self.ctx.handle, self.handle, C.c_uint32(m), C.c_void_p(values.ctypes.data),
+                                          C.c_void_p(noise.ctypes.data), C.c_void_p(rowmax.ctypes.data), C.c_void_p(count.ctypes.data)),
+               "rpvg_hip_groups_rows")
+        return np.ascontiguousarray(values.T), noise, rowmax, count
 
     def collapse_info(self):
         """(matrices whose runs were replayed, rows that took the values of their run head, matrices sorted as a
@@ -823,10 +856,11 @@ class DeviceGroups:
             lib().rpvg_hip_gibbs_sets_free(h)
 
     def bounded_pair_posteriors(self, column_counts, min_rel_likelihood: float):
-        """Per matrix: ([(first, second)...], posteriors) of the on-device branch-and-bound."""
-        cc = np.ascontiguousarray(column_counts, dtype=np.uint32)
+        """Per matrix: ([(first, second)...], posteriors) of the on-device branch-and-bound.  column_counts None: the
+        multiplicities that matrices built from_sources carry."""
+        cc = None if column_counts is None else np.ascontiguousarray(column_counts, dtype=np.uint32)
         h = C.c_void_p()
-        _check(lib().rpvg_hip_bounded_pair_posteriors(self.ctx.handle, self.handle, C.c_void_p(cc.ctypes.data),
+        _check(lib().rpvg_hip_bounded_pair_posteriors(self.ctx.handle, self.handle, C.c_void_p(cc.ctypes.data if cc is not None else None),
                                                       C.c_double(min_rel_likelihood), C.byref(h)),
                "rpvg_hip_bounded_pair_posteriors")
         try:

@@ -4,7 +4,8 @@ words of the test's own, against numpy.sort per segment.
 
 The entry writes the sorted words only: what the collapse derives from a word and its predecessor in the image ("equal to its
 predecessor", the stretch starts, also across lane and wavefront boundaries) is not checked here but by tests/test_hip_collapse.py,
-whose planted rows go through the one-wavefront, two-wavefront and chunked routes."""
+whose planted rows go through the one-wavefront, two-wavefront and chunked routes, and row by row by tests/test_hip_collapse_edges.py,
+whose runs and stretches of bit-identical rows lie across the sorted positions 64, 512, 1 024 and 2 048."""
 import numpy as np
 import pytest
 
