@@ -808,6 +808,49 @@ int rpvg_hip_estimates_table_view(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table *
 void rpvg_hip_estimates_table_limits(rpvg_estimates_table_limits * limits_out);
 void rpvg_hip_estimates_table_free(rpvg_hip_ctx * ctx, rpvg_hip_estimates_table * table);
 
+/* ---- resident estimates (rpvg_table.h; rpvg_amd/csrc/estimates_gather.hip) -------------------------------------------------
+ * The link between the nested calls and the table: their merged sets, still on the device, gathered into rpvg_estimates_flat with
+ * on_device = 1 — what NestedPathAbundanceEstimator::unpackMergedSolutions / unpackMergedSetSolutions and FlatEstimates::add do on
+ * the host, without an estimate crossing to it.
+ *   rpvg_hip_subset_em_keep_device   a property of the context, read by rpvg_hip_nested_subset_em, rpvg_hip_nested_full_subset_em and
+ *                                   rpvg_hip_nested_independent_subset_em: with keep != 0 a successful call hands its packed device
+ *                                   block to its result instead of releasing it; rpvg_hip_subset_em_free returns it to the pool.
+ *                                   THE KEPT BLOCK HAS THE SIZE OF THE CALL'S CAPACITIES (what it reserved for subsets, lists and
+ *                                   columns), NOT OF THE RESULT.  With the default, 0, nothing changes in launches, copies,
+ *                                   allocations or memory held.  The property is set, not counted: a caller that switches it on
+ *                                   and off around a call (NestedPathAbundanceEstimator::estimateBatchResident does, on each lane's
+ *                                   context) leaves it off, whatever it was before.
+ *   rpvg_hip_subset_em_kept_bytes    the device memory a result's kept block holds (its capacity); 0 when none was kept.
+ *   rpvg_hip_subset_em_part          the merged sets of a kept result as a part (on_device = 1, pointers into the kept block, valid
+ *                                   until the result is freed); unit_cluster is left NULL for the caller to fill.
+ *                                   RPVG_HIP_ERR_UNSUPPORTED when the block was not kept or the call did no merge on the device (a
+ *                                   batch without path_group_id).
+ *   rpvg_hip_flat_estimates_gather   the flat estimates of `batch` (K clusters) from num_parts parts.  Cluster c = unit_cluster[u] of
+ *                                   a unit u gets that unit's sets in slot order, each with its posterior, its members in list order
+ *                                   (repeats kept) and as many abundances; noise_count[c] = cluster_noise_count[u] when the unit has
+ *                                   subsets, the batch's read count of the cluster otherwise; a cluster in no unit has no sets and
+ *                                   its read count as noise.  abund_off[k] = member_off[set_off[k]].  Every double is copied: no
+ *                                   floating-point operation is executed.  path_effective_length: [num_paths of the batch], host
+ *                                   (copied) or device (eff_on_device != 0: borrowed, it must outlive the handle's use).
+ *                                   RPVG_HIP_ERR_INVALID, the smallest offending (part, unit) named in last_error and the context
+ *                                   left usable, for: a unit_cluster >= K; a cluster listed by two units (every unit that shares its
+ *                                   cluster offends); subset_off or path_off that are not non-decreasing offsets from 0 to S and L;
+ *                                   a set_count beyond the unit's slots; a set size outside 1 .. width (1 .. 2 at width 0); a member
+ *                                   at or beyond its cluster's number of paths; width > 8; a batch without cluster totals
+ *                                   (rpvg_hip_read_rows_to_batch).  One word for the first offender and the totals S and M come to
+ *                                   the host.
+ *   rpvg_hip_flat_estimates_view     the device view (on_device = 1; the sizes are host values; cluster_path_off is the batch's own
+ *                                   array, so the batch must outlive the view's use).
+ *   rpvg_hip_flat_estimates_get      host copies (on_device = 0): one packed copy to page-locked memory, valid until _free. */
+int rpvg_hip_subset_em_keep_device(rpvg_hip_ctx * ctx, int32_t keep);
+int rpvg_hip_subset_em_part(const rpvg_hip_subset_em * result, rpvg_estimates_part * part_out);
+uint64_t rpvg_hip_subset_em_kept_bytes(const rpvg_hip_subset_em * result);
+int rpvg_hip_flat_estimates_gather(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, const rpvg_estimates_part * parts, uint32_t num_parts,
+                                   const double * path_effective_length, int32_t eff_on_device, rpvg_hip_flat_estimates ** estimates_out);
+int rpvg_hip_flat_estimates_view(const rpvg_hip_flat_estimates * estimates, rpvg_estimates_flat * view_out);
+int rpvg_hip_flat_estimates_get(rpvg_hip_ctx * ctx, rpvg_hip_flat_estimates * estimates, rpvg_estimates_flat * host_out);
+void rpvg_hip_flat_estimates_free(rpvg_hip_ctx * ctx, rpvg_hip_flat_estimates * estimates);
+
 /* ---- Gibbs samples table (rpvg_samples.h; rpvg_amd/csrc/gibbs_table.hip) ---------------------------------------------------
  *   rpvg_hip_gibbs_table_build           the table of `<prefix>_gibbs.txt.gz` for a batch, every value as rpvg_samples.h states it: per
  *                                       path its N sample columns, what ReadCountGibbsSamplesWriter::addSamples reads transposed

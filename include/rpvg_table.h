@@ -96,6 +96,40 @@ typedef struct rpvg_estimates_table_limits {
 
 typedef struct rpvg_hip_estimates_table rpvg_hip_estimates_table;
 
+/* ---- the merged sets of some clusters as the nested calls leave them, and the flat form gathered from them on the GPU ----
+ * (rpvg_amd/csrc/estimates_gather.hip; the rules are rpvg_amd/csrc/estimates_gather_plan.hpp)
+ *
+ * A part is what rpvg_hip_subset_em_view (width 0) or rpvg_hip_subset_em_sets_view / rpvg_hip_subset_em_independent_view (width =
+ * their group size) describe: U units — the matrices of the collapsed calls, the clusters of the independent call — with S path
+ * subsets and L list entries; the merged sets of unit u sit in the slots first + q, first = path_off[subset_off[u]], q <
+ * set_count[u].
+ *   width 0      the diploid form: set_first, set_second (UINT32_MAX: the set has one path), two abundances per slot
+ *   width 1..8   set_size (1 .. width), set_member and set_abundance with `width` cells per slot
+ * A batch's clusters are split over the lanes of an engine, so a batch is gathered from one or more parts; unit_cluster names
+ * the batch cluster of every unit and is always host memory.  on_device = 1: every other array is device memory of the context's
+ * GPU, read where it lies; on_device = 0: host memory, copied by the call. */
+typedef struct rpvg_estimates_part {
+    uint32_t num_units;                  /* U */
+    uint64_t num_subsets;                /* S */
+    uint64_t num_slots;                  /* L */
+    uint32_t width;                      /* 0: diploid; 1..8 */
+    const uint32_t * unit_cluster;       /* [U]   host memory */
+    const uint64_t * subset_off;         /* [U+1] */
+    const uint64_t * path_off;           /* [S+1] */
+    const uint32_t * set_count;          /* [U]   */
+    const double * cluster_noise_count;  /* [U]   */
+    const double * set_posterior;        /* [L]   */
+    const uint32_t * set_first;          /* [L]   width 0 */
+    const uint32_t * set_second;         /* [L]   width 0 */
+    const uint32_t * set_size;           /* [L]   width > 0 */
+    const uint32_t * set_member;         /* [L x width] width > 0 */
+    const double * set_abundance;        /* [L x 2] (width 0) or [L x width] */
+    int32_t on_device;
+} rpvg_estimates_part;
+
+/* The flat estimates of a batch, resident on the GPU (rpvg_hip_flat_estimates_gather, rpvg_hip.h). */
+typedef struct rpvg_hip_flat_estimates rpvg_hip_flat_estimates;
+
 #ifdef __cplusplus
 }
 #endif

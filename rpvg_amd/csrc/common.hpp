@@ -648,6 +648,9 @@ struct rpvg_hip_ctx {
     rpvg_hip_detail::SubsetEmHints subset_hints;
     rpvg_hip_detail::SubsetEmHints subset_full_hints;  // the same for rpvg_hip_nested_full_subset_em (subset_full.hip): its lists are longer
     bool search_gate_held = false;  // the search this context has queued takes part in "one search at a time" (bounded_search.hip)
+    // rpvg_hip_subset_em_keep_device: the three nested calls hand their packed device block to their result instead of releasing it
+    // (subset_result.hpp; estimates_gather.hip reads it where it lies)
+    bool keep_subset_block = false;
     int device = 0;
     hipStream_t stream = nullptr;
     // Side streams for independent launches of one call (size bins of the batched kernels): their tails

@@ -706,6 +706,13 @@ void rpvg_hip_destroy(rpvg_hip_ctx * ctx) {
 
 const char * rpvg_hip_last_error(void) { return g_last_error; }
 
+int rpvg_hip_subset_em_keep_device(rpvg_hip_ctx * ctx, int32_t keep) {
+    RPVG_REQUIRE(ctx != nullptr, "rpvg_hip_subset_em_keep_device: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    ctx->keep_subset_block = keep != 0;
+    return RPVG_HIP_OK;
+}
+
 int rpvg_hip_synchronize(rpvg_hip_ctx * ctx) {
     RPVG_REQUIRE(ctx != nullptr, "rpvg_hip_synchronize: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mutex);

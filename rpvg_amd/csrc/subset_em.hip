@@ -1068,6 +1068,7 @@ static int nestedSubsetEmAttempt(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batc
     res->num_subsets = S;
     accountEmSolve(ctx, static_cast<uint32_t>(S), v.col_off, reinterpret_cast<const uint32_t *>(host + lay.kept_rows),
                    reinterpret_cast<const uint32_t *>(host + lay.kept_entries), v.iterations);
+    if (ctx->keep_subset_block) res->keep(d_packed, lay, got.list_length, 0, merge_here);  // (rpvg_hip_subset_em_keep_device)
     *result_out = res.release();
     return RPVG_HIP_OK;
 }

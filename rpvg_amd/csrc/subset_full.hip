@@ -1209,6 +1209,7 @@ static int nestedFullAttempt(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, c
     ctx->stats.nested_full_calls += 1;
     ctx->stats.nested_full_sets += kept.total_sets;
     ctx->stats.nested_full_retained += got.retained;
+    if (ctx->keep_subset_block) res->keep(d_packed, lay, got.list_length, GS, true);  // (rpvg_hip_subset_em_keep_device)
     *result_out = res.release();
     return RPVG_HIP_OK;
 }

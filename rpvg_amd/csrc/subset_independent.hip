@@ -877,6 +877,7 @@ static int independentAttempt(rpvg_hip_ctx * ctx, const rpvg_hip_batch * batch, 
     ctx->independent_stats.calls_completed += 1;
     ctx->independent_stats.draws += draws;
     ctx->independent_stats.subsets += S;
+    if (ctx->keep_subset_block) res->keep(d_packed, lay, got.list_length, GS, true);  // (rpvg_hip_subset_em_keep_device)
     *result_out = res.release();
     return RPVG_HIP_OK;
 }

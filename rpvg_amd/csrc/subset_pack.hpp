@@ -6,6 +6,7 @@
 
 #include "common.hpp"
 #include "subset_full_plan.hpp"
+#include "subset_result.hpp"
 
 using rpvg_subset_full::PackedLayout;
 using rpvg_subset_full::packedLayout;
@@ -216,21 +217,4 @@ __global__ __launch_bounds__(256) void packResultsKernel(const PackArgs args) {
 
 }  // namespace
 
-// the result: everything in one page-locked block
-struct rpvg_hip_subset_em {
-    uint32_t num_matrices = 0;
-    uint64_t num_subsets = 0;
-    void * block = nullptr;
-    rpvg_hip_subset_em_view view{};
-    rpvg_hip_subset_em_sets_view sets_view{};  // rpvg_hip_nested_full_subset_em's (has_sets)
-    bool has_sets = false;
-    // rpvg_hip_nested_independent_subset_em's (subset_independent.hip); its units are clusters.  draws: kept for the tests
-    // (rpvg_hip_independent_spec::keep_draws), unit k's at draw_off[k], [slot][transcript]
-    rpvg_hip_subset_em_independent_view independent_view{};
-    bool has_independent = false;
-    std::vector<uint32_t> draws;
-    std::vector<uint64_t> draw_off;
-    ~rpvg_hip_subset_em() {
-        if (block) pinnedFree(block);
-    }
-};
+// the result object: subset_result.hpp

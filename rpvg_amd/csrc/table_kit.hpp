@@ -136,6 +136,23 @@ inline int fetchDescribed(hipStream_t st, const word64 * d_bad, word64 * bad, co
     return RPVG_HIP_OK;
 }
 
+// The same for a describe pass that leaves 64-bit words behind its offender word (words[0]; the totals that size the next pass):
+// ONE copy of num_words adjacent device words into page-locked memory (a copy into pageable memory is staged by the runtime and
+// holds the calling thread), one wait.
+inline int fetchDescribedWords(hipStream_t st, const word64 * d_words, word64 * words, const size_t num_words) {
+    void * pinned = nullptr;
+    if (pinnedAlloc(&pinned, num_words * sizeof(word64)) != hipSuccess) {
+        setError("fetchDescribedWords: out of page-locked host memory");
+        return RPVG_HIP_ERR_ALLOC;
+    }
+    hipError_t e = hipMemcpyAsync(pinned, d_words, num_words * sizeof(word64), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) std::memcpy(words, pinned, num_words * sizeof(word64));
+    pinnedFree(pinned);
+    RPVG_HIP_CHECK(e);
+    return RPVG_HIP_OK;
+}
+
 // The first half of every *_free: nothing queued on the context's stream may still use the handle's blocks.  The caller deletes.
 inline void waitAndDelete(rpvg_hip_ctx * ctx) {
     if (!ctx) return;

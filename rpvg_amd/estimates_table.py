@@ -177,6 +177,13 @@ class HarnessTable(HandleOwner):
         if not self.handle:
             raise hip.EngineError(f"estimates table failed: {eng._err()}")
 
+    @classmethod
+    def from_handle(cls, handle) -> "HarnessTable":
+        """A table handle another harness entry point made (rpvg_amd_estimates_table_build_resident)."""
+        self = cls.__new__(cls)
+        self.handle = handle
+        return self
+
     def tpm(self, denominator: float):
         L, eng = _harness()
         if L.rpvg_amd_estimates_table_tpm(self.handle, denominator) != 0:

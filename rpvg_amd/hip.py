@@ -30,6 +30,8 @@ EXPORTS = [
     "rpvg_hip_alignments_upload", "rpvg_hip_alignments_free", "rpvg_hip_read_rows_build", "rpvg_hip_read_rows_to_batch",
     "rpvg_hip_read_rows_view", "rpvg_hip_read_rows_sizes", "rpvg_hip_read_rows_free", "rpvg_hip_path_clusters", "rpvg_hip_debug_log",
     "rpvg_hip_nested_subset_em", "rpvg_hip_subset_em_get", "rpvg_hip_subset_em_free",
+    "rpvg_hip_subset_em_keep_device", "rpvg_hip_subset_em_part", "rpvg_hip_subset_em_kept_bytes", "rpvg_hip_flat_estimates_gather", "rpvg_hip_flat_estimates_view",
+    "rpvg_hip_flat_estimates_get", "rpvg_hip_flat_estimates_free",
     "rpvg_hip_nested_full_subset_em", "rpvg_hip_subset_em_get_sets",
     "rpvg_hip_nested_independent_subset_em", "rpvg_hip_subset_em_get_independent", "rpvg_hip_independent_draws_get",
     "rpvg_hip_independent_limits", "rpvg_hip_independent_stats_get",
@@ -214,6 +216,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(LIB_PATH)
         L.rpvg_hip_last_error.restype = C.c_char_p
         L.rpvg_hip_full_set_count.restype = C.c_uint64
+        L.rpvg_hip_subset_em_kept_bytes.restype = C.c_uint64
         L.rpvg_hip_cover_limits.restype = None
         L.rpvg_hip_independent_limits.restype = None
         for name in EXPORTS:
@@ -675,17 +678,19 @@ class DeviceGroups:
         return np.split(out, np.cumsum(sizes)[:-1]) if sizes else []
 
     def nested_full_subset_em(self, group_size: int, log_freq, min_hap_prob: float, max_em_its: int = 10000, max_rel_em_conv: float = 1e-3,
-                              collapse_precision: float = 0.0) -> dict:
+                              collapse_precision: float = 0.0, keep_handle: bool = False):
         """rpvg_hip_nested_full_subset_em on every matrix: full enumeration, retained sets, path subsets, EM and the weighted merge
         in one call (group sizes 1 and 3 .. 8).  log_freq[m] = the log frequencies of matrix m's columns.  Returns the fields of
         rpvg_hip_subset_em_sets_view as numpy arrays (copies; set_member and set_abundance as [slots, group_size]), plus
-        num_matrices and group_size.  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
+        num_matrices and group_size; with keep_handle (the view, the rpvg_hip_subset_em handle), which the caller frees with
+        rpvg_hip_subset_em_free.  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
         lf = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in log_freq]) if len(log_freq) else np.zeros(0))
         h = C.c_void_p()
         _check(lib().rpvg_hip_nested_full_subset_em(self.ctx.handle, self.batch.handle, self.handle, C.c_uint32(group_size),
                                                     C.c_void_p(lf.ctypes.data if lf.size else None), C.c_double(float(min_hap_prob)),
                                                     C.c_uint32(max_em_its), C.c_double(float(max_rel_em_conv)),
                                                     C.c_double(float(collapse_precision)), C.byref(h)), "rpvg_hip_nested_full_subset_em")
+        free_handle = not keep_handle
         try:
             v = CSubsetEmSetsView()
             _check(lib().rpvg_hip_subset_em_get_sets(h, C.byref(v)), "rpvg_hip_subset_em_get_sets")
@@ -708,7 +713,7 @@ class DeviceGroups:
                     out[name] = np.zeros(0, dtype)
                 out["set_member"] = np.zeros((0, g), np.uint32)
                 out["set_abundance"] = np.zeros((0, g), np.float64)
-                return out
+                return (out, h) if keep_handle else out
             out["subset_off"] = take(v.subset_off, M + 1, np.uint64)
             S = int(out["subset_off"][-1])
             out["path_off"] = take(v.path_off, S + 1, np.uint64)
@@ -731,19 +736,24 @@ class DeviceGroups:
             out["set_member"] = take(v.set_member, L * g, np.uint32, (L, g))
             out["set_posterior"] = take(v.set_posterior, L, np.float64)
             out["set_abundance"] = take(v.set_abundance, L * g, np.float64, (L, g))
-            return out
+            return (out, h) if keep_handle else out
+        except BaseException:
+            free_handle = True
+            raise
         finally:
-            lib().rpvg_hip_subset_em_free(h)
+            if free_handle:
+                lib().rpvg_hip_subset_em_free(h)
 
     def nested_independent_subset_em(self, matrix_off, group_size: int, min_hap_prob: float, generator_words, column_counts=None, log_freq=None,
                                      max_em_its: int = 10000, max_rel_em_conv: float = 1e-3, collapse_precision: float = 0.0,
-                                     keep_draws: bool = False) -> dict:
+                                     keep_draws: bool = False, keep_handle: bool = False):
         """rpvg_hip_nested_independent_subset_em: unit k is the cluster whose transcripts are the matrices
         [matrix_off[k], matrix_off[k + 1]), one column per path.  column_counts (group size 2): the multiplicity of every column,
         matrices back to back; log_freq[m] (other group sizes): the log frequencies of matrix m's columns; generator_words: [K, 624]
         the next outputs of every cluster's std::mt19937.  Returns the fields of rpvg_hip_subset_em_independent_view as numpy arrays
         (copies; set_member and set_abundance as [slots, group_size]) and, with keep_draws, "draws": per unit an array
-        [num_samples, transcripts].  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
+        [num_samples, transcripts]; with keep_handle (the view, the rpvg_hip_subset_em handle), which the caller frees with
+        rpvg_hip_subset_em_free.  Raises EngineError; a refusal carries RPVG_HIP_ERR_UNSUPPORTED, "(-5)", and its reason."""
         mo = np.ascontiguousarray(matrix_off, dtype=np.uint32)
         K = len(mo) - 1
         gw = np.ascontiguousarray(generator_words, dtype=np.uint32).reshape(K, 624)
@@ -757,6 +767,7 @@ class DeviceGroups:
         h = C.c_void_p()
         _check(lib().rpvg_hip_nested_independent_subset_em(self.ctx.handle, self.batch.handle, self.handle, C.byref(spec), C.byref(h)),
                "rpvg_hip_nested_independent_subset_em")
+        free_handle = not keep_handle
         try:
             v = CSubsetEmIndependentView()
             _check(lib().rpvg_hip_subset_em_get_independent(h, C.byref(v)), "rpvg_hip_subset_em_get_independent")
@@ -797,9 +808,13 @@ class DeviceGroups:
                     d = np.zeros(max(out["num_samples"] * T, 1), dtype=np.uint32)
                     _check(lib().rpvg_hip_independent_draws_get(h, C.c_uint32(k), C.c_void_p(d.ctypes.data)), "rpvg_hip_independent_draws_get")
                     out["draws"].append(d[:out["num_samples"] * T].reshape(out["num_samples"], T))
-            return out
+            return (out, h) if keep_handle else out
+        except BaseException:
+            free_handle = True
+            raise
         finally:
-            lib().rpvg_hip_subset_em_free(h)
+            if free_handle:
+                lib().rpvg_hip_subset_em_free(h)
 
     def gibbs(self, matrix, group_size: int, num_chains, num_burn_its, num_gibbs_its, log_freq, generator_problems, generator_words):
         """rpvg_hip_group_gibbs: per problem ([sorted member tuples in order of first appearance], counts); plus the words each

@@ -23,6 +23,48 @@ EstimatesTable::EstimatesTable(std::shared_ptr<HipEngine> engine_in, const rpvg_
     build(ploidy);
 }
 
+EstimatesTable::EstimatesTable(std::shared_ptr<HipEngine> engine_in, const ResidentEstimates & resident_in, const uint32_t ploidy) : hip_engine(std::move(engine_in)), resident(&resident_in), table(nullptr), table_view(), has_view(false) {
+
+    if (resident_in.empty()) {
+
+        throw EngineError("EstimatesTable: the resident estimates are empty");
+    }
+
+    const rpvg_estimates_flat flat = resident_in.view();
+    HipEngine::check(rpvg_hip_estimates_table_build(hip_engine->ctx(), &flat, ploidy, &table), "rpvg_hip_estimates_table_build");
+}
+
+void ResidentEstimates::adopt(std::shared_ptr<HipEngine> engine_in, rpvg_hip_flat_estimates * handle_in) {
+
+    reset();
+    kept_block_bytes.clear();
+    hip_engine = std::move(engine_in);
+    handle_ = handle_in;
+}
+
+void ResidentEstimates::reset() {
+
+    if (handle_) {
+
+        rpvg_hip_flat_estimates_free(hip_engine->ctx(), handle_);
+        handle_ = nullptr;
+    }
+}
+
+rpvg_estimates_flat ResidentEstimates::view() const {
+
+    rpvg_estimates_flat flat = {};
+    HipEngine::check(rpvg_hip_flat_estimates_view(handle_, &flat), "rpvg_hip_flat_estimates_view");
+    return flat;
+}
+
+rpvg_estimates_flat ResidentEstimates::hostView() const {
+
+    rpvg_estimates_flat flat = {};
+    HipEngine::check(rpvg_hip_flat_estimates_get(hip_engine->ctx(), handle_, &flat), "rpvg_hip_flat_estimates_get");
+    return flat;
+}
+
 EstimatesTable::~EstimatesTable() {
 
     rpvg_hip_estimates_table_free(hip_engine->ctx(), table);

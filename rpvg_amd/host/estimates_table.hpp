@@ -98,9 +98,49 @@ struct FlatEstimates {
     }
 };
 
+// The flat estimates of a batch where the nested device calls left them: gathered on the GPU from the calls' kept blocks
+// (rpvg_hip_flat_estimates_gather, rpvg_amd/csrc/estimates_gather.hip; NestedPathAbundanceEstimator::estimateBatchResident fills one).
+// Owns the rpvg_hip_flat_estimates handle.  The batch it was gathered from must outlive it (cluster_path_off is the batch's array).
+class ResidentEstimates {
+
+    public:
+
+        ResidentEstimates() : handle_(nullptr) {}
+        ~ResidentEstimates() { reset(); }
+
+        ResidentEstimates(const ResidentEstimates &) = delete;
+        ResidentEstimates & operator=(const ResidentEstimates &) = delete;
+
+        // takes the handle over (the engine's main context frees it)
+        void adopt(std::shared_ptr<HipEngine> engine_in, rpvg_hip_flat_estimates * handle_in);
+        void reset();
+
+        bool empty() const { return !handle_; }
+        rpvg_hip_flat_estimates * handle() const { return handle_; }
+
+        // the device view: on_device = 1, the sizes host values
+        rpvg_estimates_flat view() const;
+
+        // host copies (one packed copy behind the first call), valid while this lives: for writers that print sets from host memory
+        rpvg_estimates_flat hostView() const;
+        FlatEstimates fetch() const { return FlatEstimates::copyOf(hostView()); }
+
+        // the device memory the kept block of every lane's nested call held while the estimates were gathered (the calls'
+        // capacities, not their results; the blocks are back in the pool by now): what the resident route costs in memory
+        std::vector<uint64_t> kept_block_bytes;
+
+    private:
+
+        std::shared_ptr<HipEngine> hip_engine;
+        rpvg_hip_flat_estimates * handle_;
+};
+
 class EstimatesTable {
 
     public:
+
+        // from estimates resident on the GPU: built with on_device = 1, nothing is flattened or uploaded.  `resident` must outlive the table.
+        EstimatesTable(std::shared_ptr<HipEngine> engine_in, const ResidentEstimates & resident_in, const uint32_t ploidy);
 
         // cluster k of the batch is estimates[k]; the effective lengths are those of its `paths`
         EstimatesTable(std::shared_ptr<HipEngine> engine_in, const std::vector<PathClusterEstimates> & estimates, const uint32_t ploidy);
@@ -122,7 +162,11 @@ class EstimatesTable {
         const rpvg_estimates_table_view & view();
 
         // what the table was made from (the writers print sets, posteriors and abundances from here)
-        rpvg_estimates_flat estimates() const { return flat_estimates.view(); }
+        rpvg_estimates_flat estimates() const { return resident ? resident->hostView() : flat_estimates.view(); }
+
+        // the same for a builder that reads device memory where it lies (table_text.hpp): the device view of a table made from
+        // resident estimates, else the host arrays
+        rpvg_estimates_flat deviceEstimates() const { return resident ? resident->view() : flat_estimates.view(); }
 
         // the resident table, for the builders that read it where it lies (table_text.hpp)
         rpvg_hip_estimates_table * handle() const { return table; }
@@ -133,6 +177,7 @@ class EstimatesTable {
 
         std::shared_ptr<HipEngine> hip_engine;
         FlatEstimates flat_estimates;
+        const ResidentEstimates * resident = nullptr;
         rpvg_hip_estimates_table * table;
         rpvg_estimates_table_view table_view;
         bool has_view;

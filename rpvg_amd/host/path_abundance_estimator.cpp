@@ -8,6 +8,9 @@
 #include <memory>
 #include <numeric>
 
+#include <mutex>
+
+#include "estimates_table.hpp"
 #include "numeric_utils.hpp"
 #include "pipeline_lanes.hpp"
 #include "trace.hpp"
@@ -400,6 +403,148 @@ static int clusterChunk() {
     }();
 
     return chunk;
+}
+
+// The resident route: what estimateBatch does on the two collapsed one-call routes, with the estimates left on the GPU.  Each lane's one device call keeps its packed block (rpvg_hip_subset_em_keep_device on the lane's context, for
+// the length of the call); the blocks of all lanes are the parts of one gather.
+bool NestedPathAbundanceEstimator::estimateBatchResident(ResidentEstimates * resident_out, const DeviceClusterBatch & cluster_batch, const std::vector<double> & path_effective_length, const std::vector<std::vector<PathInfo> > * cluster_paths) {
+
+    if (!infer_collapsed || use_group_post_gibbs || num_gibbs_samples > 0) {
+
+        return false;
+    }
+
+    // the two collapsed one-call routes of estimateClusters, under its conditions: the diploid default on device source columns,
+    // and ploidy 5 .. 8, whose matrices are formed from the source ids of the clusters' paths (findPathSourceGroups)
+    const bool diploid = (group_size == 2 && cluster_batch.hasSourceColumns() && !std::getenv("RPVG_AMD_HOST_SOURCE_GROUPS"));
+    const bool polyploid = (group_size >= 5 && cluster_paths && cluster_paths->size() == cluster_batch.numClusters());
+
+    if (!diploid && !polyploid) {
+
+        return false;
+    }
+
+    ScopedPhase whole_phase("nested: estimateBatchResident");
+
+    std::vector<uint32_t> clusters;
+
+    for (uint32_t i = 0; i < cluster_batch.numClusters(); ++i) {
+
+        if (cluster_batch.numRows(i) > 0) {
+
+            clusters.emplace_back(i);
+        }
+    }
+
+    struct LanePart {
+
+        SubsetEmResult device_result;
+        std::vector<uint32_t> clusters;
+    };
+
+    // Keeps the lane's context from holding blocks past the call, whichever way the call ends.  The property is set, not counted
+    // (include/rpvg_hip.h): it is off afterwards, also for a caller that had switched it on for this context.
+    struct KeepScope {
+
+        rpvg_hip_ctx * ctx;
+
+        explicit KeepScope(rpvg_hip_ctx * ctx_in) : ctx(ctx_in) { HipEngine::check(rpvg_hip_subset_em_keep_device(ctx, 1), "rpvg_hip_subset_em_keep_device"); }
+        ~KeepScope() { rpvg_hip_subset_em_keep_device(ctx, 0); }
+    };
+
+    std::mutex parts_mutex;
+    std::vector<std::unique_ptr<LanePart> > lane_parts;
+    bool declined = false;
+
+    runInLanes(clusters, [&](const std::vector<uint32_t> & lane_clusters, const std::function<void()> & first_device_stage) {
+
+        if (lane_clusters.empty()) {
+
+            first_device_stage();
+            return;
+        }
+
+        std::unique_ptr<LanePart> lane_part(new LanePart());
+        lane_part->clusters = lane_clusters;
+        bool taken = false;
+
+        if (diploid) {
+
+            first_device_stage();
+
+            KeepScope keep(engine->ctx());
+            taken = nestedSubsetAbundances(&lane_part->device_result, cluster_batch, lane_clusters, min_hap_prob, min_hap_prob, max_em_its, max_rel_em_conv) && lane_part->device_result.view.set_count;
+
+        } else {
+
+            std::vector<GroupPosteriorProblem> problems(lane_clusters.size());
+
+            #pragma omp parallel for schedule(static, clusterChunk()) num_threads(hostThreads())
+            for (size_t i = 0; i < lane_clusters.size(); ++i) {
+
+                problems.at(i).cluster = lane_clusters.at(i);
+                findPathSourceGroups(&problems.at(i), cluster_paths->at(lane_clusters.at(i)));
+            }
+
+            for (auto & problem: problems) {
+
+                if (problem.numColumns() == 0) {
+
+                    throw EngineError("haplotype-transcripts inference needs source (haplotype) ids on the paths of every cluster");
+                }
+            }
+
+            first_device_stage();  // (behind the host prologue, as in estimateClusters)
+
+            KeepScope keep(engine->ctx());
+            taken = nestedFullSubsetAbundances(&lane_part->device_result, cluster_batch, problems, group_size, min_hap_prob, max_em_its, max_rel_em_conv);
+        }
+
+        std::lock_guard<std::mutex> lock(parts_mutex);
+
+        if (taken) {
+
+            lane_parts.emplace_back(std::move(lane_part));
+
+        } else {
+
+            declined = true;
+        }
+    });
+
+    if (declined) {
+
+        return false;  // (the lanes' results, kept blocks included, go with lane_parts)
+    }
+
+    std::vector<rpvg_estimates_part> parts(lane_parts.size());
+
+    for (size_t i = 0; i < lane_parts.size(); ++i) {
+
+        const int status = rpvg_hip_subset_em_part(lane_parts[i]->device_result.handle(), &parts[i]);
+
+        if (status == RPVG_HIP_ERR_UNSUPPORTED) {
+
+            return false;
+        }
+
+        HipEngine::check(status, "rpvg_hip_subset_em_part");
+        parts[i].unit_cluster = lane_parts[i]->clusters.data();
+    }
+
+    std::vector<uint64_t> kept_block_bytes;
+
+    for (auto & lane_part: lane_parts) {
+
+        kept_block_bytes.emplace_back(rpvg_hip_subset_em_kept_bytes(lane_part->device_result.handle()));
+    }
+
+    rpvg_hip_flat_estimates * gathered = nullptr;
+    HipEngine::check(rpvg_hip_flat_estimates_gather(engine->ctx(), cluster_batch.handle(), parts.data(), parts.size(), path_effective_length.data(), 0, &gathered), "rpvg_hip_flat_estimates_gather");
+    resident_out->adopt(engine, gathered);
+    resident_out->kept_block_bytes = std::move(kept_block_bytes);
+
+    return true;
 }
 
 // Tens of thousands of small containers are freed by a team instead of one by one — now by the first lane (it never

@@ -79,6 +79,8 @@ class MinimumPathAbundanceEstimator : public PathAbundanceEstimator {
         std::vector<std::vector<uint32_t> > weightedMinimumPathCover(const DeviceClusterBatch & cluster_batch, const std::vector<uint32_t> & clusters) const;
 };
 
+class ResidentEstimates;
+
 class NestedPathAbundanceEstimator : public PathAbundanceEstimator {
 
     public:
@@ -96,6 +98,18 @@ class NestedPathAbundanceEstimator : public PathAbundanceEstimator {
         bool sourceColumnsOf(GroupPosteriorProblem * columns, const std::vector<PathInfo> & paths) const;
 
         void estimateBatch(std::vector<PathClusterEstimates> * path_cluster_estimates, const DeviceClusterBatch & cluster_batch, std::vector<std::mt19937> * rngs);
+
+        // The batch's estimates left on the GPU (estimates_table.hpp): every lane keeps the device block of its one nested call, and
+        // after the lanes have joined one gather on the engine's main context forms the flat estimates (cluster k of the batch is
+        // entry k; path_effective_length: one per path of the batch).  No container is filled or touched.  Covers the two collapsed
+        // one-call routes under the conditions of estimateClusters: the diploid default on a batch with device source columns
+        // (nestedSubsetAbundances(... clusters ...)), and ploidy 5 .. 8 (nestedFullSubsetAbundances), which forms its matrices from
+        // the source ids of the paths and therefore needs cluster_paths, the PathInfo of every cluster of the batch.  Returns false,
+        // having changed nothing, for every other configuration (-n > 0, --use-hap-gibbs, --ind-hap-inference, ploidy 1/3/4, a
+        // batch without columns, ploidy 5 .. 8 without cluster_paths) and when the device call declines: the caller then uses
+        // estimateBatch.  rpvg_hip_subset_em_keep_device is switched on for each lane's call and is OFF on the lanes' contexts
+        // afterwards, whatever it was before.
+        bool estimateBatchResident(ResidentEstimates * resident_out, const DeviceClusterBatch & cluster_batch, const std::vector<double> & path_effective_length, const std::vector<std::vector<PathInfo> > * cluster_paths = nullptr);
 
     private:
 

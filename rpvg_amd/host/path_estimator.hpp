@@ -224,6 +224,9 @@ class PathEstimator {
                 rpvg_hip_subset_em_view view;
                 rpvg_hip_subset_em_sets_view sets_view;  // nestedFullSubsetAbundances fills this one
 
+                // the device call's result (for rpvg_hip_subset_em_part, when the call kept its device block)
+                const rpvg_hip_subset_em * handle() const { return result; }
+
             private:
 
                 friend class PathEstimator;

@@ -193,7 +193,7 @@ class TableText {
 
             const FlatLabels labels(table_labels);
             const rpvg_table_labels flat = labels.view();
-            const rpvg_estimates_flat estimates = table.estimates();
+            const rpvg_estimates_flat estimates = table.deviceEstimates();
             HipEngine::check(rpvg_hip_estimates_table_text(hip_engine->ctx(), table.handle(), &estimates, &flat, kind, precision, &text), "rpvg_hip_estimates_table_text");
         }
 
@@ -205,7 +205,7 @@ class TableText {
             std::unique_ptr<TableText> out(new TableText(std::move(engine_in)));
             const FlatLabels labels(table_labels);
             const rpvg_table_labels flat = labels.view();
-            const rpvg_estimates_flat estimates = table.estimates();
+            const rpvg_estimates_flat estimates = table.deviceEstimates();
             HipEngine::check(rpvg_hip_estimates_set_text(out->hip_engine->ctx(), table.handle(), &estimates, &flat, kind, ploidy, min_posterior, precision, &out->text), "rpvg_hip_estimates_set_text");
 
             return out;

@@ -14,6 +14,7 @@
 #include "estimates_table.hpp"
 #include "gibbs_samples_table.hpp"
 #include "io/estimates_writers.hpp"
+#include "path_abundance_estimator.hpp"
 #include "runner_handles.hpp"
 #include "table_text.hpp"
 #include "../csrc/text_deflate_plan.hpp"
@@ -24,6 +25,12 @@ using namespace rpvg_amd_harness;
 // ---- estimates table (estimates_table.hpp; include/rpvg_table.h) ------------------------------------------------------------------
 
 namespace {
+
+// what rpvg_amd_run_resident returns: the estimates of a prepared batch resident on the engine's GPU
+struct ResidentHandle {
+
+    ResidentEstimates estimates;
+};
 
 struct TableHandle {
 
@@ -187,6 +194,96 @@ void * rpvg_amd_estimates_table_build(void * engine, void * result_handle, void 
 
             handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, prepared->estimates, ploidy));
         }
+
+        return handle.release();
+    });
+}
+
+// NestedPathAbundanceEstimator::estimateBatchResident on a prepared batch: the estimates stay on the GPU and the containers of the
+// prepared batch are not touched.  NULL with an empty rpvg_amd_last_error when the route is not taken (the model is not
+// haplotype-transcripts, or the configuration or the batch is none the route covers): the caller runs rpvg_amd_run instead.
+void * rpvg_amd_run_resident(void * engine, const char * model, const rpvg_params * params, void * prepared_batch) {
+
+    last_error.clear();
+
+    return guardedHandle([&]() -> void * {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+
+        if (!prepared->device) {
+
+            return nullptr;
+        }
+
+        auto estimator = makePathEstimator(model, *params, static_cast<Engine *>(engine)->hip);
+        NestedPathAbundanceEstimator * nested = dynamic_cast<NestedPathAbundanceEstimator *>(estimator.get());
+
+        if (!nested) {
+
+            return nullptr;
+        }
+
+        std::vector<double> effective_length;
+
+        for (auto & paths: prepared->paths) {
+
+            for (auto & path: paths) {
+
+                effective_length.emplace_back(path.effective_length);
+            }
+        }
+
+        std::unique_ptr<ResidentHandle> handle(new ResidentHandle());
+
+        if (!nested->estimateBatchResident(&handle->estimates, *prepared->device, effective_length, &prepared->paths)) {
+
+            return nullptr;
+        }
+
+        return handle.release();
+    });
+}
+
+// host copies of the resident estimates (rpvg_hip_flat_estimates_get), valid until rpvg_amd_resident_estimates_free
+int rpvg_amd_resident_estimates_get(void * resident_handle, rpvg_estimates_flat * flat_out) {
+
+    return guardedInt([&]() -> int {
+
+        *flat_out = static_cast<ResidentHandle *>(resident_handle)->estimates.hostView();
+        return 0;
+    });
+}
+
+// the bytes of the kept device block of every lane (ResidentEstimates::kept_block_bytes): the number of lanes; the first
+// `capacity` of them are written
+uint32_t rpvg_amd_resident_estimates_kept_bytes(void * resident_handle, uint64_t * bytes_out, uint32_t capacity) {
+
+    const std::vector<uint64_t> & kept = static_cast<ResidentHandle *>(resident_handle)->estimates.kept_block_bytes;
+
+    for (size_t i = 0; i < kept.size() && i < capacity; ++i) {
+
+        bytes_out[i] = kept[i];
+    }
+
+    return kept.size();
+}
+
+void rpvg_amd_resident_estimates_free(void * resident_handle) {
+
+    delete static_cast<ResidentHandle *>(resident_handle);
+}
+
+// The table of resident estimates, built with on_device = 1 and no flattening: a table handle like that of
+// rpvg_amd_estimates_table_build (_view, _tpm, _write and the text entry points take it).  The resident estimates must outlive it.
+void * rpvg_amd_estimates_table_build_resident(void * engine, void * resident_handle, void * prepared_batch, uint32_t ploidy) {
+
+    return guardedHandle([&]() -> void * {
+
+        PreparedBatch * prepared = static_cast<PreparedBatch *>(prepared_batch);
+        std::unique_ptr<TableHandle> handle(new TableHandle());
+        handle->labels = labelsOf(prepared->paths);
+        handle->ploidy = ploidy;
+        handle->table.reset(new EstimatesTable(static_cast<Engine *>(engine)->hip, static_cast<ResidentHandle *>(resident_handle)->estimates, ploidy));
 
         return handle.release();
     });
