@@ -48,7 +48,8 @@ def _assert_on_the_device(engine):
 def test_device_sampler_follows_a_python_model_draw_for_draw(hip_ctx, group_size):
     """The layout of test_device_gibbs_sampler_follows_a_python_model_draw_for_draw (test_hip_kernels.py): several matrices,
     one generator serving two problems, one single-column matrix, generators starting at stream offsets 0, 100, 623, 624,
-    1000.  The model takes its conditionals from rpvg_hip_group_conditionals and is run twice per problem — the others
+    1000.  The model takes its conditionals from rpvg_hip_group_conditionals (pinned by item 21 of docs/design/parity.md,
+    tests/test_hip_set_loglik.py) and is run twice per problem — the others
     handed over in slot order (the reference) and sorted ascending (the device): both must give the same sets, counts and
     words, or the seed sits on a last-bit tie and is a bad input (none of the committed seeds does)."""
     rng = np.random.default_rng(8100 + group_size)

@@ -1075,11 +1075,11 @@ def _mt19937_words(seed, skip, n):
     return [int(w) for w in bg.random_raw(skip + n)[skip:]]
 
 
-def _gibbs_model(G, group_size, conditional, words):
+def _gibbs_model(G, group_size, conditional, words, draws=None):
     """estimatePathGroupPosteriorsGibbs (src/path_estimator.cpp:475-589) in plain Python over a list of generator outputs,
     with libstdc++'s distributions restated (GCC 11: bits/uniform_int_dist.h:246-270, bits/random.tcc:2656-2713,3348-3380).
     conditional(others) -> log-likelihood + log frequency of every candidate column.  Returns (sets in order of first
-    appearance, counts, words taken)."""
+    appearance, counts, words taken).  draws: a list that receives (partial sums, u) of every draw from a distribution."""
     import bisect
     import math
     pos = 0
@@ -1131,6 +1131,8 @@ def _gibbs_model(G, group_size, conditional, words):
                     u = (float(first) + float(second) * 4294967296.0) / 18446744073709551616.0
                     if u >= 1.0:
                         u = math.nextafter(1.0, 0.0)
+                    if draws is not None:
+                        draws.append((memo[others], u))
                     cur[slot] = bisect.bisect_left(memo[others], u)
                 else:
                     cur[slot] = 0  # a distribution of fewer than two weights draws nothing
@@ -1156,7 +1158,9 @@ def test_device_gibbs_sampler_follows_a_python_model_draw_for_draw(hip_ctx, grou
     """rpvg_hip_group_gibbs against a sequential Python model of the reference's sampler that draws from the same
     std::mt19937 words: same sets in the same order with the same counts, the same number of words taken from every
     generator (one generator serves two problems, one matrix has a single column), and state words that continue the
-    stream.  The model takes its log-likelihoods from rpvg_hip_group_conditionals: this test is about the chains."""
+    stream.  The model takes its log-likelihoods from rpvg_hip_group_conditionals: this test is about the chains (the
+    conditionals it takes as given are pinned by item 21 of docs/design/parity.md, tests/test_hip_set_loglik.py; the sampler's own
+    conditional kernels at their shapes, with nothing from the device, by tests/test_hip_gibbs_shapes.py)."""
     import math
     clusters = small_cases.make_batch_clusters(811, n_clusters=6, with_empty=False)
     clusters.append(small_cases.make_batch_clusters(812, n_clusters=1, with_empty=False)[0])
