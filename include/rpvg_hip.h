@@ -962,6 +962,32 @@ int rpvg_hip_text_bgzf_view(rpvg_hip_text_bgzf * bgzf, rpvg_text_bgzf_view * vie
 int rpvg_hip_text_bgzf_get(rpvg_hip_text_bgzf * bgzf, uint64_t byte_begin, uint64_t byte_end, char * dst);
 int rpvg_hip_text_bgzf_guards(rpvg_hip_text_bgzf * bgzf, int32_t * intact_out);
 void rpvg_hip_text_bgzf_free(rpvg_hip_text_bgzf * bgzf);
+/*   rpvg_hip_text_rows             the --write-probs dump read back (rpvg_text.h; rpvg_amd/csrc/rows_parse.hip): n bytes of text in host
+ *                                 memory (on_device = 0, copied by the call) or in device memory of the context's GPU, parsed on the
+ *                                 GPU into resident rows and the dump's path side.  Refused before anything is queued: a
+ *                                 prob_precision the writer would refuse, a text of 2^31 - 1 bytes or more, n > 0 with a NULL
+ *                                 pointer.  Refused by the kernels: the texts rpvg_text.h lists (RPVG_HIP_ERR_INVALID; last_error
+ *                                 names the 1-based number of the first offending line; the context stays usable).  No bytes: no
+ *                                 clusters, no error.
+ *   rpvg_hip_table_text_rows       the same for a resident text, parsed where it lies: nothing is downloaded.
+ *   rpvg_hip_parsed_dump_rows      the resident rows the dump owns (freed with the dump, not with rpvg_hip_read_rows_free).
+ *   rpvg_hip_parsed_dump_view      host copies of the path side: the block of the small arrays and the names, one wait.
+ *   rpvg_hip_parsed_dump_labels    the names, lengths and ClusterIDs (k + 1) as labels with on_device = 1, valid until the dump is
+ *                                 freed: parsed rows go back to text (rpvg_hip_read_rows_text) without a copy of the names. */
+int rpvg_hip_text_rows(rpvg_hip_ctx * ctx, const char * bytes, uint64_t n, int32_t on_device, double prob_precision, rpvg_hip_parsed_dump ** dump_out);
+int rpvg_hip_table_text_rows(rpvg_hip_table_text * text, double prob_precision, rpvg_hip_parsed_dump ** dump_out);
+rpvg_hip_read_rows * rpvg_hip_parsed_dump_rows(rpvg_hip_parsed_dump * dump);
+int rpvg_hip_parsed_dump_view(rpvg_hip_parsed_dump * dump, rpvg_parsed_dump_view * view_out);
+int rpvg_hip_parsed_dump_labels(rpvg_hip_parsed_dump * dump, rpvg_table_labels * labels_out);
+void rpvg_hip_parsed_dump_free(rpvg_hip_parsed_dump * dump);
+/* counters of the two parse calls, kept apart from rpvg_hip_kernel_stats (whose layout stays); rpvg_hip_stats_reset zeroes them too */
+typedef struct rpvg_hip_parse_stats {
+    uint64_t calls_completed;        /* parses that returned RPVG_HIP_OK */
+    uint64_t exact_tokens;           /* numbers whose rounding was decided by the exact multiword comparison: exact ties and decimals
+                                        within 2^-73 relative of the middle of two doubles (rpvg_amd/csrc/number_parse.hpp); those of
+                                        refused texts included */
+} rpvg_hip_parse_stats;
+int rpvg_hip_parse_stats_get(rpvg_hip_ctx * ctx, rpvg_hip_parse_stats * stats_out);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------- */
 /* The reference is one process with OpenMP threads (src/main.cpp:829) and has no exchange step; the

@@ -90,6 +90,36 @@ typedef struct rpvg_rows_text_input {
     int32_t on_device;
 } rpvg_rows_text_input;
 
+/* ---- the dump read back (rpvg_hip_text_rows, rpvg_hip_table_text_rows; rpvg_amd/csrc/rows_parse.hip) ---------------------------------
+ * The text of the --write-probs dump above, parsed on the GPU into resident rows (rpvg_hip_read_rows, which rpvg_hip_read_rows_to_batch,
+ * _view, _sizes and rpvg_hip_read_rows_text take) and the path side the dump prints.  What readProbabilityClusters
+ * (rpvg_amd/host/io/cluster_io.cpp) makes of the same text, bit for bit: every cluster marker is a cluster, also one without a path
+ * line or without rows; empty lines vanish; a last line without '\n' is a line; the groups of a row are in the order of the
+ * ReadPathProbabilities constructor's sort (ascending probability, then lexicographic index lists).  A number is the correctly
+ * rounded double of its decimal text (glibc's strtod, ties to even), of at most 19 significant digits.  Refused, with the 1-based
+ * number of the first offending line in last_error: data before the first marker; a ranked marker that is not two numbers of at
+ * most 19 digits; a path field with fewer than two commas; a row with fewer than two fields; a group without ':'; a path index at
+ * or beyond the cluster's path count; a read count, path length or index above 2^32 - 1; a noise probability outside (0, 1]; a
+ * number that rounds to infinity, has more than 19 significant digits or is malformed ("1.5abc", "0x1p3", "+1", which std::stod
+ * takes, are refused on purpose); a space at the start or the end of a line or two in a row; an empty index ("0.5:1,", "0.5:,1"; "0.5:" is a group without indices); a row of more than 1024 groups that are not in that
+ * order (such a row is sorted by one thread; a row in order has no limit).  A parse needs about 50 bytes of device memory per byte
+ * of text while it runs. */
+typedef struct rpvg_parsed_dump_view {
+    uint32_t num_clusters;                 /* K */
+    uint64_t num_paths;                    /* P */
+    uint64_t num_name_bytes;
+    const uint64_t * cluster_path_off;     /* [K+1] */
+    const uint64_t * name_off;             /* [P+1] */
+    const char * name_bytes;
+    const uint32_t * path_length;          /* [P] */
+    const double * path_effective_length;  /* [P] */
+    const uint8_t * has_rank_key;          /* [K]: 1 for "# <lists> <index>", 0 for "#" */
+    const uint64_t * num_align_lists;      /* [K]; 0 without a rank key */
+    const uint64_t * cluster_index;        /* [K] */
+} rpvg_parsed_dump_view;
+
+typedef struct rpvg_hip_parsed_dump rpvg_hip_parsed_dump;
+
 /* ---- a text as the bytes of a .gz file (rpvg_hip_table_text_bgzf, rpvg_hip_bytes_bgzf; rpvg_amd/csrc/text_deflate.hip) -------------
  * BGZF, the blocked gzip of bgzip and htslib: the text is cut at byte positions into chunks of 65 280 bytes (the last one shorter,
  * an empty text has none), and chunk i becomes gzip member i: 18 header bytes (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C'

@@ -686,6 +686,7 @@ struct rpvg_hip_ctx {
     void foldFinishedSpans();
     std::vector<rpvg_hip_detail::TimedInterval> intervals;  // folded spans since the last reset
     rpvg_hip_kernel_stats stats;
+    rpvg_hip_parse_stats parse_stats{};              // rpvg_hip_text_rows, rpvg_hip_table_text_rows (rows_parse.hip)
     rpvg_hip_independent_stats independent_stats{};  // rpvg_hip_nested_independent_subset_em's (subset_independent.hip)
     rpvg_hip_detail::SubsetEmHints subset_independent_hints;
 

@@ -822,6 +822,7 @@ int rpvg_hip_stats_reset(rpvg_hip_ctx * ctx) {
     if (rc != RPVG_HIP_OK) return rc;
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     ctx->independent_stats = rpvg_hip_independent_stats{};
+    ctx->parse_stats = rpvg_hip_parse_stats{};
     ctx->intervals.clear();
     (void) deviceClock(ctx->device, ctx->stream, true);
     return RPVG_HIP_OK;

@@ -10,7 +10,7 @@
 //                1. v = m64 * 2^e with the significand shifted to the top of 64 bits; k = floor((e + 63) log10 2) is the decimal
 //                   exponent of v or one below it.
 //                2. v * 10^q for q = precision - 1 - k is the 64 x 128-bit product with the truncated power of ten of the table
-//                   (10^q = T * 2^E, T in [2^127, 2^128), 650 entries of 16 bytes made exactly by buildPow10Table on the host).  The
+//                   (10^q = T * 2^E, T in [2^127, 2^128), 683 entries of 16 bytes made exactly by buildPow10Table on the host).  The
 //                   top 128 bits U of the product leave the exact value inside [U, U + 2) units (one unit for the bits of m64 * T_lo
 //                   dropped, less than one for the truncation of T); they split into the integer I of `precision` digits and a
 //                   fraction of at least 64 bits.  I >= 10^precision: k was one below, once more with q - 1.
@@ -48,7 +48,8 @@ typedef unsigned __int128 u128;
 
 constexpr int kMinPrecision = 1, kMaxPrecision = 17;
 constexpr int kMaxCellBytes = 24;                     // -1.2345678901234567e-308
-constexpr int kMinPow10 = -309, kMaxPow10 = 340;      // q = precision - 1 - k, k in -324 .. 308, and q - 1
+constexpr int kMinPow10 = -342, kMaxPow10 = 340;      // formatG: q = precision - 1 - k, k in -324 .. 308, and q - 1 (-309 .. 340);
+                                                      // parseDouble (number_parse.hpp): 19 digits at the smallest subnormal, q >= -342
 constexpr int kPow10Entries = kMaxPow10 - kMinPow10 + 1;
 constexpr int kPow10Words = 2 * kPow10Entries;        // entry i: 10^(kMinPow10 + i) as words[2 i] (high) and words[2 i + 1] (low)
 constexpr int kExactWords = 28;                       // of 32 bits

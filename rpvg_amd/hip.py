@@ -53,6 +53,7 @@ EXPORTS = [
     "rpvg_hip_gibbs_table_text", "rpvg_hip_estimates_table_text", "rpvg_hip_table_text_view", "rpvg_hip_table_text_get", "rpvg_hip_table_text_guards",
     "rpvg_hip_table_text_free", "rpvg_hip_estimates_set_text", "rpvg_hip_rows_text", "rpvg_hip_read_rows_text",
     "rpvg_hip_table_text_sizes", "rpvg_hip_table_text_bgzf", "rpvg_hip_bytes_bgzf", "rpvg_hip_text_bgzf_view", "rpvg_hip_text_bgzf_get", "rpvg_hip_text_bgzf_guards", "rpvg_hip_text_bgzf_free",
+    "rpvg_hip_text_rows", "rpvg_hip_table_text_rows", "rpvg_hip_parsed_dump_rows", "rpvg_hip_parsed_dump_view", "rpvg_hip_parsed_dump_labels", "rpvg_hip_parsed_dump_free", "rpvg_hip_parse_stats_get",
     "rpvg_hip_align_index_alignments_collapsed",
     "rpvg_hip_batch_rows_sizes", "rpvg_hip_batch_rows_get",
     "rpvg_hip_segment_sort_words", "rpvg_hip_groups_rows",
@@ -140,6 +141,11 @@ class CIndependentStats(C.Structure):
     _fields_ = [("calls_completed", C.c_uint64), ("draws", C.c_uint64), ("subsets", C.c_uint64)]
 
 
+class CParseStats(C.Structure):
+    """rpvg_hip_parse_stats"""
+    _fields_ = [("calls_completed", C.c_uint64), ("exact_tokens", C.c_uint64)]
+
+
 def independent_limits() -> CIndependentLimits:
     """The numbers of rpvg_hip_nested_independent_subset_em's plan (rpvg_amd/csrc/subset_independent_plan.hpp); needs no GPU."""
     out = CIndependentLimits()
@@ -218,6 +224,10 @@ def lib() -> C.CDLL:
         L.rpvg_hip_full_set_count.restype = C.c_uint64
         L.rpvg_hip_subset_em_kept_bytes.restype = C.c_uint64
         L.rpvg_hip_cover_limits.restype = None
+        L.rpvg_hip_parsed_dump_rows.restype = C.c_void_p
+        L.rpvg_hip_parsed_dump_rows.argtypes = [C.c_void_p]
+        L.rpvg_hip_parsed_dump_free.restype = None
+        L.rpvg_hip_parsed_dump_free.argtypes = [C.c_void_p]
         L.rpvg_hip_independent_limits.restype = None
         for name in EXPORTS:
             getattr(L, name)
@@ -1207,6 +1217,12 @@ class Context:
         """rpvg_hip_independent_stats: calls of rpvg_hip_nested_independent_subset_em that completed, their draws and subsets."""
         s = CIndependentStats()
         _check(lib().rpvg_hip_independent_stats_get(self.handle, C.byref(s)), "rpvg_hip_independent_stats_get")
+        return {n: int(getattr(s, n)) for n, _ in s._fields_}
+
+    def parse_stats(self) -> dict:
+        """rpvg_hip_parse_stats: parses of a --write-probs text that completed, and the numbers the exact comparison decided."""
+        s = CParseStats()
+        _check(lib().rpvg_hip_parse_stats_get(self.handle, C.byref(s)), "rpvg_hip_parse_stats_get")
         return {n: int(getattr(s, n)) for n, _ in s._fields_}
 
     def reset_stats(self):

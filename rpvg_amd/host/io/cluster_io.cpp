@@ -134,9 +134,14 @@ std::vector<std::string> splitString(const std::string & text, const char delim)
 
 std::vector<ProbabilityCluster> readProbabilityClusters(const std::string & filename, const double prob_precision) {
 
+    return readProbabilityClustersText(readTextFile(filename), filename, prob_precision);
+}
+
+std::vector<ProbabilityCluster> readProbabilityClustersText(const std::string & text_in, const std::string & filename, const double prob_precision) {
+
     std::vector<ProbabilityCluster> clusters;
 
-    std::stringstream text(readTextFile(filename));
+    std::stringstream text(text_in);
     std::string line;
 
     bool expect_paths = false;

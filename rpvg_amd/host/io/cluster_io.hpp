@@ -7,10 +7,12 @@
 #ifndef RPVG_AMD_CLUSTER_IO_HPP
 #define RPVG_AMD_CLUSTER_IO_HPP
 
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "../../../include/rpvg_hip.h"
 #include "../../../include/rpvg_text.h"
 #include "../path_cluster_estimates.hpp"
 #include "../read_path_probabilities.hpp"
@@ -41,6 +43,49 @@ void writeTextFile(const std::string & filename, const std::string & text);
 void writeRawFile(const std::string & filename, const char * data, const size_t size);
 
 std::vector<ProbabilityCluster> readProbabilityClusters(const std::string & filename, const double prob_precision);
+
+// ... of a text that is in memory already; `source_name` is what the messages of a refused text start with
+std::vector<ProbabilityCluster> readProbabilityClustersText(const std::string & text, const std::string & source_name, const double prob_precision);
+
+class HipEngine;
+
+// A dump parsed on the GPU (rpvg_amd/csrc/rows_parse.hip): the resident rows and the path side, without any container.  The
+// handle of the C ABI behind a class; a refused text throws std::runtime_error with the line and the reason.
+class ParsedDump {
+
+    public:
+
+        // bytes: host memory, or device memory of the engine's GPU (on_device)
+        ParsedDump(const std::shared_ptr<HipEngine> & engine, const char * bytes, const uint64_t num_bytes, const bool on_device, const double prob_precision);
+        ~ParsedDump();
+
+        ParsedDump(const ParsedDump &) = delete;
+        ParsedDump & operator=(const ParsedDump &) = delete;
+
+        rpvg_hip_parsed_dump * handle() const { return dump; }
+        rpvg_hip_read_rows * rows() const { return rpvg_hip_parsed_dump_rows(dump); }
+
+        // host copies, valid until the dump dies
+        rpvg_parsed_dump_view view() const;
+        rpvg_cluster_batch rowsView() const;
+
+        // the names, lengths and ClusterIDs where they lie on the GPU
+        rpvg_table_labels labels() const;
+
+        // the batch the estimators take, made on the GPU from the resident rows (the caller's, rpvg_hip_batch_free)
+        rpvg_hip_batch * toBatch() const;
+
+    private:
+
+        std::shared_ptr<HipEngine> hip_engine;
+        rpvg_hip_parsed_dump * dump = nullptr;
+};
+
+// readProbabilityClusters through the device parse: readTextFile, the kernels, then the same containers from the views.  For
+// callers that want the containers; the device refuses some texts std::stod takes ("1.5abc", "0x1p3", "+1", a space at the end
+// of a line: docs/design/parity.md item 22), for which readProbabilityClusters stays.
+std::vector<ProbabilityCluster> readProbabilityClustersDevice(const std::shared_ptr<HipEngine> & engine, const std::string & filename, const double prob_precision);
+std::vector<ProbabilityCluster> readProbabilityClustersDeviceText(const std::shared_ptr<HipEngine> & engine, const std::string & text, const double prob_precision);
 
 // Same format as the reference's writer (a block whose cluster has a rank key gets the extended marker line); gzip when the
 // name ends in ".gz".

@@ -9,6 +9,10 @@ the rows ReadCountGibbsSamplesWriter, AbundanceEstimatesWriter and HaplotypeAbun
               bgzf: the text as the members of a .gz file, deflated on the GPU (rpvg_amd/csrc/text_deflate.hip)
   BgzfText    BGZF members resident on the GPU (rpvg_hip_text_bgzf): view / bytes / guards_intact / free; bgzf_bytes(ctx, data)
               makes one of any bytes, bgzf_model(data) the same members on the host without a GPU
+  parse_rows  the way back: the text of a --write-probs dump parsed on the GPU (rpvg_amd/csrc/rows_parse.hip) into a ParsedDump —
+              resident rows (rows / to_batch), the path side (view) and device labels (labels); TableText.parse() does it for a
+              resident text where it lies.  host_line_parse(data) is readProbabilityClusters flattened to the same arrays and
+              plan_parse(data) the kernels' functions on the host; neither needs a GPU
   HarnessTableText  over the harness entry points: the text of a HarnessGibbsTable or a HarnessTable through the host class
               (rpvg_amd/host/table_text.hpp), the file from it by the writer's addText(), and the same rows from one host thread
 """
@@ -208,8 +212,176 @@ class TableText(HandleOwner):
         hip._check(hip.lib().rpvg_hip_table_text_bgzf(self.handle, C.byref(handle)), "rpvg_hip_table_text_bgzf")
         return BgzfText(handle)
 
+    def parse(self, prob_precision: float = 1e-8) -> "ParsedDump":
+        """The text of a --write-probs dump parsed where it lies (rpvg_hip_table_text_rows): nothing is downloaded."""
+        handle = C.c_void_p()
+        hip._check(hip.lib().rpvg_hip_table_text_rows(self.handle, C.c_double(prob_precision), C.byref(handle)), "rpvg_hip_table_text_rows")
+        return ParsedDump(handle)
+
     def _release(self):
         hip.lib().rpvg_hip_table_text_free(self.handle)
+
+
+class CParsedDumpView(C.Structure):
+    """rpvg_parsed_dump_view"""
+    _fields_ = [("num_clusters", C.c_uint32), ("num_paths", C.c_uint64), ("num_name_bytes", C.c_uint64), ("cluster_path_off", C.POINTER(C.c_uint64)),
+                ("name_off", C.POINTER(C.c_uint64)), ("name_bytes", C.POINTER(C.c_char)), ("path_length", C.POINTER(C.c_uint32)),
+                ("path_effective_length", C.POINTER(C.c_double)), ("has_rank_key", C.POINTER(C.c_uint8)), ("num_align_lists", C.POINTER(C.c_uint64)),
+                ("cluster_index", C.POINTER(C.c_uint64))]
+
+
+def _array(pointer, n, dtype):
+    return np.ctypeslib.as_array(pointer, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+
+
+class ParsedDump(HandleOwner):
+    """A dump parsed on the GPU (rpvg_hip_parsed_dump): it owns the resident rows and the path side."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    @property
+    def rows(self):
+        """The handle of the resident rows (rpvg_hip_read_rows *), valid until free(): what rpvg_hip_read_rows_to_batch, _view, _sizes
+        and rpvg_hip_read_rows_text take."""
+        return C.c_void_p(hip.lib().rpvg_hip_parsed_dump_rows(self.handle))
+
+    def view(self) -> dict:
+        """Host copies of the path side by name: cluster_path_off, name_off, name_bytes (bytes), path_length, path_effective_length,
+        has_rank_key, num_align_lists, cluster_index."""
+        v = CParsedDumpView()
+        hip._check(hip.lib().rpvg_hip_parsed_dump_view(self.handle, C.byref(v)), "rpvg_hip_parsed_dump_view")
+        K, P, n = int(v.num_clusters), int(v.num_paths), int(v.num_name_bytes)
+        return dict(cluster_path_off=_array(v.cluster_path_off, K + 1, np.uint64), name_off=_array(v.name_off, P + 1, np.uint64),
+                    name_bytes=C.string_at(v.name_bytes, n) if n else b"", path_length=_array(v.path_length, P, np.uint32),
+                    path_effective_length=_array(v.path_effective_length, P, np.float64), has_rank_key=_array(v.has_rank_key, K, np.uint8),
+                    num_align_lists=_array(v.num_align_lists, K, np.uint64), cluster_index=_array(v.cluster_index, K, np.uint64))
+
+    def rows_view(self, ctx_or_engine) -> dict:
+        """Host copies of the rows by name (rpvg_hip_read_rows_view): the row arrays of rpvg_rows_text_input."""
+        v = hip.CClusterBatch()
+        hip._check(hip.lib().rpvg_hip_read_rows_view(ctx_handle(ctx_or_engine), self.rows, C.byref(v), None, None), "rpvg_hip_read_rows_view")
+        K = int(v.num_clusters)
+        cro = _array(C.cast(v.cluster_row_off, C.POINTER(C.c_uint64)), K + 1, np.uint64)
+        R = int(cro[K])
+        rgo = _array(C.cast(v.row_grp_off, C.POINTER(C.c_uint64)), R + 1, np.uint64)
+        G = int(rgo[R])
+        gio = _array(C.cast(v.grp_idx_off, C.POINTER(C.c_uint64)), G + 1, np.uint64)
+        M = int(gio[G])
+        return dict(cluster_row_off=cro, cluster_path_off=_array(C.cast(v.cluster_path_off, C.POINTER(C.c_uint64)), K + 1, np.uint64),
+                    row_count=_array(C.cast(v.row_count, C.POINTER(C.c_uint32)), R, np.uint32), row_noise=_array(C.cast(v.row_noise, C.POINTER(C.c_double)), R, np.float64),
+                    row_grp_off=rgo, grp_prob=_array(C.cast(v.grp_prob, C.POINTER(C.c_double)), G, np.float64), grp_idx_off=gio,
+                    path_idx=_array(C.cast(v.path_idx, C.POINTER(C.c_uint32)), M, np.uint32))
+
+    def labels(self) -> CTableLabels:
+        """The names, lengths and ClusterIDs where they lie on the GPU (on_device = 1), valid until free()."""
+        out = CTableLabels()
+        hip._check(hip.lib().rpvg_hip_parsed_dump_labels(self.handle, C.byref(out)), "rpvg_hip_parsed_dump_labels")
+        return out
+
+    def to_batch(self, ctx: "hip.Context") -> "hip.DeviceBatch":
+        """The batch the estimators take, made on the GPU from the resident rows (rpvg_hip_read_rows_to_batch)."""
+        rows = hip.DeviceRows(ctx, self.rows)
+        try:
+            return rows.to_batch()
+        finally:
+            rows.handle = C.c_void_p()  # the dump's, not the wrapper's
+
+    def text(self, ctx_or_engine, prob_precision: float = 1e-8) -> TableText:
+        """The rows back as text with the dump's own labels, effective lengths and markers (rpvg_hip_read_rows_text)."""
+        v = self.view()
+        ranked = bool(v["has_rank_key"].any())
+        return TableText.resident_rows(ctx_or_engine, self.rows, self.labels(), v["path_effective_length"], prob_precision,
+                                       v["num_align_lists"] if ranked else None, v["cluster_index"] if ranked else None)
+
+    def _release(self):
+        hip.lib().rpvg_hip_parsed_dump_free(self.handle)
+
+
+def parse_rows(ctx_or_engine, data, device_pointer=None, num_bytes: Optional[int] = None, prob_precision: float = 1e-8) -> ParsedDump:
+    """The text of a --write-probs dump parsed on the GPU (rpvg_hip_text_rows): data is a bytes-like object in host memory, or None
+    with device_pointer and num_bytes for a text in the memory of the context's GPU.  A refused text raises hip.EngineError with
+    the 1-based line and the reason."""
+    handle = C.c_void_p()
+    if device_pointer is not None:
+        pointer, n, on_device = C.c_void_p(device_pointer), int(num_bytes), 1
+    else:
+        raw = bytes(data)
+        pointer, n, on_device = C.cast(C.c_char_p(raw), C.c_void_p), len(raw), 0
+    hip._check(hip.lib().rpvg_hip_text_rows(ctx_handle(ctx_or_engine), pointer, C.c_uint64(n), C.c_int32(on_device), C.c_double(prob_precision), C.byref(handle)),
+               "rpvg_hip_text_rows")
+    return ParsedDump(handle)
+
+
+class CRowsParseView(C.Structure):
+    """rpvg_amd_rows_parse_view of the harness"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_clusters", "num_paths", "num_rows", "num_groups", "num_entries", "num_name_bytes")] + \
+               [(n, C.POINTER(C.c_uint64)) for n in ("cluster_row_off", "cluster_path_off", "row_grp_off", "grp_idx_off", "name_off", "num_align_lists", "cluster_index")] + \
+               [(n, C.POINTER(C.c_uint32)) for n in ("row_count", "path_idx", "path_length")] + \
+               [(n, C.POINTER(C.c_double)) for n in ("row_noise", "grp_prob", "path_effective_length")] + \
+               [("has_rank_key", C.POINTER(C.c_uint8)), ("name_bytes", C.POINTER(C.c_char)), ("seconds", C.c_double)]
+
+
+PARSED_ARRAYS = ("cluster_row_off", "cluster_path_off", "row_count", "row_noise", "row_grp_off", "grp_prob", "grp_idx_off", "path_idx", "name_off", "name_bytes",
+                 "path_length", "path_effective_length", "has_rank_key", "num_align_lists", "cluster_index")
+
+
+def _parse_harness():
+    from . import engine
+    L = engine.lib()
+    L.rpvg_amd_rows_parse_last_error.restype = C.c_char_p
+    for name, argtypes in (("rpvg_amd_rows_parse", [C.c_void_p, C.c_char_p, C.c_uint64, C.c_double]), ("rpvg_amd_rows_parse_host_line", [C.c_char_p, C.c_uint64, C.c_double]),
+                           ("rpvg_amd_rows_parse_plan", [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]), ("rpvg_amd_rows_parse_file", [C.c_void_p, C.c_char_p, C.c_double, C.c_int])):
+        getattr(L, name).restype, getattr(L, name).argtypes = C.c_void_p, argtypes
+    L.rpvg_amd_rows_parse_view.argtypes = [C.c_void_p, C.POINTER(CRowsParseView)]
+    L.rpvg_amd_rows_parse_free.argtypes = [C.c_void_p]
+    L.rpvg_amd_read_text_file_seconds.restype = C.c_double
+    L.rpvg_amd_read_text_file_seconds.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
+    return L
+
+
+def _flat_of(L, handle, what: str) -> dict:
+    """The arrays of PARSED_ARRAYS by name (copies) and the reader's seconds."""
+    if not handle:
+        raise hip.EngineError(f"{what} failed: {L.rpvg_amd_rows_parse_last_error().decode()}")
+    try:
+        v = CRowsParseView()
+        L.rpvg_amd_rows_parse_view(handle, C.byref(v))
+        K, P, R, G, M, n = (int(getattr(v, f)) for f in ("num_clusters", "num_paths", "num_rows", "num_groups", "num_entries", "num_name_bytes"))
+        sizes = dict(cluster_row_off=K + 1, cluster_path_off=K + 1, row_grp_off=R + 1, grp_idx_off=G + 1, name_off=P + 1, num_align_lists=K, cluster_index=K, row_count=R,
+                     path_idx=M, path_length=P, row_noise=R, grp_prob=G, path_effective_length=P, has_rank_key=K)
+        out = {name: _array(getattr(v, name), size, getattr(v, name)._type_) for name, size in sizes.items()}
+        out["name_bytes"] = C.string_at(v.name_bytes, n) if n else b""
+        out["seconds"] = v.seconds
+        return out
+    finally:
+        L.rpvg_amd_rows_parse_free(handle)
+
+
+def host_line_parse(data, prob_precision: float = 1e-8) -> dict:
+    """readProbabilityClusters on the text, flattened to the arrays of PARSED_ARRAYS: the reader the device parse replaces.  No GPU."""
+    L, raw = _parse_harness(), bytes(data)
+    return _flat_of(L, L.rpvg_amd_rows_parse_host_line(raw, len(raw), prob_precision), "the host reader")
+
+
+def plan_parse(data) -> dict:
+    """The functions of rpvg_amd/csrc/rows_parse_plan.hpp over serial scans on the host: the arrays the kernels make, and
+    exact_tokens; a refused text raises hip.EngineError("... line <n>: <reason>").  No GPU."""
+    L, raw, exact = _parse_harness(), bytes(data), C.c_uint64(0)
+    out = _flat_of(L, L.rpvg_amd_rows_parse_plan(raw, len(raw), C.byref(exact)), "the plan's parse")
+    return dict(out, exact_tokens=int(exact.value))
+
+
+def harness_parse(engine, data, prob_precision: float = 1e-8) -> dict:
+    """The device parse through the host class (rpvg_amd::ParsedDump), flat from its views."""
+    L, raw = _parse_harness(), bytes(data)
+    return _flat_of(L, L.rpvg_amd_rows_parse(engine.handle, raw, len(raw), prob_precision), "the device parse")
+
+
+def harness_parse_file(engine, filename: str, prob_precision: float = 1e-8, on_device: bool = True) -> dict:
+    """A file through readProbabilityClustersDevice (on_device) or readProbabilityClusters, flattened."""
+    L = _parse_harness()
+    return _flat_of(L, L.rpvg_amd_rows_parse_file(engine.handle if engine is not None else None, filename.encode(), prob_precision, int(on_device)), "the reader")
 
 
 class BgzfText(HandleOwner):
@@ -401,3 +573,12 @@ def host_line_rows(rows_input: RowsInput, labels: Labels, prob_precision: float 
     if L.rpvg_amd_rows_text_host_line(C.byref(inp), C.byref(flat), prob_precision, out, None, None, None, None) != 0:
         raise hip.EngineError(f"rows text host line failed: {engine._err()}")
     return dict(bytes=out.raw[:n.value], row_off=row_off, exact_cells=int(exact.value), seconds=secs.value, num_bytes=int(n.value))
+
+
+def read_text_file_seconds(filename: str) -> float:
+    """The seconds readTextFile takes on the file (tools/rows_parse_ab.py)."""
+    L, n = _parse_harness(), C.c_uint64(0)
+    seconds = L.rpvg_amd_read_text_file_seconds(filename.encode(), C.byref(n))
+    if seconds < 0:
+        raise hip.EngineError(f"readTextFile failed: {L.rpvg_amd_rows_parse_last_error().decode()}")
+    return seconds
